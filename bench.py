@@ -10,9 +10,18 @@ scaling, no collective in the loop; one gather of the final poses / energies / c
     python bench.py --gpus N --steps K --warmup W         # N > 1: this process only spawns the N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Timing: W warm-up iterations, then `--windows` (default 3) timed windows of EXACTLY K iterations each, every window
-bracketed by barrier + synchronize on both sides, MAX over ranks per window; the line reports the MEDIAN window
-(`ms_per_step` = median window / K, `value` = rows of all ranks * K / median window; all windows are listed).
+Timing: W warm-up iterations, then `--windows` timed windows of EXACTLY K iterations each (default: one window, so a
+plain run times exactly K steps; 3 with --full), every window bracketed by barrier + synchronize on both sides, MAX over
+ranks per window; the line reports the MEDIAN window (`ms_per_step` = median window / K, `value` = rows of all ranks * K
+/ median window; all windows are listed).
+
+A plain run sets up, warms up, times, writes the outputs (--dump-outputs DIR) and prints the line.  Everything else --
+the eager pass that times the penetration query alone, the launch-group and executed-work diagnostics, the roofline
+object, the per-launch tables from profiles/, the plugin-surface block and the CPU baselines -- runs only with --full.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as DIR/<name>.npy (float32 / float64):
+hand_pose, energy, energy_terms, accept, contact_idx (rows of all ranks for N > 1; a fixed, seeded row sample if the
+arrays would exceed 64 MB).  The inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as _ct
@@ -39,7 +48,8 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="iterations per timed window")
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps iterations; the median is reported")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps iterations; the median is reported "
+                    "(default 1, 3 with --full)")
     ap.add_argument("--event_steps", type=int, default=50, help="extra eager iterations timed with HIP events")
     ap.add_argument("--warmup", type=int, default=24)
     ap.add_argument("--batch_size", type=int, default=256)
@@ -79,9 +89,16 @@ def parse_args(argv=None):
     ap.add_argument("--plugin_surface", type=int, default=-1, help="1: after the timed region, time the reference's plugin "
                     "surface on the same workload (compute_sdf at the reference's shapes, QPFunction / SQPLsqSolver.solve, a "
                     "fit.py-shaped loop on the class surface); -1 (default): at N=1 on BASELINE configs[1] only")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every diagnostic: eager event "
+                    "pass, launch groups, executed work, roofline, static profile tables, plugin surface, CPU baselines")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--selftest_ranks", action="store_true",
                     help="launcher / rendezvous / collective sequence only (no GPU work): used by the CPU test of --gpus N")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
+    return args
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -174,6 +191,21 @@ def cpu_baseline(spec, fv, sp, n_contact, rows, reps, label):
     return {"value": rows / dt, "unit": "evals/s", "cores": cores, "kind": "port",
             "sample": f"{label}: {rows} rows x {reps} timed energy+grad evaluations (median; 1 warm-up), n_contact={n_contact}, "
                       f"{fv.shape[0]}-face mesh, {sp.shape[0]} surface points, oracle/ref_cpu fp32, {dt:.2f} s each"}
+
+
+def dump_outputs(out_dir, outputs, max_bytes=64 << 20, seed=0):
+    """outputs {name: float CPU tensor with the batch rows first; energy_terms (5, B)} -> out_dir/<name>.npy.  Above
+    `max_bytes` in all, every array keeps the same fixed, seeded sample of rows (sorted; their indices go to rows.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.numpy() for k, v in outputs.items()}
+    n = arrays["energy"].shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        keep = np.sort(np.random.default_rng(seed).choice(n, int(n * max_bytes / total * 0.99), replace=False))
+        arrays = {k: (a[..., keep] if k == "energy_terms" else a[keep]) for k, a in arrays.items()}
+        arrays["rows"] = keep.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def _load_json(name):
@@ -274,7 +306,8 @@ def rank_main(args):
         st.step()
     st.realign_draws()  # a warm-up that is not a multiple of the graph length ends with eager iterations (untimed);
     sync()              # the timed windows then start on a fresh draw buffer: whole graph replays only
-    st.start_kernel_timing()
+    if args.full:
+        st.start_kernel_timing()
     window_s, enq_s = [], []
     cdev = "cuda" if args.dist_backend == "nccl" else "cpu"
     for _ in range(max(1, args.windows)):
@@ -292,95 +325,109 @@ def rank_main(args):
             dt = float(tt.item())
         window_s.append(dt)
         enq_s.append(t_enq)
-    _, span_ms, n_span = st.kernel_times_ms()
+    span_ms, n_span = st.kernel_times_ms()[1:] if args.full else (None, 0)
     assert torch.isfinite(st.energy).all(), "non-finite energies"
+    # what the timed path computed in its last step (the state a caller of GraspStepper.step receives), taken before any
+    # diagnostic iteration of --full changes it
+    final = (st.hand_pose.clone(), st.energy.clone(), st.contact_idx.clone())
+    final_extra = (st.terms.t().contiguous(), st.accept.float(), st.contact_idx.clone())  # rows first, for the gather
+    outputs = {"hand_pose": st.hand_pose.float().cpu(), "energy": st.energy.float().cpu(),
+               "energy_terms": st.terms.float().cpu(), "accept": st.accept.float().cpu(),
+               "contact_idx": st.contact_idx.double().cpu()}
+    mean_energy, accept_rate = float(st.energy.mean()), float(st.accept.float().mean())
 
-    # ---- after the timed region --------------------------------------------------------------------------------------
-    # (1) the same loop launched eagerly on one stream with a HIP event pair around every hand-penetration query (events
-    # cannot bracket a node of a replayed hipGraph) -> the query's isolated duration
-    g, st._graph = st._graph, None
-    st.start_kernel_timing()
-    for _ in range(args.event_steps):
-        st.step()
-    torch.cuda.synchronize()
-    evs, span_iso_ms, _ = st.kernel_times_ms()
-    # (2) the fused launch sequence issued eagerly, a torch event pair around every C-ABI call (they run on torch's
-    # current stream): live duration of each launch group
-    group_ms = {}
-    if args.fused != 0 and st.penetration_only == 1:
-        names = ["fk_forward(+propose" + ("+object SDF)" if B <= 512 else ")"), "object_sdf", "stage_a+stop+stage_b",
-                 "fk_backward(+energies+accept)"]
-        acc = {k: [] for k in names}
-        for _ in range(max(args.event_steps // 2, 8)):
-            st.draw()
-            stream = _C.stream_ptr()
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-            attach = B <= 512
-            ev[0].record()
-            st._eval_fk(st.pose_new, st.idx_new, stream, True, sdf=attach, spheres=False)
-            ev[1].record()
-            if not attach:
-                _C.call("gq_sdf_forward_meshset", st.objs.handle, _C.f32(st.cpts), B * st.n, st.be * st.n, _C.f32(st.d2),
-                        _C.i32(st.sgn), _C.f32(st.onrm), _C.f32(st.closest), stream)
-            ev[2].record()
-            st._pen_desc.hand_pose = st.pose_new.data_ptr()
-            _C.call("gq_fc_pen_step", _ct.byref(st._fc_desc), _ct.byref(st._pen_desc), stream)
-            ev[3].record()
-            st._eval_tail(st.pose_new, st.idx_new, stream, True)
-            ev[4].record()
-            torch.cuda.synchronize()
-            for i, k in enumerate(names):
-                acc[k].append(ev[i].elapsed_time(ev[i + 1]))
-        group_ms = {k: float(np.median(v)) for k, v in acc.items() if (k != "object_sdf" or B > 512)}
-    # (3) executed work of the two SDF kernels on the final state (debug counters, stand-alone launches)
-    executed = {}
-    try:
-        cnt = torch.zeros(12, dtype=torch.int64, device="cuda")
-        _C.call("gq_debug_set_pen_counters", _ct.c_void_p(cnt.data_ptr()))
-        # the counting launch of the query (every block adds to the same 12 global counters: ~0.6 ms) runs as the two-points-
-        # per-thread instantiation -- the form the query has as the role of stage A -- so that it does not sit in the
-        # rocprofv3 statistics of gq_pen_grid_kernel<..., 1>, the kernel the eager pass above times alone
-        _C.call("gq_debug_set_pen_ppt", 2)
-        stream = _C.stream_ptr()
-        st._eval_fk(st.hand_pose, st.contact_idx, stream)
-        _C.call("gq_sdf_forward_meshset", st.objs.handle, _C.f32(st.cpts), B * st.n, st.be * st.n, _C.f32(st.d2),
-                _C.i32(st.sgn), _C.f32(st.onrm), _C.f32(st.closest), stream)
-        if st.grid is not None:
-            _C.call("gq_hand_pen_forward_cells", hand.links.handle, st.grid.handle, _C.f32(st.surf), st.n_obj, st.P, st.be,
-                    _C.f32(st.hand_pose), st.D, _C.f32(st.Rg), _C.f32(st.link_T), _C.f32(st.pen_dis), _C.i32(st.pen_link),
-                    _C.f32(st.pen_gvec), None, None, stream)
-        else:
-            _C.call("gq_hand_pen_forward", hand.links.handle, _C.f32(st.surf), st.n_obj, st.P, st.be, _C.f32(st.hand_pose),
-                    st.D, _C.f32(st.Rg), _C.f32(st.link_T), 1, _C.f32(st.pen_dis), _C.i32(st.pen_link), _C.f32(st.pen_gvec),
-                    None, 0, None, None, _C.f32(st.patch), stream)
+    # ---- after the timed region (--full only) -------------------------------------------------------------------------
+    evs, span_iso_ms, group_ms, executed = [], None, {}, {}
+    if args.full:
+        # (1) the same loop launched eagerly on one stream with a HIP event pair around every hand-penetration query
+        # (events cannot bracket a node of a replayed hipGraph) -> the query's isolated duration
+        g, st._graph = st._graph, None
+        st.start_kernel_timing()
+        for _ in range(args.event_steps):
+            st.step()
         torch.cuda.synchronize()
-        _C.call("gq_debug_set_pen_counters", None)
-        c = [int(v) for v in cnt.tolist()]
-        executed = {"object_sdf": {"queries": c[1], "cluster_visits": c[0], "point_triangle_tests": c[0] * 64,
-                                   "max_visits_per_query": c[2]},
-                    "hand_pen": {"point_link_pairs": B * st.P * hand.L, "pairs_reaching_candidates": c[4],
-                                 "point_triangle_tests": c[5], "pairs_ranked_inline": c[6], "blocks": c[7],
-                                 "scanning_wavefronts": c[11], "wavefront_link_sphere_tests": c[8],
-                                 "wavefront_link_sphere_hits": c[9], "point_link_pairs_in_box": c[10],
-                                 "link_cell_pairs_walked": c[0] if st.grid is not None else None,
-                                 "query": "link-driven (point grid)" if st.grid is not None else
-                                          "point-driven, two surface points per thread (the stage-A role)"}}
-    except Exception as e:  # diagnostics must never cost the bench line
-        executed = {"error": repr(e)}
-    finally:
-        _C.call("gq_debug_set_pen_ppt", int(args.pen_ppt or 0))
-    st._graph = g
+        evs, span_iso_ms, _ = st.kernel_times_ms()
+        # (2) the fused launch sequence issued eagerly, a torch event pair around every C-ABI call (they run on torch's
+        # current stream): live duration of each launch group
+        if args.fused != 0 and st.penetration_only == 1:
+            names = ["fk_forward(+propose" + ("+object SDF)" if B <= 512 else ")"), "object_sdf", "stage_a+stop+stage_b",
+                     "fk_backward(+energies+accept)"]
+            acc = {k: [] for k in names}
+            for _ in range(max(args.event_steps // 2, 8)):
+                st.draw()
+                stream = _C.stream_ptr()
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+                attach = B <= 512
+                ev[0].record()
+                st._eval_fk(st.pose_new, st.idx_new, stream, True, sdf=attach, spheres=False)
+                ev[1].record()
+                if not attach:
+                    _C.call("gq_sdf_forward_meshset", st.objs.handle, _C.f32(st.cpts), B * st.n, st.be * st.n, _C.f32(st.d2),
+                            _C.i32(st.sgn), _C.f32(st.onrm), _C.f32(st.closest), stream)
+                ev[2].record()
+                st._pen_desc.hand_pose = st.pose_new.data_ptr()
+                _C.call("gq_fc_pen_step", _ct.byref(st._fc_desc), _ct.byref(st._pen_desc), stream)
+                ev[3].record()
+                st._eval_tail(st.pose_new, st.idx_new, stream, True)
+                ev[4].record()
+                torch.cuda.synchronize()
+                for i, k in enumerate(names):
+                    acc[k].append(ev[i].elapsed_time(ev[i + 1]))
+            group_ms = {k: float(np.median(v)) for k, v in acc.items() if (k != "object_sdf" or B > 512)}
+        # (3) executed work of the two SDF kernels on the final state (debug counters, stand-alone launches)
+        try:
+            cnt = torch.zeros(12, dtype=torch.int64, device="cuda")
+            _C.call("gq_debug_set_pen_counters", _ct.c_void_p(cnt.data_ptr()))
+            # the counting launch of the query (every block adds to the same 12 global counters: ~0.6 ms) runs as the
+            # two-points-per-thread instantiation -- the form the query has as the role of stage A -- so that it does not sit
+            # in the rocprofv3 statistics of gq_pen_grid_kernel<..., 1>, the kernel the eager pass above times alone
+            _C.call("gq_debug_set_pen_ppt", 2)
+            stream = _C.stream_ptr()
+            st._eval_fk(st.hand_pose, st.contact_idx, stream)
+            _C.call("gq_sdf_forward_meshset", st.objs.handle, _C.f32(st.cpts), B * st.n, st.be * st.n, _C.f32(st.d2),
+                    _C.i32(st.sgn), _C.f32(st.onrm), _C.f32(st.closest), stream)
+            if st.grid is not None:
+                _C.call("gq_hand_pen_forward_cells", hand.links.handle, st.grid.handle, _C.f32(st.surf), st.n_obj, st.P, st.be,
+                        _C.f32(st.hand_pose), st.D, _C.f32(st.Rg), _C.f32(st.link_T), _C.f32(st.pen_dis), _C.i32(st.pen_link),
+                        _C.f32(st.pen_gvec), None, None, stream)
+            else:
+                _C.call("gq_hand_pen_forward", hand.links.handle, _C.f32(st.surf), st.n_obj, st.P, st.be, _C.f32(st.hand_pose),
+                        st.D, _C.f32(st.Rg), _C.f32(st.link_T), 1, _C.f32(st.pen_dis), _C.i32(st.pen_link), _C.f32(st.pen_gvec),
+                        None, 0, None, None, _C.f32(st.patch), stream)
+            torch.cuda.synchronize()
+            _C.call("gq_debug_set_pen_counters", None)
+            c = [int(v) for v in cnt.tolist()]
+            executed = {"object_sdf": {"queries": c[1], "cluster_visits": c[0], "point_triangle_tests": c[0] * 64,
+                                       "max_visits_per_query": c[2]},
+                        "hand_pen": {"point_link_pairs": B * st.P * hand.L, "pairs_reaching_candidates": c[4],
+                                     "point_triangle_tests": c[5], "pairs_ranked_inline": c[6], "blocks": c[7],
+                                     "scanning_wavefronts": c[11], "wavefront_link_sphere_tests": c[8],
+                                     "wavefront_link_sphere_hits": c[9], "point_link_pairs_in_box": c[10],
+                                     "link_cell_pairs_walked": c[0] if st.grid is not None else None,
+                                     "query": "link-driven (point grid)" if st.grid is not None else
+                                              "point-driven, two surface points per thread (the stage-A role)"}}
+        except Exception as e:  # diagnostics must never cost the bench line
+            executed = {"error": repr(e)}
+        finally:
+            _C.call("gq_debug_set_pen_ppt", int(args.pen_ppt or 0))
+        st._graph = g
 
     # ---- end-of-run gather: the only collective of a run (<= 0.5 MB per rank) -----------------------------------------
     per_rank = None
     if dist is not None:
-        poses, energies, cidx = gather_results(st.hand_pose.to(cdev), st.energy.to(cdev), st.contact_idx.to(cdev))
+        poses, energies, cidx = gather_results(*(t.to(cdev) for t in final))
+        terms, accepts, _ = gather_results(*(t.to(cdev) for t in final_extra))  # for --dump-outputs (< 10 KB per rank)
         mine = torch.tensor([B * args.steps / float(np.median(window_s))], device=cdev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [float(v.item()) for v in allr]
         if rank == 0:
             assert sum(p.shape[0] for p in poses) == B * world and all(torch.isfinite(e).all() for e in energies)
+            outputs = {"hand_pose": torch.cat(poses).float().cpu(), "energy": torch.cat(energies).float().cpu(),
+                       "energy_terms": torch.cat(terms).t().float().cpu().contiguous(),
+                       "accept": torch.cat(accepts).float().cpu(), "contact_idx": torch.cat(cidx).double().cpu()}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
 
     if rank == 0:
         dt = float(np.median(window_s))
@@ -442,13 +489,13 @@ def rank_main(args):
         # per-launch table: durations from the rocprofv3 kernel trace and HBM bytes from the PMC passes of THIS command
         # (tools/profile_round.sh writes profiles/<tag>_launches.json); live numbers: launch_groups_ms above
         ltag = next((t for t in (PROFILE_TAG, "r02") if _load_json(f"{t}_launches.json")), PROFILE_TAG)
-        launches = _load_json(f"{ltag}_launches.json") if is_cfg2 and args.energy_type == "graspqp" else None
+        launches = _load_json(f"{ltag}_launches.json") if args.full and is_cfg2 and args.energy_type == "graspqp" else None
         if launches:
             launches["source"] = f"static, from profiles/{ltag}_launches.json"
         # executed instructions per wavefront and VALU issue-slot utilisation of every kernel (SQ counters of the same
         # command, tools/pmc_instr.sh): the "how far from the machine's limit" figure of kernels that are neither HBM- nor
         # MFMA-bound
-        instr = _load_json(f"{ltag}_cfg2_instr.json") if is_cfg2 else None
+        instr = _load_json(f"{ltag}_cfg2_instr.json") if args.full and is_cfg2 else None
         if launches and instr:
             for k in launches.get("kernels", []):
                 rec = instr.get("kernels", {}).get(k["name"])
@@ -479,12 +526,14 @@ def rank_main(args):
                        "branches": getattr(st, "graph_mode", "eager") if args.graph else "eager"},
             "timing": {"windows": len(window_s), "window_ms": [w * 1e3 for w in window_s], "statistic": "median",
                        "host_enqueue_ms_per_step": float(np.median(enq_s)) / args.steps * 1e3},
-            "mean_energy": float(st.energy.mean()), "accept_rate_last": float(st.accept.float().mean()),
-            "roofline": roof, "launch_groups_ms": group_ms, "executed_work": executed, "launches": launches,
+            "mean_energy": mean_energy, "accept_rate_last": accept_rate,
         }
+        if args.full:
+            res.update(roofline=roof, launch_groups_ms=group_ms, executed_work=executed, launches=launches)
         if per_rank is not None:
             res["per_rank_evals_per_s"] = per_rank
-        want_plugin = args.plugin_surface == 1 or (args.plugin_surface < 0 and world == 1 and is_cfg2 and args.energy_type == "graspqp")
+        want_plugin = args.full and (args.plugin_surface == 1 or (args.plugin_surface < 0 and world == 1 and is_cfg2
+                                                                  and args.energy_type == "graspqp"))
         if want_plugin:
             # the reference's plugin surface on the same workload (what an unchanged scripts/fit.py calls), after the timed
             # region and BEFORE the CPU baseline (its class-surface loop is bound by host time per call: measured 0.25 M
@@ -499,7 +548,7 @@ def rank_main(args):
                 res["plugin_surface"]["stepper_evals_per_s"] = res["value"]
             except Exception as e:  # diagnostics must never cost the bench line
                 res["plugin_surface"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the CPU port on configs 1 and 2 of BASELINE.json; `cpu_baseline` = the metric's configuration
             res["cpu_baseline"] = cpu_baseline(spec, fvs[0], sps[0], args.n_contact, args.cpu_rows, args.cpu_reps,
                                                "BASELINE configs[1] sample (Allegro, superquadric mesh)")

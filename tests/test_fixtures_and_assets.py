@@ -1,15 +1,13 @@
 """CPU checks of the inputs every other test relies on:
 
 * the hand data (graspqp_amd/assets/hands/*.npz, built by graspqp_amd/hands/spec.py from the reference's URDF / OBJ /
-  JSON assets) against hard-coded link face counts / joint orders and -- where the reference tree is present (build
-  container only) -- against an INDEPENDENT stdlib reading of the same asset files (oracle and product share one
-  parser, so a parsing error would otherwise be invisible to every parity test);
-* tools/make_golden.py reproduces the committed fixtures (array for array) from the reference's own files;
+  JSON assets) against hard-coded link face counts / joint orders and against an INDEPENDENT stdlib reading of the same
+  URDF files (oracle and product share one parser, so a parsing error would otherwise be invisible to every parity
+  test): the URDFs and the triangle counts of their OBJ meshes are stored under tests/golden/urdf;
 * the oracle's MALA* restatement against the extended fixture of the reference's optimizer.py (step counter started at
   149, a re-initialisation iteration, clip_grad with NaN / inf gradient entries)."""
+import json
 import os
-import subprocess
-import sys
 import xml.etree.ElementTree as ET
 
 import numpy as np
@@ -20,8 +18,9 @@ import ref_cpu
 from ref_cpu import mala, models
 from graspqp_amd.hands import get_hand_spec
 
-REF_ASSETS = "/root/reference/graspqp/assets"
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+# the three URDFs + {hand: {OBJ file: triangles}}, counted from the OBJ files with an n-gon face line as n - 2 triangles
+URDF_FIXTURES = os.path.join(ROOT, "tests", "golden", "urdf")
 
 EXPECT = {
     "allegro": dict(
@@ -47,15 +46,10 @@ EXPECT = {
 }
 
 
-def _obj_triangles(path):
-    """Triangles of an OBJ file: an n-gon face line counts n - 2 (fan triangulation)."""
-    return sum(len(line.split()) - 3 for line in open(path, errors="ignore") if line.startswith("f "))
-
-
-def _independent_reading(urdf_path, mesh_dir):
+def _independent_reading(urdf_path, mesh_triangles):
     """(non-fixed joint names in depth-first document order from the root link, [(link, faces)] for links with a mesh:
     collision meshes if the link has any, else visual meshes) -- reference hand_model.py:224-235 / pytorch_kinematics'
-    get_joint_parameter_names, re-read here with nothing but ElementTree."""
+    get_joint_parameter_names, re-read here with nothing but ElementTree.  `mesh_triangles`: mesh file name -> count."""
     root = ET.parse(urdf_path).getroot()
     joints = root.findall("joint")
     children = {j.find("child").get("link") for j in joints}
@@ -81,7 +75,7 @@ def _independent_reading(urdf_path, mesh_dir):
         for g in geoms:
             m = g.find("geometry").find("mesh")
             if m is not None:
-                n += _obj_triangles(os.path.join(mesh_dir, os.path.basename(m.get("filename"))))
+                n += mesh_triangles(os.path.basename(m.get("filename")))
         if n:
             faces.append((name, n))
     return order, faces
@@ -94,29 +88,10 @@ def test_hand_spec_face_counts_and_joint_order(hand):
     assert list(s.joint_names) == e["joints"]
     assert [s.link_faces(l).shape[0] for l in range(s.n_links)] == e["faces"]
     assert (np.asarray(s.node_parent) < np.arange(s.n_dofs)).all()  # parents precede children (DFS order)
-    if os.path.isdir(REF_ASSETS):
-        order, faces = _independent_reading(os.path.join(REF_ASSETS, e["urdf"]), os.path.join(REF_ASSETS, e["mesh"]))
-        assert order == e["joints"]
-        assert [n for _, n in faces] == e["faces"] and [l for l, _ in faces] == list(s.link_names)
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/graspqp/src/graspqp"), reason="needs the reference tree (build container)")
-def test_make_golden_reproduces_the_committed_fixtures(tmp_path, golden_dir):
-    """tools/make_golden.py executes the reference's own span.py / registry.py / energy.py / optimizer.py in place; its
-    output must equal the committed fixtures array for array (npz containers carry zip timestamps, so files are compared
-    by content)."""
-    src = open(os.path.join(ROOT, "tools", "make_golden.py")).read()
-    assert 'OUT = os.path.join(ROOT, "tests", "golden")' in src
-    env = dict(os.environ, GRASPQP_GOLDEN_OUT=str(tmp_path))
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_golden.py")], env=env,
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
-    names = sorted(f for f in os.listdir(golden_dir) if f.endswith(".npz"))
-    assert sorted(f for f in os.listdir(tmp_path) if f.endswith(".npz")) == names
-    for f in names:
-        a, b = np.load(os.path.join(golden_dir, f)), np.load(os.path.join(tmp_path, f))
-        assert sorted(a.files) == sorted(b.files), f
-        for k in a.files:
-            assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k], equal_nan=True), (f, k)
+    counts = json.load(open(os.path.join(URDF_FIXTURES, "mesh_triangles.json")))[hand]
+    order, faces = _independent_reading(os.path.join(URDF_FIXTURES, os.path.basename(e["urdf"])), counts.__getitem__)
+    assert order == e["joints"]
+    assert [n for _, n in faces] == e["faces"] and [l for l, _ in faces] == list(s.link_names)
 
 
 def _scene(g, dtype):

@@ -5,8 +5,8 @@ R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 for v in 1 0; do
   rm -rf /tmp/xs_$v /tmp/xp_$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/xs_$v -o run -- python3 $R/bench.py --no_cpu_baseline --n_objects 8 --event_steps 0 --sdf_plain_mapping $v > /tmp/xs_$v.json 2>/dev/null
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/xp_$v -o run -- python3 $R/bench.py --no_cpu_baseline --n_objects 8 --event_steps 0 --steps 40 --windows 1 --warmup 8 --sdf_plain_mapping $v > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/xs_$v -o run -- python3 $R/bench.py --full --no_cpu_baseline --n_objects 8 --event_steps 0 --sdf_plain_mapping $v > /tmp/xs_$v.json 2>/dev/null
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/xp_$v -o run -- python3 $R/bench.py --full --no_cpu_baseline --n_objects 8 --event_steps 0 --steps 40 --windows 1 --warmup 8 --sdf_plain_mapping $v > /dev/null 2>&1
   python3 - <<PY
 import csv, json
 rows=[r for r in csv.DictReader(open('/tmp/xs_$v/run_kernel_stats.csv')) if 'gq_sdf_wave' in r['Name']]

@@ -10,7 +10,7 @@
   (c) a scripts/fit.py:399-458-shaped loop on HandModel / ObjectModel / calculate_energy / MalaStar.
 
 The HBM figure of (a) is physical: N*(12 B in + 32 B out) + 36 B * F bytes really move per call.
-Used by bench.py (``plugin_surface`` block, after the timed region) and stand-alone:  python tools/plugin_surface.py
+Used by bench.py --full (``plugin_surface`` block, after the timed region) and stand-alone:  python tools/plugin_surface.py
 """
 import json
 import os
