@@ -83,6 +83,7 @@ def _fusable(hand_model, object_model, energy_fnc, method, energy_names):
     from ..metrics.ops.registry import SpanMetricWrapper
 
     return (FUSED and not ops._ROUTE["dispatcher"] and not torch.compiler.is_compiling() and isinstance(energy_fnc, SpanMetricWrapper)
+            and not energy_fnc.exact  # only the PDIPM overall metric has a fused form; the exact metrics are composed
             and "E_manipulativity" not in energy_names  # its directions carry a gradient to `distance`
             and method in ("gendexgrasp", "dexgraspnet") and getattr(object_model, "_meshset", None) is not None
             and object_model.surface_points_each is not None and getattr(hand_model, "_fk_ws", None) is not None)

@@ -8,6 +8,8 @@ pytorch_kinematics / trimesh objects.
 
 from __future__ import annotations
 
+import math
+
 import torch
 
 from .. import ops
@@ -129,6 +131,42 @@ class HandModel:
                             self.global_rotation.detach(), self.current_status.detach(), self._fk_ws,
                             self._fk_ws.numel(), penetration_only)
 
+    # reference hand_model.py:698-760 (scripts/fit.py:462-470, --log_entropy): diversity of the grasp set as the mean
+    # entropy of 32-bin histograms.  Evaluated in fp64 on the device (not a hot path), returned in the pose dtype.
+    @staticmethod
+    def _hist_entropy(values, lo, hi, bins=32):
+        p = values.histc(bins, lo, hi)
+        p = p / p.sum()
+        return -(p * torch.log(torch.where(p > 0, p, torch.ones_like(p)))).sum()
+
+    def joint_entropy(self):
+        """Mean over the joints of the entropy of the joint angles' histogram over [lower, upper] -> 0-dim tensor."""
+        q = self.hand_pose[:, 9:].detach().double()
+        lo, hi = self.joints_lower.double().tolist(), self.joints_upper.double().tolist()
+        ent = sum(self._hist_entropy(q[:, j], lo[j], hi[j]) for j in range(q.shape[1])) / q.shape[1]
+        return ent.to(self.hand_pose.dtype)
+
+    def pose_entropy(self):
+        """(translation entropy, rotation entropy), each the mean of three 32-bin histogram entropies -> two 0-dim tensors.
+        Translation: each axis over [-0.1, 0.1].  Rotation: the rotation vector of the hand's 6-D rotation in spherical
+        coordinates (|v| over [0, pi], polar angle over [0, pi], azimuth over [-pi, pi])."""
+        hp = self.hand_pose.detach().double()
+        t = hp[:, 0:3]
+        trans = sum(self._hist_entropy(t[:, i], -0.1, 0.1) for i in range(3)) / 3
+        # Gram-Schmidt of the two 3-vectors (columns x, y, x cross y), as roma.special_gramschmidt
+        x = torch.nn.functional.normalize(hp[:, 3:6], dim=-1)
+        y = hp[:, 6:9]
+        y = torch.nn.functional.normalize(y - (x * y).sum(-1, keepdim=True) * x, dim=-1)
+        R = torch.stack([x, y, torch.linalg.cross(x, y)], -1)
+        v = _rotvec(R)
+        r = v.norm(dim=-1)
+        theta = torch.acos(v[:, 2] / r)
+        phi = torch.sign(v[:, 1]) * torch.acos(v[:, 0] / v[:, :2].norm(dim=-1))
+        sph = torch.stack([r, theta, phi], -1)
+        limits = [(0.0, math.pi), (0.0, math.pi), (-math.pi, math.pi)]
+        rot = sum(self._hist_entropy(sph[:, i], *limits[i]) for i in range(3)) / 3
+        return trans.to(self.hand_pose.dtype), rot.to(self.hand_pose.dtype)
+
     # reference hand_model.py:989-1040
     def self_penetration(self):
         return ops.self_pen(self._sphere_centers, self._hand)
@@ -248,6 +286,36 @@ class HandModel:
     @property
     def n_actutated_joints(self):  # (sic) reference hand_model.py:779-781
         return self.n_dofs
+
+
+def _rotvec(R):
+    """Rotation vectors of rotation matrices (B,3,3): through the unit quaternion, the largest of its four components
+    taken from the diagonal (numerically safe at every angle), then angle = 2 atan2(|v|, w) with w >= 0."""
+    tr = R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2]
+    d = torch.stack([R[:, 0, 0], R[:, 1, 1], R[:, 2, 2], tr], -1)
+    k = d.argmax(-1)
+    q = torch.empty(R.shape[0], 4, dtype=R.dtype, device=R.device)  # (x, y, z, w)
+    for i in range(3):  # the largest component is x, y or z
+        j, l = (i + 1) % 3, (i + 2) % 3
+        m = k == i
+        qi = torch.sqrt((1 + 2 * R[:, i, i] - tr).clamp_min(0)) / 2
+        s = 4 * qi
+        qq = torch.empty_like(q)
+        qq[:, i] = qi
+        qq[:, j] = (R[:, j, i] + R[:, i, j]) / s
+        qq[:, l] = (R[:, l, i] + R[:, i, l]) / s
+        qq[:, 3] = (R[:, l, j] - R[:, j, l]) / s
+        q = torch.where(m.unsqueeze(-1), qq, q)
+    m = k == 3
+    w = torch.sqrt((1 + tr).clamp_min(0)) / 2
+    s = 4 * w
+    qq = torch.stack([(R[:, 2, 1] - R[:, 1, 2]) / s, (R[:, 0, 2] - R[:, 2, 0]) / s, (R[:, 1, 0] - R[:, 0, 1]) / s, w], -1)
+    q = torch.where(m.unsqueeze(-1), qq, q)
+    q = torch.where(q[:, 3:4] < 0, -q, q)
+    vn = q[:, :3].norm(dim=-1, keepdim=True)
+    ang = 2 * torch.atan2(vn, q[:, 3:4])
+    scale = torch.where(vn > 1e-12, ang / vn.clamp_min(1e-300), torch.full_like(vn, 2.0))
+    return q[:, :3] * scale
 
 
 def get_hand_model(hand_name: str, device="cuda", asset_dir=None, grasp_type=None, **kwargs) -> HandModel:

@@ -12,7 +12,8 @@ import torch
 
 from ... import ops
 from ..solver.qp_solver import SQPLsqSolver
-from .span import OverallFrictionConeSpanMetric
+from ..solver.scipy_solver import ScipyLsqSolver
+from .span import EucledianGraspSpanMetric, OverallFrictionConeSpanMetric, _is_exact
 
 
 def _require_hip_solver(solver_cls):
@@ -33,12 +34,44 @@ class SpanMetricWrapper(torch.nn.Module):
         self._initialized = False
         self.metric_kwargs = dict(metric_kwargs)
         self.last_n_iter = None
+        self._exact = None
+
+    @property
+    def exact(self) -> bool:
+        """True for the exact metrics (solver_cls=ScipyLsqSolver: GRASPQP_SCIPY / GRASPQP_EUCLIDIAN_SCIPY, registry.py:108-131),
+        which are evaluated by the metric module and have no gradient; False for the PDIPM overall metric of the loop."""
+        self._resolve()
+        return self._exact is not None
+
+    def _resolve(self):
+        if self._initialized:
+            return
+        if _is_exact(self.metric_kwargs.get("solver_cls")):
+            # the reference's lazy construction (registry.py:44-64): max_limit is taken out, everything else goes to
+            # from_dim, which keeps friction / n_cone_vecs and warns about the rest
+            kw = dict(self.metric_kwargs)
+            max_limit = kw.pop("max_limit", None)
+            if not (isinstance(self.metric, type) and issubclass(self.metric, (OverallFrictionConeSpanMetric, EucledianGraspSpanMetric))):
+                raise NotImplementedError(f"SpanMetricWrapper: metric {self.metric} has no exact HIP form")
+            self._exact = self.metric.from_dim(1, 6, **kw)
+            if max_limit is not None:
+                self._exact._max_limit_value = max_limit
+            self._initialized = True
+            return
+        self._exact = None
+        self.fc_config()
 
     def forward(self, contact_pts, contact_normals, cog=None, contact_threshold: float = 0.0, torque_weight: float = 5.0,
                 **kwargs):
         svd_gain = kwargs.pop("svd_gain", 0.1)
         values_gain = kwargs.pop("values_gain", 2.0)
         with_solution = kwargs.pop("with_solution", False)
+        if self.exact:  # registry.py:66-89: E = values_gain (mean_i res_i + 0.01) exp(-svd_gain svd)
+            res = self._exact(contact_pts, contact_normals, cog, contact_threshold=contact_threshold,
+                              return_solution=with_solution, torque_weight=torque_weight)
+            values, svd_scales = res[0], res[2]
+            e = values_gain * (values.mean(-1) + 1e-2) * (-svd_gain * svd_scales.mean(-1)).exp()
+            return (e, res[3]) if with_solution else e
         e, xs = ops.fc_energy(contact_pts, contact_normals, cog, **self.fc_config(svd_gain, values_gain, torque_weight))
         if with_solution:
             return e, xs
@@ -48,6 +81,7 @@ class SpanMetricWrapper(torch.nn.Module):
         """Keyword arguments of ``ops.fc_energy`` for this wrapper's metric_kwargs (resolved on first use, like the
         reference's lazy metric construction, registry.py:44-52)."""
         if not self._initialized:
+            self._exact = None
             self._max_limit = self.metric_kwargs.pop("max_limit", None)
             self._friction = self.metric_kwargs.pop("friction", None)
             self._n_cone = self.metric_kwargs.pop("n_cone_vecs", 4)

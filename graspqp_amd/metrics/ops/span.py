@@ -3,12 +3,22 @@
 ``OverallFrictionConeSpanMetric`` here is a thin module over the fused HIP op ``ops.fc_energy`` pieces: the
 friction cone, grasp matrix, box-QP and svd scale all run in the kernels of csrc/fc.hip + csrc/qp*.hip.
 ``forward`` returns ``(res (B,1), basis (B,1,6), svd_scales (B,1)[, values (B,n)])`` like the reference.
+
+With ``solver_cls=ScipyLsqSolver`` the metric is solved exactly instead (the reference's GRASPQP_SCIPY,
+registry.py:108-118): one launch of ``ops.span_exact`` builds F and solves the bounded least squares to optimality.
+``EucledianFrictionConeSpanMetric`` (the reference's spelling, span.py:94-231) is the 12-direction Euclidean span metric,
+exact only (GRASPQP_EUCLIDIAN_SCIPY).  The exact metrics have no gradient.
 """
 
 import torch
 
 from ... import ops
 from ..solver.qp_solver import SQPLsqSolver
+from ..solver.scipy_solver import ScipyLsqSolver
+
+
+def _is_exact(solver_cls):
+    return isinstance(solver_cls, type) and issubclass(solver_cls, ScipyLsqSolver)
 
 
 class OverallFrictionConeSpanMetric(torch.nn.Module):
@@ -19,10 +29,11 @@ class OverallFrictionConeSpanMetric(torch.nn.Module):
         self._mu = friction if friction is not None else 0.2
         self.n_cone_vecs = n_cone_vecs
         self._max_limit_value = 50  # span.py:28 default; SpanMetricWrapper overrides it
-        if not (isinstance(solver_cls, type) and issubclass(solver_cls, SQPLsqSolver)):
+        if not (isinstance(solver_cls, type) and issubclass(solver_cls, SQPLsqSolver)) and not _is_exact(solver_cls):
             raise NotImplementedError(
                 f"solver_cls={getattr(solver_cls, '__name__', solver_cls)!r}: the QP is solved inside the HIP force-closure "
-                "kernels; only graspqp_amd.metrics.SQPLsqSolver (or a subclass) can be honoured (reference span.py:23-37)")
+                "kernels; only graspqp_amd.metrics.SQPLsqSolver or ScipyLsqSolver (or subclasses) can be honoured "
+                "(reference span.py:23-37)")
         self._solver_cls = solver_cls
         self._cache = {}
 
@@ -39,6 +50,14 @@ class OverallFrictionConeSpanMetric(torch.nn.Module):
     def forward(self, contact_pts, contact_normals, cog=None, contact_threshold=0.0, reg=0.0, env_ids=None,
                 return_solution=True, torque_weight=5):
         B = contact_pts.shape[0]
+        if _is_exact(self._solver_cls):  # span.py:365-371: b = 0, bounds [1, max_limit + 1]
+            value, xs, svd, status = ops.span_exact(contact_pts, contact_normals, cog, self.n_cone_vecs, self._mu,
+                                                    torque_weight, 1, 1.0, float(self._max_limit_value) + 1.0)
+            self._cache["status"] = status
+            basis = torch.zeros(B, 1, 6, device=contact_pts.device)
+            if not return_solution:
+                return value, basis, svd.unsqueeze(-1)
+            return value, basis, svd.unsqueeze(-1), xs.squeeze(1)
         # values_gain=1, eps_add folded out: ask the fused op for val and svd separately
         e, xs, val, svd = _fc_parts(contact_pts, contact_normals, cog, self._mu, self.n_cone_vecs, torque_weight,
                                     self._max_limit_value)
@@ -93,3 +112,68 @@ class _FcParts(torch.autograd.Function):
 
 def _fc_parts(cp, cn, cog, mu, k, tw, max_limit):
     return _FcParts.apply(cp, cn, cog, mu, k, tw, max_limit)
+
+
+class EucledianGraspSpanMetric(torch.nn.Module):
+    """Euclidean span metric (reference span.py:94-122): for each of the 2 x 6 directions +-e_i of wrench space, the
+    least-squares residual 1/2 |F x - (+-e_i)|^2 over 0 <= x <= max_limit, solved exactly.  This base class uses the
+    contact normals themselves as the force columns (no friction cone); ``EucledianFrictionConeSpanMetric`` adds the
+    cone.  ``forward`` returns ``(res (B,12), basis (B,12,6), svd_scales (B,1)[, values (B,12,n)])``."""
+
+    n_basis_vectors = 12
+
+    def __init__(self, solver_cls=ScipyLsqSolver):
+        super().__init__()
+        if not _is_exact(solver_cls):
+            raise NotImplementedError(
+                f"solver_cls={getattr(solver_cls, '__name__', solver_cls)!r}: graspqp_amd evaluates the Euclidean span metric "
+                "exactly only; pass graspqp_amd.metrics.ScipyLsqSolver (reference registry.py:120-131)")
+        self._solver_cls = solver_cls
+        self._max_limit_value = 50  # span.py:28 default; SpanMetricWrapper overrides it
+        self._mu, self.n_cone_vecs = 0.0, 1  # columns = the normals (span.py:62-63)
+        self._cache = {}
+
+    @classmethod
+    def from_dim(cls, num_wrenches, wrench_dim, batch_size=1, device="cuda", solver_cls=ScipyLsqSolver, **kwargs):
+        if len(kwargs) > 0:
+            print("WARNING: Unknown kwargs", kwargs.keys())
+        if wrench_dim != 6:
+            raise NotImplementedError("graspqp_amd span metric supports 3-D contacts (wrench_dim=6) only")
+        return cls(solver_cls=solver_cls)
+
+    def _basis(self, B, device):
+        eye = torch.eye(6, device=device)
+        return torch.cat([eye, -eye]).unsqueeze(0).expand(B, -1, -1).contiguous()
+
+    def forward(self, contact_pts, contact_normals, cog=None, contact_threshold=0.0, reg=0.0, env_ids=None,
+                return_solution=True, torque_weight=5):
+        B = contact_pts.shape[0]
+        value, xs, svd, status = ops.span_exact(contact_pts, contact_normals, cog, self.n_cone_vecs, self._mu, torque_weight,
+                                                12, 0.0, float(self._max_limit_value))
+        self._cache["status"] = status
+        basis = self._basis(B, contact_pts.device)
+        if not return_solution:
+            return value, basis, svd.unsqueeze(-1)
+        return value, basis, svd.unsqueeze(-1), xs
+
+
+class EucledianFrictionConeSpanMetric(EucledianGraspSpanMetric):
+    """The Euclidean span metric on the friction-cone grasp matrix (reference span.py:125-231), the metric of
+    GRASPQP_EUCLIDIAN_SCIPY and scripts/vis/visualize_result.py:835-852."""
+
+    def __init__(self, solver_cls=ScipyLsqSolver, friction=0.2, n_cone_vecs=4):
+        super().__init__(solver_cls=solver_cls)
+        self._mu = friction if friction is not None else 0.2
+        self.n_cone_vecs = n_cone_vecs
+
+    @classmethod
+    def from_dim(cls, num_wrenches, wrench_dim, batch_size=1, device="cuda", solver_cls=ScipyLsqSolver, **kwargs):
+        # span.py:146-168: friction / n_cone_vecs are taken, anything else (e.g. registry.py's nested solver_kwargs=) is
+        # warned about and ignored
+        friction = kwargs.pop("friction", 0.2)
+        n_cone_vecs = kwargs.pop("n_cone_vecs", 4)
+        if len(kwargs) > 0:
+            print("WARNING: Unknown kwargs", kwargs.keys())
+        if wrench_dim != 6:
+            raise NotImplementedError("graspqp_amd span metric supports 3-D contacts (wrench_dim=6) only")
+        return cls(solver_cls=solver_cls, friction=friction, n_cone_vecs=n_cone_vecs)

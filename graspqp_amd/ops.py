@@ -602,6 +602,75 @@ def fc_energy(contact_pts, contact_normals, cog, return_n_iter=False, **cfg):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# exact grasp-quality metrics: bounded least squares to optimality (csrc/exact.hip).  No autograd: the outputs are
+# values of a finished grasp set, as the reference's numpy-solved ones are.
+# ----------------------------------------------------------------------------------------------------------
+LSQ_EXACT_MAX_ITER = 512  # free-set solves per problem (scipy's BVLS needed <= 39 at nz = 96 on span problems)
+
+
+@_custom_op("graspqp_amd::lsq_box_exact", mutates_args=(), device_types="cuda")
+def _lsq_box_exact_op(A: Tensor, b: Tensor, lower: float, upper: float, max_iter: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """argmin 1/2 |A x - b|^2, lower <= x <= upper, exactly (scipy_solver.py:61-131) -> (x (B,nz), cost (B), status (B))."""
+    dt = A.dtype if A.dtype in (torch.float32, torch.float64) else torch.float32
+    Ac, bc = _c(A, dt), _c(b, dt)
+    B, m, nz = Ac.shape
+    x = torch.empty(B, nz, device=Ac.device, dtype=dt)
+    cost = torch.empty(B, device=Ac.device, dtype=dt)
+    status = torch.empty(B, device=Ac.device, dtype=torch.int32)
+    _C.call("gq_lsq_exact_forward", _C.ptr(Ac), _C.ptr(bc), int(dt == torch.float64), ctypes.c_int64(B), m, nz,
+            float(lower), float(upper), int(max_iter), _C.ptr(x), _C.ptr(cost), _C.i32(status), _C.stream_ptr())
+    return x, cost, status
+
+
+@_lsq_box_exact_op.register_fake
+def _(A, b, lower, upper, max_iter):
+    B, m, nz = A.shape
+    dt = A.dtype if A.dtype in (torch.float32, torch.float64) else torch.float32
+    return A.new_empty(B, nz, dtype=dt), A.new_empty(B, dtype=dt), A.new_empty(B, dtype=torch.int32)
+
+
+def lsq_box_exact(A, b, lower, upper, max_iter=LSQ_EXACT_MAX_ITER):
+    """Batched exact bounded least squares: A (B,m,nz) with m <= 8, nz <= 128, b (B,m), scalar bounds; fp32 or fp64 in,
+    fp64 arithmetic, outputs in the input dtype.  status >= 0: solves used, -1: iteration cap, -2: non-finite input."""
+    return _Eager.lsq_box_exact(A.detach(), b.detach(), float(lower), float(upper), int(max_iter))
+
+
+@_custom_op("graspqp_amd::span_exact", mutates_args=(), device_types="cuda")
+def _span_exact_op(contact_pts: Tensor, contact_normals: Tensor, cog: Tensor, n_cone_vecs: int, friction: float,
+                   torque_weight: float, n_basis: int, lower: float, upper: float,
+                   max_iter: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Span metric solved exactly, F built once per row on the device -> (value (B,nb), x_sum (B,nb,n), svd (B),
+    status (B,nb)); n_basis 1: overall (span.py:313-415), 12: Euclidean (span.py:94-231)."""
+    cp, cn, cg = _c(contact_pts), _c(contact_normals), _c(cog)
+    B, n, _ = cp.shape
+    dev = cp.device
+    value = torch.empty(B, n_basis, device=dev)
+    x_sum = torch.empty(B, n_basis, n, device=dev)
+    svd = torch.empty(B, device=dev)
+    status = torch.empty(B, n_basis, device=dev, dtype=torch.int32)
+    _C.call("gq_span_exact_forward", _C.f32(cp), _C.f32(cn), _C.f32(cg), ctypes.c_int64(B), n, int(n_cone_vecs),
+            float(friction), float(torque_weight), int(n_basis), float(lower), float(upper), int(max_iter), _C.f32(value),
+            _C.f32(x_sum), _C.f32(svd), _C.i32(status), _C.stream_ptr())
+    return value, x_sum, svd, status
+
+
+@_span_exact_op.register_fake
+def _(contact_pts, contact_normals, cog, n_cone_vecs, friction, torque_weight, n_basis, lower, upper, max_iter):
+    B, n, _ = contact_pts.shape
+    f = dict(dtype=torch.float32)
+    return (contact_pts.new_empty(B, n_basis, **f), contact_pts.new_empty(B, n_basis, n, **f), contact_pts.new_empty(B, **f),
+            contact_pts.new_empty(B, n_basis, dtype=torch.int32))
+
+
+def span_exact(contact_pts, contact_normals, cog, n_cone_vecs=4, friction=0.2, torque_weight=5.0, n_basis=1, lower=1.0,
+               upper=51.0, max_iter=LSQ_EXACT_MAX_ITER):
+    """-> (value, x_sum, svd, status); non-differentiable."""
+    return _Eager.span_exact(contact_pts.detach(), contact_normals.detach(), cog.detach(), int(n_cone_vecs),
+                             float(friction), float(torque_weight), int(n_basis), float(lower), float(upper),
+                             int(max_iter))
+
+
+# ----------------------------------------------------------------------------------------------------------
 # the reference's other force-closure energies: dexgrasp (||G'n||^2) and TDG (grasp-wrench-space directions)
 # ----------------------------------------------------------------------------------------------------------
 @_custom_op("graspqp_amd::dexgrasp_energy", mutates_args=(), device_types="cuda")
@@ -1169,6 +1238,8 @@ _eager("lsq_box_qp", _lsq_box_qp_op, _lsq_bwd, _lsq_setup)
 _eager("lsq_box_qp_backward", _lsq_box_qp_bwd_op)
 _eager("fc_energy", _fc_energy_op, _fc_bwd, _fc_setup)
 _eager("fc_energy_backward", _fc_energy_bwd_op)
+_eager("lsq_box_exact", _lsq_box_exact_op)
+_eager("span_exact", _span_exact_op)
 _eager("dexgrasp_energy", _dexgrasp_op, _alt_bwd, _alt_setup)
 _eager("tdg_energy", _tdg_op, _alt_bwd, _alt_setup)
 _eager("fk_contacts", _fk_op, _fk_bwd, _fk_setup)

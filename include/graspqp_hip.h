@@ -121,6 +121,31 @@ int gq_fc_step(const float* dist_sq, const int32_t* sign, const float* obj_dir, 
                float* g_hand_normals, float* e_fc, float* x_sum, int32_t* n_iter, void* workspace,
                size_t workspace_bytes, void* stream);
 
+/* ---- exact grasp-quality metrics: scipy.optimize.lsq_linear behind ScipyLsqSolver -------------------------------------
+ * reference: metrics/solver/scipy_solver.py:61-131 (one lsq_linear per problem), metrics/ops/registry.py:108-131
+ * (GRASPQP_SCIPY, GRASPQP_EUCLIDIAN_SCIPY), metrics/ops/span.py:94-231 (Euclidean), 313-415 (overall);
+ * scripts/vis/visualize_result.py:835-852 scores grasps with the Euclidean one.
+ * gq_lsq_exact_forward: x = argmin 1/2 |A x - b|^2 s.t. lower <= x <= upper, solved TO OPTIMALITY (BVLS, fp64 arithmetic)
+ *   for each of `batch` problems; A (B,m,nz), b (B,m), m <= 8, nz <= 128, scalar finite bounds lower <= upper.
+ *   fp64 = 0: A, b, x (B,nz), cost (B) are float32; fp64 = 1: float64.  cost = 1/2 |A x - b|^2 (scipy's res.cost).
+ *   status (B) int32: free-set solves used (>= 0), -1 if max_iter was reached (the last iterate is returned), -2 if
+ *   A or b holds a non-finite value (x and cost NaN).  Bitwise reproducible; no workspace.
+ * gq_span_exact_forward: the metric's grasp matrix F (6, n_contact * n_cone) of every row, built as gq_fc_forward does,
+ *   and n_basis problems per row on it: n_basis = 1 (overall: b = 0), n_basis = 12 (Euclidean: b = +e_i, then -e_i).
+ *   value (B,n_basis) = cost, x_sum (B,n_basis,n_contact) per-contact sums of x (or NULL), svd (B) = det(F F')^(1/12),
+ *   status (B,n_basis) as above.  The overall metric uses [1, max_limit + 1], the Euclidean one [0, max_limit].
+ * The *_check functions validate the sizes and bounds without a GPU (the forward entry points call them first).      */
+int gq_lsq_exact_check(int64_t batch, int m, int nz, double lower, double upper, int max_iter);
+int gq_lsq_exact_forward(const void* A, const void* b, int fp64, int64_t batch, int m, int nz, double lower,
+                         double upper, int max_iter, void* x, void* cost, int32_t* status, void* stream);
+int gq_span_exact_check(int64_t batch, int n_contact, int n_cone, int n_basis, double lower, double upper,
+                        int max_iter);
+int gq_span_exact_forward(const float* contact_pts, const float* contact_normals, const float* cog, int64_t batch,
+                          int n_contact, int n_cone, float friction, float torque_weight, int n_basis, double lower,
+                          double upper, int max_iter, float* value /* (B,n_basis) */,
+                          float* x_sum /* (B,n_basis,n_contact) or NULL */, float* svd /* (B) */,
+                          int32_t* status /* (B,n_basis) */, void* stream);
+
 /* ---- the reference's other force-closure energies (scripts/fit.py:343-347, --energy_type dexgrasp | tdg) -------------
  * Same inputs as the graspqp energy: contact points, OBJECT normals at the contacts (constants), cog (B,3).  One launch
  * gives the energy and its gradient w.r.t. the contact points: g_contact_pts (+)= upstream * dE/dp with upstream =
