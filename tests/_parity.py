@@ -3,7 +3,10 @@
 E_fc: <= 1e-4 rel at the median and, at p99 / max, <= 2x the error the ORACLE ITSELF makes when it runs the same algorithm
 in fp32 instead of fp64 on the same inputs (the PDIPM iterate path has an fp32 noise tail of 1e-4 .. 1e-3 on ~1 % of the
 rows; measured per configuration in profiles/r03_parity_report.json).  Errors below the contract's per-row figure of 1e-4
-need no such excuse, hence the floor.  Total energy: <= 1e-4 rel per row with the same noise allowance.
+need no such excuse, hence the floor.  Total energy: <= 1e-4 rel per row with the same noise allowance.  Whatever the
+oracle's noise, p99 and max stay under an absolute ceiling (5e-3 by default; the call sites measured <= ~4e-4 over up to
+5 000 rows, profiles/r03_parity_report.json): one noisy oracle row must not let any HIP error through on another row.
+A caller that needs a higher ceiling states why.
 """
 import numpy as np
 
@@ -13,12 +16,13 @@ def rel_err(a, b, floor=1e-12):
     return np.abs(a - b) / np.maximum(np.abs(b), floor)
 
 
-def assert_tail_within_fp32_noise(rel_hip, rel_noise, what, median_cap=1e-4, floor=1e-4):
+def assert_tail_within_fp32_noise(rel_hip, rel_noise, what, median_cap=1e-4, floor=1e-4, ceiling=5e-3):
     rel_hip, rel_noise = np.asarray(rel_hip), np.asarray(rel_noise)
     assert np.median(rel_hip) < median_cap, f"{what}: median {np.median(rel_hip):.3g}"
     for q in (99, 100):
         h, o = np.percentile(rel_hip, q), np.percentile(rel_noise, q)
         assert h <= max(2.0 * o, floor), f"{what}: p{q} {h:.3g} > 2 x oracle fp32 noise {o:.3g} (floor {floor:g})"
+        assert h <= ceiling, f"{what}: p{q} {h:.3g} > absolute ceiling {ceiling:g}"
 
 
 def oracle_fc_fp32_noise(ospan, cpts, onrm, cog, k, e64=None):
