@@ -14,13 +14,13 @@ SIG="$(echo "$FLAGS ${GQ_EXTRA_FLAGS:-}" | md5sum | cut -d' ' -f1)"
 echo "$SIG" > "$OUT/.flags"
 deps() {  # headers each translation unit includes
   case "$1" in
-    qp_lr|fcstep) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h fc_dev.h fcstep_dev.h" ;;
-    qp_dense) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h" ;;
+    qp_lr) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h" ;;
+    fcstep) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h fc_dev.h fcstep_dev.h" ;;
+    qp|qp_dense|qp_nz*) echo "common.h qp_core.h qp_kernels.h wave.h" ;;
     stage) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h fc_dev.h fcstep_dev.h pen_dev.h tri.h kin_dev.h metric_dev.h" ;;
-    qp|qp_nz*) echo "common.h qp_core.h qp_kernels.h" ;;
     sdf) echo "common.h tri.h pen_dev.h sdf_dev.h wave.h" ;;
     bvh) echo "common.h tri.h" ;;
-    fc) echo "common.h fc_dev.h wave.h" ;;
+    fc) echo "common.h fc_dev.h qp_core.h wave.h" ;;
     loop) echo "common.h fc_dev.h loop_dev.h wave.h" ;;
     metric) echo "common.h wave.h metric_dev.h" ;;
     init) echo "common.h wave.h" ;;

@@ -4,6 +4,7 @@
 // and its gradient with respect to the contact points (contact normals come from the object SDF and are
 // constants for autograd, object_model.py:246).
 #include "fc_dev.h"
+#include "qp_core.h"
 
 int gq_lsq_boxqp_iterate_(const float* A, float lower_s, float upper_s, int64_t batch, int m, int nz, float ridge,
                           float eps, int max_iter, int32_t* n_iter, void* workspace, size_t workspace_bytes,
@@ -52,19 +53,7 @@ struct GqFcArgs {
 __global__ __launch_bounds__(GQ_WAVE) void gq_fc_energy_kernel(GqFcArgs g) {
   const int row = blockIdx.x, lane = gq_lane();
   const int nz = g.n * g.k;
-  // best iterate of this row among iterations 0..k* (qpth returns the per-row best, not the last)
-  int bi = 0;
-  {
-    const int ks = g.kstar[0];
-    float bst = 0.0f;
-    for (int it = 0; it <= ks; ++it) {
-      const float rs = g.resid[(size_t)row * g.max_iter + it];
-      if (it == 0 || rs < bst) {
-        bst = rs;
-        bi = it;
-      }
-    }
-  }
+  const int bi = gq_qp_best_iter(g.resid, row, g.max_iter, g.kstar[0], lane);
   const float* sn = g.snap + (((size_t)row * g.max_iter + bi) * 5) * nz;
   double gr[21];
 #pragma unroll

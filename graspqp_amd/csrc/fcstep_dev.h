@@ -105,7 +105,7 @@ __device__ __forceinline__ void gq_fc_head_body(const GqFcStepArgs& g, int row, 
   q.resid = g.resid;
   q.mu = g.mu_tab;
   q.snap = g.snap;
-  gq_qp_lr_iterate<6, NC>(q, row, lane, S, live, p, hu, hl, hist_resid, hist_mu);
+  gq_qp_lr_iterate(q, row, lane, S, live, p, hu, hl, hist_resid, hist_mu);
 }
 
 // qpth's batch-global stop rule without a launch of its own, for any batch size (max_iter <= 16).  Called by every

@@ -2,12 +2,15 @@
 //
 // Forward = qpth-style primal-dual interior point with batch-global stopping, split in three launches
 // so that no wave ever waits for another:
-//   gq_qp_iter_kernel    every row runs all max_iter iterations, recording resid/mu per iteration and a
-//                        snapshot (x, lam, slack) at each iteration that improves the row's best residual
-//   gq_qp_stop_kernel    one block replays qpth's batch-global rule (notImproved == 3 | max best < eps |
+//   iterations           every row runs all max_iter iterations, recording resid/mu per iteration and a snapshot
+//                        (x, lam, slack) at each iteration that improves the row's best residual.  Kernel by form of
+//                        Q: A'A + ridge I -> gq_qp_lr_iter_kernel (qp_lr.h), dense 65..128 -> gq_qp_dense_iter_kernel
+//                        (qp_dense.hip), both on the shared loop qp_kernels.h::gq_qp_lr_iterate; dense nz <= 64 ->
+//                        gq_qp_iter_kernel<NZ> (qp_kernels.h, qp_nz*.hip)
+//   gq_qp_stop_*_kernel  one block replays qpth's batch-global rule (notImproved == 3 | max best < eps |
 //                        min mu > 1e32) on the (B, max_iter) residual table -> stop iteration k*
 //   gq_qp_select_kernel  each row returns its best snapshot among iterations 0..k*
-// Backward = one more reduced-KKT solve at the returned point (qpth QPFunction.backward).
+// Backward = one more reduced-KKT solve at the returned point (qpth QPFunction.backward, qp_kernels.h::gq_qp_bwd_row).
 #include "qp_kernels.h"
 
 // ---- batch-global stopping rule (single block) -----------------------------------------------------------
@@ -54,22 +57,14 @@ __global__ __launch_bounds__(256) void gq_qp_stop_kernel(const float* __restrict
       }
       __syncthreads();
     }
-    if (tid == 0) {
-      if (it == 0) not_improved = 0;
-      else not_improved = s_any ? 0 : not_improved + 1;
-      s_stop = (not_improved == not_improved_lim) || (s_red[0] < eps) || (s_red2[0] > 1e32f);
-    }
+    if (tid == 0) s_stop = gq_qp_stop_now(it, s_any != 0, s_red[0], s_red2[0], eps, not_improved_lim, not_improved);
     __syncthreads();
     if (s_stop) {
       stop_at = it;
       break;
     }
   }
-  if (tid == 0) {
-    kstar[0] = stop_at;      // last iteration whose record counts
-    kstar[1] = stop_at + 1;  // qpth-style iteration count
-    if (n_iter_out) *n_iter_out = stop_at + 1;
-  }
+  if (tid == 0) gq_qp_write_kstar(kstar, n_iter_out, stop_at);
 }
 
 // same rule, one wavefront (B <= 1024): the (B, max_iter) residual / mu tables are staged in LDS with all loads in
@@ -80,8 +75,7 @@ __global__ __launch_bounds__(256) void gq_qp_stop_kernel(const float* __restrict
 __global__ __launch_bounds__(GQ_WAVE) void gq_qp_stop_wave_kernel(const float* __restrict__ resid,
                                                                   const float* __restrict__ mu, int B, int max_iter,
                                                                   float eps, int not_improved_lim,
-                                                                  float* __restrict__ runmin, int* __restrict__ kstar,
-                                                                  int* __restrict__ n_iter_out) {
+                                                                  int* __restrict__ kstar, int* __restrict__ n_iter_out) {
   __shared__ float s_res[GQ_STOP_MAXB * GQ_STOP_MAXIT];
   __shared__ float s_mu[GQ_STOP_MAXB * GQ_STOP_MAXIT];
   const int lane = gq_lane();
@@ -118,17 +112,12 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_qp_stop_wave_kernel(const float* _
     const bool any_w = __ballot(any) != 0ull;
     const float mxw = -gq_dpp_nanmin(-mx);  // NaN-propagating max
     const float mnw = gq_dpp_nanmin(mn);
-    not_improved = (it == 0) ? 0 : (any_w ? 0 : not_improved + 1);
-    if ((not_improved == not_improved_lim) || (mxw < eps) || (mnw > 1e32f)) {
+    if (gq_qp_stop_now(it, any_w, mxw, mnw, eps, not_improved_lim, not_improved)) {
       stop_at = it;
       break;
     }
   }
-  if (lane == 0) {
-    kstar[0] = stop_at;
-    kstar[1] = stop_at + 1;
-    if (n_iter_out) *n_iter_out = stop_at + 1;
-  }
+  if (lane == 0) gq_qp_write_kstar(kstar, n_iter_out, stop_at);
 }
 
 // same rule for any number of rows, one block of 1024 threads.  The per-row running best does not depend on where the
@@ -219,15 +208,12 @@ __global__ __launch_bounds__(1024) void gq_qp_stop_tiled_kernel(const float* __r
         bmx = gq_nanmax(bmx, s_mx[w][it]);
         bmn = gq_nanmin(bmn, s_mn[w][it]);
       }
-      not_improved = (it == 0) ? 0 : (((any >> it) & 1u) ? 0 : not_improved + 1);
-      if ((not_improved == not_improved_lim) || (bmx < eps) || (bmn > 1e32f)) {
+      if (gq_qp_stop_now(it, ((any >> it) & 1u) != 0u, bmx, bmn, eps, not_improved_lim, not_improved)) {
         stop_at = it;
         break;
       }
     }
-    kstar[0] = stop_at;
-    kstar[1] = stop_at + 1;
-    if (n_iter_out) *n_iter_out = stop_at + 1;
+    gq_qp_write_kstar(kstar, n_iter_out, stop_at);
   }
 }
 
@@ -239,16 +225,7 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_qp_select_kernel(const float* __re
                                                                int* __restrict__ best_iter) {
   const int row = blockIdx.x;
   const int lane = gq_lane();
-  const int ks = kstar[0];
-  float bst = 0.0f;
-  int bi = 0;
-  for (int it = 0; it <= ks; ++it) {
-    const float rs = resid[(size_t)row * max_iter + it];
-    if (it == 0 || rs < bst) {
-      bst = rs;
-      bi = it;
-    }
-  }
+  const int bi = gq_qp_best_iter(resid, row, max_iter, kstar[0], lane);
   for (int k = lane; k < nz; k += GQ_WAVE) {
     const float* s = snap + (((size_t)row * max_iter + bi) * 5) * nz + k;
     x[(size_t)row * nz + k] = s[0];
@@ -292,8 +269,8 @@ static GqQpWs gq_qp_carve(void* base, int B, int nz, int max_iter) {
 static void gq_qp_stop_dispatch(const float* resid, const float* mu, int B, int max_iter, float eps, int lim,
                                 float* runmin, int* kstar, int32_t* n_iter, hipStream_t st) {
   if (B <= GQ_STOP_MAXB && max_iter <= GQ_STOP_MAXIT)
-    hipLaunchKernelGGL(gq_qp_stop_wave_kernel, dim3(1), dim3(GQ_WAVE), 0, st, resid, mu, B, max_iter, eps, lim, runmin,
-                       kstar, n_iter);
+    hipLaunchKernelGGL(gq_qp_stop_wave_kernel, dim3(1), dim3(GQ_WAVE), 0, st, resid, mu, B, max_iter, eps, lim, kstar,
+                       n_iter);
   else if (max_iter <= GQ_STOP_MAXIT)
     hipLaunchKernelGGL(gq_qp_stop_tiled_kernel, dim3(1), dim3(1024), 0, st, resid, mu, B, max_iter, eps, lim, kstar,
                        n_iter);
@@ -305,36 +282,37 @@ static void gq_qp_stop_dispatch(const float* resid, const float* mu, int B, int 
 int gq_qp_launch_iter_dense_lds(const GqQpArgs& a, hipStream_t st);    // qp_dense.hip: dense Q, 65..128 variables
 int gq_qp_launch_bwd_dense_lds(const GqQpBwdArgs& a, hipStream_t st);
 
-static int gq_launch_iter(const GqQpArgs& a, int mode, hipStream_t st) {
-  if (mode == 0) return gq_qp_lr_launch_iter(a, st);
+// A set: the low-rank form Q = A'A + ridge I; otherwise a dense Q
+static int gq_launch_iter(const GqQpArgs& a, hipStream_t st) {
+  if (a.A) return gq_qp_lr_launch_iter(a, st);
   if (a.nz > 64) return gq_qp_launch_iter_dense_lds(a, st);
-  if (a.nz <= 16) return gq_qp_launch_iter_16(a, mode, st);
-  if (a.nz <= 32) return gq_qp_launch_iter_32(a, mode, st);
-  if (a.nz <= 48) return gq_qp_launch_iter_48(a, mode, st);
-  return gq_qp_launch_iter_64(a, mode, st);
+  if (a.nz <= 16) return GqQpRegLaunch<16>::iter(a, st);
+  if (a.nz <= 32) return GqQpRegLaunch<32>::iter(a, st);
+  if (a.nz <= 48) return GqQpRegLaunch<48>::iter(a, st);
+  return GqQpRegLaunch<64>::iter(a, st);
 }
-static int gq_launch_bwd(const GqQpBwdArgs& a, int mode, hipStream_t st) {
-  if (mode == 0) return gq_qp_lr_launch_bwd(a, st);
+static int gq_launch_bwd(const GqQpBwdArgs& a, hipStream_t st) {
+  if (a.A) return gq_qp_lr_launch_bwd(a, st);
   if (a.nz > 64) return gq_qp_launch_bwd_dense_lds(a, st);
-  if (a.nz <= 16) return gq_qp_launch_bwd_16(a, mode, st);
-  if (a.nz <= 32) return gq_qp_launch_bwd_32(a, mode, st);
-  if (a.nz <= 48) return gq_qp_launch_bwd_48(a, mode, st);
-  return gq_qp_launch_bwd_64(a, mode, st);
+  if (a.nz <= 16) return GqQpRegLaunch<16>::bwd(a, st);
+  if (a.nz <= 32) return GqQpRegLaunch<32>::bwd(a, st);
+  if (a.nz <= 48) return GqQpRegLaunch<48>::bwd(a, st);
+  return GqQpRegLaunch<64>::bwd(a, st);
 }
 
 static int gq_qp_forward_common(GqQpArgs a, float eps, int not_improved_lim, float* x, float* lam, float* slack,
-                                int* best_iter, int* n_iter, void* ws, size_t ws_bytes, hipStream_t st, int mode) {
+                                int* best_iter, int* n_iter, void* ws, size_t ws_bytes, hipStream_t st) {
   GQ_REQUIRE(a.B > 0 && a.nz > 0, "boxqp: empty batch (B=%d nz=%d)", a.B, a.nz);
   GQ_REQUIRE(a.nz <= 128, "boxqp: nz=%d exceeds the supported size (128)", a.nz);
   GQ_REQUIRE(a.max_iter >= 1 && a.max_iter <= 64, "boxqp: max_iter=%d out of range", a.max_iter);
-  GQ_REQUIRE(mode == 1 || (a.m >= 1 && a.m <= 8), "boxqp: m=%d must be in [1,8]", a.m);
+  GQ_REQUIRE(!a.A || (a.m >= 1 && a.m <= 8), "boxqp: m=%d must be in [1,8]", a.m);
   GQ_REQUIRE(ws, "boxqp: null workspace pointer");
   GqQpWs w = gq_qp_carve(ws, a.B, a.nz, a.max_iter);
   GQ_REQUIRE(ws_bytes >= w.total, "boxqp: workspace too small (%zu < %zu)", ws_bytes, w.total);
   a.resid = w.resid;
   a.mu = w.mu;
   a.snap = w.snap;
-  int rc = gq_launch_iter(a, mode, st);
+  int rc = gq_launch_iter(a, st);
   if (rc) return rc;
   gq_qp_stop_dispatch(w.resid, w.mu, a.B, a.max_iter, eps, not_improved_lim, w.runmin, w.kstar, n_iter, st);
   GQ_LAUNCH_CHECK();
@@ -380,7 +358,7 @@ int gq_lsq_boxqp_iterate_(const float* A, float lower_s, float upper_s, int64_t 
   a.nz = nz;
   a.max_iter = max_iter;
   int rc = gq_qp_forward_common(a, eps, 3, nullptr, nullptr, nullptr, nullptr, n_iter, workspace, workspace_bytes,
-                                (hipStream_t)stream, 0);
+                                (hipStream_t)stream);
   if (rc) return rc;
   GqQpWs w = gq_qp_carve(workspace, a.B, a.nz, a.max_iter);
   *resid = w.resid;
@@ -408,7 +386,7 @@ int gq_lsq_boxqp_backward_scaled_(const float* A, const float* lam, const float*
   a.scale_svd = scale_svd;
   a.svd_gain = svd_gain;
   a.values_gain = values_gain;
-  return gq_launch_bwd(a, 0, (hipStream_t)stream);
+  return gq_launch_bwd(a, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -437,7 +415,7 @@ int gq_lsq_boxqp_forward(const float* A, const float* b, const float* lower, con
   a.nz = nz;
   a.max_iter = max_iter;
   return gq_qp_forward_common(a, eps, not_improved_lim, x, lam, slack, best_iter, n_iter, workspace, workspace_bytes,
-                              (hipStream_t)stream, 0);
+                              (hipStream_t)stream);
 }
 
 int gq_boxqp_forward(const float* Q, const float* p, const float* lower, const float* upper, float lower_s,
@@ -457,7 +435,7 @@ int gq_boxqp_forward(const float* Q, const float* p, const float* lower, const f
   a.nz = nz;
   a.max_iter = max_iter;
   return gq_qp_forward_common(a, eps, not_improved_lim, x, lam, slack, best_iter, n_iter, workspace, workspace_bytes,
-                              (hipStream_t)stream, 1);
+                              (hipStream_t)stream);
 }
 
 // qpth's batch-global stop rule on a (B, max_iter) residual / mu table (what the forward entry points run after
@@ -485,7 +463,7 @@ int gq_lsq_boxqp_backward(const float* A, const float* lam, const float* slack, 
   a.nz = nz;
   a.dx = dx;
   a.dlam = dlam;
-  return gq_launch_bwd(a, 0, (hipStream_t)stream);
+  return gq_launch_bwd(a, (hipStream_t)stream);
 }
 
 int gq_boxqp_backward(const float* Q, const float* lam, const float* slack, const float* grad_x, int64_t batch, int nz,
@@ -502,7 +480,7 @@ int gq_boxqp_backward(const float* Q, const float* lam, const float* slack, cons
   a.nz = nz;
   a.dx = dx;
   a.dlam = dlam;
-  return gq_launch_bwd(a, 1, (hipStream_t)stream);
+  return gq_launch_bwd(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

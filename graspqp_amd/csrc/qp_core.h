@@ -1,13 +1,15 @@
-// One box-constrained QP per wavefront, entirely in registers.
+// Device building blocks of the batched box QP, one problem per wavefront:
 //
 //   min 1/2 x'Qx + p'x   s.t.  lower <= x <= upper          (G = [I; -I], h = [upper; -lower])
 //
-// Replaces qpth's batched PDIPM as driven by the reference (metrics/solver/qp_solver.py:8,101-126;
-// algorithm restated in oracle/ref_cpu/qp.py::pdipm_forward_box).  Lane i owns variable i: row i of
-// the (symmetric) KKT matrix lives in NZ VGPRs of lane i, vectors are one VGPR per lane.  The reduced
-// KKT system (Q + diag(d_u + d_l)) dx = rhs is factored by a right-looking Cholesky whose pivot row
-// is broadcast with v_readlane (no LDS): after the factorisation register k of lane i holds
-// L[max(i,k)][min(i,k)], so both triangular solves are broadcast + masked FMA sweeps as well.
+// qpth's PDIPM as driven by the reference (metrics/solver/qp_solver.py:8,101-126; algorithm restated in
+// oracle/ref_cpu/qp.py::pdipm_forward_box).
+//
+// GqChol: dense Q of nz <= 64 variables entirely in registers.  Lane i owns variable i: row i of the (symmetric) KKT
+// matrix lives in NZ VGPRs of lane i, vectors are one VGPR per lane.  The reduced KKT system (Q + diag(d_u + d_l)) dx =
+// rhs is factored by a right-looking Cholesky whose pivot row is broadcast with v_readlane (no LDS): after the
+// factorisation register k of lane i holds L[max(i,k)][min(i,k)], so both triangular solves are broadcast + masked FMA
+// sweeps as well.
 #pragma once
 #include "common.h"
 
@@ -84,17 +86,59 @@ __device__ __forceinline__ float gq_step_ratio(float v, float dv) {
   return (dv > 0.0f) ? GQ_INF : a;
 }
 
-// load row `lane` of Q = A'A + ridge*I from the lane's column of A (m <= 8 rows); idle lanes get identity rows
+// Register-resident solver (NC = 1) of the shared backward row (qp_kernels.h): the lane's row of Q and of the factor of
+// Q + diag(lam).  Rows of lanes >= nz are identity rows, so the padding decouples from the live block.
 template <int NZ>
-__device__ __forceinline__ void gq_build_q_from_cols(float (&q)[NZ], const float (&col)[8], int m, int nz, int lane,
-                                                     float ridge) {
+struct GqRegChol {
+  float q[NZ];  // row `lane` of Q
+  float a[NZ];  // factor of Q + diag(lam), GqChol storage
+  float dinv = 1.0f;
+  int lane;
+
+  // row `lane` of this problem's Q (B, nz, nz); rows and columns past nz are those of the identity
+  __device__ __forceinline__ void load(const float* Q, int row, int nz, int ln) {
+    lane = ln;
 #pragma unroll
-  for (int k = 0; k < NZ; ++k) {
-    float acc = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-      if (r < m) acc = fmaf(col[r], gq_readlane(col[r], k), acc);
-    const bool live = (lane < nz) && (k < nz);
-    q[k] = live ? acc + ((lane == k) ? ridge : 0.0f) : ((lane == k) ? 1.0f : 0.0f);
+    for (int k = 0; k < NZ; ++k)
+      q[k] = (lane < nz && k < nz) ? Q[((size_t)row * nz + lane) * nz + k] : ((lane == k) ? 1.0f : 0.0f);
   }
+  __device__ __forceinline__ void factor(const float (&lam)[1], const bool (&)[1]) {
+    GqChol<NZ>::form(a, q, lam[0], lane);
+    GqChol<NZ>::factor(a, dinv, lane);
+  }
+  __device__ __forceinline__ void solve(const float (&rhs)[1], float (&dx)[1]) const {
+    dx[0] = GqChol<NZ>::solve(a, dinv, lane, rhs[0]);
+  }
+};
+
+// ---- qpth's batch-global stop rule and per-row selection: the stop, select and fc energy kernels.  The fused
+// force-closure step (fcstep_dev.h) keeps inline copies: through these helpers its timed kernels compile differently.
+// The sequential decision after iteration it, from that iteration's batch aggregates: did any row improve its best
+// residual, the largest running best residual, the smallest mu (NaN-propagating, like torch).  not_improved carries the
+// count of iterations without improvement from one call to the next.
+__device__ __forceinline__ bool gq_qp_stop_now(int it, bool improved, float max_best, float min_mu, float eps, int lim,
+                                               int& not_improved) {
+  not_improved = (it == 0) ? 0 : (improved ? 0 : not_improved + 1);
+  return (not_improved == lim) || (max_best < eps) || (min_mu > 1e32f);
+}
+// kstar = [last iteration whose record counts, qpth-style iteration count]
+__device__ __forceinline__ void gq_qp_write_kstar(int* kstar, int32_t* n_iter, int stop_at) {
+  kstar[0] = stop_at;
+  kstar[1] = stop_at + 1;
+  if (n_iter) *n_iter = stop_at + 1;
+}
+// Best iterate of one row among iterations 0..ks (qpth returns the per-row best, not the last; a NaN never becomes best):
+// the row's residuals are fetched together (lane it holds iteration it), then scanned from registers.
+__device__ __forceinline__ int gq_qp_best_iter(const float* resid, int row, int max_iter, int ks, int lane) {
+  const float mine = (lane < max_iter && lane < 64) ? resid[(size_t)row * max_iter + lane] : 0.0f;
+  float bst = 0.0f;
+  int bi = 0;
+  for (int it = 0; it <= ks; ++it) {
+    const float rs = it < 64 ? gq_readlane(mine, it) : resid[(size_t)row * max_iter + it];
+    if (it == 0 || rs < bst) {
+      bst = rs;
+      bi = it;
+    }
+  }
+  return bi;
 }

@@ -1,8 +1,8 @@
 // Box QP with a DENSE Hessian of 65..128 variables: qpth.qp.QPFunction(Q, p, G = [I; -I], h) as the reference's
 // metrics/solver/qp_solver.py:101-125 calls it with 8-edge friction cones (nz = 96 at 12 contacts, 128 at 16).  The
 // register-resident Cholesky of qp_core.h stops at 64 variables (one matrix row per lane in VGPRs); here the matrix lives
-// in LDS.  One problem per wavefront, lane l owns variables l and l + 64; the PDIPM control flow is the shared
-// gq_qp_lr_iterate (qp_lr.h; qpth 0.0.18 semantics), only the linear algebra differs:
+// in LDS.  One problem per wavefront, lane l owns variables l and l + 64; the PDIPM loop and the backward row are the
+// shared ones of qp_kernels.h (qpth 0.0.18 semantics), only the linear algebra differs:
 //
 //   one nz x LD square in LDS holds BOTH matrices: the strict UPPER triangle keeps Q (symmetric: Q_ik for i < k at [i][k]),
 //   the strict LOWER triangle receives the Cholesky factor L of M = Q + diag(lam) (L_ik for i > k at [i][k]); the two
@@ -16,7 +16,7 @@
 //
 // All fp32, like the register kernels for nz <= 64 (the low-rank route behind SQPLsqSolver / energy_type graspqp, which
 // knows Q = A'A + ridge I, stays the fast and the more accurate path: DESIGN.md section 4).
-#include "qp_lr.h"
+#include "qp_kernels.h"
 
 template <int NC>
 struct GqDenseLds {
@@ -25,7 +25,6 @@ struct GqDenseLds {
   float* di;    // nz: 1 / L_ii
   float* vec;   // nz: broadcast scratch (matvec operand, backward-substitution results)
   int nz, LD, lane;
-  float ridge;  // unused (interface of gq_qp_lr_iterate): the caller passes g.ridge = 0, lam = d_u + d_l
 
   // s[c] = sum_{k < len} L_{i_c,k} L_{j,k} for the lane's rows i_c = lane + 64 c (clamped to a valid row when the lane has
   // none: the result is discarded).  Both rows share the broadcast reads of row j; the loop is unrolled so that eight
@@ -98,8 +97,7 @@ struct GqDenseLds {
   }
 
   // dx = M^-1 rhs
-  __device__ __forceinline__ void solve(const float (&rhs)[NC], float (&dx)[NC], float* y_out = nullptr) const {
-    (void)y_out;
+  __device__ __forceinline__ void solve(const float (&rhs)[NC], float (&dx)[NC]) const {
     float b[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) b[c] = rhs[c];
@@ -160,8 +158,7 @@ struct GqDenseLds {
   }
 
   // out = Q x
-  __device__ __forceinline__ void matvec(const float (&x)[NC], float (&out)[NC], const float* ax_known = nullptr) const {
-    (void)ax_known;
+  __device__ __forceinline__ void matvec(const float (&x)[NC], float (&out)[NC]) const {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const int i = lane + GQ_WAVE * c;
@@ -193,7 +190,6 @@ __device__ __forceinline__ GqDenseLds<NC> gq_dense_setup(const float* __restrict
   S.nz = nz;
   S.LD = (nz + 3) / 4 * 4 + 8;  // 16-byte aligned rows with 8 words of slack (masked tail reads), not a multiple of 32 words
   S.lane = lane;
-  S.ridge = 0.0f;
   S.U = lds;
   const int nzp = (nz + 3) / 4 * 4;  // 16-byte aligned vectors
   S.qd = lds + (size_t)nz * S.LD;
@@ -231,41 +227,15 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_qp_dense_iter_kernel(GqQpArgs g) {
     hl[c] = -lo;
   }
   g.ridge = 0.0f;  // lam = d_u + d_l: the ridge, if any, is part of Q
-  gq_qp_lr_iterate<1, 2, GqDenseLds<2>>(g, row, lane, S, live, p, hu, hl);
+  gq_qp_lr_iterate(g, row, lane, S, live, p, hu, hl);
 }
 
 __global__ __launch_bounds__(GQ_WAVE) void gq_qp_dense_bwd_kernel(GqQpBwdArgs g) {
   extern __shared__ float gq_dense_lds[];
-  const int row = blockIdx.x, lane = gq_lane(), nz = g.nz;
-  GqDenseLds<2> S = gq_dense_setup<2>(g.Q, row, nz, lane, gq_dense_lds);
-  bool live[2];
-  float du[2], dl[2], lam[2], rhs[2], dx[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int k = lane + GQ_WAVE * c;
-    live[c] = k < nz;
-    du[c] = dl[c] = 1.0f;
-    rhs[c] = 0.0f;
-    if (live[c]) {
-      const float* lm = g.lam + (size_t)row * 2 * nz;
-      const float* sk = g.slack + (size_t)row * 2 * nz;
-      du[c] = fmaxf(lm[k], 1e-8f) / fmaxf(sk[k], 1e-8f);
-      dl[c] = fmaxf(lm[nz + k], 1e-8f) / fmaxf(sk[nz + k], 1e-8f);
-      rhs[c] = -g.grad_x[(size_t)row * nz + k];  // solve_kkt(d, grad_x, 0, 0): rhs = -rx (qp_kernels.h::gq_qp_bwd_kernel)
-    }
-    lam[c] = du[c] + dl[c];
-  }
-  S.factor(lam, live);
-  S.solve(rhs, dx);
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    if (live[c]) {
-      const int k = lane + GQ_WAVE * c;
-      g.dx[(size_t)row * nz + k] = dx[c];
-      g.dlam[(size_t)row * 2 * nz + k] = du[c] * dx[c];
-      g.dlam[(size_t)row * 2 * nz + nz + k] = -dl[c] * dx[c];
-    }
-  }
+  const int row = blockIdx.x, lane = gq_lane();
+  GqDenseLds<2> S = gq_dense_setup<2>(g.Q, row, g.nz, lane, gq_dense_lds);
+  g.ridge = 0.0f;
+  gq_qp_bwd_row<2>(g, S, row, lane);
 }
 
 int gq_qp_launch_iter_dense_lds(const GqQpArgs& a, hipStream_t st) {

@@ -1,3 +1,3 @@
-// NZ = 16 instantiation of the box-QP kernels.
+// NZ = 16 instantiation of the register-Cholesky box-QP kernels.
 #include "qp_kernels.h"
-GQ_DEFINE_QP_NZ(16)
+template struct GqQpRegLaunch<16>;

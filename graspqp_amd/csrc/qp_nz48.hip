@@ -1,3 +1,3 @@
-// NZ = 48 instantiation of the box-QP kernels.
+// NZ = 48 instantiation of the register-Cholesky box-QP kernels.
 #include "qp_kernels.h"
-GQ_DEFINE_QP_NZ(48)
+template struct GqQpRegLaunch<48>;

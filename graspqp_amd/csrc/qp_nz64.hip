@@ -1,3 +1,3 @@
-// NZ = 64 instantiation of the box-QP kernels.
+// NZ = 64 instantiation of the register-Cholesky box-QP kernels.
 #include "qp_kernels.h"
-GQ_DEFINE_QP_NZ(64)
+template struct GqQpRegLaunch<64>;

@@ -1,7 +1,7 @@
 """Every box-QP kernel variant against the fp64 oracle (oracle/ref_cpu/qp.py), step by step.
 
 The box-QP is a dispatch table (csrc/qp.hip gq_launch_iter / gq_launch_bwd, csrc/qp_lr.hip):
-  dense Q   nz <= 16 / 32 / 48 / 64      gq_qp_iter_kernel<NZ,1>, gq_qp_bwd_kernel<NZ,1>   (register Cholesky)
+  dense Q   nz <= 16 / 32 / 48 / 64      gq_qp_iter_kernel<NZ>, gq_qp_bwd_kernel<NZ>       (register Cholesky)
             65 <= nz <= 128              gq_qp_dense_iter_kernel, gq_qp_dense_bwd_kernel   (matrix in LDS)
   low rank  m <= 6 | m in {7, 8}  x  nz <= 64 | nz > 64
                                          gq_qp_lr_iter_kernel<M,NC>, gq_qp_lr_bwd_kernel<M,NC>  (Woodbury)
