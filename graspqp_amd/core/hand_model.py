@@ -116,6 +116,7 @@ class HandModel:
     def cal_distance(self, x, penetration_only=False):
         """x: (B,N,3) object surface points, identical for the rows of one object (object_model.py:182-184), or the
         un-expanded (n_obj,N,3).  Returns (B,N) max-over-links signed distance, inside positive."""
+        penetration_only = ops.pen_mode(penetration_only)
         B = self.hand_pose.shape[0]
         if x.shape[0] == B and B > 0:
             # recover the per-object tensor: rows of an object share their points

@@ -66,8 +66,8 @@ struct GqPenArgs {
   // surface points -- lets a block drop, before anything else, the links whose box cannot reach its slice
   const float* patch;
   unsigned long long* dbg;  // optional counters (12 words, gq_debug_set_pen_counters): [0] needing (point,link) pairs,
-                            // [1] (wave,link) evaluations, [2] (wave,sub-cluster) evaluations, [3] waves (AABB / queue
-                            // kernels); gq_pen_grid_body: [4] entries = (point,link) pairs that reach a non-empty
+                            // [1] (wave,link) evaluations, [2] (wave,sub-cluster) evaluations, [3] waves (exact
+                            // kernel); gq_pen_grid_body: [4] entries = (point,link) pairs that reach a non-empty
                             // voxel, [5] executed point-triangle rankings, [6] entries ranked inline (LDS capacity
                             // overflow), [7] blocks
 };
@@ -884,6 +884,8 @@ __device__ __forceinline__ void gq_pen_bwd_body(const GqPenBwdArgs& g, int row, 
 
 
 // ---- host side: argument blocks of the penetration-only query and its fused-E_pen backward ---------------------------
+// surface points per thread of the query as a role of a fused step (sdf.hip; gq_debug_set_pen_ppt)
+int gq_pen_points_per_thread_();
 static inline int gq_pen_fill(const gqMeshSet* links, const float* surface_points, int64_t n_obj, int64_t n_surface,
                               int64_t batch_each, const float* hand_pose, int pose_dim, const float* Rg,
                               const float* link_T, float* dis, int32_t* link, float* gvec, uint64_t* span, GqPenArgs* out,

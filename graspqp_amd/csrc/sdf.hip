@@ -11,6 +11,46 @@
 #include "tri.h"
 #include <hip/hip_ext.h>
 
+#include "pen_dev.h"
+#include "sdf_dev.h"
+
+// ---- debug switches (A/B runs and diagnostics; no result depends on them) ------------------------------------------------
+static int gq_sdf_topk_ = 0;           // 0 = default (4 clusters per round), 2 / 4 forced
+static int gq_sdf_plain_mapping_ = 0;  // 1 = plain instead of XCD-aware query placement in gq_sdf_forward_meshset
+static int gq_pen_caps_ = 0;           // LDS lists of the stand-alone grid query: 0 / 1 = 512, 2 = 256, 3 = 128 entries
+static unsigned long long* gq_pen_dbg_ = nullptr;  // device counters (12 words) or null
+// Surface points per thread of the penetration query (0 = defaults, 1 / 2 forced).  Two points per thread halve the
+// wavefronts and share prologue, loop overhead and list phases: +1.5..2 % at 256 rows, where the query is a role of stage
+// A.  As a launch of its own beside the force-closure branch the same variant is much faster alone (167 -> 124 us at 2048
+// rows) but holds 84 instead of 62 VGPRs per wavefront, and the iteration gets 18 % SLOWER -- the stand-alone kernel keeps
+// one point per thread.
+static int gq_pen_ppt_ = 0;
+int gq_pen_points_per_thread_() { return gq_pen_ppt_ == 1 ? 1 : 2; }  // fused (stage A role)
+static int gq_pen_points_per_thread_standalone_() { return gq_pen_ppt_ == 2 ? 2 : 1; }
+
+extern "C" {
+int gq_debug_set_sdf_topk(int topk) {
+  gq_sdf_topk_ = (topk == 2 || topk == 4) ? topk : 0;
+  return GQ_OK;
+}
+int gq_debug_set_sdf_mapping(int plain) {
+  gq_sdf_plain_mapping_ = plain;
+  return GQ_OK;
+}
+int gq_debug_set_pen_caps(int mode) {
+  gq_pen_caps_ = mode;
+  return GQ_OK;
+}
+int gq_debug_set_pen_ppt(int ppt) {
+  gq_pen_ppt_ = (ppt == 1 || ppt == 2) ? ppt : 0;
+  return GQ_OK;
+}
+int gq_debug_set_pen_counters(uint64_t* counters) {
+  gq_pen_dbg_ = (unsigned long long*)counters;
+  return GQ_OK;
+}
+}  // extern "C"
+
 // rec[i] = record of face perm[i] (perm == nullptr: identity)
 __global__ void gq_face_prep_kernel(const float* __restrict__ fv, const int32_t* __restrict__ perm,
                                     GqFace* __restrict__ rec, int64_t F) {
@@ -20,8 +60,6 @@ __global__ void gq_face_prep_kernel(const float* __restrict__ fv, const int32_t*
   const float* v = fv + src * 9;
   rec[i] = gq_make_face(gq_mk(v[0], v[1], v[2]), gq_mk(v[3], v[4], v[5]), gq_mk(v[6], v[7], v[8]), (int)src);
 }
-
-#include "sdf_dev.h"
 
 template <int TOPK>  // 4: <= 128 VGPRs, 4 wavefronts per SIMD; 2 (large launches): see gq_sdf_wave_query
 __global__ __launch_bounds__(256, TOPK == 4 ? 4 : 5) void gq_sdf_wave_kernel(GqWaveArgs g) {
@@ -38,7 +76,6 @@ __global__ __launch_bounds__(256, TOPK == 4 ? 4 : 5) void gq_sdf_wave_kernel(GqW
   const GqSdfPre pre = gq_sdf_wave_prefetch(g, q, lane);
   gq_sdf_wave_query<TOPK>(g, q, gq_mk(g.points[q * 3 + 0], g.points[q * 3 + 1], g.points[q * 3 + 2]), lane, pre);
 }
-static int gq_sdf_topk_ = 0;  // gq_debug_set_sdf_topk: 0 = default (4), 2 / 4 forced (A/B runs)
 static void gq_sdf_wave_launch(const GqWaveArgs& w, unsigned blocks, int64_t n_queries, hipStream_t st) {
   // two clusters per round: 86 instead of 128 VGPRs and 6 % fewer cluster visits, but every query lives longer --
   // -1.4 % at 2048 / 4096 rows, +1 % at 512 (tools: bench.py --sdf_topk): four stays the default at every size
@@ -90,14 +127,28 @@ __global__ void gq_sdf_bwd_kernel(const float* __restrict__ g, const float* __re
   grad_points[i] = 2.0f * (points[i] - closest[i]) * g[i / 3];
 }
 
-#include "pen_dev.h"
-
 template <bool EVAL, int ECAP, int ICAP, int PPT = 1>
 __global__ __launch_bounds__(256) void gq_pen_grid_kernel(GqPenArgs g) {
   extern __shared__ char gq_lds[];
   // slice-major grid (x = row, y = slice block): the blocks dispatched last are those of the last, partly filled slice of
   // every row rather than all slices of the last rows -- the late starters decide when the launch ends
   gq_pen_grid_body<EVAL, ECAP, ICAP, PPT>(g, (int)blockIdx.y, (int)blockIdx.x, gq_lds);
+}
+// Stand-alone launch of the voxel-candidate query (e0 / e1: optional start / stop events of the kernel itself).
+// LDS list capacities (caps 2 / 3): smaller lists double the blocks per CU and make THIS kernel faster (168 -> 115 us at
+// 2048 rows) but not the iteration -- the branch it runs beside loses the slots it gains (tools/ab_caps.sh) -- and the
+// smallest ones overflow into inline ranking; so the large lists stay the default.
+static void gq_pen_grid_launch(const GqPenArgs& a, int ppt, int caps, hipEvent_t e0, hipEvent_t e1, hipStream_t st) {
+  const dim3 grid_sm((unsigned)a.B, (unsigned)((a.P + 255) / 256)), block(256);  // x = row, y = slice block
+  if (caps == 3)
+    hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, 128, 1024>), grid_sm, block, gq_pen_grid_lds_bytes(a.L, 128, 1024), st, e0, e1, 0, a);
+  else if (caps == 2)
+    hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, 256, 2048>), grid_sm, block, gq_pen_grid_lds_bytes(a.L, 256, 2048), st, e0, e1, 0, a);
+  else if (ppt == 2)
+    hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, GQ_PG_ECAP, GQ_PG_ICAP, 2>), dim3((unsigned)a.B, (unsigned)((a.P + 511) / 512)),
+                          block, gq_pen_grid_lds_bytes(a.L, GQ_PG_ECAP, GQ_PG_ICAP, 2), st, e0, e1, 0, a);
+  else
+    hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, GQ_PG_ECAP, GQ_PG_ICAP>), grid_sm, block, gq_pen_grid_lds_bytes(a.L), st, e0, e1, 0, a);
 }
 __global__ __launch_bounds__(256) void gq_pen_cells_kernel(GqPenArgs g) {
   extern __shared__ char gq_lds[];
@@ -109,13 +160,9 @@ __global__ __launch_bounds__(256) void gq_hand_pen_bwd_kernel(GqPenBwdArgs g) {
   gq_pen_bwd_body<K>(g, (int)blockIdx.x, gq_lds);
 }
 
-// MODE 0 ("exact"): dis is the exact max over links for every point.  A link is skipped for a whole wavefront
-//   only when, for every lane, its AABB lower bound already proves dis_l <= best (points outside a link's AABB
-//   are outside the link, so dis_l = -sqrt(d_l^2+1e-8) <= -sqrt(lb^2+1e-8)).
-// MODE 1 ("penetration only"): what E_pen needs (energy.py:59-61 zeroes dis <= 0): a link is evaluated only if
-//   some lane's point lies in a voxel of the link's 32^3 occupancy grid that touches the surface or the interior;
-//   dis is exact wherever it is > 0 and merely <= 0 elsewhere.  MODE 2: the same with the AABB test only.
-template <int MODE>
+// The exact query: dis is the exact max over links for every point.  A link is skipped for a whole wavefront only when,
+// for every lane, its AABB lower bound already proves dis_l <= best (points outside a link's AABB are outside the link,
+// so dis_l = -sqrt(d_l^2+1e-8) <= -sqrt(lb^2+1e-8)).
 __global__ __launch_bounds__(256) void gq_hand_pen_kernel(GqPenArgs g) {
   const int row = blockIdx.y;
   const int pt = blockIdx.x * blockDim.x + threadIdx.x;
@@ -138,22 +185,8 @@ __global__ __launch_bounds__(256) void gq_hand_pen_kernel(GqPenArgs g) {
     const gq3 tl = gq_mk(T[3], T[7], T[11]);
     const gq3 xl = gq_mtv(Rl, xh - tl);
     const float lb2 = gq_aabb_dist2(g.aabb + l * 8, xl);  // squared distance to the link's AABB
-    bool need;
-    if (MODE == 1 || MODE == 2) {
-      need = ok && (lb2 <= 0.0f);
-      if (MODE == 1 && need && g.occ) {
-        // 32^3 occupancy grid over the link's AABB: a point in a voxel that neither touches the surface nor lies
-        // inside the mesh is outside -> this link cannot be penetrated by it
-        const float* bb = g.aabb + l * 8;
-        const float ux = (xl.x - bb[0]) * bb[3], uy = (xl.y - bb[1]) * bb[7];  // bb[3], bb[7]: 32/extent x, y
-        const float uz = (xl.z - bb[2]) * g.occ_invz[l];
-        const int ix = min(max((int)ux, 0), 31), iy = min(max((int)uy, 0), 31), iz = min(max((int)uz, 0), 31);
-        need = (g.occ[(size_t)l * 1024 + iz * 32 + iy] >> ix) & 1u;
-      }
-    } else {
-      // can link l still beat best_dis?  only if it may be penetrated (inside AABB) or closer than the best so far
-      need = ok && ((lb2 <= 0.0f) || (best_dis < 0.0f && fmaf(lb2, 0.9999f, 1e-8f) < best_dis * best_dis));
-    }
+    // can link l still beat best_dis?  only if it may be penetrated (inside AABB) or closer than the best so far
+    const bool need = ok && ((lb2 <= 0.0f) || (best_dis < 0.0f && fmaf(lb2, 0.9999f, 1e-8f) < best_dis * best_dis));
     if (__ballot(need) == 0ull) continue;  // wave-uniform skip
     if (g.dbg) {
       const unsigned long long nm = __ballot(need);
@@ -208,202 +241,6 @@ __global__ __launch_bounds__(256) void gq_hand_pen_kernel(GqPenArgs g) {
     g.gvec[o * 3 + 2] = best_g.z;
   }
   if (g.span) {  // last store of the block is done: close the launch's time span
-    __syncthreads();
-    if (threadIdx.x == 0) gq_span_close(g.span, blockIdx.x + blockIdx.y * gridDim.x);
-  }
-}
-
-// ---- load-balanced penetration-only query (penetration_only = 1 with a workspace) -------------------------------------
-// Only ~3 % of the (wavefront, link) combinations contain a point that can penetrate the link, but they cluster in a
-// few wavefronts (the points in the middle of the hand touch many links), so a single kernel ends on a handful of
-// waves that each walk 10+ link meshes.  The query is therefore split in three launches:
-//   scan      every wavefront tests its 64 points against every link (AABB + occupancy grid) and appends one work
-//             item (row, first point, link, 64-bit lane mask) per hit to a queue;
-//   eval      the queue is processed by 8192 wavefronts in parallel: one link mesh for <= 64 points per item; a
-//             penetrating point publishes max(dis) with a 64-bit atomicMax key (dis bits | 255-link | face), which is
-//             independent of the order in which items are processed;
-//   finalize  points with a key recompute closest point / gradient of the winning (link, face).
-struct GqPenItem {  // one surface point that may penetrate the queue's link
-  int row, pt;
-};
-struct GqPenQ {
-  GqPenItem* items;  // (L, cap_link): one queue per link so that a block can stage the link's mesh in LDS once
-  int* count;        // (L)
-  unsigned long long* keys;  // (B, P)
-  long long cap_link;        // = B * P: a queue can never overflow
-};
-
-__global__ __launch_bounds__(256) void gq_pen_scan_kernel(GqPenArgs g, GqPenQ q) {
-  extern __shared__ float s_link[];  // L x 24: link transform (12) + padded AABB (8) + occupancy z scale (1) + pad
-  const int row = blockIdx.y;
-  const int pt = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g.span && threadIdx.x == 0) gq_span_open(g.span, blockIdx.x + blockIdx.y * gridDim.x);
-  for (int i = threadIdx.x; i < g.L * 24; i += blockDim.x) {
-    const int l = i / 24, k = i % 24;
-    float v = 0.0f;
-    if (k < 12) v = g.link_T[((size_t)row * g.L + l) * 12 + k];
-    else if (k < 20) v = g.aabb[l * 8 + (k - 12)];
-    else if (k == 20) v = g.occ ? g.occ_invz[l] : 0.0f;
-    s_link[i] = v;
-  }
-  const bool ok = pt < g.P;
-  const int obj = row / g.batch_each;
-  const float* sp = g.surf + ((size_t)obj * g.P + (ok ? pt : 0)) * 3;
-  const float* hp = g.hand_pose + (size_t)row * g.D;
-  const float* R = g.Rg + (size_t)row * 9;
-  const gq3 xh = gq_mtv(R, gq_mk(sp[0] - hp[0], sp[1] - hp[1], sp[2] - hp[2]));
-  if (ok) q.keys[(size_t)row * g.P + pt] = 0ull;
-  __syncthreads();
-  const int lane = gq_lane();
-  for (int l = 0; l < g.L; ++l) {
-    const float* T = s_link + l * 24;
-    const float Rl[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-    const gq3 xl = gq_mtv(Rl, xh - gq_mk(T[3], T[7], T[11]));
-    const float* bb = T + 12;
-    bool need = ok && (g.off[l + 1] > g.off[l]) && (gq_aabb_dist2(bb, xl) <= 0.0f);
-    if (need && g.occ) {
-      const float ux = (xl.x - bb[0]) * bb[3], uy = (xl.y - bb[1]) * bb[7], uz = (xl.z - bb[2]) * T[20];
-      const int ix = min(max((int)ux, 0), 31), iy = min(max((int)uy, 0), 31), iz = min(max((int)uz, 0), 31);
-      need = (g.occ[(size_t)l * 1024 + iz * 32 + iy] >> ix) & 1u;
-    }
-    const unsigned long long m = __ballot(need);
-    if (m != 0ull) {
-      int base = 0;
-      if (lane == 0) base = atomicAdd(&q.count[l], __popcll(m));
-      base = gq_readlane_i(base, 0);
-      if (need) {
-        GqPenItem it;
-        it.row = row;
-        it.pt = pt;
-        q.items[(size_t)l * q.cap_link + base + __popcll(m & ((1ull << lane) - 1ull))] = it;
-      }
-    }
-  }
-}
-
-// A block = 8 wavefronts takes one chunk of 64 queue entries of one link (chunks of all links are numbered
-// consecutively, so blocks spread over the queues in proportion to their length).  Lane j of EVERY wavefront owns
-// entry j; wavefront w ranks the w-th eighth of the link's faces (records are wave-uniform -> scalar loads), the eight
-// partial minima meet in LDS and wavefront 0 finishes the winner.  All 64 lanes work, a block lasts a few us, and
-// there are enough blocks (entries / 64) to cover the chip.
-#define GQ_PEN_EVAL_BLOCKS 4096
-__global__ __launch_bounds__(512) void gq_pen_eval_kernel(GqPenArgs g, GqPenQ q) {
-  __shared__ float s_d[8][GQ_WAVE];
-  __shared__ unsigned s_o[8][GQ_WAVE];
-  __shared__ int s_i[8][GQ_WAVE];
-  __shared__ int s_sel[2];
-  const int lane = gq_lane(), wv = threadIdx.x / GQ_WAVE;
-  for (int chunk = blockIdx.x;; chunk += gridDim.x) {
-    __syncthreads();  // LDS of the previous chunk fully consumed
-    if (threadIdx.x == 0) {
-      int c = chunk, l = 0;
-      for (; l < g.L; ++l) {
-        const int nc = (q.count[l] + GQ_WAVE - 1) / GQ_WAVE;
-        if (c < nc) break;
-        c -= nc;
-      }
-      s_sel[0] = (l < g.L) ? l : -1;
-      s_sel[1] = c;
-    }
-    __syncthreads();
-    const int l = s_sel[0];
-    if (l < 0) return;  // block-uniform: past the last chunk
-    const int count = q.count[l];
-    const int i = s_sel[1] * GQ_WAVE + lane;
-    const bool need = i < count;
-    const int f0 = g.off[l], f1 = g.off[l + 1];
-    GqPenItem it;
-    it.row = 0;
-    it.pt = 0;
-    if (need) it = q.items[(size_t)l * q.cap_link + i];
-    const int row = it.row, pt = it.pt;
-    const int obj = row / g.batch_each;
-    const float* sp = g.surf + ((size_t)obj * g.P + pt) * 3;
-    const float* hp = g.hand_pose + (size_t)row * g.D;
-    const float* R = g.Rg + (size_t)row * 9;
-    const gq3 xh = gq_mtv(R, gq_mk(sp[0] - hp[0], sp[1] - hp[1], sp[2] - hp[2]));
-    const float* T = g.link_T + ((size_t)row * g.L + l) * 12;
-    const float Rl[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-    const gq3 xl = gq_mtv(Rl, xh - gq_mk(T[3], T[7], T[11]));
-    const int per = (f1 - f0 + 7) / 8;
-    const int fa = f0 + wv * per, fb = min(fa + per, f1);
-    float bd = GQ_INF_F;
-    unsigned bo = 0xffffffffu;
-    int bi = f0;
-    if (fa < fb) {
-      GqFace cur = g.rec[fa];
-      for (int f = fa; f < fb; ++f) {  // f is wave-uniform: scalar loads, next record prefetched
-        const GqFace nxt = g.rec[(f + 1 < fb) ? f + 1 : f];
-        const gq3 d = xl - gq_mk(cur.r0.x, cur.r0.y, cur.r0.z);
-        const float d2 = gq_tri_rank(cur, d);
-        const unsigned orig = (unsigned)__float_as_int(cur.r5.z);
-        if (d2 < bd || (d2 == bd && orig < bo)) {
-          bd = d2;
-          bo = orig;
-          bi = f;
-        }
-        cur = nxt;
-      }
-    }
-    s_d[wv][lane] = bd;
-    s_o[wv][lane] = bo;
-    s_i[wv][lane] = bi;
-    __syncthreads();
-    if (wv == 0 && need) {
-#pragma unroll
-      for (int w = 1; w < 8; ++w) {
-        const float d2 = s_d[w][lane];
-        const unsigned orig = s_o[w][lane];
-        if (d2 < bd || (d2 == bd && orig < bo)) {
-          bd = d2;
-          bo = orig;
-          bi = s_i[w][lane];
-        }
-      }
-      const GqSdfOut o = gq_tri_finish(g.rec[bi], xl);
-      if (o.sign < 0) {  // inside link l: dis = +sqrt(d^2 + 1e-8) > 0
-        const float dis = sqrtf(o.dist2 + 1e-8f);
-        const unsigned long long key = ((unsigned long long)__float_as_uint(dis) << 32) |
-                                       ((unsigned long long)(255 - l) << 24) | (unsigned long long)(bi - f0);
-        atomicMax(&q.keys[(size_t)row * g.P + pt], key);
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void gq_pen_finalize_kernel(GqPenArgs g, GqPenQ q) {
-  const int row = blockIdx.y;
-  const int pt = blockIdx.x * blockDim.x + threadIdx.x;
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < g.L) q.count[threadIdx.x] = 0;  // ready for the next query
-  if (pt < g.P) {
-    const size_t o = (size_t)row * g.P + pt;
-    const unsigned long long key = q.keys[o];
-    float dis = -1e30f;
-    int link = 0;
-    gq3 gh = gq_mk(0, 0, 0);
-    if (key != 0ull) {
-      link = 255 - (int)((key >> 24) & 0xffull);
-      const int face = g.off[link] + (int)(key & 0xffffffull);
-      const int obj = row / g.batch_each;
-      const float* sp = g.surf + ((size_t)obj * g.P + pt) * 3;
-      const float* hp = g.hand_pose + (size_t)row * g.D;
-      const float* R = g.Rg + (size_t)row * 9;
-      const gq3 xh = gq_mtv(R, gq_mk(sp[0] - hp[0], sp[1] - hp[1], sp[2] - hp[2]));
-      const float* T = g.link_T + ((size_t)row * g.L + link) * 12;
-      const float Rl[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-      const gq3 xl = gq_mtv(Rl, xh - gq_mk(T[3], T[7], T[11]));
-      const GqSdfOut r = gq_tri_finish(g.rec[face], xl);
-      const float root = sqrtf(r.dist2 + 1e-8f);
-      dis = root * (float)(-r.sign);
-      gh = gq_mv(Rl, ((float)(-r.sign) / root) * (xl - r.closest));
-    }
-    g.dis[o] = dis;
-    g.link[o] = link;
-    g.gvec[o * 3 + 0] = gh.x;
-    g.gvec[o * 3 + 1] = gh.y;
-    g.gvec[o * 3 + 2] = gh.z;
-  }
-  if (g.span) {
     __syncthreads();
     if (threadIdx.x == 0) gq_span_close(g.span, blockIdx.x + blockIdx.y * gridDim.x);
   }
@@ -539,18 +376,6 @@ static void gq_box_of(const float* fv, const int32_t* perm, int64_t a, int64_t b
   out8[4] = hi[0]; out8[5] = hi[1]; out8[6] = hi[2]; out8[7] = 0.0f;
 }
 
-static unsigned long long* gq_pen_dbg_ = nullptr;
-// Surface points per thread of the penetration query (gq_debug_set_pen_ppt: 0 = defaults, 1 / 2 forced).  Two points per
-// thread halve the wavefronts and share prologue, loop overhead and list phases: +1.5..2 % at 256 rows, where the query is
-// a role of stage A.  As a launch of its own beside the force-closure branch the same variant is much faster alone (167 ->
-// 124 us at 2048 rows) but holds 84 instead of 62 VGPRs per wavefront, and the iteration gets 18 % SLOWER -- the
-// stand-alone kernel keeps one point per thread.
-static int gq_pen_ppt_ = 0;
-int gq_pen_points_per_thread_() { return gq_pen_ppt_ == 1 ? 1 : 2; }          // fused (stage A role)
-static int gq_pen_points_per_thread_standalone_() { return gq_pen_ppt_ == 2 ? 2 : 1; }
-static int gq_pen_caps_ = 0;  // gq_debug_set_pen_caps: 0 = by launch size, 1 / 2 / 3 = 512 / 256 / 128 entries (A/B runs)
-static int gq_sdf_plain_mapping_ = 0;  // gq_debug_set_sdf_mapping(1): A/B switch for the XCD-aware query placement
-
 // Bound of a 64-face cluster: an oriented box, 16 floats = [centre.xyz, h_u][u.xyz, h_v][v.xyz, h_n][n.xyz, 0].
 // n = area-weighted mean normal of the patch, u = principal direction of its vertices in the plane orthogonal to n,
 // v = n x u.  A Morton patch of a surface mesh is nearly planar, so the box is ~1 mm thick along n and hugs the patch
@@ -662,29 +487,6 @@ int gq_sdf_wave_args_(const gqMeshSet* ms, int64_t n_points, int64_t queries_per
 }
 
 extern "C" {
-
-// diagnostics: device pointer to 4 uint64 counters filled by gq_hand_pen_forward (NULL = off, the default)
-int gq_debug_set_sdf_topk(int topk) {
-  gq_sdf_topk_ = (topk == 2 || topk == 4) ? topk : 0;
-  return GQ_OK;
-}
-int gq_debug_set_pen_ppt(int ppt) {
-  gq_pen_ppt_ = (ppt == 1 || ppt == 2) ? ppt : 0;
-  return GQ_OK;
-}
-int gq_debug_set_pen_caps(int mode) {
-  gq_pen_caps_ = mode;
-  return GQ_OK;
-}
-int gq_debug_set_sdf_mapping(int plain) {
-  gq_sdf_plain_mapping_ = plain;
-  return GQ_OK;
-}
-
-int gq_debug_set_pen_counters(uint64_t* counters) {
-  gq_pen_dbg_ = (unsigned long long*)counters;
-  return GQ_OK;
-}
 
 int gq_meshset_create(const float* face_verts_host, const int32_t* face_offset_host, int n_mesh, gqMeshSet** out) {
   GQ_REQUIRE(face_verts_host && face_offset_host && out && n_mesh > 0, "meshset_create: bad arguments");
@@ -922,70 +724,37 @@ int gq_sdf_backward(const float* grad_dist_sq, const float* points, const float*
   return GQ_OK;
 }
 
+// gqTimer = hipEvent_t[2]: the kernel's own start / stop timestamps (hipExtLaunchKernelGGL), not stream markers
+static hipEvent_t gq_timer_event(void* timer, int i) { return timer ? ((hipEvent_t*)timer)[i] : nullptr; }
+
 // Fused hand-penetration query (HandModel.cal_distance, hand_model.py:875-987).
 int gq_hand_pen_forward(const gqMeshSet* links, const float* surface_points, int64_t n_obj, int64_t n_surface,
                         int64_t batch_each, const float* hand_pose, int pose_dim, const float* Rg, const float* link_T,
                         int penetration_only, float* dis, int32_t* link, float* gvec, void* workspace,
                         size_t workspace_bytes, void* timer, uint64_t* span, const float* patch_spheres, void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  GQ_REQUIRE(penetration_only == 0 || penetration_only == 1 || penetration_only == 9,
+             "hand_pen_forward: penetration_only=%d; accepted values: 0 (exact), 1 (voxel candidates), 9 (scan-only diagnostic)",
+             penetration_only);
   GqPenArgs a{};
-  int rc0 = gq_pen_fill(links, surface_points, n_obj, n_surface, batch_each, hand_pose, pose_dim, Rg, link_T, dis, link,
-                        gvec, span, &a);
-  if (rc0) return rc0;
+  int rc = gq_pen_fill(links, surface_points, n_obj, n_surface, batch_each, hand_pose, pose_dim, Rg, link_T, dis, link, gvec,
+                       span, &a);
+  if (rc) return rc;
   a.dbg = gq_pen_dbg_;
   a.patch = patch_spheres;
-  const dim3 grid((unsigned)((a.P + 255) / 256), (unsigned)a.B);
-  const dim3 grid_sm((unsigned)a.B, (unsigned)((a.P + 255) / 256));  // gq_pen_grid_kernel: x = row, y = slice block
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timer) {  // gqTimer: the kernel's own start/stop timestamps (hipExtLaunchKernelGGL), not stream markers
-    e0 = ((hipEvent_t*)timer)[0];
-    e1 = ((hipEvent_t*)timer)[1];
+  const hipEvent_t e0 = gq_timer_event(timer, 0), e1 = gq_timer_event(timer, 1);
+  hipStream_t st = (hipStream_t)stream;
+  if (penetration_only == 0) {
+    hipExtLaunchKernelGGL(gq_hand_pen_kernel, dim3((unsigned)((a.P + 255) / 256), (unsigned)a.B), dim3(256), 0, st, e0, e1, 0, a);
+  } else {
+    GQ_REQUIRE(a.occ && a.cand_off, "hand_pen_forward: the link mesh set has no voxel candidate lists (gq_meshset_build_occupancy)");
+    if (penetration_only == 1)
+      gq_pen_grid_launch(a, gq_pen_points_per_thread_standalone_(), gq_pen_caps_, e0, e1, st);
+    else  // diagnostics: the scan without candidate evaluation
+      hipExtLaunchKernelGGL((gq_pen_grid_kernel<false, GQ_PG_ECAP, GQ_PG_ICAP>), dim3((unsigned)a.B, (unsigned)((a.P + 255) / 256)),
+                            dim3(256), gq_pen_grid_lds_bytes(a.L), st, e0, e1, 0, a);
   }
-  if (penetration_only == 1 && a.occ && a.cand_off) {
-    // one pass over the (point, link) pairs, candidate faces from the voxel grid (see gq_pen_grid_kernel)
-    // LDS list capacities: smaller lists double the blocks per CU and make THIS kernel faster (168 -> 115 us at 2048
-    // rows) but not the iteration -- the branch it runs beside loses the slots it gains (tools/ab_caps.sh) -- and the
-    // smallest ones overflow into inline ranking; so the large lists stay the default
-    const int caps = gq_pen_caps_ ? gq_pen_caps_ : 1;
-    if (caps == 3)
-      hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, 128, 1024>), grid_sm, dim3(256), gq_pen_grid_lds_bytes(a.L, 128, 1024),
-                            (hipStream_t)stream, e0, e1, 0, a);
-    else if (caps == 2)
-      hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, 256, 2048>), grid_sm, dim3(256), gq_pen_grid_lds_bytes(a.L, 256, 2048),
-                            (hipStream_t)stream, e0, e1, 0, a);
-    else if (gq_pen_points_per_thread_standalone_() == 2)
-      hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, GQ_PG_ECAP, GQ_PG_ICAP, 2>), dim3((unsigned)a.B, (unsigned)((a.P + 511) / 512)),
-                            dim3(256), gq_pen_grid_lds_bytes(a.L, GQ_PG_ECAP, GQ_PG_ICAP, 2), (hipStream_t)stream, e0, e1, 0, a);
-    else
-      hipExtLaunchKernelGGL((gq_pen_grid_kernel<true, GQ_PG_ECAP, GQ_PG_ICAP>), grid_sm, dim3(256), gq_pen_grid_lds_bytes(a.L),
-                            (hipStream_t)stream, e0, e1, 0, a);
-  } else if (penetration_only == 9 && a.occ && a.cand_off) {  // diagnostics: the scan without candidate evaluation
-    hipExtLaunchKernelGGL((gq_pen_grid_kernel<false, GQ_PG_ECAP, GQ_PG_ICAP>), grid_sm, dim3(256), gq_pen_grid_lds_bytes(a.L),
-                          (hipStream_t)stream, e0, e1, 0, a);
-  } else if ((penetration_only == 1 || penetration_only == 3) && workspace != nullptr) {
-    // queue-based, load-balanced path without candidate lists (see gq_pen_scan_kernel); 3 forces it for A/B tests
-    const size_t cap_link = (size_t)a.B * a.P;
-    const size_t cap = cap_link * a.L;
-    const size_t need = 1024 + cap * sizeof(GqPenItem) + (size_t)a.B * a.P * 8;
-    GQ_REQUIRE(workspace_bytes >= need, "hand_pen_forward: workspace too small (%zu < %zu)", workspace_bytes, need);
-    GQ_REQUIRE(a.L <= 255 && cap_link < (1ull << 31), "hand_pen_forward: too many links / items for the queue path");
-    GqPenQ q;
-    q.count = (int*)workspace;
-    q.items = (GqPenItem*)((char*)workspace + 1024);
-    q.keys = (unsigned long long*)((char*)workspace + 1024 + cap * sizeof(GqPenItem));
-    q.cap_link = (long long)cap_link;
-    // q.count is zero on entry: the workspace starts zeroed and gq_pen_finalize_kernel re-zeroes it after use
-    hipExtLaunchKernelGGL(gq_pen_scan_kernel, grid, dim3(256), (size_t)a.L * 24 * sizeof(float), (hipStream_t)stream, e0,
-                          nullptr, 0, a, q);
-    GQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gq_pen_eval_kernel, dim3(GQ_PEN_EVAL_BLOCKS), dim3(512), 0, (hipStream_t)stream, a, q);
-    GQ_LAUNCH_CHECK();
-    hipExtLaunchKernelGGL(gq_pen_finalize_kernel, grid, dim3(256), 0, (hipStream_t)stream, nullptr, e1, 0, a, q);
-  } else if (penetration_only == 1 || penetration_only == 3)
-    hipExtLaunchKernelGGL(gq_hand_pen_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-  else if (penetration_only == 2)  // AABB test only, no occupancy grid (kept for A/B tests)
-    hipExtLaunchKernelGGL(gq_hand_pen_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
-  else
-    hipExtLaunchKernelGGL(gq_hand_pen_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, e0, e1, 0, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }
@@ -1110,26 +879,15 @@ int gq_hand_pen_forward_cells(const gqMeshSet* links, const gqPointGrid* grid, c
                               void* stream) {
   GQ_REQUIRE(grid, "hand_pen_forward_cells: null point grid");
   GqPenArgs a{};
-  int rc0 = gq_pen_fill(links, surface_points, n_obj, n_surface, batch_each, hand_pose, pose_dim, Rg, link_T, dis, link,
-                        gvec, span, &a, grid);
-  if (rc0) return rc0;
+  int rc = gq_pen_fill(links, surface_points, n_obj, n_surface, batch_each, hand_pose, pose_dim, Rg, link_T, dis, link, gvec,
+                       span, &a, grid);
+  if (rc) return rc;
   GQ_REQUIRE(a.occ && a.cand_off, "hand_pen_forward_cells: the link mesh set has no voxel candidate lists (gq_meshset_build_occupancy)");
   a.dbg = gq_pen_dbg_;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timer) {
-    e0 = ((hipEvent_t*)timer)[0];
-    e1 = ((hipEvent_t*)timer)[1];
-  }
+  const hipEvent_t e0 = gq_timer_event(timer, 0), e1 = gq_timer_event(timer, 1);
   hipExtLaunchKernelGGL(gq_pen_cells_kernel, dim3((unsigned)a.B), dim3(256), gq_pen_cells_lds_bytes(a.L, a.P),
                         (hipStream_t)stream, e0, e1, 0, a);
   GQ_LAUNCH_CHECK();
-  return GQ_OK;
-}
-
-int gq_hand_pen_workspace_bytes(int64_t batch, int64_t n_surface, int n_links, size_t* bytes) {
-  GQ_REQUIRE(bytes && batch > 0 && n_surface > 0 && n_links > 0, "hand_pen_workspace_bytes: bad arguments");
-  const size_t cap = (size_t)batch * n_surface * n_links;
-  *bytes = 1024 + cap * sizeof(GqPenItem) + (size_t)batch * n_surface * 8;
   return GQ_OK;
 }
 

@@ -19,7 +19,6 @@
 
 int gq_qp_stop_launch_(const float* resid, const float* mu, int B, int max_iter, float eps, int not_improved_lim,
                        float* runmin, int* kstar, int32_t* n_iter, void* stream);
-int gq_pen_points_per_thread_();  // sdf.hip: surface points per thread of the penetration query (gq_debug_set_pen_ppt)
 
 // STOP: the large-batch stop-rule epilogue is compiled in (its 70 extra registers would cost the small-batch
 // instantiation one wavefront per SIMD: 166 instead of 127 VGPRs)
@@ -177,21 +176,47 @@ __global__ __launch_bounds__(256) void gq_stage_b_alt_kernel(GqPenBwdArgs p, GqS
   else gq_pen_bwd_body(p, b, gq_lds);
 }
 
-static int gq_spen_role_fill(const gqPenStepDesc* pen, GqSpenRole* sp, int B, int* n_sp) {
-  *n_sp = 0;
-  if (!pen->hand) return GQ_OK;
+// Penetration side of a fused step: query role of the first launch, backward (+ self-penetration) roles of the second.
+struct GqPenStep {
+  GqPenArgs p;
+  GqPenBwdArgs pb;
+  GqSpenRole sp;
+  int ppt, gx;           // points per thread; slice blocks per row (0: the link-driven query, one block per row)
+  int n_q, n_sp;         // blocks of the query / self-penetration role (n_sp 0 = absent)
+  size_t lds_q, lds_sp;  // dynamic LDS of a block of these roles
+};
+// who = entry point named in the messages; B = batch of the caller's first role; *s zero-initialised by the caller
+static int gq_pen_step_fill(const gqPenStepDesc* pen, const char* who, int B, GqPenStep* s) {
+  int rc = gq_pen_fill(pen->links, pen->surface_points, pen->n_obj, pen->n_surface, pen->batch_each, pen->hand_pose,
+                       pen->pose_dim, pen->Rg, pen->link_T, pen->dis, pen->link, pen->gvec, pen->span, &s->p, pen->grid);
+  if (rc) return rc;
+  GqPenArgs& p = s->p;
+  p.patch = pen->patch_spheres;
+  GQ_REQUIRE(p.occ && p.cand_off, "%s: the link mesh set has no voxel candidate lists (gq_meshset_build_occupancy)", who);
+  GQ_REQUIRE(p.B == B, "%s: the two descriptors disagree on the batch (%d vs %d)", who, p.B, B);
+  rc = gq_pen_bwd_fill(p.L, pen->surface_points, pen->n_obj, pen->n_surface, pen->batch_each, pen->hand_pose, pen->pose_dim,
+                       pen->Rg, nullptr, pen->link, pen->gvec, pen->link_wrench, pen->gRt, pen->dis, pen->w_pen, pen->e_pen,
+                       pen->span, pen->span_acc, &s->pb);
+  if (rc) return rc;
+  s->ppt = gq_pen_points_per_thread_();
+  s->gx = pen->grid ? 0 : (p.P + 256 * s->ppt - 1) / (256 * s->ppt);
+  s->lds_q = pen->grid ? gq_pen_cells_lds_bytes(p.L, p.P) : gq_pen_grid_lds_bytes(p.L, GQ_PG_ECAP, GQ_PG_ICAP, s->ppt);
+  s->n_q = (pen->grid ? 1 : s->gx) * p.B;
+  if (!pen->hand) return GQ_OK;  // no self-penetration role: n_sp = 0
   GQ_REQUIRE(pen->e_spen && pen->g_sphere_centers && pen->hand->S > 0 && pen->hand->S <= 256,
              "pen step: the self-penetration role needs e_spen, g_sphere_centers and 1..256 spheres");
-  sp->h = *pen->hand;
-  sp->sa.spheres = pen->sphere_centers;
-  sp->sa.e_spen = pen->e_spen;
-  sp->sa.g_spheres = pen->g_sphere_centers;
-  sp->sa.spen_scale = pen->w_spen;
-  sp->Rg = pen->Rg;
-  sp->hand_pose = pen->hand_pose;
-  sp->link_T = pen->link_T;
-  sp->D = pen->pose_dim;
-  *n_sp = (B + 3) / 4;
+  GqSpenRole& sp = s->sp;
+  sp.h = *pen->hand;
+  sp.sa.spheres = pen->sphere_centers;
+  sp.sa.e_spen = pen->e_spen;
+  sp.sa.g_spheres = pen->g_sphere_centers;
+  sp.sa.spen_scale = pen->w_spen;
+  sp.Rg = pen->Rg;
+  sp.hand_pose = pen->hand_pose;
+  sp.link_T = pen->link_T;
+  sp.D = pen->pose_dim;
+  s->n_sp = (B + 3) / 4;
+  s->lds_sp = (size_t)4 * ((size_t)sp.h.S * 16 + 512);
   return GQ_OK;
 }
 
@@ -219,40 +244,24 @@ int gq_alt_pen_step(const gqAltFcDesc* alt, const gqPenStepDesc* pen, void* stre
   a.tdg.inv_obb = alt->obb_length > 0.0f ? 1.0f / alt->obb_length : 0.0f; a.tdg.scale = alt->scale;
   a.tdg.density = alt->enable_density; a.tdg.grad_e = nullptr; a.tdg.w = alt->w_fc; a.tdg.accumulate = 1;
   a.tdg.e = alt->e_fc; a.tdg.g_cpts = alt->g_contact_pts;
-  GqPenArgs p{};
-  int rc = gq_pen_fill(pen->links, pen->surface_points, pen->n_obj, pen->n_surface, pen->batch_each, pen->hand_pose,
-                       pen->pose_dim, pen->Rg, pen->link_T, pen->dis, pen->link, pen->gvec, pen->span, &p, pen->grid);
-  if (rc) return rc;
-  p.patch = pen->patch_spheres;
-  GQ_REQUIRE(p.occ && p.cand_off, "alt_pen_step: the link mesh set has no voxel candidate lists (gq_meshset_build_occupancy)");
-  GQ_REQUIRE(p.B == a.B, "alt_pen_step: the two descriptors disagree on the batch (%d vs %d)", p.B, a.B);
-  GqPenBwdArgs pb{};
-  rc = gq_pen_bwd_fill(p.L, pen->surface_points, pen->n_obj, pen->n_surface, pen->batch_each, pen->hand_pose, pen->pose_dim,
-                       pen->Rg, nullptr, pen->link, pen->gvec, pen->link_wrench, pen->gRt, pen->dis, pen->w_pen, pen->e_pen,
-                       pen->span, pen->span_acc, &pb);
-  if (rc) return rc;
-  const int ppt = gq_pen_points_per_thread_();
-  const int gx = pen->grid ? 0 : (p.P + 256 * ppt - 1) / (256 * ppt);
-  GqSpenRole sp{};
-  int n_sp = 0;
-  rc = gq_spen_role_fill(pen, &sp, a.B, &n_sp);
+  GqPenStep ps{};
+  int rc = gq_pen_step_fill(pen, "alt_pen_step", a.B, &ps);
   if (rc) return rc;
   const int nalt = alt->energy == 1 ? (a.B + 3) / 4 : a.B;
   const size_t lds_alt = alt->energy == 1 ? (size_t)4 * a.n * 6 * sizeof(float)
                                           : ((size_t)a.n * 6 + gq_tdg_lds_floats(a.n)) * sizeof(float);
-  const size_t lds_a = std::max(pen->grid ? gq_pen_cells_lds_bytes(p.L, p.P) : gq_pen_grid_lds_bytes(p.L, GQ_PG_ECAP, GQ_PG_ICAP, ppt),
-                                lds_alt);
-  const size_t lds_b = std::max(gq_pen_bwd_lds_bytes(), n_sp ? (size_t)4 * ((size_t)sp.h.S * 16 + 512) : (size_t)0);
-  const dim3 grid_a((unsigned)(nalt + (pen->grid ? 1 : gx) * p.B)), grid_b((unsigned)(a.B + n_sp)), block(256);
+  const size_t lds_a = std::max(ps.lds_q, lds_alt);
+  const size_t lds_b = std::max(gq_pen_bwd_lds_bytes(), ps.lds_sp);
+  const dim3 grid_a((unsigned)(nalt + ps.n_q)), grid_b((unsigned)(a.B + ps.n_sp)), block(256);
   if (alt->energy == 1) {
-    if (ppt == 2) hipLaunchKernelGGL((gq_stage_alt_kernel<1, 2>), grid_a, block, lds_a, st, a, p, gx, nalt);
-    else hipLaunchKernelGGL((gq_stage_alt_kernel<1, 1>), grid_a, block, lds_a, st, a, p, gx, nalt);
+    if (ps.ppt == 2) hipLaunchKernelGGL((gq_stage_alt_kernel<1, 2>), grid_a, block, lds_a, st, a, ps.p, ps.gx, nalt);
+    else hipLaunchKernelGGL((gq_stage_alt_kernel<1, 1>), grid_a, block, lds_a, st, a, ps.p, ps.gx, nalt);
   } else {
-    if (ppt == 2) hipLaunchKernelGGL((gq_stage_alt_kernel<2, 2>), grid_a, block, lds_a, st, a, p, gx, nalt);
-    else hipLaunchKernelGGL((gq_stage_alt_kernel<2, 1>), grid_a, block, lds_a, st, a, p, gx, nalt);
+    if (ps.ppt == 2) hipLaunchKernelGGL((gq_stage_alt_kernel<2, 2>), grid_a, block, lds_a, st, a, ps.p, ps.gx, nalt);
+    else hipLaunchKernelGGL((gq_stage_alt_kernel<2, 1>), grid_a, block, lds_a, st, a, ps.p, ps.gx, nalt);
   }
   GQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gq_stage_b_alt_kernel, grid_b, block, lds_b, st, pb, sp, a.B);
+  hipLaunchKernelGGL(gq_stage_b_alt_kernel, grid_b, block, lds_b, st, ps.pb, ps.sp, a.B);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }
@@ -289,35 +298,18 @@ int gq_fc_pen_step(const gqFcStepDesc* fc, const gqPenStepDesc* pen, void* strea
                            fc->g_contact_pts, fc->g_hand_normals, fc->e_fc, fc->x_sum, fc->n_iter, fc->workspace,
                            fc->workspace_bytes, &f, &runmin);
   if (rc) return rc;
-  GqPenArgs p{};
-  rc = gq_pen_fill(pen->links, pen->surface_points, pen->n_obj, pen->n_surface, pen->batch_each, pen->hand_pose,
-                   pen->pose_dim, pen->Rg, pen->link_T, pen->dis, pen->link, pen->gvec, pen->span, &p, pen->grid);
+  GqPenStep ps{};
+  rc = gq_pen_step_fill(pen, "fc_pen_step", f.B, &ps);
   if (rc) return rc;
-  p.patch = pen->patch_spheres;
-  GQ_REQUIRE(p.occ && p.cand_off, "fc_pen_step: the link mesh set has no voxel candidate lists (gq_meshset_build_occupancy)");
-  GQ_REQUIRE(p.B == f.B, "fc_pen_step: the two descriptors disagree on the batch (%d vs %d)", p.B, f.B);
-  GqPenBwdArgs pb{};
-  rc = gq_pen_bwd_fill(p.L, pen->surface_points, pen->n_obj, pen->n_surface, pen->batch_each, pen->hand_pose, pen->pose_dim,
-                       pen->Rg, nullptr, pen->link, pen->gvec, pen->link_wrench, pen->gRt, pen->dis, pen->w_pen, pen->e_pen,
-                       pen->span, pen->span_acc, &pb);
-  if (rc) return rc;
-  const int ppt = gq_pen_points_per_thread_();
-  const int gx = pen->grid ? 0 : (p.P + 256 * ppt - 1) / (256 * ppt);  // 0: the link-driven query, one block per row
   const bool two = f.nz > GQ_WAVE;
-  GqSpenRole sp{};
-  int n_sp = 0;
-  rc = gq_spen_role_fill(pen, &sp, f.B, &n_sp);
-  if (rc) return rc;
   const int nfc = (f.B + GQ_HEAD_ROWS - 1) / GQ_HEAD_ROWS;
-  const size_t lds_a = std::max(pen->grid ? gq_pen_cells_lds_bytes(p.L, p.P) : gq_pen_grid_lds_bytes(p.L, GQ_PG_ECAP, GQ_PG_ICAP, ppt),
-                                (size_t)GQ_HEAD_ROWS * f.n * 6 * sizeof(float) + GQ_HEAD_LDS_WORDS * sizeof(unsigned));
-  const size_t lds_b = std::max(std::max(gq_pen_bwd_lds_bytes(), (size_t)f.nz * 3 * sizeof(float)),
-                                n_sp ? (size_t)4 * ((size_t)sp.h.S * 16 + 512) : (size_t)0);
-  const dim3 grid_a((unsigned)(nfc + (pen->grid ? 1 : gx) * p.B)), grid_b((unsigned)(2 * f.B + n_sp)), block(256);
-#define GQ_STAGE_A(NCV, STOPV)                                                                                        \
-  do {                                                                                                                \
-    if (ppt == 2) hipLaunchKernelGGL((gq_stage_a_kernel<NCV, STOPV, 2>), grid_a, block, lds_a, st, f, p, gx, nfc);    \
-    else hipLaunchKernelGGL((gq_stage_a_kernel<NCV, STOPV, 1>), grid_a, block, lds_a, st, f, p, gx, nfc);             \
+  const size_t lds_a = std::max(ps.lds_q, (size_t)GQ_HEAD_ROWS * f.n * 6 * sizeof(float) + GQ_HEAD_LDS_WORDS * sizeof(unsigned));
+  const size_t lds_b = std::max(std::max(gq_pen_bwd_lds_bytes(), (size_t)f.nz * 3 * sizeof(float)), ps.lds_sp);
+  const dim3 grid_a((unsigned)(nfc + ps.n_q)), grid_b((unsigned)(2 * f.B + ps.n_sp)), block(256);
+#define GQ_STAGE_A(NCV, STOPV)                                                                                               \
+  do {                                                                                                                       \
+    if (ps.ppt == 2) hipLaunchKernelGGL((gq_stage_a_kernel<NCV, STOPV, 2>), grid_a, block, lds_a, st, f, ps.p, ps.gx, nfc);  \
+    else hipLaunchKernelGGL((gq_stage_a_kernel<NCV, STOPV, 1>), grid_a, block, lds_a, st, f, ps.p, ps.gx, nfc);              \
   } while (0)
   if (f.agg) {
     if (two) GQ_STAGE_A(2, true);
@@ -334,11 +326,11 @@ int gq_fc_pen_step(const gqFcStepDesc* fc, const gqPenStepDesc* pen, void* strea
     if (rc) return rc;
   }
   if (two) {
-    if (fused_stop) hipLaunchKernelGGL((gq_stage_b_kernel<2, 4>), grid_b, block, lds_b, st, f, pb, sp);
-    else hipLaunchKernelGGL((gq_stage_b_kernel<2, 0>), grid_b, block, lds_b, st, f, pb, sp);
+    if (fused_stop) hipLaunchKernelGGL((gq_stage_b_kernel<2, 4>), grid_b, block, lds_b, st, f, ps.pb, ps.sp);
+    else hipLaunchKernelGGL((gq_stage_b_kernel<2, 0>), grid_b, block, lds_b, st, f, ps.pb, ps.sp);
   } else {
-    if (fused_stop) hipLaunchKernelGGL((gq_stage_b_kernel<1, 4>), grid_b, block, lds_b, st, f, pb, sp);
-    else hipLaunchKernelGGL((gq_stage_b_kernel<1, 0>), grid_b, block, lds_b, st, f, pb, sp);
+    if (fused_stop) hipLaunchKernelGGL((gq_stage_b_kernel<1, 4>), grid_b, block, lds_b, st, f, ps.pb, ps.sp);
+    else hipLaunchKernelGGL((gq_stage_b_kernel<1, 0>), grid_b, block, lds_b, st, f, ps.pb, ps.sp);
   }
   GQ_LAUNCH_CHECK();
   return GQ_OK;

@@ -987,12 +987,8 @@ def _hand_pen_op(hand_pose: Tensor, surface_points: Tensor, batch_each: int, han
     dis = torch.empty(B, P, device=dev)
     link = torch.zeros(B, P, dtype=torch.int32, device=dev)  # mode 1 writes link / gvec only where dis > 0
     gvec = torch.zeros(B, P, 3, device=dev)
-    pws, pnb = None, 0
-    if int(penetration_only) == 3:  # queue path without candidate lists (kept for A/B tests)
-        pnb = _size_call("gq_hand_pen_workspace_bytes", ctypes.c_int64(B), ctypes.c_int64(P), h.L)
-        pws = torch.zeros(pnb, dtype=torch.uint8, device=dev)  # queue counters must start at zero
     _C.call("gq_hand_pen_forward", h.links.handle, _C.f32(sp), n_obj, P, int(batch_each), _C.f32(hp), hp.shape[1],
-            _C.f32(_c(Rg)), _C.f32(_c(LT)), int(penetration_only), _C.f32(dis), _C.i32(link), _C.f32(gvec), _C.ptr(pws), pnb,
+            _C.f32(_c(Rg)), _C.f32(_c(LT)), int(penetration_only), _C.f32(dis), _C.i32(link), _C.f32(gvec), None, 0,
             None, None, None, _C.stream_ptr())
     return dis, link, gvec
 
@@ -1023,10 +1019,18 @@ def _(n_links, surface_points, batch_each, hand_pose, Rg, g, link, gvec):
     return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
 
 
+def pen_mode(penetration_only) -> int:
+    """0 (False: the exact query) or 1 (True: exact only where dis > 0, which is all E_pen reads); anything else raises."""
+    if penetration_only not in (0, 1):  # bools included
+        raise ValueError(f"penetration_only={penetration_only!r}: accepted values are False / 0 (exact query) and "
+                         "True / 1 (penetration-only query)")
+    return int(penetration_only)
+
+
 def hand_pen(hand_pose, surface_points, batch_each, hand, idx, Rg, LT, ws, nb=None, penetration_only=False):
     """(B,P) max-over-links signed distance, differentiable w.r.t. hand_pose (see the op's docstring)."""
     return _HandPen.apply(hand_pose, surface_points, int(batch_each), hand, idx, Rg.detach(), LT.detach(), ws,
-                          int(penetration_only))
+                          pen_mode(penetration_only))
 
 
 class _HandPen(torch.autograd.Function):

@@ -35,6 +35,7 @@ class GraspStepper:
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
+        self.penetration_only = ops.pen_mode(penetration_only)  # 1: E_pen only needs dis > 0 (energy.py:59-61)
         self.split_self_pen = bool(split_self_pen)  # False: A/B switch, self penetration stays in the FK forward launch
         self.hand, self.objs = hand, object_meshes
         self.dev = torch.device(device)
@@ -96,10 +97,6 @@ class GraspStepper:
         self.fc_nb = ops._size_call("gq_fc_workspace_bytes", ctypes.c_int64(B), n, int(self.fc["n_cone_vecs"]),
                                     int(self.fc["max_iter"]))
         self.fc_ws = ops._ws(self.fc_nb, self.dev).zero_()  # zero once: block counter of the large-batch stop rule
-        self.pen_nb, self.pen_ws = 0, None
-        if int(penetration_only) == 3:  # queue path of the penetration query (A/B tests); counters start at zero
-            self.pen_nb = ops._size_call("gq_hand_pen_workspace_bytes", ctypes.c_int64(B), ctypes.c_int64(P), self.L)
-            self.pen_ws = torch.zeros(self.pen_nb, dtype=torch.uint8, device=self.dev)
         self._graph, self._graph_iters, self._graph_pending = None, 1, 0
         self._after_reset = False
         self._reinit = None  # 0-dim device flag of the last step_reset: did its mask select any row (fit.py:412)
@@ -108,7 +105,6 @@ class GraspStepper:
         self._span[:, 0] = -1  # {~0, 0}: armed
         self._span_acc = torch.zeros(2, dtype=torch.int64, device=self.dev)
         self._side = None
-        self.penetration_only = int(penetration_only)  # E_pen only needs dis > 0 (energy.py:59-61)
         self._can_fuse = self.penetration_only == 1  # every energy type has a fused form (gq_fc_pen_step / gq_alt_pen_step)
         # bounding spheres of the 256-point slices of the surface points: block-level link pre-cull of the penetration query
         self.patch = torch.empty(self.n_obj, (self.P + 255) // 256, 4, device=self.dev)
@@ -258,7 +254,7 @@ class GraspStepper:
             _C.call("gq_hand_pen_forward", self.hand.links.handle, _C.f32(self.surf), self.n_obj, self.P, self.be,
                     _C.f32(pose), self.D, _C.f32(self.Rg), _C.f32(self.link_T), int(self.penetration_only),
                     _C.f32(self.pen_dis), _C.i32(self.pen_link), _C.f32(self.pen_gvec),
-                    _C.ptr(self.pen_ws), self.pen_nb, timer, _C.ptr(self._span), _C.f32(self.patch), st)
+                    None, 0, timer, _C.ptr(self._span), _C.f32(self.patch), st)
         _C.call("gq_hand_pen_backward", self.L, _C.f32(self.surf), self.n_obj, self.P, self.be, _C.f32(pose), self.D,
                 _C.f32(self.Rg), None, _C.i32(self.pen_link), _C.f32(self.pen_gvec), _C.f32(self.wrench), _C.f32(self.gRt),
                 _C.f32(self.pen_dis), float(self.w["E_pen"]), _C.f32(self.terms_new[2]), _C.ptr(self._span),

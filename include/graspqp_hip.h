@@ -38,7 +38,7 @@ typedef struct gqMeshSet gqMeshSet; /* n_mesh triangle soups resident on the dev
 int gq_meshset_create(const float* face_verts_host /* (sumF,3,3) */, const int32_t* face_offset_host /* (n_mesh+1) */,
                       int n_mesh, gqMeshSet** out);
 int gq_meshset_destroy(gqMeshSet* ms);
-/* setup-time 32^3 occupancy grid per mesh; enables the penetration_only = 1 fast path of gq_hand_pen_forward */
+/* setup-time 32^3 occupancy grid + per-voxel candidate faces per mesh; required by penetration_only = 1 and the fused steps */
 int gq_meshset_build_occupancy(gqMeshSet* ms);
 int gq_meshset_num_faces(const gqMeshSet* ms, int mesh /* -1 = all */, int64_t* n);
 int gq_sdf_workspace_bytes(int64_t n_faces, size_t* bytes);
@@ -334,17 +334,19 @@ int gq_root_pose_wxyz(const float* hand_pose, int64_t batch, int pose_dim, float
 /* ---- hand penetration: HandModel.cal_distance (E_pen) --------------------------------------------------
  * reference: core/hand_model.py:875-987, core/energy.py:57-62.  links = mesh set of the L link meshes.
  * dis (B,P) = max over links of sqrt(d^2 + 1e-8) * (-sign); link (B,P) argmax; gvec (B,P,3) = d dis / d x_h.
- * penetration_only = 0: dis exact everywhere.
+ * penetration_only = 0: the exact query, dis exact everywhere (links culled by their boxes only).
  * penetration_only = 1: what E_pen uses (energy.py:59-61 zeroes dis <= 0): dis is exact where it is > 0 and -1e30
  *   elsewhere; link / gvec are WRITTEN ONLY where dis > 0 (pass zero-initialised buffers).  Per link a point is looked
- *   up in the 32^3 voxel grid of the link mesh (gq_meshset_build_occupancy) and only the voxel's candidate faces are
- *   ranked.  = 2: AABB culling only, = 3: occupancy grid + load-balancing queues (needs the workspace) -- both kept
- *   for A/B tests; they write link / gvec everywhere.                                                          */
+ *   up in the 32^3 voxel grid of the link mesh and only the voxel's candidate faces are ranked; the mesh set must have
+ *   its voxel lists (gq_meshset_build_occupancy), otherwise the call fails.
+ * penetration_only = 9: diagnostics -- the scan of the voxel query without candidate evaluation (timing runs; the
+ *   outputs are meaningless).  Any other value is refused with an error status.
+ * workspace / workspace_bytes are ignored (pass NULL, 0); they remain for ABI stability.                          */
 int gq_hand_pen_forward(const gqMeshSet* links, const float* surface_points /* (n_obj,P,3) */, int64_t n_obj,
                         int64_t n_surface, int64_t batch_each, const float* hand_pose, int pose_dim, const float* Rg,
                         const float* link_T, int penetration_only, float* dis, int32_t* link, float* gvec,
-                        void* workspace /* NULL, or gq_hand_pen_workspace_bytes (ZEROED before first use): load-balanced path */,
-                        size_t workspace_bytes, void* timer /* gqTimer or NULL */,
+                        void* workspace /* ignored: NULL */, size_t workspace_bytes /* ignored: 0 */,
+                        void* timer /* gqTimer or NULL */,
                         uint64_t* span /* NULL, or {min start, max end} in 100 MHz device ticks, pre-set to {~0, 0} */,
                         const float* patch_spheres /* NULL, or gq_surface_patches of surface_points: lets every block of
                                                       the penetration_only = 1 query drop the links out of reach first */,
@@ -352,7 +354,6 @@ int gq_hand_pen_forward(const gqMeshSet* links, const float* surface_points /* (
 /* Bounding sphere (centre xyz, radius) of every 256-point slice of every object's surface points, (n_obj, ceil(P/256), 4);
  * set-up time.  Surface points in Morton order (graspqp_amd.utils.meshes.surface_points) give compact slices.        */
 int gq_surface_patches(const float* surface_points, int64_t n_obj, int64_t n_surface, float* patch_spheres, void* stream);
-int gq_hand_pen_workspace_bytes(int64_t batch, int64_t n_surface, int n_links, size_t* bytes);
 /* The same penetration-only query (penetration_only = 1: dis exact where > 0, -1e30 elsewhere; link / gvec written only
  * where dis > 0) driven by the LINKS: a coarse uniform grid over every object's surface points (gqPointGrid, set-up
  * time; cells_per_axis 0 = default 8) lets a row's block test only the points filed under the cells a link's box can

@@ -560,7 +560,7 @@ def test_hand_penetration_and_self_penetration(gq):
     # penetration-only mode (what E_pen uses): same values where dis > 0 (two template instantiations of one
     # kernel: FMA contraction may differ in the last bit), non-positive elsewhere
     pos = dis > 1e-6
-    for mode in (1, 3, 2):  # 1 = voxel candidate lists, 3 = occupancy grid + queues, 2 = AABB culling only
+    for mode in (1,):  # the voxel-candidate query
         dis3 = hm.cal_distance(om.surface_points_each, penetration_only=mode)
         # ranking distances carry ~1e-10 m^2 of round-off -> near-tied faces may swap: 3e-6 m on the distance
         torch.testing.assert_close(dis3[pos], dis[pos], rtol=2e-4, atol=3e-6)
@@ -572,6 +572,44 @@ def test_hand_penetration_and_self_penetration(gq):
         torch.relu(hm.cal_distance(om.surface_points_each, penetration_only=mode)).sum().backward()
         grads.append(hm.hand_pose.grad.clone())
     assert (grads[0] - grads[1]).norm() <= 5e-3 * grads[1].norm()
+
+
+def test_retired_penetration_modes_are_refused(gq):
+    """penetration_only = 2 / 3 (AABB-only and queue routes, retired) never reach the C ABI from Python, and the C ABI
+    itself refuses them before it launches anything: the output buffers keep their sentinel."""
+    from graspqp_amd.core.hand_model import HandModel
+    from graspqp_amd.core.object_model import ObjectModel
+
+    _C, ops = gq.C, gq.ops
+    spec = get_hand_spec("allegro")
+    be, P = 2, 300
+    fvs = [meshes.icosphere(2, 0.05)]
+    sps = [meshes.surface_points(f, P, oversample=4) for f in fvs]
+    hp = _rand_pose(spec, be, 11, spread=0.03).float().cuda()
+    idx = torch.randint(spec.n_contact_candidates, (be, 4), generator=torch.Generator().manual_seed(2)).cuda()
+    hm = HandModel(spec, "cuda")
+    om = ObjectModel(batch_size_each=be, num_samples=P)
+    om.initialize_from_meshes(fvs, surface_points_list=sps)
+    hm.set_parameters(hp, idx)
+    surf = om.surface_points_each
+    for mode in (2, 3):
+        with pytest.raises(ValueError, match="accepted values"):
+            hm.cal_distance(surf, penetration_only=mode)
+        with pytest.raises(ValueError, match="accepted values"):
+            ops.hand_pen(hm.hand_pose, surf, be, hm._hand, hm.contact_point_indices, hm.global_rotation, hm.current_status,
+                         hm._fk_ws, penetration_only=mode)
+        with pytest.raises(ValueError, match="accepted values"):
+            gq.stepper.GraspStepper(hm._hand, ops.MeshSet(fvs), surf, be, 4, penetration_only=mode)
+    dis = torch.full((be, P), 12345.0, device="cuda")
+    link = torch.full((be, P), -7, dtype=torch.int32, device="cuda")
+    gvec = torch.full((be, P, 3), 12345.0, device="cuda")
+    Rg, LT = hm.global_rotation.detach().contiguous(), hm.current_status.detach().contiguous()
+    with pytest.raises(RuntimeError, match="accepted values"):  # _C.call turns a non-zero status into RuntimeError
+        _C.call("gq_hand_pen_forward", hm._hand.links.handle, _C.f32(surf), 1, P, be, _C.f32(hm.hand_pose.detach()),
+                hm.hand_pose.shape[1], _C.f32(Rg), _C.f32(LT), 3, _C.f32(dis), _C.i32(link), _C.f32(gvec), None, 0, None, None,
+                None, _C.stream_ptr())
+    torch.cuda.synchronize()
+    assert (dis == 12345.0).all() and (link == -7).all() and (gvec == 12345.0).all()
 
 
 # ---------------------------------------------------------------------------------------------------------------
