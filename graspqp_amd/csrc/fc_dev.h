@@ -81,6 +81,19 @@ __device__ __forceinline__ GqContactTerm gq_contact_term(float d2, float sg, gq3
   o.g_n = (w_dis * e * root) * o.vC;
   return o;
 }
+// the three global outputs of contact t: (B,n,3) each
+__device__ __forceinline__ void gq_contact_term_store(const GqContactTerm& c, size_t t, float* obj_normal, float* g_cpts,
+                                                      float* g_cnrm) {
+  obj_normal[t * 3] = c.vC.x;
+  obj_normal[t * 3 + 1] = c.vC.y;
+  obj_normal[t * 3 + 2] = c.vC.z;
+  g_cpts[t * 3] = c.g_p.x;
+  g_cpts[t * 3 + 1] = c.g_p.y;
+  g_cpts[t * 3 + 2] = c.g_p.z;
+  g_cnrm[t * 3] = c.g_n.x;
+  g_cnrm[t * 3 + 1] = c.g_n.y;
+  g_cnrm[t * 3 + 2] = c.g_n.z;
+}
 
 // ---- host side: layout of the E_fc workspace (gq_fc_workspace_bytes) ----------------------------------------------
 static inline size_t gq_al(size_t v) { return (v + 255) & ~(size_t)255; }

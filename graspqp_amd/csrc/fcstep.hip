@@ -51,15 +51,17 @@ int gq_fc_step(const float* dist_sq, const int32_t* sign, const float* obj_dir, 
   hipStream_t st = (hipStream_t)stream;
   GqFcStepArgs a{};
   float* runmin = nullptr;
-  int rc = gq_fc_step_fill(dist_sq, sign, obj_dir, closest, contact_pts, hand_normals, cog, batch, n_contact, n_cone,
-                           friction, torque_weight, max_limit, svd_gain, values_gain, eps, max_iter, w_dis, w_fc, obj_normal,
-                           g_contact_pts, g_hand_normals, e_fc, x_sum, n_iter, workspace, workspace_bytes, &a, &runmin);
+  const gqFcStepDesc d = {dist_sq, sign, obj_dir, closest, contact_pts, hand_normals, cog, batch, n_contact, n_cone,
+                          friction, torque_weight, max_limit, svd_gain, values_gain, eps, max_iter, w_dis, w_fc,
+                          obj_normal, g_contact_pts, g_hand_normals, e_fc, x_sum, n_iter, workspace, workspace_bytes};
+  GqFcStop stop;
+  int rc = gq_fc_step_fill(d, &a, &runmin, &stop);
   if (rc) return rc;
   const int nz = a.nz;
   const dim3 grid((unsigned)batch), block(GQ_WAVE);
   const size_t lds_head = (size_t)n_contact * 6 * sizeof(float), lds_tail = (size_t)nz * 3 * sizeof(float);
   const bool two = nz > GQ_WAVE;
-  if (a.agg) {  // the stop rule rides in the head launch (see gq_fc_head_epilogue)
+  if (stop == GQ_STOP_HEAD) {  // the stop rule rides in the head launch (see gq_fc_head_epilogue)
     const dim3 hgrid((unsigned)a.head_blocks), hblock(GQ_HEAD_ROWS * GQ_WAVE);
     const size_t lds = GQ_HEAD_ROWS * lds_head + GQ_HEAD_LDS_WORDS * sizeof(unsigned);
     if (two) hipLaunchKernelGGL((gq_fc_head_stop_kernel<2>), hgrid, hblock, lds, st, a);
@@ -70,8 +72,8 @@ int gq_fc_step(const float* dist_sq, const int32_t* sign, const float* obj_dir, 
     hipLaunchKernelGGL((gq_fc_head_kernel<1>), grid, block, lds_head, st, a);
   }
   GQ_LAUNCH_CHECK();
-  const bool fused_stop = batch <= 4 * GQ_WAVE && max_iter <= 16;
-  if (!fused_stop && !a.agg) {
+  const bool fused_stop = stop == GQ_STOP_TAIL;
+  if (stop == GQ_STOP_LAUNCH) {
     rc = gq_qp_stop_launch_(a.resid, a.mu_tab, a.B, max_iter, eps, a.not_improved_lim, runmin, a.kstar, n_iter, stream);
     if (rc) return rc;
   }

@@ -53,15 +53,7 @@ __device__ __forceinline__ void gq_fc_head_body(const GqFcStepArgs& g, int row, 
     const gq3 p = gq_mk(g.cpts[t * 3], g.cpts[t * 3 + 1], g.cpts[t * 3 + 2]);
     const gq3 cl = gq_mk(g.closest[t * 3], g.closest[t * 3 + 1], g.closest[t * 3 + 2]);
     const GqContactTerm ct = gq_contact_term(g.dist_sq[t], (float)g.sign[t], on, nH, p, cl, g.w_dis);
-    g.obj_normal[t * 3] = ct.vC.x;
-    g.obj_normal[t * 3 + 1] = ct.vC.y;
-    g.obj_normal[t * 3 + 2] = ct.vC.z;
-    g.g_cpts[t * 3] = ct.g_p.x;
-    g.g_cpts[t * 3 + 1] = ct.g_p.y;
-    g.g_cpts[t * 3 + 2] = ct.g_p.z;
-    g.g_cnrm[t * 3] = ct.g_n.x;
-    g.g_cnrm[t * 3 + 1] = ct.g_n.y;
-    g.g_cnrm[t * 3 + 2] = ct.g_n.z;
+    gq_contact_term_store(ct, t, g.obj_normal, g.g_cpts, g.g_cnrm);
     s_cp[c * 3] = p.x;
     s_cp[c * 3 + 1] = p.y;
     s_cp[c * 3 + 2] = p.z;
@@ -498,69 +490,68 @@ __device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, 
 }
 
 
-// ---- host side: argument block of the fused step (parameters of gq_fc_step) ----------------------------------------
+// ---- host side: argument block of the fused step (fields of gqFcStepDesc = parameters of gq_fc_step) ----------------------------------------
 int gq_qp_tables_(void* workspace, size_t workspace_bytes, int B, int nz, int max_iter, float** resid, float** mu,
                   float** snap, float** runmin, int** kstar, unsigned** agg);
 
-static inline int gq_fc_step_fill(const float* dist_sq, const int32_t* sign, const float* obj_dir, const float* closest,
-                                  const float* contact_pts, const float* hand_normals, const float* cog, int64_t batch,
-                                  int n_contact, int n_cone, float friction, float torque_weight, float max_limit,
-                                  float svd_gain, float values_gain, float eps, int max_iter, float w_dis, float w_fc,
-                                  float* obj_normal, float* g_contact_pts, float* g_hand_normals, float* e_fc,
-                                  float* x_sum, int32_t* n_iter, void* workspace, size_t workspace_bytes,
-                                  GqFcStepArgs* out, float** runmin) {
-  GQ_REQUIRE(dist_sq && sign && obj_dir && closest && contact_pts && hand_normals && cog && obj_normal &&
-                 g_contact_pts && g_hand_normals && e_fc && workspace,
+// where qpth's batch-global stop rule runs: replayed per row by the tail (small batches) | as epilogue of the head block
+// that finishes last (gq_fc_head_epilogue) | in a launch of its own between head and tail (max_iter > 16)
+enum GqFcStop { GQ_STOP_TAIL, GQ_STOP_HEAD, GQ_STOP_LAUNCH };
+
+static inline int gq_fc_step_fill(const gqFcStepDesc& d, GqFcStepArgs* out, float** runmin, GqFcStop* stop) {
+  GQ_REQUIRE(d.dist_sq && d.sign && d.obj_dir && d.closest && d.contact_pts && d.hand_normals && d.cog && d.obj_normal &&
+                 d.g_contact_pts && d.g_hand_normals && d.e_fc && d.workspace,
              "fc_step: null pointer");
-  GQ_REQUIRE(batch > 0 && n_contact > 0 && n_cone > 0, "fc_step: bad sizes");
-  const int nz = n_contact * n_cone;
+  GQ_REQUIRE(d.batch > 0 && d.n_contact > 0 && d.n_cone > 0, "fc_step: bad sizes");
+  const int nz = d.n_contact * d.n_cone;
   GQ_REQUIRE(nz <= 128, "fc_step: n_contact * n_cone = %d exceeds 128", nz);
-  GQ_REQUIRE(max_iter >= 1 && max_iter <= 64, "fc_step: max_iter=%d out of range", max_iter);
+  GQ_REQUIRE(d.max_iter >= 1 && d.max_iter <= 64, "fc_step: max_iter=%d out of range", d.max_iter);
   size_t need = 0;
-  int rc = gq_fc_workspace_bytes(batch, n_contact, n_cone, max_iter, &need);
+  int rc = gq_fc_workspace_bytes(d.batch, d.n_contact, d.n_cone, d.max_iter, &need);
   if (rc) return rc;
-  GQ_REQUIRE(workspace_bytes >= need, "fc_step: workspace too small (%zu < %zu)", workspace_bytes, need);
-  GqFcWs w = gq_fc_carve(workspace, (size_t)batch, (size_t)nz, workspace_bytes);
+  GQ_REQUIRE(d.workspace_bytes >= need, "fc_step: workspace too small (%zu < %zu)", d.workspace_bytes, need);
+  GqFcWs w = gq_fc_carve(d.workspace, (size_t)d.batch, (size_t)nz, d.workspace_bytes);
   GqFcStepArgs a{};
-  rc = gq_qp_tables_(w.qp, w.qp_bytes, (int)batch, nz, max_iter, &a.resid, &a.mu_tab, &a.snap, runmin, &a.kstar, &a.agg);
+  rc = gq_qp_tables_(w.qp, w.qp_bytes, (int)d.batch, nz, d.max_iter, &a.resid, &a.mu_tab, &a.snap, runmin, &a.kstar, &a.agg);
   if (rc) return rc;
   a.head_ctr = reinterpret_cast<unsigned*>(a.kstar) + 8;
-  a.head_blocks = ((int)batch + GQ_HEAD_ROWS - 1) / GQ_HEAD_ROWS;
-  if (max_iter > 16 || batch <= 4 * GQ_WAVE) a.agg = nullptr;  // stop launch | replayed per row by the tail
-  a.dist_sq = dist_sq;
-  a.sign = sign;
-  a.onrm = obj_dir;
-  a.closest = closest;
-  a.cpts = contact_pts;
-  a.cnrm = hand_normals;
-  a.cog = cog;
-  a.B = (int)batch;
-  a.n = n_contact;
-  a.k = n_cone;
+  a.head_blocks = ((int)d.batch + GQ_HEAD_ROWS - 1) / GQ_HEAD_ROWS;
+  *stop = d.max_iter > 16 ? GQ_STOP_LAUNCH : d.batch <= 4 * GQ_WAVE ? GQ_STOP_TAIL : GQ_STOP_HEAD;
+  if (*stop != GQ_STOP_HEAD) a.agg = nullptr;
+  a.dist_sq = d.dist_sq;
+  a.sign = d.sign;
+  a.onrm = d.obj_dir;
+  a.closest = d.closest;
+  a.cpts = d.contact_pts;
+  a.cnrm = d.hand_normals;
+  a.cog = d.cog;
+  a.B = (int)d.batch;
+  a.n = d.n_contact;
+  a.k = d.n_cone;
   a.nz = nz;
-  a.max_iter = max_iter;
+  a.max_iter = d.max_iter;
   a.not_improved_lim = 3;
-  a.mu = friction;
-  a.tw = torque_weight;
-  a.w_dis = w_dis;
-  a.w_fc = w_fc;
+  a.mu = d.friction;
+  a.tw = d.torque_weight;
+  a.w_dis = d.w_dis;
+  a.w_fc = d.w_fc;
   a.lower = 1.0f;  // bounds 1 <= x <= max_limit + 1, b = 0, ridge 1e-4 (span.py:348-349, qp_solver.py:101-112)
-  a.upper = max_limit + 1.0f;
+  a.upper = d.max_limit + 1.0f;
   a.ridge = 1e-4f;
-  a.svd_gain = svd_gain;
-  a.values_gain = values_gain;
+  a.svd_gain = d.svd_gain;
+  a.values_gain = d.values_gain;
   a.eps_add = 1e-2f;
-  a.eps = eps;
-  a.obj_normal = obj_normal;
-  a.g_cpts = g_contact_pts;
-  a.g_cnrm = g_hand_normals;
+  a.eps = d.eps;
+  a.obj_normal = d.obj_normal;
+  a.g_cpts = d.g_contact_pts;
+  a.g_cnrm = d.g_hand_normals;
   a.F = w.F;
-  a.n_iter = n_iter;
-  a.e_fc = e_fc;
+  a.n_iter = d.n_iter;
+  a.e_fc = d.e_fc;
   a.val = w.val;
   a.svd = w.svd;
   a.x = w.x;
-  a.x_sum = x_sum;
+  a.x_sum = d.x_sum;
   *out = a;
   return GQ_OK;
 }

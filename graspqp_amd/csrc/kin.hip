@@ -2,9 +2,10 @@
 // and the analytic backward pass (geometric Jacobian via per-node wrench accumulation) that replaces autograd
 // through pytorch_kinematics (reference hand_model.py:762-766, 787-873, 1220-1267; utils/transforms.py:5-13).
 //
-// Work shape: one thread per grasp candidate (row).  Per row the work is ~2 kflop of strictly sequential 3x3
-// products down a 16-24 joint tree, i.e. latency- not throughput-bound; the per-row scratch (node transforms,
-// node wrenches) lives in a caller-provided workspace so nothing is dynamically indexed in registers.
+// Work shape: one wavefront per grasp candidate (row), lane j = joint node j.  Per row the work is ~2 kflop of
+// sequential 3x3 products down a 16-24 joint tree, i.e. latency- not throughput-bound.  The node frames of the forward
+// pass live in a caller-provided workspace (the backward pass and the export-time Jacobians read them); the node
+// wrenches of the backward pass are folded in LDS.
 #include "kin_dev.h"
 #include "loop_dev.h"
 #include "sdf_dev.h"
@@ -247,7 +248,8 @@ struct GqFkBwdArgs {
   const float* g_theta;    // (B,J) direct joint-angle gradient (E_joints) or null
   const float* g_R;        // (B,9) direct gradient on the global rotation matrix or null
   int B, n, D;
-  float* node_F;     // (B, J, 6) workspace
+  float* reserved;   // unread (once a (B, J, 6) workspace; the kernel folds in LDS): keeps the kernel-argument offsets of
+                     // the members below, and with them the instructions of this timed kernel, as they were
   float* grad_pose;  // (B, D)
   gqRowEnergyDesc en;  // en.total != nullptr: E_dis, E_joints (+ its gradient) and the weighted total ride along
   int has_accept;      // MalaStar.accept_step runs last in the same wavefront (needs en.total)
@@ -526,66 +528,16 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_fk_backward_kernel(GqFkBwdArgs g) 
   }
 }
 
-// ---- self penetration (hand_model.py:989-1040) ----------------------------------------------------------------------
-// block = 64 threads = 4 rows x 16 lanes; lane (row, q) scans sphere groups q, q+16, ... (a group = the spheres of
-// one link), finds each group's most penetrating pair against all LATER groups, then lane q == 0 folds the groups
-// in order (bitwise reproducible) into the energy and the centre gradients.
-__global__ __launch_bounds__(64) void gq_self_pen_kernel(gqHand h, const float* __restrict__ centers, int B,
-                                                         float gscale, float* __restrict__ e_spen,
-                                                         float* __restrict__ g_centers) {
-  __shared__ float s_pen[4][64];
-  __shared__ int s_a[4][64], s_b[4][64];
-  __shared__ float s_c[4][256 * 3];
-  const int r4 = threadIdx.x >> 4, q = threadIdx.x & 15;
-  const int row = blockIdx.x * 4 + r4;
-  const bool ok = row < B;
-  for (int i = q; i < h.S * 3; i += 16) s_c[r4][i] = centers[(size_t)(ok ? row : 0) * h.S * 3 + i];
-  __syncthreads();
-  const float* c = s_c[r4];
-  const int ng = h.NG - 1;  // the last group has nothing after it
-  for (int gi = q; gi < ng && gi < 64; gi += 16) {
-    const int a0 = h.group_off[gi], a1 = h.group_off[gi + 1];
-    float best = GQ_INF_F;
-    int ba = -1, bb = -1;
-    for (int a = a0; a < a1; ++a) {
-      const gq3 pa = gq_mk(c[a * 3], c[a * 3 + 1], c[a * 3 + 2]);
-      const float ra = h.sphere[a * 4 + 3];
-      for (int b = a1; b < h.S; ++b) {
-        const gq3 d = gq_mk(pa.x - c[b * 3] + 1e-13f, pa.y - c[b * 3 + 1] + 1e-13f, pa.z - c[b * 3 + 2] + 1e-13f);
-        const float pen = sqrtf(gq_dot(d, d)) - (ra + h.sphere[b * 4 + 3]);
-        if (pen < best) {
-          best = pen;
-          ba = a;
-          bb = b;
-        }
-      }
-    }
-    s_pen[r4][gi] = best;
-    s_a[r4][gi] = ba;
-    s_b[r4][gi] = bb;
-  }
-  __syncthreads();
-  if (!ok) return;
-  float* gc = g_centers + (size_t)row * h.S * 3;
-  for (int i = q; i < h.S * 3; i += 16) gc[i] = 0.0f;
-  __syncthreads();
-  if (q != 0) return;
-  float e = 0.0f;
-  for (int gi = 0; gi < ng && gi < 64; ++gi) {
-    const float best = s_pen[r4][gi];
-    const int ba = s_a[r4][gi], bb = s_b[r4][gi];
-    if (best < 0.0f && ba >= 0) {
-      e -= best;
-      const gq3 d = gq_mk(c[ba * 3] - c[bb * 3] + 1e-13f, c[ba * 3 + 1] - c[bb * 3 + 1] + 1e-13f,
-                          c[ba * 3 + 2] - c[bb * 3 + 2] + 1e-13f);
-      const float inv = 1.0f / sqrtf(gq_dot(d, d));
-      // E += -|a-b| + ... : dE/da = -(a-b)/|a-b|, dE/db = +(a-b)/|a-b|
-      const float sc = gscale * inv;
-      gc[ba * 3] -= d.x * sc; gc[ba * 3 + 1] -= d.y * sc; gc[ba * 3 + 2] -= d.z * sc;
-      gc[bb * 3] += d.x * sc; gc[bb * 3 + 1] += d.y * sc; gc[bb * 3 + 2] += d.z * sc;
-    }
-  }
-  e_spen[row] = e;
+// ---- self penetration (hand_model.py:989-1040) on given world centres ----------------------------------------------
+// one wavefront per row stages the centres and the radii in LDS and runs the scan of the fused forms (kin_dev.h)
+__global__ __launch_bounds__(GQ_WAVE) void gq_self_pen_row_kernel(gqHand h, GqSpenArgs g, const float* __restrict__ centers) {
+  __shared__ float sC[256 * 3];
+  __shared__ unsigned long long sKey[64];
+  __shared__ float sRad[256];
+  const int row = blockIdx.x, lane = gq_lane();
+  for (int i = lane; i < h.S * 3; i += GQ_WAVE) sC[i] = centers[(size_t)row * h.S * 3 + i];
+  for (int sidx = lane; sidx < h.S; sidx += GQ_WAVE) sRad[sidx] = h.sphere[sidx * 4 + 3];
+  gq_self_pen_scan(h, g, row, lane, sC, sKey, sRad);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -699,10 +651,10 @@ int gq_hand_destroy(gqHand* h) {
   return GQ_OK;
 }
 
-// workspace: node_W (B,J,12) floats [kept for backward] + node_F (B,J,6) floats
+// workspace: node_W (B,J,12) floats, the node frames kept for the backward pass and the export-time Jacobians
 int gq_fk_workspace_bytes(const gqHand* h, int64_t batch, size_t* bytes) {
   GQ_REQUIRE(h && bytes && batch >= 0, "fk_workspace_bytes: bad arguments");
-  *bytes = (size_t)batch * h->J * 18 * sizeof(float) + 256;
+  *bytes = (size_t)batch * h->J * 12 * sizeof(float) + 256;
   return GQ_OK;
 }
 
@@ -715,7 +667,7 @@ int gq_fk_forward(const gqHand* h, const float* hand_pose, const int64_t* contac
              "fk_forward: the fused self-penetration term needs sphere_centers and g_sphere_centers");
   GQ_REQUIRE(batch > 0 && n_contact >= 0, "fk_forward: bad sizes");
   GQ_REQUIRE(n_contact == 0 || (contact_idx && contact_points && contact_normals), "fk_forward: null contact buffers");
-  GQ_REQUIRE(workspace_bytes >= (size_t)batch * h->J * 18 * sizeof(float), "fk_forward: workspace too small");
+  GQ_REQUIRE(workspace_bytes >= (size_t)batch * h->J * 12 * sizeof(float), "fk_forward: workspace too small");
   GqFkArgs a{};
   a.h = *h;
   a.hand_pose = hand_pose;
@@ -734,37 +686,12 @@ int gq_fk_forward(const gqHand* h, const float* hand_pose, const int64_t* contac
   a.spen_scale = spen_scale;
   if (propose) {
     const gqProposeDesc& p = *propose;
-    GQ_REQUIRE(p.hand_pose && p.grad && p.contact_idx && p.u_switch && p.new_idx && p.ema && p.step && p.slot_ctr &&
-                   p.slots > 0 && p.stepsize_period > 0 && contact_idx && a.D <= 128,
-               "fk_forward: incomplete gqProposeDesc");
-    GQ_REQUIRE(p.g2_scratch, "fk_forward: gqProposeDesc.g2_scratch (D floats) is missing");
-    GQ_REQUIRE(!p.energy || (p.z_out && p.batch_each > 1), "fk_forward: z-score needs z_out and batch_each > 1");
+    GQ_REQUIRE(p.slot_ctr && contact_idx, "fk_forward: incomplete gqProposeDesc");
+    GQ_REQUIRE(!p.energy || p.batch_each > 1, "fk_forward: z-score needs z_out and batch_each > 1");
+    const int rc = gq_propose_fill(p, "fk_forward", batch, a.D, n_contact, const_cast<float*>(hand_pose),
+                                   const_cast<int64_t*>(contact_idx), &a.pr);
+    if (rc) return rc;
     a.has_propose = 1;
-    a.pr.hand_pose = p.hand_pose;
-    a.pr.grad = p.grad;
-    a.pr.g2 = p.g2_scratch;
-    a.pr.idx = p.contact_idx;
-    a.pr.u_switch = p.u_switch;
-    a.pr.new_idx = p.new_idx;
-    a.pr.B = (int)batch;
-    a.pr.D = a.D;
-    a.pr.n = n_contact;
-    a.pr.clip = p.clip_grad;
-    a.pr.step_size = p.step_size;
-    a.pr.decay = p.decay;
-    a.pr.mu = p.mu;
-    a.pr.switch_p = p.switch_possibility;
-    a.pr.stepsize_period = p.stepsize_period;
-    a.pr.ema = p.ema;
-    a.pr.step = p.step;
-    a.pr.pose_out = const_cast<float*>(hand_pose);
-    a.pr.idx_out = const_cast<int64_t*>(contact_idx);
-    a.pr.s_out = p.step_size_out;
-    a.pr.energy = p.energy;
-    a.pr.batch_each = (int)p.batch_each;
-    a.pr.z_out = p.z_out;
-    a.pr.slot_ctr = p.slot_ctr;
-    a.pr.slots = p.slots;
   }
   int nw = 1;
   if (sdf) {  // the contact queries of a row are answered by the row's block: up to 12 query wavefronts
@@ -807,7 +734,7 @@ int gq_fk_backward(const gqHand* h, const float* hand_pose, const int64_t* conta
                "fk_backward: incomplete gqRowEnergyDesc");
   }
   GQ_REQUIRE(batch > 0 && n_contact >= 0, "fk_backward: bad sizes");
-  GQ_REQUIRE(workspace_bytes >= (size_t)batch * h->J * 18 * sizeof(float), "fk_backward: workspace too small");
+  GQ_REQUIRE(workspace_bytes >= (size_t)batch * h->J * 12 * sizeof(float), "fk_backward: workspace too small");
   GqFkBwdArgs a{};
   a.h = *h;
   a.hand_pose = hand_pose;
@@ -825,41 +752,15 @@ int gq_fk_backward(const gqHand* h, const float* hand_pose, const int64_t* conta
   a.B = (int)batch;
   a.n = (g_contact_points || g_contact_normals) ? n_contact : 0;
   a.D = 9 + h->JA;
-  a.node_F = (float*)workspace + (size_t)batch * h->J * 12;
   a.grad_pose = grad_pose;
   if (energy) a.en = *energy;
   if (accept) {
     const gqAcceptDesc& c = *accept;
     GQ_REQUIRE(energy && contact_idx, "fk_backward: the fused accept step needs the gqRowEnergyDesc and contact_idx");
-    GQ_REQUIRE(c.u_accept && c.step && c.energy && c.pose && c.idx && c.grad && c.accept && c.slot_ctr && c.slots > 0 &&
-                   c.annealing_period > 0 && (c.n_terms == 0 || (c.terms_new && c.terms)),
-               "fk_backward: incomplete gqAcceptDesc");
+    GQ_REQUIRE(c.slot_ctr, "fk_backward: incomplete gqAcceptDesc");
+    const int rc = gq_accept_fill(c, "fk_backward", energy->total, hand_pose, contact_idx, grad_pose, batch, a.D, n_contact, &a.ac);
+    if (rc) return rc;
     a.has_accept = 1;
-    a.ac.new_energy = energy->total;
-    a.ac.u_accept = c.u_accept;
-    a.ac.z = c.z;
-    a.ac.reset_mask = c.reset_mask;
-    a.ac.step = c.step;
-    a.ac.pose_new = hand_pose;
-    a.ac.idx_new = contact_idx;
-    a.ac.grad_new = grad_pose;
-    a.ac.B = (int)batch;
-    a.ac.D = 9 + h->JA;
-    a.ac.n = n_contact;
-    a.ac.T0 = c.starting_temperature;
-    a.ac.decay = c.decay;
-    a.ac.annealing_period = c.annealing_period;
-    a.ac.energy = c.energy;
-    a.ac.pose = c.pose;
-    a.ac.idx = c.idx;
-    a.ac.grad = c.grad;
-    a.ac.accept = c.accept;
-    a.ac.temperature = c.temperature;
-    a.ac.n_terms = c.n_terms;
-    a.ac.terms_new = c.terms_new;
-    a.ac.terms = c.terms;
-    a.ac.slot_ctr = c.slot_ctr;
-    a.ac.slots = c.slots;
   }
   GQ_REQUIRE(a.n + h->S <= GQ_FK_MAX_ITEMS, "fk_backward: n_contact + n_spheres = %d exceeds %d", a.n + h->S,
              GQ_FK_MAX_ITEMS);
@@ -871,8 +772,11 @@ int gq_fk_backward(const gqHand* h, const float* hand_pose, const int64_t* conta
 int gq_self_pen_forward(const gqHand* h, const float* sphere_centers, int64_t batch, float grad_scale, float* e_spen,
                         float* g_centers, void* stream) {
   GQ_REQUIRE(h && sphere_centers && e_spen && g_centers && batch > 0, "self_pen_forward: bad arguments");
-  hipLaunchKernelGGL(gq_self_pen_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, (hipStream_t)stream, *h,
-                     sphere_centers, (int)batch, grad_scale, e_spen, g_centers);
+  GqSpenArgs sa{};
+  sa.e_spen = e_spen;
+  sa.g_spheres = g_centers;
+  sa.spen_scale = grad_scale;
+  hipLaunchKernelGGL(gq_self_pen_row_kernel, dim3((unsigned)batch), dim3(GQ_WAVE), 0, (hipStream_t)stream, *h, sa, sphere_centers);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

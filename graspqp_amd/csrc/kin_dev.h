@@ -108,9 +108,80 @@ struct GqSpenArgs {
   float spen_scale;
 };
 
-// World centres of the penetration spheres of one row and, with e_spen, their self penetration
-// (hand_model.py:989-1040).  One wavefront; LT = the row's link transforms (LDS or global), R / tg = global rotation and
-// translation; sC (3 S floats), sKey (64 x u64), sRad (S floats) = LDS scratch of this wavefront.
+// Self penetration of one row (hand_model.py:989-1040) on world centres sC (3 S floats) and radii sRad (S floats) that
+// the calling wavefront has just written to LDS (the first barrier below orders those writes too): e_spen[row] and
+// g_spheres of the row.  sKey (64 x u64) = LDS scratch.  The one scan behind gq_fk_forward, the self-penetration role of
+// the stage kernels, gq_spheres_self_pen and gq_self_pen_forward.
+__device__ __forceinline__ void gq_self_pen_scan(const gqHand& h, const GqSpenArgs& g, int row, int lane, const float* sC,
+                                                 unsigned long long* sKey, const float* sRad) {
+  const int ng = min(h.NG - 1, 64);  // the last sphere group has nothing after it
+  // For every sphere group (= link) the most penetrating pair against all LATER groups.  Lanes take the partners b of
+  // one sphere a at a time; the per-group minimum is taken on the 64-bit key (pen, a, b) -- the first minimal pair in
+  // (a, b) order, like a serial scan.
+  sKey[lane] = ~0ull;
+  gq_wave_sync();
+  // four lanes per group (16 groups per pass): lane (g, q) scans the pairs (a in g) x (b = first later sphere + q,
+  // + 4, ...), everything from LDS; the four partial minima of a group meet through two quad DPP steps on the
+  // (pen, a, b) key, whose order is the serial scan's order.
+  for (int g0 = 0; g0 < ng; g0 += 16) {
+    const int gi = g0 + (lane >> 2), q = lane & 3;
+    unsigned long long key = ~0ull;
+    if (gi < ng) {
+      const int a0 = h.group_off[gi], a1 = h.group_off[gi + 1];
+      for (int a = a0; a < a1; ++a) {
+        const gq3 pa = gq_mk(sC[a * 3], sC[a * 3 + 1], sC[a * 3 + 2]);
+        const float ra = sRad[a];
+#pragma unroll 4
+        for (int b = a1 + q; b < h.S; b += 4) {
+          const gq3 d = gq_mk(pa.x - sC[b * 3] + 1e-13f, pa.y - sC[b * 3 + 1] + 1e-13f, pa.z - sC[b * 3 + 2] + 1e-13f);
+          const float pen = sqrtf(gq_dot(d, d)) - (ra + sRad[b]);
+          const unsigned long long k =
+              ((unsigned long long)gq_f2o(pen) << 32) | ((unsigned long long)a << 16) | (unsigned long long)b;
+          key = k < key ? k : key;
+        }
+      }
+    }
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      const int lo = (int)(key & 0xffffffffull), hi = (int)(key >> 32);
+      const int olo = st == 0 ? __builtin_amdgcn_mov_dpp(lo, 0xb1, 0xf, 0xf, true) : __builtin_amdgcn_mov_dpp(lo, 0x4e, 0xf, 0xf, true);
+      const int ohi = st == 0 ? __builtin_amdgcn_mov_dpp(hi, 0xb1, 0xf, 0xf, true) : __builtin_amdgcn_mov_dpp(hi, 0x4e, 0xf, 0xf, true);
+      const unsigned long long other = ((unsigned long long)(unsigned)ohi << 32) | (unsigned)olo;
+      key = other < key ? other : key;
+    }
+    if (gi < ng && q == 0) sKey[gi] = key;
+  }
+  gq_wave_sync();
+  // energy: fixed DPP tree over the groups; gradient: lane s collects, in group order, what lands on sphere s
+  float e = 0.0f;
+  if (lane < ng) {
+    const unsigned long long k = sKey[lane];
+    const float best = gq_o2f((unsigned)(k >> 32));
+    if (k != ~0ull && best < 0.0f) e = -best;
+  }
+  e = gq_dpp_sum(e);
+  if (lane == 0) g.e_spen[row] = e;
+  for (int sidx = lane; sidx < h.S; sidx += GQ_WAVE) {
+    gq3 acc = gq_mk(0, 0, 0);
+    for (int gi = 0; gi < ng; ++gi) {
+      const unsigned long long k = sKey[gi];
+      const float best = gq_o2f((unsigned)(k >> 32));
+      const int ba = (int)((k >> 16) & 0xffffull), bb = (int)(k & 0xffffull);
+      if (k == ~0ull || !(best < 0.0f) || (ba != sidx && bb != sidx)) continue;
+      const gq3 d = gq_mk(sC[ba * 3] - sC[bb * 3] + 1e-13f, sC[ba * 3 + 1] - sC[bb * 3 + 1] + 1e-13f,
+                          sC[ba * 3 + 2] - sC[bb * 3 + 2] + 1e-13f);
+      // E += -|a-b| + ... : dE/da = -(a-b)/|a-b|, dE/db = +(a-b)/|a-b|
+      const float sc = g.spen_scale / sqrtf(gq_dot(d, d)) * (ba == sidx ? -1.0f : 1.0f);
+      acc = gq_mk(fmaf(sc, d.x, acc.x), fmaf(sc, d.y, acc.y), fmaf(sc, d.z, acc.z));
+    }
+    float* o = g.g_spheres + ((size_t)row * h.S + sidx) * 3;
+    o[0] = acc.x; o[1] = acc.y; o[2] = acc.z;
+  }
+}
+
+// World centres of the penetration spheres of one row and, with e_spen, their self penetration.  One wavefront; LT = the
+// row's link transforms (LDS or global), R / tg = global rotation and translation; sC (3 S floats), sKey (64 x u64),
+// sRad (S floats) = LDS scratch of this wavefront.
 __device__ __forceinline__ void gq_spheres_row(const gqHand& h, const GqSpenArgs& g, const float* LT, const float* R,
                                                gq3 tg, int row, int lane, float* sC, unsigned long long* sKey,
                                                float* sRad) {
@@ -139,69 +210,5 @@ __device__ __forceinline__ void gq_spheres_row(const gqHand& h, const GqSpenArgs
       }
     }
   }
-  if (g.e_spen) {
-    const int ng = min(h.NG - 1, 64);  // the last sphere group has nothing after it
-    // Self penetration (hand_model.py:989-1040) on the centres just computed: for every sphere group (= link) the most
-    // penetrating pair against all LATER groups.  Lanes take the partners b of one sphere a at a time; the per-group
-    // minimum is a 64-bit LDS atomicMin on (pen, a, b) -- the first minimal pair in (a, b) order, like a serial scan.
-    sKey[lane] = ~0ull;
-    gq_wave_sync();
-    // four lanes per group (16 groups per pass): lane (g, q) scans the pairs (a in g) x (b = first later sphere + q,
-    // + 4, ...), everything from LDS; the four partial minima of a group meet through two quad DPP steps on the
-    // (pen, a, b) key, whose order is the serial scan's order.
-    for (int g0 = 0; g0 < ng; g0 += 16) {
-      const int gi = g0 + (lane >> 2), q = lane & 3;
-      unsigned long long key = ~0ull;
-      if (gi < ng) {
-        const int a0 = h.group_off[gi], a1 = h.group_off[gi + 1];
-        for (int a = a0; a < a1; ++a) {
-          const gq3 pa = gq_mk(sC[a * 3], sC[a * 3 + 1], sC[a * 3 + 2]);
-          const float ra = sRad[a];
-#pragma unroll 4
-          for (int b = a1 + q; b < h.S; b += 4) {
-            const gq3 d = gq_mk(pa.x - sC[b * 3] + 1e-13f, pa.y - sC[b * 3 + 1] + 1e-13f, pa.z - sC[b * 3 + 2] + 1e-13f);
-            const float pen = sqrtf(gq_dot(d, d)) - (ra + sRad[b]);
-            const unsigned long long k =
-                ((unsigned long long)gq_f2o(pen) << 32) | ((unsigned long long)a << 16) | (unsigned long long)b;
-            key = k < key ? k : key;
-          }
-        }
-      }
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const int lo = (int)(key & 0xffffffffull), hi = (int)(key >> 32);
-        const int olo = st == 0 ? __builtin_amdgcn_mov_dpp(lo, 0xb1, 0xf, 0xf, true) : __builtin_amdgcn_mov_dpp(lo, 0x4e, 0xf, 0xf, true);
-        const int ohi = st == 0 ? __builtin_amdgcn_mov_dpp(hi, 0xb1, 0xf, 0xf, true) : __builtin_amdgcn_mov_dpp(hi, 0x4e, 0xf, 0xf, true);
-        const unsigned long long other = ((unsigned long long)(unsigned)ohi << 32) | (unsigned)olo;
-        key = other < key ? other : key;
-      }
-      if (gi < ng && q == 0) sKey[gi] = key;
-    }
-    gq_wave_sync();
-    // energy: fixed DPP tree over the groups; gradient: lane s collects, in group order, what lands on sphere s
-    float e = 0.0f;
-    if (lane < ng) {
-      const unsigned long long k = sKey[lane];
-      const float best = gq_o2f((unsigned)(k >> 32));
-      if (k != ~0ull && best < 0.0f) e = -best;
-    }
-    e = gq_dpp_sum(e);
-    if (lane == 0) g.e_spen[row] = e;
-    for (int sidx = lane; sidx < h.S; sidx += GQ_WAVE) {
-      gq3 acc = gq_mk(0, 0, 0);
-      for (int gi = 0; gi < ng; ++gi) {
-        const unsigned long long k = sKey[gi];
-        const float best = gq_o2f((unsigned)(k >> 32));
-        const int ba = (int)((k >> 16) & 0xffffull), bb = (int)(k & 0xffffull);
-        if (k == ~0ull || !(best < 0.0f) || (ba != sidx && bb != sidx)) continue;
-        const gq3 d = gq_mk(sC[ba * 3] - sC[bb * 3] + 1e-13f, sC[ba * 3 + 1] - sC[bb * 3 + 1] + 1e-13f,
-                            sC[ba * 3 + 2] - sC[bb * 3 + 2] + 1e-13f);
-        // E += -|a-b| + ... : dE/da = -(a-b)/|a-b|, dE/db = +(a-b)/|a-b|
-        const float sc = g.spen_scale / sqrtf(gq_dot(d, d)) * (ba == sidx ? -1.0f : 1.0f);
-        acc = gq_mk(fmaf(sc, d.x, acc.x), fmaf(sc, d.y, acc.y), fmaf(sc, d.z, acc.z));
-      }
-      float* o = g.g_spheres + ((size_t)row * h.S + sidx) * 3;
-      o[0] = acc.x; o[1] = acc.y; o[2] = acc.z;
-    }
-  }
+  if (g.e_spen) gq_self_pen_scan(h, g, row, lane, sC, sKey, sRad);
 }

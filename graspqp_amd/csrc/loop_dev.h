@@ -191,36 +191,9 @@ struct GqAcceptArgs {
   int slots;
 };
 
-__device__ __forceinline__ void gq_accept_body(const GqAcceptArgs& g, int row, int lane) {
-  const size_t draw0 = g.slot_ctr ? (size_t)((g.slot_ctr[1] - 1) % g.slots) * g.B : 0;
-  if (g.slot_ctr && row == 0 && lane == 0) g.slot_ctr[0] = g.slot_ctr[1];
-  float T = g.T0 * powf(g.decay, (float)((int)g.step[row] / g.annealing_period));
-  if (g.z) {
-    const float proba = 0.5f * (1.0f + erff(g.z[row] * 0.70710678118654752f));
-    T = T * (1.0f + proba);
-  }
-  const float e_old = g.energy[row], e_new = g.new_energy[row];
-  bool acc = g.u_accept[draw0 + row] < expf((e_old - e_new) / T);
-  if (g.reset_mask && g.reset_mask[row]) acc = true;
-  if (lane == 0) {
-    g.accept[row] = acc ? 1 : 0;
-    if (g.temperature) g.temperature[row] = T;
-    if (acc) g.energy[row] = e_new;
-  }
-  if (acc) {  // wave-uniform
-    for (int d = lane; d < g.D; d += GQ_WAVE) {
-      const size_t o = (size_t)row * g.D + d;
-      g.pose[o] = g.pose_new[o];
-      g.grad[o] = g.grad_new[o];
-    }
-    for (int c = lane; c < g.n; c += GQ_WAVE) g.idx[(size_t)row * g.n + c] = g.idx_new[(size_t)row * g.n + c];
-    for (int t = lane; t < g.n_terms; t += GQ_WAVE) g.terms[(size_t)t * g.B + row] = g.terms_new[(size_t)t * g.B + row];
-  }
-}
-
-// The same step split for the FK backward kernel: everything that does not depend on the new energy is loaded (and
-// the temperature computed) at the top of the kernel; the finish takes the new energy and gradient from registers /
-// LDS instead of re-reading what the wavefront has just stored.
+// The step in two halves, so that the FK backward kernel can run them around its own work: everything that does not
+// depend on the new energy is loaded (and the temperature computed) at the top of the kernel; the finish takes the new
+// energy and gradient from registers / LDS instead of re-reading what the wavefront has just stored.
 struct GqAcceptPre {
   float u, e_old, T;
   bool reset;
@@ -244,8 +217,8 @@ __device__ __forceinline__ GqAcceptPre gq_accept_prefetch(const GqAcceptArgs& g,
   p.T = T;
   return p;
 }
-// e_new: the row's new total (wave-uniform); sG: the row's new gradient (D floats, LDS); term: lane t < n_terms holds
-// the t-th energy term of the new state.
+// e_new: the row's new total (wave-uniform); sG: the row's new gradient (D <= 128 floats, LDS or global); term: lane
+// t < n_terms <= 64 holds the t-th energy term of the new state.
 __device__ __forceinline__ void gq_accept_finish(const GqAcceptArgs& g, const GqAcceptPre& p, int row, int lane,
                                                  float e_new, const float* sG, float term) {
   if (g.slot_ctr && row == 0 && lane == 0) g.slot_ctr[0] = g.slot_ctr[1];
@@ -271,4 +244,90 @@ __device__ __forceinline__ void gq_accept_finish(const GqAcceptArgs& g, const Gq
     if (lane < g.n_terms) g.terms[(size_t)lane * g.B + row] = term;
   }
 }
+// stand-alone form (loop.hip): the new energy, the gradient row and the terms are read from memory
+__device__ __forceinline__ void gq_accept_body(const GqAcceptArgs& g, int row, int lane) {
+  const GqAcceptPre p = gq_accept_prefetch(g, row, lane);
+  const float term = lane < g.n_terms ? g.terms_new[(size_t)lane * g.B + row] : 0.0f;
+  gq_accept_finish(g, p, row, lane, g.new_energy[row], g.grad_new + (size_t)row * g.D, term);
+}
 
+// ---- host side: one filler per descriptor (who = entry point named in the messages) --------------------------------
+// The proposal of the (B,D) poses / (B,n) indices goes to pose_out / idx_out.  slot_ctr == null: u_switch / new_idx hold
+// the draws of one iteration.  g2_inline is the business of gq_fk_forward.
+static inline int gq_propose_fill(const gqProposeDesc& p, const char* who, int64_t batch, int D, int n, float* pose_out,
+                                  int64_t* idx_out, GqProposeArgs* out) {
+  GQ_REQUIRE(p.hand_pose && p.grad && p.contact_idx && p.u_switch && p.new_idx && p.ema && p.step && pose_out && idx_out &&
+                 p.stepsize_period > 0 && D <= 2 * GQ_WAVE && (!p.slot_ctr || p.slots > 0),
+             "%s: incomplete gqProposeDesc", who);
+  GQ_REQUIRE(p.g2_scratch, "%s: gqProposeDesc.g2_scratch (D floats) is missing", who);
+  GQ_REQUIRE(!p.energy || (p.z_out && p.batch_each > 0 && batch % p.batch_each == 0),
+             "%s: z-score needs z_out and batch_each dividing batch", who);
+  GqProposeArgs a{};
+  a.hand_pose = p.hand_pose;
+  a.grad = p.grad;
+  a.g2 = p.g2_scratch;
+  a.idx = p.contact_idx;
+  a.u_switch = p.u_switch;
+  a.new_idx = p.new_idx;
+  a.B = (int)batch;
+  a.D = D;
+  a.n = n;
+  a.clip = p.clip_grad;
+  a.step_size = p.step_size;
+  a.decay = p.decay;
+  a.mu = p.mu;
+  a.switch_p = p.switch_possibility;
+  a.stepsize_period = p.stepsize_period;
+  a.ema = p.ema;
+  a.step = p.step;
+  a.pose_out = pose_out;
+  a.idx_out = idx_out;
+  a.s_out = p.step_size_out;
+  a.energy = p.energy;
+  a.batch_each = (int)p.batch_each;
+  a.z_out = p.z_out;
+  a.slot_ctr = p.slot_ctr;
+  a.slots = p.slots;
+  *out = a;
+  return GQ_OK;
+}
+// The Metropolis test on new_energy and the merge of (pose_new, idx_new, grad_new) into the accepted state.  slot_ctr ==
+// null: u_accept holds the draws of one iteration.
+static inline int gq_accept_fill(const gqAcceptDesc& c, const char* who, const float* new_energy, const float* pose_new,
+                                 const int64_t* idx_new, const float* grad_new, int64_t batch, int D, int n,
+                                 GqAcceptArgs* out) {
+  GQ_REQUIRE(new_energy && pose_new && idx_new && grad_new && c.u_accept && c.step && c.energy && c.pose && c.idx &&
+                 c.grad && c.accept && c.annealing_period > 0 && D <= 2 * GQ_WAVE && (!c.slot_ctr || c.slots > 0),
+             "%s: incomplete gqAcceptDesc", who);
+  GQ_REQUIRE(c.n_terms == 0 || (c.terms_new && c.terms), "%s: null term buffers", who);
+  GQ_REQUIRE(c.n_terms >= 0 && c.n_terms <= GQ_WAVE, "%s: n_terms = %d exceeds the limit of %d (one term per lane)", who,
+             c.n_terms, GQ_WAVE);
+  GqAcceptArgs a{};
+  a.new_energy = new_energy;
+  a.u_accept = c.u_accept;
+  a.z = c.z;
+  a.reset_mask = c.reset_mask;
+  a.step = c.step;
+  a.pose_new = pose_new;
+  a.idx_new = idx_new;
+  a.grad_new = grad_new;
+  a.B = (int)batch;
+  a.D = D;
+  a.n = n;
+  a.T0 = c.starting_temperature;
+  a.decay = c.decay;
+  a.annealing_period = c.annealing_period;
+  a.energy = c.energy;
+  a.pose = c.pose;
+  a.idx = c.idx;
+  a.grad = c.grad;
+  a.accept = c.accept;
+  a.temperature = c.temperature;
+  a.n_terms = c.n_terms;
+  a.terms_new = c.terms_new;
+  a.terms = c.terms;
+  a.slot_ctr = c.slot_ctr;
+  a.slots = c.slots;
+  *out = a;
+  return GQ_OK;
+}

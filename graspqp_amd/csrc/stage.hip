@@ -88,6 +88,25 @@ __global__ __launch_bounds__(256) void gq_spheres_kernel(GqSpenRole sp, int B) {
   gq_spen_role_body(sp, (int)blockIdx.x, B, gq_lds);
 }
 
+// host side: the role's argument block and the dynamic LDS of one of its blocks (who = entry point named in the messages)
+static int gq_spen_role_fill(const gqHand* h, const char* who, const float* hand_pose, int pose_dim, const float* Rg,
+                             const float* link_T, float w_spen, float* sphere_centers, float* e_spen,
+                             float* g_sphere_centers, GqSpenRole* sp, size_t* lds) {
+  GQ_REQUIRE(h && hand_pose && Rg && link_T && e_spen && g_sphere_centers && h->S > 0 && h->S <= 256,
+             "%s: the self-penetration role needs the kinematics, e_spen, g_sphere_centers and 1..256 spheres", who);
+  sp->h = *h;
+  sp->sa.spheres = sphere_centers;
+  sp->sa.e_spen = e_spen;
+  sp->sa.g_spheres = g_sphere_centers;
+  sp->sa.spen_scale = w_spen;
+  sp->Rg = Rg;
+  sp->hand_pose = hand_pose;
+  sp->link_T = link_T;
+  sp->D = pose_dim;
+  *lds = (size_t)4 * ((size_t)h->S * 16 + 512);
+  return GQ_OK;
+}
+
 template <int NC, int RPL>
 __global__ __launch_bounds__(256) void gq_stage_b_kernel(GqFcStepArgs f, GqPenBwdArgs p, GqSpenRole sp) {
   extern __shared__ char gq_lds[];
@@ -130,9 +149,7 @@ __device__ __forceinline__ void gq_alt_contact_terms(const GqAltArgs& a, int row
     const gq3 p = gq_mk(a.cpts[t * 3], a.cpts[t * 3 + 1], a.cpts[t * 3 + 2]);
     const gq3 cl = gq_mk(a.closest[t * 3], a.closest[t * 3 + 1], a.closest[t * 3 + 2]);
     const GqContactTerm ct = gq_contact_term(a.dist_sq[t], (float)a.sign[t], on, nH, p, cl, a.w_dis);
-    a.obj_normal[t * 3] = ct.vC.x; a.obj_normal[t * 3 + 1] = ct.vC.y; a.obj_normal[t * 3 + 2] = ct.vC.z;
-    a.g_cpts[t * 3] = ct.g_p.x; a.g_cpts[t * 3 + 1] = ct.g_p.y; a.g_cpts[t * 3 + 2] = ct.g_p.z;
-    a.g_cnrm[t * 3] = ct.g_n.x; a.g_cnrm[t * 3 + 1] = ct.g_n.y; a.g_cnrm[t * 3 + 2] = ct.g_n.z;
+    gq_contact_term_store(ct, t, a.obj_normal, a.g_cpts, a.g_cnrm);
     s_cp[c * 3] = p.x; s_cp[c * 3 + 1] = p.y; s_cp[c * 3 + 2] = p.z;
     s_on[c * 3] = ct.vC.x; s_on[c * 3 + 1] = ct.vC.y; s_on[c * 3 + 2] = ct.vC.z;
   }
@@ -203,21 +220,9 @@ static int gq_pen_step_fill(const gqPenStepDesc* pen, const char* who, int B, Gq
   s->lds_q = pen->grid ? gq_pen_cells_lds_bytes(p.L, p.P) : gq_pen_grid_lds_bytes(p.L, GQ_PG_ECAP, GQ_PG_ICAP, s->ppt);
   s->n_q = (pen->grid ? 1 : s->gx) * p.B;
   if (!pen->hand) return GQ_OK;  // no self-penetration role: n_sp = 0
-  GQ_REQUIRE(pen->e_spen && pen->g_sphere_centers && pen->hand->S > 0 && pen->hand->S <= 256,
-             "pen step: the self-penetration role needs e_spen, g_sphere_centers and 1..256 spheres");
-  GqSpenRole& sp = s->sp;
-  sp.h = *pen->hand;
-  sp.sa.spheres = pen->sphere_centers;
-  sp.sa.e_spen = pen->e_spen;
-  sp.sa.g_spheres = pen->g_sphere_centers;
-  sp.sa.spen_scale = pen->w_spen;
-  sp.Rg = pen->Rg;
-  sp.hand_pose = pen->hand_pose;
-  sp.link_T = pen->link_T;
-  sp.D = pen->pose_dim;
   s->n_sp = (B + 3) / 4;
-  s->lds_sp = (size_t)4 * ((size_t)sp.h.S * 16 + 512);
-  return GQ_OK;
+  return gq_spen_role_fill(pen->hand, who, pen->hand_pose, pen->pose_dim, pen->Rg, pen->link_T, pen->w_spen,
+                           pen->sphere_centers, pen->e_spen, pen->g_sphere_centers, &s->sp, &s->lds_sp);
 }
 
 extern "C" {
@@ -269,20 +274,13 @@ int gq_alt_pen_step(const gqAltFcDesc* alt, const gqPenStepDesc* pen, void* stre
 int gq_spheres_self_pen(const gqHand* h, const float* hand_pose, int pose_dim, const float* Rg, const float* link_T,
                         int64_t batch, float w_spen, float* sphere_centers, float* e_spen, float* g_sphere_centers,
                         void* stream) {
-  GQ_REQUIRE(h && hand_pose && Rg && link_T && e_spen && g_sphere_centers && batch > 0 && h->S > 0 && h->S <= 256,
-             "spheres_self_pen: bad arguments");
+  GQ_REQUIRE(batch > 0, "spheres_self_pen: bad arguments");
   GqSpenRole sp{};
-  sp.h = *h;
-  sp.sa.spheres = sphere_centers;
-  sp.sa.e_spen = e_spen;
-  sp.sa.g_spheres = g_sphere_centers;
-  sp.sa.spen_scale = w_spen;
-  sp.Rg = Rg;
-  sp.hand_pose = hand_pose;
-  sp.link_T = link_T;
-  sp.D = pose_dim;
-  hipLaunchKernelGGL(gq_spheres_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), (size_t)4 * ((size_t)h->S * 16 + 512),
-                     (hipStream_t)stream, sp, (int)batch);
+  size_t lds = 0;
+  const int rc = gq_spen_role_fill(h, "spheres_self_pen", hand_pose, pose_dim, Rg, link_T, w_spen, sphere_centers, e_spen,
+                                   g_sphere_centers, &sp, &lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(gq_spheres_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), lds, (hipStream_t)stream, sp, (int)batch);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }
@@ -292,11 +290,8 @@ int gq_fc_pen_step(const gqFcStepDesc* fc, const gqPenStepDesc* pen, void* strea
   hipStream_t st = (hipStream_t)stream;
   GqFcStepArgs f{};
   float* runmin = nullptr;
-  int rc = gq_fc_step_fill(fc->dist_sq, fc->sign, fc->obj_dir, fc->closest, fc->contact_pts, fc->hand_normals, fc->cog,
-                           fc->batch, fc->n_contact, fc->n_cone, fc->friction, fc->torque_weight, fc->max_limit,
-                           fc->svd_gain, fc->values_gain, fc->eps, fc->max_iter, fc->w_dis, fc->w_fc, fc->obj_normal,
-                           fc->g_contact_pts, fc->g_hand_normals, fc->e_fc, fc->x_sum, fc->n_iter, fc->workspace,
-                           fc->workspace_bytes, &f, &runmin);
+  GqFcStop stop;
+  int rc = gq_fc_step_fill(*fc, &f, &runmin, &stop);
   if (rc) return rc;
   GqPenStep ps{};
   rc = gq_pen_step_fill(pen, "fc_pen_step", f.B, &ps);
@@ -311,7 +306,7 @@ int gq_fc_pen_step(const gqFcStepDesc* fc, const gqPenStepDesc* pen, void* strea
     if (ps.ppt == 2) hipLaunchKernelGGL((gq_stage_a_kernel<NCV, STOPV, 2>), grid_a, block, lds_a, st, f, ps.p, ps.gx, nfc);  \
     else hipLaunchKernelGGL((gq_stage_a_kernel<NCV, STOPV, 1>), grid_a, block, lds_a, st, f, ps.p, ps.gx, nfc);              \
   } while (0)
-  if (f.agg) {
+  if (stop == GQ_STOP_HEAD) {
     if (two) GQ_STAGE_A(2, true);
     else GQ_STAGE_A(1, true);
   } else {
@@ -320,8 +315,8 @@ int gq_fc_pen_step(const gqFcStepDesc* fc, const gqPenStepDesc* pen, void* strea
   }
 #undef GQ_STAGE_A
   GQ_LAUNCH_CHECK();
-  const bool fused_stop = f.B <= 4 * GQ_WAVE && f.max_iter <= 16;
-  if (!fused_stop && !f.agg) {
+  const bool fused_stop = stop == GQ_STOP_TAIL;
+  if (stop == GQ_STOP_LAUNCH) {
     rc = gq_qp_stop_launch_(f.resid, f.mu_tab, f.B, f.max_iter, f.eps, f.not_improved_lim, runmin, f.kstar, f.n_iter, stream);
     if (rc) return rc;
   }

@@ -352,11 +352,12 @@ class GraspStepper:
           f32(self.pose_new), i64(self.idx_new), f32(self.s_out), f32(self.g2), f32(self.energy), self.be, f32(self.z),
           st)  # the z-score of the OLD energies (fit.py:403-406) rides in the same launch
 
-    def _accept(self, st):
+    def _accept(self, st, reset_mask=None):
+        """MalaStar.accept_step + state merge; the rows of ``reset_mask`` (uint8, device) are accepted unconditionally."""
         B, D, n, m = self.B, self.D, self.n, self.mala
         C, f32, i64 = _C.call, _C.f32, _C.i64
-        C("gq_mala_accept", f32(self.total_new), f32(self._cur[2]), f32(self.z) if self.optimizer == "mala_star" else None, None,
-          i64(self.step_count), f32(self.pose_new), i64(self.idx_new), f32(self.grad_new), B, D, n,
+        C("gq_mala_accept", f32(self.total_new), f32(self._cur[2]), f32(self.z) if self.optimizer == "mala_star" else None,
+          _C.u8(reset_mask), i64(self.step_count), f32(self.pose_new), i64(self.idx_new), f32(self.grad_new), B, D, n,
           float(m["starting_temperature"]), float(m["temperature_decay"]), int(m["annealing_period"]), f32(self.energy),
           f32(self.hand_pose), i64(self.contact_idx), f32(self.grad), _C.u8(self.accept), f32(self.temperature), 5,
           f32(self.terms_new), f32(self.terms), st)
@@ -479,13 +480,8 @@ class GraspStepper:
         # their proposal's indices as state -- so this iteration's energies are evaluated at ``new_idx`` everywhere
         # (``idx_all`` is the proposal's ``idx_new`` when the mask is empty, see above)
         self._evaluate(self.pose_new, idx_all, st)
-        rm = m.to(torch.uint8).contiguous() if mala else None  # AnnealingDexGraspNet.accept_step ignores reset_mask
-        B, D, n, mc = self.B, self.D, self.n, self.mala
-        _C.call("gq_mala_accept", _C.f32(self.total_new), _C.f32(self._cur[2]), _C.f32(self.z) if mala else None, _C.u8(rm),
-                _C.i64(self.step_count), _C.f32(self.pose_new), _C.i64(self.idx_new), _C.f32(self.grad_new), B, D, n,
-                float(mc["starting_temperature"]), float(mc["temperature_decay"]), int(mc["annealing_period"]),
-                _C.f32(self.energy), _C.f32(self.hand_pose), _C.i64(self.contact_idx), _C.f32(self.grad),
-                _C.u8(self.accept), _C.f32(self.temperature), 5, _C.f32(self.terms_new), _C.f32(self.terms), st)
+        # AnnealingDexGraspNet.accept_step ignores reset_mask
+        self._accept(st, m.to(torch.uint8).contiguous() if mala else None)
         self._slot_ctr += 1
         self._after_reset = True
 

@@ -395,7 +395,10 @@ int gq_hand_pen_backward(int n_links, const float* surface_points, int64_t n_obj
                          float* link_wrench /* (B,L,6) */, float* gRt /* (B,12) */, const float* dis /* (B,P) */,
                          float w_pen, float* e_pen /* (B) */, uint64_t* span, uint64_t* span_acc, void* stream);
 
-/* ---- self penetration: HandModel.self_penetration (E_spen), core/hand_model.py:989-1040 ------------------ */
+/* ---- self penetration: HandModel.self_penetration (E_spen), core/hand_model.py:989-1040 ------------------
+ * On given world centres: one wavefront per row stages the centres and the radii in LDS and runs the SAME pair scan as
+ * the fused forms (the e_spen tail of gq_fk_forward, the self-penetration role of gq_fc_pen_step, gq_spheres_self_pen),
+ * with grad_scale in the place of their w_spen: same bits on the same centres.  S <= 256, at most 64 scanned groups. */
 int gq_self_pen_forward(const gqHand* h, const float* sphere_centers /* (B,S,3) world */, int64_t batch,
                         float grad_scale, float* e_spen /* (B) */,
                         float* g_centers /* (B,S,3) grad_scale * dE/dcentre */, void* stream);
@@ -413,12 +416,6 @@ int gq_contact_terms(const float* dist_sq, const int32_t* sign, const float* onr
                      const float* contact_pts, const float* contact_normals, int64_t batch, int n_contact, float w_dis,
                      float* obj_normal /* (B,n,3) = onrm*sign */, float* g_contact_pts, float* g_contact_normals,
                      void* stream);
-int gq_row_energy(const float* dist_sq, const int32_t* sign, const float* onrm, const float* contact_normals,
-                  const float* hand_pose, const float* joints_lower, const float* joints_upper, const float* e_fc,
-                  const float* pen_dis, const float* e_spen, int64_t batch, int n_contact, int n_dofs,
-                  int64_t n_surface, float w_dis, float w_fc, float w_pen, float w_spen, float w_joints, float* e_dis,
-                  float* e_joints, float* e_pen, float* total, float* g_theta /* (B,J) */, float* g_pen /* (B,P) */,
-                  void* stream);
 /* The same terms one by one, each with its derivative, for the autograd route of the class surface (calculate_energy on
  * HandModel / ObjectModel): the derivative is written by the forward launch and the backward is a broadcast multiply with
  * the upstream row gradient -- one launch per term where the reference's torch expressions issue a dozen.
@@ -438,8 +435,6 @@ int gq_energy_dis(const float* distance /* (B,n) */, const float* obj_normal /* 
 int gq_energy_joints(const float* hand_pose, const float* joints_lower, const float* joints_upper, int64_t batch, int pose_dim,
                      int n_dofs, float* e_joints /* (B) */, float* g_hand_pose /* (B,pose_dim) */, void* stream);
 int gq_energy_pen(const float* distances /* (B,P) */, int64_t batch, int64_t n_surface, float* e_pen /* (B) */, void* stream);
-int gq_axpy(float* y, const float* x, float a, int64_t n, void* stream);
-int gq_scale(float* y, const float* x, float a, int64_t n, void* stream);
 int gq_fill(float* y, float a, int64_t n, void* stream);
 
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
@@ -481,7 +476,8 @@ int gq_surface_fps(const float* face_verts, const float* area_cdf, const int32_t
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- MALA* optimiser: MalaStar.try_step / accept_step, core/optimizer.py:199-273,289-340; fit.py:403-406,454-458
- * random draws are inputs: u_switch (B,n) U[0,1), new_idx (B,n) in [0,C), u_accept (B) U[0,1).               */
+ * random draws are inputs: u_switch (B,n) U[0,1), new_idx (B,n) in [0,C), u_accept (B) U[0,1).  pose_dim <= 128;
+ * gq_mala_accept merges n_terms <= 64 rows of terms_new (n_terms,B) into terms, one term per lane.           */
 int gq_mala_propose(const float* hand_pose, const float* grad, const int64_t* contact_idx, const float* u_switch,
                     const int64_t* new_idx, int64_t batch, int pose_dim, int n_contact, float step_size,
                     int stepsize_period, float decay, float mu, float switch_possibility, int clip_grad,
@@ -489,7 +485,6 @@ int gq_mala_propose(const float* hand_pose, const float* grad, const int64_t* co
                     float* step_size_out /* (B) or NULL */, float* g2_scratch /* (D) */,
                     const float* energy /* (B) or NULL: also emit the per-object z-score of the accepted energies */,
                     int64_t batch_each, float* z_out /* (B) */, void* stream);
-int gq_zscore(const float* energy, int64_t n_obj, int64_t batch_each, float* z, void* stream);
 int gq_mala_accept(const float* new_energy, const float* u_accept, const float* z, const uint8_t* reset_mask,
                    const int64_t* step, const float* pose_new, const int64_t* idx_new, const float* grad_new,
                    int64_t batch, int pose_dim, int n_contact, float starting_temperature, float decay,

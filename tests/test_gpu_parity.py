@@ -574,6 +574,53 @@ def test_hand_penetration_and_self_penetration(gq):
     assert (grads[0] - grads[1]).norm() <= 5e-3 * grads[1].norm()
 
 
+def test_self_pen_forward_is_the_scan_of_the_fused_forms(gq):
+    """gq_self_pen_forward (the class surface: given world centres) and gq_spheres_self_pen (the stepper: centres from the
+    kinematics) run one device body, so on the same centres they give the same e_spen and the same centre gradients bit
+    for bit.  The scene is the one of the test above with the fingers curled further (joints + 0.8): on the fp64 oracle
+    all six rows self-penetrate, with four to five penetrating groups in rows 0, 1, 3 and one sphere hit by two pairs in
+    each of them -- both asserted below on the centres the GPU produced, so that neither the order of the energy sum nor
+    the order of the per-sphere accumulation can go untested."""
+    spec = get_hand_spec("allegro")
+    B, w_spen = 6, 10.0
+    hp = _rand_pose(spec, B, 11, spread=0.03)
+    hp[:, 9:] += 0.8
+    idx = torch.randint(spec.n_contact_candidates, (B, 4), generator=torch.Generator().manual_seed(2))
+    hand = gq.ops.HandHandle(spec)
+    hpg = hp.float().cuda()
+    Rg, LT, _, _, _, _ = gq.ops.fk_contacts(hpg, idx.cuda(), hand)
+    C, f32 = gq.C.call, gq.C.f32
+    S = spec.n_spheres
+    sc = torch.zeros(B, S, 3, device="cuda")
+    e1, e2 = torch.full((B,), -1.0, device="cuda"), torch.full((B,), -2.0, device="cuda")
+    g1, g2 = torch.full((B, S, 3), -1.0, device="cuda"), torch.full((B, S, 3), -2.0, device="cuda")
+    C("gq_spheres_self_pen", hand.handle, f32(hpg), hpg.shape[1], f32(Rg.contiguous()), f32(LT.contiguous()), B, w_spen,
+      f32(sc), f32(e1), f32(g1), gq.C.stream_ptr())
+    C("gq_self_pen_forward", hand.handle, f32(sc), B, w_spen, f32(e2), f32(g2), gq.C.stream_ptr())
+    torch.cuda.synchronize()
+    # what the scene exercises, from the GPU's centres: per sphere group (= run of one link) the most penetrating pair
+    # against all later groups
+    c = sc.cpu().double().numpy()
+    rad = np.asarray(spec.sphere, dtype=np.float64)[:, 3]
+    link = np.asarray(spec.sphere_link)
+    starts = [s for s in range(S) if s == 0 or link[s] != link[s - 1]] + [S]
+    n_pen, hits = np.zeros(B, dtype=int), np.zeros((B, S), dtype=int)
+    for r in range(B):
+        for a0, a1 in zip(starts[:-2], starts[1:-1]):
+            d = np.linalg.norm(c[r, a0:a1, None] - c[r, None, a1:] + 1e-13, axis=-1) - (rad[a0:a1, None] + rad[None, a1:])
+            a, b = np.unravel_index(np.argmin(d), d.shape)
+            if d[a, b] < 0:
+                n_pen[r] += 1
+                hits[r, a0 + a] += 1
+                hits[r, a1 + b] += 1
+    print("penetrating groups per row", n_pen.tolist(), "max contributions on one sphere", int(hits.max()))
+    assert n_pen.max() >= 3, "test scene must have a row with at least three penetrating groups"
+    assert hits.max() >= 2, "test scene must have a sphere that receives two contributions"
+    assert float(e1.min()) > 0.0
+    assert torch.equal(e2, e1)
+    assert torch.equal(g2, g1)
+
+
 def test_retired_penetration_modes_are_refused(gq):
     """penetration_only = 2 / 3 (AABB-only and queue routes, retired) never reach the C ABI from Python, and the C ABI
     itself refuses them before it launches anything: the output buffers keep their sentinel."""
@@ -1161,6 +1208,41 @@ def test_mala_clip_grad_with_nan_inf_matches_reference_optimizer(gq, golden_dir)
         st.step(draws=draws("C_s2"))
         torch.cuda.synchronize()
         _check_iteration(st, g, "C_s2")
+
+
+def test_mala_accept_refuses_more_than_64_terms(gq):
+    """The accept step keeps one energy term per lane: n_terms = 65 is refused with an error status that names the limit,
+    before anything is launched -- no output buffer is touched."""
+    B, D, n, T = 8, 25, 4, 65
+    g = torch.Generator().manual_seed(0)
+    r = lambda *s: torch.rand(*s, generator=g).cuda()
+    e_new, u, pose_new, grad_new, terms_new = r(B), r(B), r(B, D), r(B, D), r(T, B)
+    idx_new = torch.randint(100, (B, n), generator=g).cuda()
+    step = torch.ones(B, dtype=torch.int64, device="cuda")
+    outs = [r(B) + 5.0, r(B, D) + 5.0, torch.randint(100, (B, n), generator=g).cuda() + 500, r(B, D) + 5.0,
+            torch.full((B,), 7, dtype=torch.uint8, device="cuda"), r(B) + 5.0, r(T, B) + 5.0]
+    before = [o.clone() for o in outs]
+    energy, pose, idx, grad, accept, temperature, terms = outs
+    f32, i64, u8 = gq.C.f32, gq.C.i64, gq.C.u8
+    lib = gq.C.lib()
+    rc = lib.gq_mala_accept(f32(e_new), f32(u), None, None, i64(step), f32(pose_new), i64(idx_new), f32(grad_new), B, D, n,
+                            18.0, 0.95, 30, f32(energy), f32(pose), i64(idx), f32(grad), u8(accept), f32(temperature), T,
+                            f32(terms_new), f32(terms), gq.C.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc != 0
+    msg = lib.gq_last_error()
+    assert b"mala_accept" in msg and b"n_terms = 65" in msg and b"64" in msg, msg
+    for o, b in zip(outs, before):
+        assert torch.equal(o, b)
+    # the limit itself is served
+    rc = lib.gq_mala_accept(f32(e_new), f32(u), None, None, i64(step), f32(pose_new), i64(idx_new), f32(grad_new), B, D, n,
+                            18.0, 0.95, 30, f32(energy), f32(pose), i64(idx), f32(grad), u8(accept), f32(temperature), 64,
+                            f32(terms_new), f32(terms), gq.C.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0, lib.gq_last_error()
+    acc = accept.bool()
+    assert torch.equal(terms[:64, acc], terms_new[:64, acc]) and torch.equal(terms[:64, ~acc], before[6][:64, ~acc])
+    assert torch.equal(terms[64], before[6][64])
 
 
 # ---------------------------------------------------------------------------------------------------------------
