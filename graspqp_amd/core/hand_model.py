@@ -190,19 +190,7 @@ class HandModel:
             from ..utils import meshes as mesh_utils
 
             spec = self.spec
-            fvs = [spec.link_faces(l).astype(np.float64) for l in range(spec.n_links)]
-            areas = [0.5 * np.linalg.norm(np.cross(f[:, 1] - f[:, 0], f[:, 2] - f[:, 0]), axis=1).sum() if len(f) else 0.0 for f in fvs]
-            tot = sum(areas)
-            counts = [int(a / tot * self._n_surface_points) for a in areas]
-            counts[0] += self._n_surface_points - sum(counts)
-            pts, lnk = [], []
-            for l, (f, k) in enumerate(zip(fvs, counts)):
-                if k == 0 or len(f) == 0:
-                    continue
-                dense = mesh_utils.sample_surface(f, 100 * k, seed=42)
-                pts.append(mesh_utils.farthest_point_sampling(dense, k))
-                lnk.append(np.full(k, l, dtype=np.int32))
-            pts, lnk = np.concatenate(pts).astype(np.float32), np.concatenate(lnk)
+            pts, lnk = mesh_utils.hand_surface_samples(spec, self._n_surface_points)
             import copy
 
             s2 = copy.copy(spec)

@@ -1055,6 +1055,117 @@ class _HandPen(torch.autograd.Function):
         return gp, None, None, None, None, None, None, None, None
 
 
+# ----------------------------------------------------------------------------------------------------------
+# tabletop terms (core/energy.py:68-78): E_prior and E_wall on the hand's surface samples, one launch (csrc/tabletop.hip)
+# ----------------------------------------------------------------------------------------------------------
+class SurfaceSamples:
+    """Samples of a hand's surface on the device: ``points`` (Ns,3) float32 in the link frames, ``link`` (Ns) int32.  They
+    are RE-ORDERED by link (stable sort), which keeps the 64-sample chunks of the kernel on few links: ``points`` / ``link``
+    hold the same set as the arrays passed in, but not in the caller's order unless that was already by link -- read the
+    samples back from here when they must match (HandModel.set_surface_points, the oracle).  The terms depend on the order
+    only in their last bits.  ``spec_or_hand``: the HandSpec or HandHandle the link ids refer to."""
+
+    def __init__(self, spec_or_hand, points, link_ids, device="cuda"):
+        spec = getattr(spec_or_hand, "spec", spec_or_hand)
+        pts = np.ascontiguousarray(np.asarray(points.detach().cpu() if torch.is_tensor(points) else points, dtype=np.float32))
+        lnk = np.ascontiguousarray(np.asarray(link_ids.detach().cpu() if torch.is_tensor(link_ids) else link_ids, dtype=np.int32))
+        if pts.ndim != 2 or pts.shape[1] != 3 or lnk.shape != (pts.shape[0],):
+            raise ValueError(f"SurfaceSamples: points must be (Ns,3) and link_ids (Ns), got {pts.shape} / {lnk.shape}")
+        self.n_links, self.Ns = int(spec.n_links), int(pts.shape[0])
+        _C.call("gq_tabletop_check", ctypes.c_int64(1), self.n_links, ctypes.c_int64(self.Ns))
+        if lnk.min() < 0 or lnk.max() >= self.n_links:
+            raise ValueError(f"SurfaceSamples: link ids must lie in [0, {self.n_links})")
+        order = np.argsort(lnk, kind="stable")
+        self.points = torch.from_numpy(pts[order]).to(device).contiguous()
+        self.link = torch.from_numpy(lnk[order]).to(device).contiguous()
+
+
+def _axis3(grasp_axis) -> List[float]:
+    a = grasp_axis.detach().cpu().tolist() if torch.is_tensor(grasp_axis) else [float(x) for x in grasp_axis]
+    if len(a) != 3:
+        raise ValueError(f"grasp_axis must have 3 entries, got {len(a)}")
+    return [float(x) for x in a]
+
+
+def _tabletop_call(hp, points, link, n_links, Rg, LT, axis, table_z, up_wall, w_wall, up_prior, w_prior, e_wall, e_prior,
+                   accumulate, wrench, gRt, gR, st=None):
+    ax = (ctypes.c_float * 3)(*axis)
+    _C.call("gq_tabletop_terms", _C.f32(points), _C.i32(link), ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp),
+            hp.shape[1], _C.f32(Rg), _C.f32(LT), ctypes.c_int64(hp.shape[0]), ctypes.cast(ax, ctypes.c_void_p), float(table_z),
+            _C.f32(up_wall), float(w_wall), _C.f32(up_prior), float(w_prior), _C.f32(e_wall), _C.f32(e_prior),
+            int(accumulate), _C.f32(wrench), _C.f32(gRt), _C.f32(gR), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::tabletop_terms", mutates_args=(), device_types="cuda")
+def _tabletop_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, grasp_axis: List[float],
+                 table_z: float) -> Tuple[Tensor, Tensor]:
+    """-> (E_prior (B), E_wall (B)), unweighted (core/energy.py:68-78 with the plane z = table_z).  The kinematic state
+    (Rg, link_T) is the one of ``hand_pose``, passed in detached, as for hand_pen."""
+    hp = _c(hand_pose)
+    B = hp.shape[0]
+    e_prior, e_wall = torch.empty(B, device=hp.device), torch.empty(B, device=hp.device)
+    _tabletop_call(hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT), grasp_axis, table_z, None, 0.0, None, 0.0,
+                   e_wall, e_prior, 0, None, None, None)
+    return e_prior, e_wall
+
+
+@_tabletop_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, grasp_axis, table_z):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B), hand_pose.new_empty(B)
+
+
+@_custom_op("graspqp_amd::tabletop_terms_backward", mutates_args=(), device_types="cuda")
+def _tabletop_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor,
+                     grasp_axis: List[float], table_z: float, g_prior: Tensor, g_wall: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """Upstream row gradients (B) on (E_prior, E_wall) -> (link wrench (B,L,6), gRt (B,12), g_R (B,9)) for fk_backward."""
+    hp = _c(hand_pose)
+    B, dev = hp.shape[0], hp.device
+    wrench, gRt, gR = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev), torch.empty(B, 9, device=dev)
+    _tabletop_call(hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT), grasp_axis, table_z, _c(g_wall), 0.0,
+                   _c(g_prior), 0.0, None, None, 0, wrench, gRt, gR)
+    return wrench, gRt, gR
+
+
+@_tabletop_bwd_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, grasp_axis, table_z, g_prior, g_wall):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12), hand_pose.new_empty(B, 9)
+
+
+class _TabletopTerms(torch.autograd.Function):
+    """Glue between two registered ops (tabletop_terms + fk_backward), as _HandPen: the terms hand link wrenches and the
+    global-pose gradients to the analytic FK backward, which needs the hand's FK workspace and contact indices."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, samples, idx, Rg, LT, ws, axis, table_z):
+        hp = _c(hand_pose.detach())
+        e_prior, e_wall = _Eager.tabletop_terms(hp, samples.points, samples.link, hand.L, Rg, LT, axis, table_z)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, samples.points, samples.link)
+        ctx.hand, ctx.axis, ctx.table_z = hand, axis, table_z
+        return e_prior, e_wall
+
+    @staticmethod
+    def backward(ctx, g_prior, g_wall):
+        hp, idx, Rg, LT, ws, points, link = ctx.saved_tensors
+        hand = ctx.hand
+        wrench, gRt, gR = _Eager.tabletop_terms_backward(hp, points, link, hand.L, Rg, LT, ctx.axis, ctx.table_z, g_prior, g_wall)
+        gp = _fk_backward(hand, hp, idx, Rg, LT, ws, None, None, None, wrench, gRt, gR)
+        return gp, None, None, None, None, None, None, None, None
+
+
+def tabletop_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, LT, ws, grasp_axis, table_z=0.0):
+    """-> (E_prior (B), E_wall (B)) of core/energy.py:68-78 on ``samples``, unweighted, differentiable w.r.t. ``hand_pose``.
+    ``idx``, ``Rg``, ``LT``, ``ws`` are the kinematic state of ``hand_pose`` (fk_contacts); ``table_z`` is the height of the
+    table plane (0 in the reference)."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if samples.n_links != hand.L:
+        raise ValueError(f"tabletop_terms: the samples refer to {samples.n_links} links, the hand has {hand.L}")
+    return _TabletopTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws,
+                                _axis3(grasp_axis), float(table_z))
+
+
 @_custom_op("graspqp_amd::self_pen", mutates_args=(), device_types="cuda")
 def _self_pen_op(centers: Tensor, hand: int) -> Tuple[Tensor, Tensor]:
     """E_spen (B,) of world sphere centres (B,S,3) and dE/dcentres (hand_model.py:989-1040)."""
@@ -1250,6 +1361,8 @@ _eager("fk_contacts", _fk_op, _fk_bwd, _fk_setup)
 _eager("fk_backward", _fk_bwd_op)
 _eager("hand_pen", _hand_pen_op)
 _eager("hand_pen_backward", _hand_pen_bwd_op)
+_eager("tabletop_terms", _tabletop_op)
+_eager("tabletop_terms_backward", _tabletop_bwd_op)
 _eager("self_pen", _self_pen_op, _self_pen_bwd, _self_pen_setup)
 _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_distance_setup)
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)

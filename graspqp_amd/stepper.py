@@ -9,6 +9,11 @@ route (``graspqp_amd.core``) runs, in the reference's order:
 
 State (device tensors): hand_pose (B,D), contact_idx (B,n) i64, grad (B,D), energy (B), ema (B,D), step (B) i64,
 terms (5,B) = accepted [E_dis, E_fc, E_pen, E_spen, E_joints].
+
+Tabletop mode (a weight on "E_prior" or "E_wall", scripts/fit.py:77-78,369-373; core/energy.py:68-78): the two terms are one
+more launch (gq_tabletop_terms) between the joined branches and the FK backward, which adds their link wrenches and
+global-pose gradients to the penetration branch's; ``terms`` is then (7,B) with [E_prior, E_wall] appended, and the
+proposal and the accept step are the stand-alone launches.
 """
 
 from __future__ import annotations
@@ -20,18 +25,37 @@ import torch
 from . import _C, ops
 
 TERM_NAMES = ("E_dis", "E_fc", "E_pen", "E_spen", "E_joints")
+TABLETOP_TERMS = ("E_prior", "E_wall")
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
+
+
+def merge_weights(weights=None):
+    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms) updated with ``weights``; a key that names no term of the
+    stepper raises (it would otherwise be accepted and never used), and so does a negative weight of a tabletop term."""
+    w = dict(DEFAULT_WEIGHTS)
+    w.update({k: 0.0 for k in TABLETOP_TERMS})
+    for k, v in (weights or {}).items():
+        if k not in w:
+            raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
+        w[k] = float(v)
+        if k in TABLETOP_TERMS and not w[k] >= 0.0:  # these terms are switched by their weight: > 0 on, 0 off
+            raise ValueError(f"GraspStepper: weights[{k!r}] = {v!r} must be >= 0")
+    return w
 
 
 class GraspStepper:
     def __init__(self, hand: ops.HandHandle, object_meshes: ops.MeshSet, surface_points: torch.Tensor, batch_each: int,
                  n_contact: int, weights=None, fc_cfg=None, mala_cfg=None, device="cuda", seed=1,
                  penetration_only: bool = True, energy_type: str = "graspqp", optimizer: str = "mala_star",
-                 tdg_directions=None, point_grid: int = 0, split_self_pen: bool = True):
+                 tdg_directions=None, point_grid: int = 0, split_self_pen: bool = True, n_surface_points: int = 512,
+                 surface_samples=None, table_z: float = 0.0):
         """energy_type: "graspqp" (default) | "dexgrasp" | "tdg" (scripts/fit.py:343-347); every type has the fused four-
         launch form (the force-closure role of the first stage launch is the contact terms + that energy) and the per-role
         form on two graph branches.  optimizer: "mala_star" | "dexgraspnet"
-        (AnnealingDexGraspNet, core/optimizer.py:11-149: no z-score in the temperature, no re-initialisation)."""
+        (AnnealingDexGraspNet, core/optimizer.py:11-149: no z-score in the temperature, no re-initialisation).
+        weights["E_prior"] / weights["E_wall"] > 0 select the tabletop mode (module docstring): the hand surface is sampled
+        with ``n_surface_points`` (as HandModel does) unless ``surface_samples`` = (points (Ns,3) in the link frames, link ids
+        (Ns)) is given; ``table_z`` is the height of the table plane."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -45,9 +69,10 @@ class GraspStepper:
         self.B = self.n_obj * self.be
         self.J, self.L, self.S = hand.J, hand.L, hand.S
         self.D = 9 + self.J
-        self.w = dict(DEFAULT_WEIGHTS)
-        if weights:
-            self.w.update(weights)
+        self.w = merge_weights(weights)
+        self.tabletop = any(self.w[k] > 0 for k in TABLETOP_TERMS)
+        self.term_names = TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ())
+        nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
             self.fc.update(fc_cfg)
@@ -67,7 +92,7 @@ class GraspStepper:
         self.contact_idx = torch.zeros(B, n, dtype=torch.long, device=self.dev)
         self.energy = f(B)
         self.step_count = torch.zeros(B, dtype=torch.long, device=self.dev)
-        self.terms = f(5, B)
+        self.terms = f(nT, B)
         # proposal / scratch
         self.pose_new, self.grad_new = f(B, D), f(B, D)
         self.idx_new = torch.zeros(B, n, dtype=torch.long, device=self.dev)
@@ -80,7 +105,7 @@ class GraspStepper:
         self.pen_link = torch.zeros(B, P, dtype=torch.int32, device=self.dev)
         self.wrench, self.gRt = f(B, L, 6), f(B, 12)
         self.e_spen, self.g_sph, self.g_sph_w = f(B), f(B, S, 3), f(B, S, 3)
-        self.terms_new, self.total_new = f(5, B), f(B)
+        self.terms_new, self.total_new = f(nT, B), f(B)
         self.g_theta, self.w_fc_vec = f(B, self.J), torch.full((B,), float(self.w["E_fc"]), device=self.dev)
         self.z, self.temperature, self.s_out = f(B), f(B), f(B)
         self.accept = torch.zeros(B, dtype=torch.uint8, device=self.dev)
@@ -172,7 +197,20 @@ class GraspStepper:
             ad.e_fc = self.terms_new[1].data_ptr()
             self._alt_desc = ad
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
-        self._fuse_loop = True
+        self._fuse_loop = not self.tabletop
+        self.samples, self.g_R = None, None
+        if self.tabletop:
+            if surface_samples is None:
+                from .utils import meshes as mesh_utils
+
+                surface_samples = mesh_utils.hand_surface_samples(hand.spec, int(n_surface_points))
+            self.samples = ops.SurfaceSamples(hand, surface_samples[0], surface_samples[1], device=self.dev)
+            self.g_R = f(B, 9)
+            self.table_z = float(table_z)
+            self._grasp_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
+            # d (w_prior E_prior) / d R = w_prior * grasp_axis in row 2 does not depend on the pose: set here, once; the launch
+            # of every evaluation adds to wrench / gRt and is given no g_R
+            self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._grasp_axis), device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
         pr.hand_pose, pr.grad, pr.contact_idx = self.hand_pose.data_ptr(), self.grad.data_ptr(), self.contact_idx.data_ptr()
@@ -190,7 +228,10 @@ class GraspStepper:
                                                                   int(m["annealing_period"]))
         ac.energy, ac.pose, ac.idx, ac.grad = (t.data_ptr() for t in (self.energy, self.hand_pose, self.contact_idx, self.grad))
         ac.accept, ac.temperature = self.accept.data_ptr(), self.temperature.data_ptr()
-        ac.n_terms, ac.terms_new, ac.terms = 5, self.terms_new.data_ptr(), self.terms.data_ptr()
+        # the fused accept tail merges the five terms of the FK backward's own total; tabletop mode (seven terms) never takes
+        # the fused loop (_fuse_loop above) and merges its terms in the stand-alone accept launch
+        assert self._fuse_loop == (nT == len(TERM_NAMES))
+        ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
         self._propose_desc, self._accept_desc = pr, ac
         sd = _C.SdfDesc()
@@ -260,12 +301,21 @@ class GraspStepper:
                 _C.f32(self.pen_dis), float(self.w["E_pen"]), _C.f32(self.terms_new[2]), _C.ptr(self._span),
                 _C.ptr(self._span_acc), st)
 
+    def _eval_tabletop(self, pose, st):
+        """E_prior / E_wall -> terms_new[5:7]; the gradient of w_wall E_wall is added to the penetration branch's link
+        wrenches and gRt (inputs of the FK backward, like the constant g_R of w_prior E_prior)."""
+        f32, sm = _C.f32, self.samples
+        _C.call("gq_tabletop_terms", f32(sm.points), _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D,
+                f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), ctypes.cast(self._grasp_axis, ctypes.c_void_p),
+                self.table_z, None, float(self.w["E_wall"]), None, float(self.w["E_prior"]), f32(self.terms_new[6]),
+                f32(self.terms_new[5]), 1, f32(self.wrench), f32(self.gRt), None, st)
+
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
         f32 = _C.f32
         _C.call("gq_fk_backward", self.hand.handle, f32(pose), _C.i64(idx), B, n, f32(self.Rg), f32(self.link_T),
                 f32(self.g_cpts), f32(self.g_cnrm), f32(self.g_sph_w) if self.S > 0 else None, f32(self.wrench),
-                f32(self.gRt), None, None, f32(self.grad_new), ctypes.byref(self._row_energy),
+                f32(self.gRt), None, f32(self.g_R), f32(self.grad_new), ctypes.byref(self._row_energy),
                 ctypes.byref(self._accept_desc) if loop else None, _C.ptr(self.fk_ws), self.fk_nb, st)
 
     def _evaluate(self, pose, idx, st, fork=False, timer=None, fused=False, loop=False):
@@ -304,14 +354,19 @@ class GraspStepper:
                 self._eval_spen(pose, ctypes.c_void_p(sb.cuda_stream))
             self._eval_pen(pose, ctypes.c_void_p(sb.cuda_stream), timer)
             main.wait_stream(sb)
+        if self.tabletop:
+            self._eval_tabletop(pose, st)
         self._eval_tail(pose, idx, st, loop)
+        if self.tabletop:  # the FK backward's total holds the five terms
+            _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
+                    _C.f32(self.terms_new[6]), float(self.w["E_wall"]), ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):
         """Energy terms, total and d total / d pose at an arbitrary (pose, idx); returns clones."""
         self.pose_new.copy_(pose)
         self.idx_new.copy_(idx)
         self._evaluate(self.pose_new, self.idx_new, _C.stream_ptr())
-        return ({k: self.terms_new[i].clone() for i, k in enumerate(TERM_NAMES)}, self.total_new.clone(),
+        return ({k: self.terms_new[i].clone() for i, k in enumerate(self.term_names)}, self.total_new.clone(),
                 self.grad_new.clone())
 
     def reset(self, hand_pose, contact_idx):
@@ -359,8 +414,8 @@ class GraspStepper:
         C("gq_mala_accept", f32(self.total_new), f32(self._cur[2]), f32(self.z) if self.optimizer == "mala_star" else None,
           _C.u8(reset_mask), i64(self.step_count), f32(self.pose_new), i64(self.idx_new), f32(self.grad_new), B, D, n,
           float(m["starting_temperature"]), float(m["temperature_decay"]), int(m["annealing_period"]), f32(self.energy),
-          f32(self.hand_pose), i64(self.contact_idx), f32(self.grad), _C.u8(self.accept), f32(self.temperature), 5,
-          f32(self.terms_new), f32(self.terms), st)
+          f32(self.hand_pose), i64(self.contact_idx), f32(self.grad), _C.u8(self.accept), f32(self.temperature),
+          len(self.term_names), f32(self.terms_new), f32(self.terms), st)
 
     def start_kernel_timing(self):
         """Time the hand-penetration query from now on (bench.py): clears the in-kernel span accumulator; outside a

@@ -158,6 +158,26 @@ def surface_points(face_verts: np.ndarray, num_samples: int = 2500, oversample: 
     return pts.astype(np.float32)
 
 
+def hand_surface_samples(spec, n_surface_points: int = 512, oversample: int = 100, seed: int = 42):
+    """Default samples of a hand's surface (reference hand_model.py:604-629): ``n_surface_points`` spread over the links in
+    proportion to their mesh area (the rounding remainder goes to link 0), per link ``oversample`` x as many area-weighted
+    samples thinned by farthest-point sampling.  -> (points (Ns,3) float32 in the link frames, link ids (Ns) int32), ordered
+    by link.  Shared by HandModel.get_surface_points and the tabletop mode of GraspStepper."""
+    fvs = [spec.link_faces(l).astype(np.float64) for l in range(spec.n_links)]
+    areas = [0.5 * np.linalg.norm(np.cross(f[:, 1] - f[:, 0], f[:, 2] - f[:, 0]), axis=1).sum() if len(f) else 0.0 for f in fvs]
+    tot = sum(areas)
+    counts = [int(a / tot * n_surface_points) for a in areas]
+    counts[0] += n_surface_points - sum(counts)
+    pts, lnk = [], []
+    for l, (f, k) in enumerate(zip(fvs, counts)):
+        if k == 0 or len(f) == 0:
+            continue
+        dense = sample_surface(f, oversample * k, seed=seed)
+        pts.append(farthest_point_sampling(dense, k))
+        lnk.append(np.full(k, l, dtype=np.int32))
+    return np.concatenate(pts).astype(np.float32), np.concatenate(lnk)
+
+
 def convex_hull_faces(verts: np.ndarray) -> np.ndarray:
     """Outward-oriented triangles (F,3,3) float64 of the convex hull of ``verts`` (qhull through scipy; the reference
     takes ``trimesh.Trimesh.convex_hull``, initializations.py:42).  Degenerate faces are dropped (:47)."""

@@ -437,6 +437,36 @@ int gq_energy_joints(const float* hand_pose, const float* joints_lower, const fl
 int gq_energy_pen(const float* distances /* (B,P) */, int64_t batch, int64_t n_surface, float* e_pen /* (B) */, void* stream);
 int gq_fill(float* y, float a, int64_t n, void* stream);
 
+/* ---- tabletop terms of the stepper: core/energy.py:68-78 (scripts/fit.py:77-78,369-373: --w_prior, --w_wall) ------
+ * One launch for both terms and their gradient, in the form gq_fk_backward takes.  Per hand surface sample (link-frame
+ * point p of link sample_link): x_h = T_link p, x_w = R x_h + t with t = hand_pose[:, :3].
+ *   E_wall  = sum_s max(table_z - x_w.z, 0)   (energy.py:76-78 with the plane z = table_z; the reference has table_z = 0)
+ *   E_prior = 1 + (R grasp_axis)_z            (energy.py:68-74: 1 - (R grasp_axis) . (0,0,-1))
+ * e_wall / e_prior are written UNWEIGHTED.  The gradient carries the upstream factor of the row: up_*[row] if the pointer
+ * is given, else w_* (the idiom of gq_dexgrasp_energy).  With g_h = R' (0,0,-up) for the samples below the plane:
+ *   link_wrench (B,L,6): f_l = sum g_h, m_l = sum x_h x g_h (about the hand origin, hand frame)
+ *   gRt (B,12) = [gsum(3), K(9)]: gsum = -sum g_h, K = sum g_h (x) x_h  (grad_t = -R gsum, grad_R = R K)
+ *   g_R (B,9): row 2 = up_prior * grasp_axis, zero elsewhere
+ * accumulate = 1 adds to the three gradient buffers (the penetration branch's wrench / gRt), 0 overwrites them; links
+ * without samples get a zero wrench when overwriting and are left alone when accumulating.  Fixed-order sums, no atomics:
+ * bitwise reproducible run to run (the sums follow the order of the samples).  n_links <= 64; n_samples need not be a multiple of 64.
+ * gq_tabletop_check is the argument check of the launch on its own (host only, no GPU).                            */
+int gq_tabletop_check(int64_t batch, int n_links, int64_t n_samples);
+int gq_tabletop_terms(const float* samples /* (Ns,3) link frame, device */, const int32_t* sample_link /* (Ns) */,
+                      int64_t n_samples, int n_links, const float* hand_pose, int pose_dim,
+                      const float* Rg /* (B,9) */, const float* link_T /* (B,L,12) */, int64_t batch,
+                      const float* grasp_axis /* 3 floats, host */, float table_z,
+                      const float* up_wall /* (B) or NULL */, float w_wall,
+                      const float* up_prior /* (B) or NULL */, float w_prior,
+                      float* e_wall /* (B) or NULL, unweighted */, float* e_prior /* (B) or NULL, unweighted */,
+                      int accumulate /* 1: add to the three gradient buffers, 0: overwrite */,
+                      float* link_wrench /* (B,L,6) or NULL */, float* gRt /* (B,12) or NULL */,
+                      float* g_R /* (B,9) or NULL */, void* stream);
+/* total[row] += w_prior * e_prior[row] + w_wall * e_wall[row] (scripts/fit.py:434-438 for the two terms): the row total that
+ * gq_fk_backward writes holds the five terms of its own tail.                                                        */
+int gq_tabletop_total(float* total /* (B) in/out */, const float* e_prior, float w_prior, const float* e_wall, float w_wall,
+                      int64_t batch, void* stream);
+
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
  * Per object: samples_per_object points on its convex hull (area-weighted), pushed out by `inflate` (0.01 in the
  * reference) along the face normal; farthest-point sampling of batch_each of them (start = sample 0); per row the look-at

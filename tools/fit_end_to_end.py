@@ -11,6 +11,8 @@ then three independent checks of what came out:
 Evidence run, not a test: writes one JSON record (default gpurun_out/fit_end_to_end.json).
 
 usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_iter 7000] [--out file.json]
+       [--w_wall 0] [--w_prior 0]   (scripts/fit.py:77-78: tabletop synthesis; the class surface and the oracle then carry
+       E_wall / E_prior on the stepper's surface samples, st.samples)
 """
 import argparse
 import json
@@ -33,6 +35,8 @@ ap.add_argument("--n_contact", type=int, default=12)
 ap.add_argument("--n_iter", type=int, default=7000)
 ap.add_argument("--reset_epochs", type=int, default=600)
 ap.add_argument("--oracle_rows", type=int, default=6)
+ap.add_argument("--w_wall", type=float, default=0.0)
+ap.add_argument("--w_prior", type=float, default=0.0)
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "fit_end_to_end.json"))
 args = ap.parse_args()
 
@@ -47,6 +51,9 @@ from graspqp_amd.stepper import GraspStepper
 from graspqp_amd.utils import meshes
 
 W = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
+TABLETOP = args.w_wall > 0 or args.w_prior > 0
+if TABLETOP:
+    W.update({"E_prior": args.w_prior, "E_wall": args.w_wall})  # fit.py:369-370
 spec = get_hand_spec(args.hand)
 n_obj, be, n = args.n_objects, args.batch_size, args.n_contact
 B = n_obj * be
@@ -56,7 +63,8 @@ sps = [meshes.surface_points(f, 2500, oversample=4, seed=42) for f in fvs]
 om = ObjectModel(batch_size_each=be, num_samples=2500)
 om.initialize_from_meshes(fvs, codes, surface_points_list=sps)
 hand = ops.HandHandle(spec)
-st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1)
+st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1,
+                  weights={"E_prior": args.w_prior, "E_wall": args.w_wall} if TABLETOP else None)
 st.set_hulls(om.convex_hulls())
 st.initialize()  # on-device initialize_convex_hull + the first evaluation
 e0, t0_terms = st.energy.clone(), st.terms.clone()
@@ -82,8 +90,11 @@ assert torch.isfinite(st.energy).all() and torch.isfinite(st.hand_pose).all()
 hm = HandModel(spec, "cuda")
 hp = st.hand_pose.clone().requires_grad_()
 hm.set_parameters(hp, st.contact_idx.clone())
+if TABLETOP:
+    hm.set_surface_points(st.samples.points.cpu().numpy(), st.samples.link.cpu().numpy())
 metric = GraspSpanMetricFactory.create(GraspSpanMetricFactory.MetricType.GRASPQP, {"friction": 0.2, "max_limit": 20.0, "n_cone_vecs": 4})
-losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1)
+losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1,
+                          energy_names=["E_prior", "E_wall"] if TABLETOP else [])
 total_cls = sum(W[k] * losses[k] for k in W)
 rel_cls = ((total_cls.detach() - st.energy).abs() / st.energy.abs().clamp_min(1e-6))
 
@@ -94,14 +105,22 @@ from ref_cpu import models as omodels
 rows = torch.linspace(0, be - 1, args.oracle_rows).long().tolist()
 oh = omodels.OracleHand(spec, torch.float64)
 oo = omodels.OracleObject([fvs[0]], [sps[0]], len(rows), torch.float64)
+if TABLETOP:
+    oh.surface_points, oh.surface_link = st.samples.points.double().cpu().numpy(), st.samples.link.cpu().numpy()
 oh.set_parameters(st.hand_pose[rows].double().cpu(), st.contact_idx[rows].cpu())
 lo = ref_cpu.calculate_energy(oh, oo, box_form=True)
 # every term but E_fc row by row (E_fc's stop rule is batch-global: it is compared on whole batches in tests/)
 rel_oracle = {}
-names = ["E_dis", "E_fc", "E_pen", "E_spen", "E_joints"]
+names = list(st.term_names)
 for k in ("E_dis", "E_pen", "E_spen", "E_joints"):
     got = st.terms[names.index(k)][rows].double().cpu()
     rel_oracle[k] = float(((got - lo[k]).abs() / lo[k].abs().clamp_min(1e-4)).max())
+if TABLETOP:
+    from ref_cpu import energy as oenergy
+
+    for k, v in oenergy.optional_terms(oh).items():
+        got = st.terms[names.index(k)][rows].double().cpu()
+        rel_oracle[k] = float(((got - v).abs() / v.abs().clamp_min(1e-4)).max())
 
 # ---- (3) export + reload the way the consumer does ----------------------------------------------------------------------
 with tempfile.TemporaryDirectory() as tmp:

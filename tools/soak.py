@@ -2,8 +2,13 @@
 every `reset_epochs`) on the bench scene, at one or several batch sizes: energies must stay finite and fall, the debug
 counters must not show inline-ranked overflow growing, the stop iteration is histogrammed.  Development aid, not a test.
 
-usage: python tools/soak.py [n_objects ...]        (256 rows each; default 1 8)
+usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--out file.json]
+       (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
+       schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
+       hand surface samples left below the plane; --out writes the records as JSON.
 """
+import argparse
+import json
 import os
 import sys
 import time
@@ -19,18 +24,42 @@ from graspqp_amd.hands import get_hand_spec
 from graspqp_amd.stepper import GraspStepper
 from graspqp_amd.utils import meshes
 
+ap = argparse.ArgumentParser()
+ap.add_argument("n_objects", type=int, nargs="*", default=[1, 8])
+ap.add_argument("--w_wall", type=float, default=0.0)
+ap.add_argument("--w_prior", type=float, default=0.0)
+ap.add_argument("--table_z", type=float, default=0.0)
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
+TABLETOP = args.w_wall > 0 or args.w_prior > 0
+weights = {"E_wall": args.w_wall, "E_prior": args.w_prior} if TABLETOP else None
+records = []
+
+
+def samples_below(st):
+    """Per row: how many hand surface samples of the accepted poses lie below the table plane (torch, from the link
+    transforms of an evaluation at the accepted state)."""
+    st.evaluate(st.hand_pose.clone(), st.contact_idx.clone())
+    T = st.link_T.view(st.B, st.L, 3, 4)[:, st.samples.link.long()]  # (B,Ns,3,4)
+    xh = (T[..., :3] @ st.samples.points.view(1, -1, 3, 1)).squeeze(-1) + T[..., 3]
+    z = (st.Rg.view(st.B, 3, 3)[:, 2].unsqueeze(1) * xh).sum(-1) + st.hand_pose[:, 2:3]
+    return (z < st.table_z).sum(-1)
+
+
 spec = get_hand_spec("allegro")
 hand = ops.HandHandle(spec)
-for n_obj in [int(a) for a in sys.argv[1:]] or [1, 8]:
+for n_obj in args.n_objects:
     fvs = [meshes.superquadric(o) for o in range(n_obj)]
     sps = [meshes.surface_points(f, 2500, oversample=4, seed=42) for f in fvs]
     om = ObjectModel(batch_size_each=256, num_samples=2500)
     om.initialize_from_meshes(fvs, surface_points_list=sps)
-    st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3)
+    st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3, weights=weights,
+                      table_z=args.table_z)
     st.set_hulls(om.convex_hulls())
     st.initialize()
     e0 = st.energy.clone()
+    wall0 = float(st.terms[6].mean()) if TABLETOP else None
     st.capture(iters=8)
     hist = {}
     acc = []
@@ -56,3 +85,18 @@ for n_obj in [int(a) for a in sys.argv[1:]] or [1, 8]:
     assert int(st.contact_idx.max()) < spec.n_contact_candidates and int(st.contact_idx.min()) >= 0
     print(f"{n_obj} x 256 rows: {N_ITER} iterations in {dt:.2f} s (callback every step: host-bound), mean E {float(e0.mean()):.2f} -> "
           f"{float(e1.mean()):.2f}, stop-iteration histogram {dict(sorted(hist.items()))}, graph mode {st.graph_mode}", flush=True)
+    rec = {"n_objects": n_obj, "batch_size_each": 256, "n_iter": N_ITER, "reset_epochs": RESET, "wall_s": dt,
+           "graph_mode": st.graph_mode, "energy_mean_initial": float(e0.mean()), "energy_mean_final": float(e1.mean())}
+    if TABLETOP:
+        below = samples_below(st)
+        rec.update({"w_wall": args.w_wall, "w_prior": args.w_prior, "table_z": args.table_z, "n_surface_samples": st.samples.Ns,
+                    "E_wall_mean_initial": wall0, "E_wall_mean_final": float(st.terms[6].mean()),
+                    "E_prior_mean_final": float(st.terms[5].mean()), "samples_below_plane_final_total": int(below.sum()),
+                    "rows_with_samples_below_plane_final": int((below > 0).sum())})
+        print(f"  tabletop: mean E_wall {wall0:.4f} -> {rec['E_wall_mean_final']:.6f}, mean E_prior {rec['E_prior_mean_final']:.4f}, "
+              f"{rec['samples_below_plane_final_total']} samples below the plane in {rec['rows_with_samples_below_plane_final']} "
+              f"of {st.B} rows", flush=True)
+    records.append(rec)
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(records, open(args.out, "w"), indent=1)
