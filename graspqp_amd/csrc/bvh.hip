@@ -3,7 +3,8 @@
 // points against every hand-link mesh, N = 640 000 at BASELINE configs[1] -- and core/object_model.py:217-220 for large
 // batches).  Replaces the per-lane loop over ALL faces (gq_sdf_points_kernel: F x 36 VALU operations per query).
 //
-// Layout (one contiguous blob of 16-byte words, built once per mesh on the host, staged into LDS by every block when it fits):
+// Layout (one contiguous blob of 16-byte words, built once per mesh -- boxes on the host, face records by the set-up kernel of
+// sdf.hip -- and staged into LDS by every block when it fits):
 //   faces are Morton-sorted; level 0 groups 4 consecutive faces ("leaf"), level k groups 4 nodes of level k-1, until at most
 //   4 nodes are left (DEPTH levels).  No child pointers: the children of node i of level k are nodes 4i .. 4i+3 of level k-1.
 //   node box = 2 words (lo.xyz hi.x | hi.yz - -); every level is padded to a multiple of 4 with empty boxes (lo = +inf);
@@ -18,19 +19,19 @@
 // shape (far-field queries) the hierarchy beats the face loop and the cluster search at every mesh size either way; for many
 // CONTACT-like queries (within centimetres of a 9 k-face surface) the cluster search is the faster one
 // (tools/ab_contact_routes.py, profiles/r03_ab_sdf_routes.txt) -- the reference never issues such a call with >= 32 768 queries.
+#include "setup.h"
 #include "tri.h"
 
-#include <algorithm>
-#include <vector>
+#include <memory>
 
 struct gqBvh {
+  GqOwner mem;
   float4* blob;      // device
   size_t words;      // 16-byte words in the blob
   int F, Fp, depth;  // faces, padded faces (4 * n[0]), levels
   int lvl_off[8];    // word offset of level k's boxes
   int lvl_n[8];      // padded node count of level k
   int fbox_off, rec_off;
-  float centre[3];   // centre of the mesh's bounding box (direction bins of the sorted kernel)
 };
 
 struct GqBvhArgs {
@@ -159,176 +160,11 @@ __global__ __launch_bounds__(1024, GQ_BVH_MIN_BLOCKS) void gq_sdf_bvh_kernel(GqB
   }
 }
 
-// The same traversal with the queries of a 2048-point chunk first ORDERED BY DIRECTION from the mesh centre inside the block
-// (LDS counting sort over 96 direction bins: cube face x 4 x 4 cells): the 64 lanes of a wavefront then walk nearly the same
-// nodes, so their LDS reads coalesce into broadcasts instead of conflicting and the wavefront's cost (its slowest lane)
-// approaches the mean.  The order in which equal-bin queries land on lanes depends on LDS atomics, the result of every
-// query does not.  Results are written back to the query's own slot.  OFF by default: see gq_bvh_sorted_ below.
-#define GQ_BVH_CHUNK 2048
-#define GQ_BVH_BINS 96
-__device__ __forceinline__ int gq_bvh_dir_bin(gq3 d) {
-  const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
-  int face;
-  float u, v, m;
-  if (ax >= ay && ax >= az) { face = d.x < 0.0f ? 1 : 0; m = ax; u = d.y; v = d.z; }
-  else if (ay >= az) { face = d.y < 0.0f ? 3 : 2; m = ay; u = d.x; v = d.z; }
-  else { face = d.z < 0.0f ? 5 : 4; m = az; u = d.x; v = d.y; }
-  const float inv = m > 0.0f ? 2.0f / m : 0.0f;  // u / m in [-1, 1] -> cell 0..3
-  int iu = (int)fminf(fmaxf(fmaf(u, inv, 2.0f), 0.0f), 3.0f);
-  int iv = (int)fminf(fmaxf(fmaf(v, inv, 2.0f), 0.0f), 3.0f);
-  if (iv & 1) iu = 3 - iu;  // boustrophedon inside the face: consecutive bins are neighbours
-  return face * 16 + iv * 4 + iu;
-}
-
-template <int DEPTH, bool LDS>
-__global__ __launch_bounds__(512) void gq_sdf_bvh_sorted_kernel(GqBvhArgs g, float cx, float cy, float cz) {
-  extern __shared__ float4 gq_bvh_sh[];
-  __shared__ unsigned s_hist[GQ_BVH_BINS + 32];
-  __shared__ unsigned short s_perm[GQ_BVH_CHUNK];
-  const float4* base = g.blob;
-  if (LDS) {
-    for (unsigned i = threadIdx.x; i < g.words; i += 512) gq_bvh_sh[i] = g.blob[i];
-    base = gq_bvh_sh;
-  }
-  const int tid = (int)threadIdx.x;
-  const long long nchunk = (g.N + GQ_BVH_CHUNK - 1) / GQ_BVH_CHUNK;
-  for (long long ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
-    const long long q0 = ch * GQ_BVH_CHUNK;
-    if (tid < GQ_BVH_BINS + 32) s_hist[tid] = 0u;
-    __syncthreads();
-    int bin[4];
-    unsigned pos[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const long long q = q0 + r * 512 + tid;
-      bin[r] = -1;
-      if (q < g.N) {
-        const gq3 d = gq_mk(g.points[q * 3 + 0] - cx, g.points[q * 3 + 1] - cy, g.points[q * 3 + 2] - cz);
-        bin[r] = gq_bvh_dir_bin(d);
-        pos[r] = atomicAdd(&s_hist[bin[r]], 1u);
-      }
-    }
-    __syncthreads();
-    if (tid < GQ_WAVE) {  // exclusive scan of the 96 counters by one wavefront (two per lane)
-      const unsigned a = s_hist[2 * tid], b = (2 * tid + 1 < GQ_BVH_BINS + 32) ? s_hist[2 * tid + 1] : 0u;
-      unsigned incl = a + b;
-#pragma unroll
-      for (int o = 1; o < GQ_WAVE; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o, GQ_WAVE);
-        if (tid >= o) incl += t;
-      }
-      const unsigned excl = incl - (a + b);
-      s_hist[2 * tid] = excl;
-      if (2 * tid + 1 < GQ_BVH_BINS + 32) s_hist[2 * tid + 1] = excl + a;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (bin[r] >= 0) s_perm[s_hist[bin[r]] + pos[r]] = (unsigned short)(r * 512 + tid);
-    __syncthreads();
-    const int n_here = (int)((g.N - q0) < GQ_BVH_CHUNK ? (g.N - q0) : GQ_BVH_CHUNK);
-#pragma unroll 1
-    for (int r = 0; r < 4; ++r) {
-      const int slot = r * 512 + tid;
-      const bool ok = slot < n_here;
-      const long long q = q0 + (ok ? (int)s_perm[slot] : 0);
-      const gq3 p = gq_mk(g.points[q * 3 + 0], g.points[q * 3 + 1], g.points[q * 3 + 2]);
-      GqBvhBest b{GQ_INF_F, 0, 0x7fffffff};
-      const float4* cb = base + g.lvl_off[DEPTH - 1];
-      float lb[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) lb[k] = gq_bvh_box_lb(cb[2 * k], cb[2 * k + 1], p);
-#pragma unroll 1
-      for (int rr = 0; rr < 4; ++rr) {
-        const float m = fminf(fminf(lb[0], lb[1]), fminf(lb[2], lb[3]));
-        if (!(m <= gq_bvh_thr(b.d2)) || m == GQ_INF_F) break;
-        const int k = (m == lb[0]) ? 0 : (m == lb[1]) ? 1 : (m == lb[2]) ? 2 : 3;
-#pragma unroll
-        for (int qk = 0; qk < 4; ++qk) lb[qk] = (qk == k) ? GQ_INF_F : lb[qk];
-        GqBvhVisit<DEPTH - 1>::run(base, g, p, k, b);
-      }
-      if (!ok) continue;
-      const GqFace fc = *reinterpret_cast<const GqFace*>(base + g.rec_off + 6 * b.idx);
-      const GqSdfOut o = gq_tri_finish(fc, p);
-      g.dist_sq[q] = o.dist2;
-      g.sign[q] = o.sign;
-      if (g.normal) {
-        g.normal[q * 3 + 0] = o.normal.x;
-        g.normal[q * 3 + 1] = o.normal.y;
-        g.normal[q * 3 + 2] = o.normal.z;
-      }
-      g.closest[q * 3 + 0] = o.closest.x;
-      g.closest[q * 3 + 1] = o.closest.y;
-      g.closest[q * 3 + 2] = o.closest.z;
-    }
-    __syncthreads();  // s_perm / s_hist are reused by the next chunk
-  }
-}
-
-static inline uint32_t gq_bvh_spread10(uint32_t v) {
-  v &= 0x3ff;
-  v = (v | (v << 16)) & 0x030000ff;
-  v = (v | (v << 8)) & 0x0300f00f;
-  v = (v | (v << 4)) & 0x030c30c3;
-  v = (v | (v << 2)) & 0x09249249;
-  return v;
-}
-
-__global__ void gq_bvh_rec_kernel(const float* __restrict__ fv, const int32_t* __restrict__ perm, int F, int Fp, float4* __restrict__ rec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Fp) return;
-  GqFace f;
-  if (i < F) {
-    const float* v = fv + (size_t)perm[i] * 9;
-    f = gq_make_face(gq_mk(v[0], v[1], v[2]), gq_mk(v[3], v[4], v[5]), gq_mk(v[6], v[7], v[8]), perm[i]);
-  } else {  // padding: never passes its (empty) face box; a far-away point in any case
-    const gq3 far = gq_mk(1e18f, 1e18f, 1e18f);
-    f = gq_make_face(far, far, far, 0x7fffffff);
-  }
-  float4* o = rec + (size_t)6 * i;
-  o[0] = f.r0; o[1] = f.r1; o[2] = f.r2; o[3] = f.r3; o[4] = f.r4; o[5] = f.r5;
-}
-
-// gq_debug_set_bvh_sorted: 1 = order every 2048-query chunk by direction first (A/B runs).  Measured SLOWER on the reference's
-// call shape (14 Allegro links x 640 000 queries: 2.42 ms against 1.60 ms in plain order, profiles/r03_plugin_surface_*.json):
-// the counting sort, its barriers and the scattered point / result accesses cost more than the coherence returns.
-static int gq_bvh_sorted_ = 0;
-
 extern "C" {
-
-int gq_debug_set_bvh_sorted(int on) {
-  gq_bvh_sorted_ = on;
-  return GQ_OK;
-}
 
 int gq_bvh_create(const float* face_verts_host, int64_t n_faces, gqBvh** out) {
   GQ_REQUIRE(face_verts_host && out && n_faces > 0 && n_faces <= 65536, "bvh_create: 1..65536 faces, got %lld", (long long)n_faces);
   const int F = (int)n_faces;
-  // Morton order of the face centroids
-  float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
-  for (int64_t i = 0; i < (int64_t)F * 9; ++i) {
-    const int c = (int)(i % 3);
-    lo[c] = std::min(lo[c], face_verts_host[i]);
-    hi[c] = std::max(hi[c], face_verts_host[i]);
-  }
-  std::vector<std::pair<uint32_t, int32_t>> keys(F);
-  for (int i = 0; i < F; ++i) {
-    const float* v = face_verts_host + (size_t)i * 9;
-    uint32_t code = 0;
-    for (int c = 0; c < 3; ++c) {
-      const float ctr = (v[c] + v[3 + c] + v[6 + c]) * (1.0f / 3.0f), ext = hi[c] - lo[c];
-      float t = ext > 0.0f ? (ctr - lo[c]) / ext : 0.0f;
-      t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-      code |= gq_bvh_spread10((uint32_t)(t * 1023.0f)) << c;
-    }
-    keys[i] = {code, i};
-  }
-  std::stable_sort(keys.begin(), keys.end());
-  std::vector<int32_t> perm(F);
-  for (int i = 0; i < F; ++i) perm[i] = keys[i].second;
-  gqBvh* b = new gqBvh();
-  b->F = F;
-  for (int c = 0; c < 3; ++c) b->centre[c] = 0.5f * (lo[c] + hi[c]);
   // levels
   int n = (F + 3) / 4, depth = 0;
   std::vector<int> ln;
@@ -339,6 +175,14 @@ int gq_bvh_create(const float* face_verts_host, int64_t n_faces, gqBvh** out) {
     n = (n + 3) / 4;
   }
   GQ_REQUIRE(depth <= 8, "bvh_create: too deep");
+  // Morton order of the face centroids
+  std::vector<int32_t> perm(F);
+  for (int i = 0; i < F; ++i) perm[i] = i;
+  float box[8];
+  gq_box_of(face_verts_host, perm.data(), 0, F, box);
+  gq_morton_order(face_verts_host, perm.data(), 0, F, box);
+  auto b = std::make_unique<gqBvh>();
+  b->F = F;
   b->depth = depth;
   b->Fp = 4 * ln[0];
   // (padding nodes have empty boxes and are never entered, so their children need not exist: level k-1 holds exactly
@@ -392,31 +236,24 @@ int gq_bvh_create(const float* face_verts_host, int64_t n_faces, gqBvh** out) {
     chi.swap(nhi);
     cn = ln[k];
   }
-  float* fv_dev = nullptr;
-  int32_t* perm_dev = nullptr;
-  GQ_CHECK_HIP(hipMalloc(&b->blob, w * 16));
-  GQ_CHECK_HIP(hipMalloc(&fv_dev, (size_t)F * 9 * 4));
-  GQ_CHECK_HIP(hipMalloc(&perm_dev, (size_t)F * 4));
-  GQ_CHECK_HIP(hipMemcpy(b->blob, host.data(), w * 16, hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(fv_dev, face_verts_host, (size_t)F * 9 * 4, hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(perm_dev, perm.data(), (size_t)F * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(gq_bvh_rec_kernel, dim3((unsigned)((b->Fp + 255) / 256)), dim3(256), 0, 0, fv_dev, perm_dev, F, b->Fp,
-                     b->blob + b->rec_off);
-  GQ_LAUNCH_CHECK();
-  GQ_CHECK_HIP(hipDeviceSynchronize());
-  GQ_CHECK_HIP(hipFree(fv_dev));
-  GQ_CHECK_HIP(hipFree(perm_dev));
-  *out = b;
+  GqOwner scratch;
+  b->blob = (float4*)b->mem.upload(host.data(), w * 4);
+  const float* fv_dev = scratch.upload(face_verts_host, (size_t)F * 9);
+  const int32_t* perm_dev = scratch.upload(perm.data(), (size_t)F);
+  if (b->mem.rc || scratch.rc) return GQ_ERR_HIP;
+  int rc = gq_face_records_(fv_dev, perm_dev, F, b->Fp, reinterpret_cast<GqFace*>(b->blob + b->rec_off), 0);
+  if (rc) return rc;
+  GQ_CHECK_HIP(hipStreamSynchronize(0));  // the kernel reads the scratch buffers
+  *out = b.release();
   return GQ_OK;
 }
 
 int gq_bvh_destroy(gqBvh* b) {
-  if (!b) return GQ_OK;
-  (void)hipFree(b->blob);
   delete b;
   return GQ_OK;
 }
 
+// One kernel, gq_sdf_bvh_kernel<depth, LDS-resident>; block size, grid and LDS residency follow from the blob size and the depth.
 int gq_sdf_forward_bvh(const gqBvh* b, const float* points, int64_t n_points, float* dist_sq, int32_t* sign, float* normal,
                        float* closest, void* stream) {
   if (n_points == 0) return GQ_OK;
@@ -434,38 +271,25 @@ int gq_sdf_forward_bvh(const gqBvh* b, const float* points, int64_t n_points, fl
   a.normal = normal;
   a.closest = closest;
   const size_t bytes = b->words * 16;
-  const bool sorted = gq_bvh_sorted_ != 0 && n_points >= 4 * GQ_BVH_CHUNK;
   // LDS-resident while the blob fits: two or more 512-thread blocks per CU up to 80 KB, one 1024-thread block per CU above
   // (a hierarchy walked from global memory costs about twice as much per query: 140 us at 456 faces in LDS against 256 us at
-  // 502 faces from L2 on the reference's per-link call shape, profiles/r03_ab_sdf_routes.txt); the A/B sorted variant keeps
-  // its 64 KB limit
-  const bool lds = b->depth <= 5 && bytes <= (sorted ? (size_t)64 * 1024 : (size_t)GQ_BVH_LDS_MAX);
+  // 502 faces from L2 on the reference's per-link call shape, profiles/r03_ab_sdf_routes.txt)
+  const bool lds = b->depth <= 5 && bytes <= (size_t)GQ_BVH_LDS_MAX;
 #ifndef GQ_BVH_SMALL_THREADS
 #define GQ_BVH_SMALL_THREADS 512u  // A/B: 640 (two blocks = five wavefronts per SIMD for the <= 3-level hierarchies) is 20 % SLOWER
 #endif                             // on the 188 ... 232-face Allegro links (profiles/r03_ab_bvh_occupancy.txt): LDS-bound, not latency-bound
-  const unsigned threads = (!sorted && lds && bytes > 80 * 1024) ? 1024u : ((!sorted && lds && b->depth <= 3) ? GQ_BVH_SMALL_THREADS : 512u);
-  const long long per_chunk = sorted ? GQ_BVH_CHUNK : (long long)threads;
-  const long long nchunk = (n_points + per_chunk - 1) / per_chunk;
-  const size_t stat = sorted ? 5 * 1024 : 0;  // static LDS of the sorted kernel (histogram + permutation)
-  const int per_cu = lds ? (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / (bytes + stat))) : 4;
+  const unsigned threads = (lds && bytes > 80 * 1024) ? 1024u : ((lds && b->depth <= 3) ? GQ_BVH_SMALL_THREADS : 512u);
+  const long long nchunk = (n_points + threads - 1) / threads;
+  const int per_cu = lds ? (int)std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / bytes)) : 4;
   const unsigned grid = (unsigned)std::min<long long>(nchunk, 256ll * per_cu);
   hipStream_t st = (hipStream_t)stream;
-#define GQ_BVH_LAUNCH(D, L)                                                                                                   \
-  do {                                                                                                                        \
-    if (sorted) {                                                                                                             \
-      hipLaunchKernelGGL((gq_sdf_bvh_sorted_kernel<D, L>), dim3(grid), dim3(512), (L) ? bytes : 0, st, a, b->centre[0],       \
-                         b->centre[1], b->centre[2]);                                                                         \
-    } else {                                                                                                                  \
-      if ((L) && bytes > 64 * 1024) { /* more dynamic LDS than the 64 KB a kernel may use without asking */                    \
-        static bool raised = false;                                                                                           \
-        if (!raised) {                                                                                                        \
-          GQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gq_sdf_bvh_kernel<D, L>),                           \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GQ_BVH_LDS_MAX));                      \
-          raised = true;                                                                                                      \
-        }                                                                                                                     \
-      }                                                                                                                       \
-      hipLaunchKernelGGL((gq_sdf_bvh_kernel<D, L>), dim3(grid), dim3(threads), (L) ? bytes : 0, st, a);                       \
-    }                                                                                                                         \
+#define GQ_BVH_LAUNCH(D, L)                                                                                       \
+  do {                                                                                                            \
+    if ((L) && bytes > 64 * 1024) { /* more dynamic LDS than the 64 KB a kernel may use without asking */          \
+      const int rc = gq_allow_dynamic_lds(reinterpret_cast<const void*>(&gq_sdf_bvh_kernel<D, L>), GQ_BVH_LDS_MAX); \
+      if (rc) return rc;                                                                                          \
+    }                                                                                                             \
+    hipLaunchKernelGGL((gq_sdf_bvh_kernel<D, L>), dim3(grid), dim3(threads), (L) ? bytes : 0, st, a);             \
   } while (0)
   switch (b->depth) {
     case 1: if (lds) GQ_BVH_LAUNCH(1, true); else GQ_BVH_LAUNCH(1, false); break;

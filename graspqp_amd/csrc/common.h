@@ -5,6 +5,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <mutex>
+#include <utility>
+#include <vector>
+
 #include "../../include/graspqp_hip.h"  // every definition is checked against the published prototypes
 
 #define GQ_WAVE 64
@@ -31,6 +35,22 @@ extern "C" void gq_set_error_(const char* msg);
 #define GQ_LAUNCH_CHECK() GQ_CHECK_HIP(hipGetLastError())
 
 enum { GQ_OK = 0, GQ_ERR_ARG = 2, GQ_ERR_HIP = 3, GQ_ERR_UNSUPPORTED = 4 };
+
+// A kernel may use more than 64 KB of dynamic LDS only after hipFuncAttributeMaxDynamicSharedMemorySize has been raised for it
+// on the device it runs on.  `bytes` is the most the kernel is ever launched with: the attribute is raised once per kernel
+// and device, afterwards a call costs hipGetDevice and a look at the list.
+inline int gq_allow_dynamic_lds(const void* kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::vector<std::pair<const void*, int>> raised;  // (kernel, device)
+  int dev = 0;
+  GQ_CHECK_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  for (const auto& r : raised)
+    if (r.first == kernel && r.second == dev) return GQ_OK;
+  GQ_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  raised.emplace_back(kernel, dev);
+  return GQ_OK;
+}
 
 // ---- lane helpers -----------------------------------------------------------------------------------
 __device__ __forceinline__ int gq_lane() { return threadIdx.x & (GQ_WAVE - 1); }

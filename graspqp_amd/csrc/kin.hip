@@ -9,7 +9,10 @@
 #include "kin_dev.h"
 #include "loop_dev.h"
 #include "sdf_dev.h"
+#include "setup.h"
 #include "wave.h"
+
+#include <memory>
 
 #ifndef GQ_FK_QUERY_TOPK
 // clusters per round of the contact queries that ride in the FK forward block.  2 (round 3): two instead of four face records in
@@ -541,14 +544,10 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_self_pen_row_kernel(gqHand h, GqSp
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-template <typename T>
-static int gq_upload(T** dst, const T* src, size_t n) {
-  *dst = nullptr;
-  if (n == 0) return GQ_OK;
-  GQ_CHECK_HIP(hipMalloc((void**)dst, n * sizeof(T)));
-  GQ_CHECK_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return GQ_OK;
-}
+// gqHand itself is the table of device pointers that every kernel takes by value; the created object adds the owner
+struct GqHandObject : gqHand {
+  GqOwner mem;
+};
 
 int gq_colsq_launch_(const float* grad, int B, int D, int clip, float* g2, void* stream);  // loop.hip
 int gq_sdf_wave_args_(const gqMeshSet* ms, int64_t n_points, int64_t queries_per_mesh, float* dist_sq, int32_t* sign,
@@ -573,11 +572,10 @@ int gq_hand_create(const gqHandDesc* d, gqHand** out) {
   }
   const int JA = (d->n_actuated > 0 && d->coupling) ? d->n_actuated : d->n_dofs;
   GQ_REQUIRE(JA > 0 && JA <= 64 && (d->n_actuated <= 0 || d->coupling), "hand_create: n_actuated without a coupling matrix");
-  gqHand* h = new gqHand();
+  auto h = std::make_unique<GqHandObject>();
+  GqOwner& mem = h->mem;
   h->J = d->n_dofs;
   h->JA = JA;
-  h->coup = nullptr;
-  h->coup0 = nullptr;
   h->L = d->n_links;
   h->C = d->n_cand;
   h->S = d->n_spheres;
@@ -587,26 +585,25 @@ int gq_hand_create(const gqHandDesc* d, gqHand** out) {
     if (s == 0 || d->sphere_link[s] != d->sphere_link[s - 1]) groups[ng++] = s;
   groups[ng] = d->n_spheres;
   h->NG = ng;
-  int rc = 0;
-  rc |= gq_upload(&h->node_parent, d->node_parent, h->J);
-  rc |= gq_upload(&h->node_type, d->node_type, h->J);
-  rc |= gq_upload(&h->node_pre, d->node_pre, (size_t)h->J * 12);
-  rc |= gq_upload(&h->node_axis, d->node_axis, (size_t)h->J * 3);
-  rc |= gq_upload(&h->link_node, d->link_node, h->L);
-  rc |= gq_upload(&h->link_offset, d->link_offset, (size_t)h->L * 12);
-  rc |= gq_upload(&h->cand_pos, d->cand_pos, (size_t)h->C * 3);
-  rc |= gq_upload(&h->cand_nrm, d->cand_nrm, (size_t)h->C * 3);
-  rc |= gq_upload(&h->cand_link, d->cand_link, h->C);
-  rc |= gq_upload(&h->sphere, d->sphere, (size_t)h->S * 4);
-  rc |= gq_upload(&h->sphere_link, d->sphere_link, h->S);
-  rc |= gq_upload(&h->jlo, d->joints_lower, h->JA);
-  rc |= gq_upload(&h->jhi, d->joints_upper, h->JA);
+  h->node_parent = mem.upload(d->node_parent, h->J);
+  h->node_type = mem.upload(d->node_type, h->J);
+  h->node_pre = mem.upload(d->node_pre, (size_t)h->J * 12);
+  h->node_axis = mem.upload(d->node_axis, (size_t)h->J * 3);
+  h->link_node = mem.upload(d->link_node, h->L);
+  h->link_offset = mem.upload(d->link_offset, (size_t)h->L * 12);
+  h->cand_pos = mem.upload(d->cand_pos, (size_t)h->C * 3);
+  h->cand_nrm = mem.upload(d->cand_nrm, (size_t)h->C * 3);
+  h->cand_link = mem.upload(d->cand_link, h->C);
+  h->sphere = mem.upload(d->sphere, (size_t)h->S * 4);
+  h->sphere_link = mem.upload(d->sphere_link, h->S);
+  h->jlo = mem.upload(d->joints_lower, h->JA);
+  h->jhi = mem.upload(d->joints_upper, h->JA);
   if (d->n_actuated > 0 && d->coupling) {
     float zero[64] = {0};
-    rc |= gq_upload(&h->coup, d->coupling, (size_t)h->J * h->JA);
-    rc |= gq_upload(&h->coup0, d->coupling_offset ? d->coupling_offset : (const float*)zero, (size_t)h->J);
+    h->coup = mem.upload(d->coupling, (size_t)h->J * h->JA);
+    h->coup0 = mem.upload(d->coupling_offset ? d->coupling_offset : (const float*)zero, (size_t)h->J);
   }
-  rc |= gq_upload(&h->group_off, (const int32_t*)groups, (size_t)ng + 1);
+  h->group_off = mem.upload((const int32_t*)groups, (size_t)ng + 1);
   {
     int32_t grp[256];
     int gcur = 0;
@@ -614,7 +611,7 @@ int gq_hand_create(const gqHandDesc* d, gqHand** out) {
       while (gcur + 1 < ng && s >= groups[gcur + 1]) ++gcur;
       grp[s] = gcur;
     }
-    rc |= gq_upload(&h->sphere_grp, (const int32_t*)grp, (size_t)h->S);
+    h->sphere_grp = mem.upload((const int32_t*)grp, (size_t)h->S);
   }
   {
     int32_t depth[64], coff[65], cidx[64];
@@ -631,23 +628,17 @@ int gq_hand_create(const gqHandDesc* d, gqHand** out) {
     }
     coff[h->J] = k;
     h->max_depth = md;
-    rc |= gq_upload(&h->node_depth, (const int32_t*)depth, h->J);
-    rc |= gq_upload(&h->child_off, (const int32_t*)coff, (size_t)h->J + 1);
-    rc |= gq_upload(&h->child_idx, (const int32_t*)cidx, (size_t)(k > 0 ? k : 1));
+    h->node_depth = mem.upload((const int32_t*)depth, h->J);
+    h->child_off = mem.upload((const int32_t*)coff, (size_t)h->J + 1);
+    h->child_idx = mem.upload((const int32_t*)cidx, (size_t)(k > 0 ? k : 1));
   }
-  if (rc) return GQ_ERR_HIP;
-  *out = h;
+  if (mem.rc) return mem.rc;
+  *out = h.release();
   return GQ_OK;
 }
 
 int gq_hand_destroy(gqHand* h) {
-  if (!h) return GQ_OK;
-  void* p[] = {h->node_parent, h->node_type, h->node_pre, h->node_axis, h->link_node, h->link_offset, h->cand_pos,
-               h->cand_nrm, h->cand_link, h->sphere, h->sphere_link, h->jlo, h->jhi, h->group_off, h->node_depth,
-               h->child_off, h->child_idx, h->sphere_grp, h->coup, h->coup0};
-  for (void* q : p)
-    if (q) (void)hipFree(q);
-  delete h;
+  delete static_cast<GqHandObject*>(h);
   return GQ_OK;
 }
 

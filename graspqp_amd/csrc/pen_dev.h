@@ -3,15 +3,18 @@
 // the block's dynamic LDS instead of reading blockIdx / declaring static __shared__ arrays, so that several bodies
 // can live in one kernel and share one LDS allocation.
 #pragma once
+#include "setup.h"
 #include "tri.h"
 #include "wave.h"
 
 // ---- mesh-set handle: concatenated face records of n_mesh meshes on the device -----------------------------------
 struct gqMeshSet {
+  GqOwner mem;         // every pointer below
   GqFace* rec;         // records, faces Morton-sorted inside each mesh
   int32_t* off_dev;    // (n_mesh+1) face offsets
   int32_t* off_host;
-  float* aabb_dev;     // (n_mesh, 8) box of each mesh in its own frame
+  float* aabb_host;    // (n_mesh, 8) box of each mesh in its own frame, as built
+  float* aabb_dev;     // the same, grown a little with the voxel scales in its pads once the occupancy grid exists
   float* sub_aabb_dev; // (n_sub, 8) boxes of 16-face sub-clusters
   int32_t* sub_off_dev;   // (n_mesh+1)
   float* cl_aabb_dev;  // (n_cl, 16) oriented boxes of the 64-face clusters (gq_cluster_bound)
@@ -28,6 +31,7 @@ struct gqMeshSet {
 
 // ---- uniform grid over the surface points of every object (set-up data of the cell-driven penetration query) --------
 struct gqPointGrid {
+  GqOwner mem;
   float* box_dev;        // (n_obj,8): lo.xyz, -, cells per metre x y z, -
   int32_t* start_dev;    // (n_obj, G^3 + 1)
   uint16_t* pts_dev;     // (n_obj, P)

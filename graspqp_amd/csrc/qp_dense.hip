@@ -238,12 +238,21 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_qp_dense_bwd_kernel(GqQpBwdArgs g)
   gq_qp_bwd_row<2>(g, S, row, lane);
 }
 
+// nz <= 128: up to 71 168 B of dynamic LDS, more than a kernel may use without asking
+static int gq_dense_allow_lds(const void* kernel, int nz) {
+  return gq_dense_lds_bytes(nz) > 64 * 1024 ? gq_allow_dynamic_lds(kernel, gq_dense_lds_bytes(128)) : GQ_OK;
+}
+
 int gq_qp_launch_iter_dense_lds(const GqQpArgs& a, hipStream_t st) {
+  const int rc = gq_dense_allow_lds(reinterpret_cast<const void*>(&gq_qp_dense_iter_kernel), a.nz);
+  if (rc) return rc;
   hipLaunchKernelGGL(gq_qp_dense_iter_kernel, dim3(a.B), dim3(GQ_WAVE), gq_dense_lds_bytes(a.nz), st, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }
 int gq_qp_launch_bwd_dense_lds(const GqQpBwdArgs& a, hipStream_t st) {
+  const int rc = gq_dense_allow_lds(reinterpret_cast<const void*>(&gq_qp_dense_bwd_kernel), a.nz);
+  if (rc) return rc;
   hipLaunchKernelGGL(gq_qp_dense_bwd_kernel, dim3(a.B), dim3(GQ_WAVE), gq_dense_lds_bytes(a.nz), st, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;

@@ -51,14 +51,25 @@ int gq_debug_set_pen_counters(uint64_t* counters) {
 }
 }  // extern "C"
 
-// rec[i] = record of face perm[i] (perm == nullptr: identity)
+// rec[i] = record of face perm[i] (perm == nullptr: identity) for i < F; F <= i < Fp (the box hierarchy pads its leaves to
+// 4 faces): a far-away point that never passes its (empty) face box
 __global__ void gq_face_prep_kernel(const float* __restrict__ fv, const int32_t* __restrict__ perm,
-                                    GqFace* __restrict__ rec, int64_t F) {
+                                    GqFace* __restrict__ rec, int64_t F, int64_t Fp) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= F) return;
-  const int64_t src = perm ? perm[i] : i;
-  const float* v = fv + src * 9;
-  rec[i] = gq_make_face(gq_mk(v[0], v[1], v[2]), gq_mk(v[3], v[4], v[5]), gq_mk(v[6], v[7], v[8]), (int)src);
+  if (i >= Fp) return;
+  if (i < F) {
+    const int64_t src = perm ? perm[i] : i;
+    const float* v = fv + src * 9;
+    rec[i] = gq_make_face(gq_mk(v[0], v[1], v[2]), gq_mk(v[3], v[4], v[5]), gq_mk(v[6], v[7], v[8]), (int)src);
+  } else {
+    const gq3 far = gq_mk(1e18f, 1e18f, 1e18f);
+    rec[i] = gq_make_face(far, far, far, 0x7fffffff);
+  }
+}
+int gq_face_records_(const float* fv, const int32_t* perm, int64_t F, int64_t Fp, GqFace* rec, hipStream_t st) {
+  hipLaunchKernelGGL(gq_face_prep_kernel, dim3((unsigned)((Fp + 255) / 256)), dim3(256), 0, st, fv, perm, rec, F, Fp);
+  GQ_LAUNCH_CHECK();
+  return GQ_OK;
 }
 
 template <int TOPK>  // 4: <= 128 VGPRs, 4 wavefronts per SIMD; 2 (large launches): see gq_sdf_wave_query
@@ -349,32 +360,8 @@ __global__ __launch_bounds__(256) void gq_occ_centres_kernel(const GqFace* __res
   if (inside) atomicOr(&occ[(size_t)m * 1024 + iz * 32 + iy], 1u << ix);
 }
 
-#include <algorithm>
 #include <cmath>
-#include <vector>
-
-static inline uint32_t gq_spread10(uint32_t v) {
-  v &= 0x3ff;
-  v = (v | (v << 16)) & 0x030000ff;
-  v = (v | (v << 8)) & 0x0300f00f;
-  v = (v | (v << 4)) & 0x030c30c3;
-  v = (v | (v << 2)) & 0x09249249;
-  return v;
-}
-
-static void gq_box_of(const float* fv, const int32_t* perm, int64_t a, int64_t b, float* out8) {
-  float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
-  for (int64_t i = a; i < b; ++i) {
-    const float* v = fv + (int64_t)perm[i] * 9;
-    for (int k = 0; k < 9; ++k) {
-      const int c = k % 3;
-      lo[c] = v[k] < lo[c] ? v[k] : lo[c];
-      hi[c] = v[k] > hi[c] ? v[k] : hi[c];
-    }
-  }
-  out8[0] = lo[0]; out8[1] = lo[1]; out8[2] = lo[2]; out8[3] = 0.0f;
-  out8[4] = hi[0]; out8[5] = hi[1]; out8[6] = hi[2]; out8[7] = 0.0f;
-}
+#include <memory>
 
 // Bound of a 64-face cluster: an oriented box, 16 floats = [centre.xyz, h_u][u.xyz, h_v][v.xyz, h_n][n.xyz, 0].
 // n = area-weighted mean normal of the patch, u = principal direction of its vertices in the plane orthogonal to n,
@@ -494,11 +481,6 @@ int gq_meshset_create(const float* face_verts_host, const int32_t* face_offset_h
   GQ_REQUIRE(F > 0 && face_offset_host[0] == 0 && F < (1ll << 31), "meshset_create: empty or oversized face list");
   for (int i = 0; i < n_mesh; ++i)
     GQ_REQUIRE(face_offset_host[i + 1] >= face_offset_host[i], "meshset_create: offsets must be non-decreasing");
-  gqMeshSet* ms = new gqMeshSet();
-  ms->n_mesh = n_mesh;
-  ms->n_faces = F;
-  ms->off_host = new int32_t[n_mesh + 1];
-  memcpy(ms->off_host, face_offset_host, sizeof(int32_t) * (n_mesh + 1));
   // Morton order of the face centroids inside each mesh, then cluster boxes
   std::vector<int32_t> perm(F);
   std::vector<float> mesh_bb((size_t)n_mesh * 8), sub_bb, cl_bb;
@@ -507,23 +489,7 @@ int gq_meshset_create(const float* face_verts_host, const int32_t* face_offset_h
     const int64_t a = face_offset_host[m], b = face_offset_host[m + 1];
     for (int64_t i = a; i < b; ++i) perm[i] = (int32_t)i;
     gq_box_of(face_verts_host, perm.data(), a, b, &mesh_bb[(size_t)m * 8]);
-    const float* bb = &mesh_bb[(size_t)m * 8];
-    std::vector<std::pair<uint32_t, int32_t>> keys;
-    keys.reserve(b - a);
-    for (int64_t i = a; i < b; ++i) {
-      const float* v = face_verts_host + i * 9;
-      uint32_t code = 0;
-      for (int c = 0; c < 3; ++c) {
-        const float ctr = (v[c] + v[3 + c] + v[6 + c]) * (1.0f / 3.0f);
-        const float ext = bb[4 + c] - bb[c];
-        float t = ext > 0.0f ? (ctr - bb[c]) / ext : 0.0f;
-        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-        code |= gq_spread10((uint32_t)(t * 1023.0f)) << c;
-      }
-      keys.emplace_back(code, (int32_t)i);
-    }
-    std::stable_sort(keys.begin(), keys.end());
-    for (int64_t i = a; i < b; ++i) perm[i] = keys[i - a].second;
+    gq_morton_order(face_verts_host, perm.data(), a, b, &mesh_bb[(size_t)m * 8]);
     for (int64_t i = a; i < b; i += 16) {
       sub_bb.resize(sub_bb.size() + 8);
       gq_box_of(face_verts_host, perm.data(), i, std::min<int64_t>(i + 16, b), &sub_bb[sub_bb.size() - 8]);
@@ -535,43 +501,40 @@ int gq_meshset_create(const float* face_verts_host, const int32_t* face_offset_h
     sub_off[m + 1] = (int32_t)(sub_bb.size() / 8);
     cl_off[m + 1] = (int32_t)(cl_bb.size() / 16);
   }
-  float* tmp = nullptr;
-  int32_t* perm_dev = nullptr;
-  GQ_CHECK_HIP(hipMalloc(&tmp, (size_t)F * 9 * 4));
-  GQ_CHECK_HIP(hipMalloc(&perm_dev, (size_t)F * 4));
-  GQ_CHECK_HIP(hipMalloc(&ms->rec, (size_t)F * sizeof(GqFace)));
-  GQ_CHECK_HIP(hipMalloc(&ms->off_dev, sizeof(int32_t) * (n_mesh + 1)));
-  GQ_CHECK_HIP(hipMalloc(&ms->aabb_dev, sizeof(float) * n_mesh * 8));
-  GQ_CHECK_HIP(hipMalloc(&ms->sub_aabb_dev, sizeof(float) * sub_bb.size()));
-  GQ_CHECK_HIP(hipMalloc(&ms->cl_aabb_dev, sizeof(float) * cl_bb.size()));
-  GQ_CHECK_HIP(hipMalloc(&ms->sub_off_dev, sizeof(int32_t) * (n_mesh + 1)));
-  GQ_CHECK_HIP(hipMalloc(&ms->cl_off_dev, sizeof(int32_t) * (n_mesh + 1)));
-  GQ_CHECK_HIP(hipMemcpy(tmp, face_verts_host, (size_t)F * 9 * 4, hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(perm_dev, perm.data(), (size_t)F * 4, hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(ms->off_dev, face_offset_host, sizeof(int32_t) * (n_mesh + 1), hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(ms->aabb_dev, mesh_bb.data(), sizeof(float) * n_mesh * 8, hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(ms->sub_aabb_dev, sub_bb.data(), sizeof(float) * sub_bb.size(), hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(ms->cl_aabb_dev, cl_bb.data(), sizeof(float) * cl_bb.size(), hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(ms->sub_off_dev, sub_off.data(), sizeof(int32_t) * (n_mesh + 1), hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(ms->cl_off_dev, cl_off.data(), sizeof(int32_t) * (n_mesh + 1), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(gq_face_prep_kernel, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, 0, tmp, perm_dev, ms->rec, F);
-  GQ_LAUNCH_CHECK();
-  GQ_CHECK_HIP(hipDeviceSynchronize());
-  GQ_CHECK_HIP(hipFree(tmp));
-  GQ_CHECK_HIP(hipFree(perm_dev));
-  *out = ms;
+  auto ms = std::make_unique<gqMeshSet>();
+  GqOwner& mem = ms->mem;
+  GqOwner scratch;
+  ms->n_mesh = n_mesh;
+  ms->n_faces = F;
+  ms->off_host = mem.host_copy(face_offset_host, (size_t)n_mesh + 1);
+  ms->aabb_host = mem.host_copy(mesh_bb.data(), mesh_bb.size());
+  ms->rec = mem.alloc<GqFace>(F);
+  ms->off_dev = mem.upload(face_offset_host, (size_t)n_mesh + 1);
+  ms->aabb_dev = mem.upload(mesh_bb.data(), mesh_bb.size());
+  ms->sub_aabb_dev = mem.upload(sub_bb.data(), sub_bb.size());
+  ms->cl_aabb_dev = mem.upload(cl_bb.data(), cl_bb.size());
+  ms->sub_off_dev = mem.upload(sub_off.data(), sub_off.size());
+  ms->cl_off_dev = mem.upload(cl_off.data(), cl_off.size());
+  const float* fv_dev = scratch.upload(face_verts_host, (size_t)F * 9);
+  const int32_t* perm_dev = scratch.upload(perm.data(), (size_t)F);
+  if (mem.rc || scratch.rc) return GQ_ERR_HIP;
+  int rc = gq_face_records_(fv_dev, perm_dev, F, F, ms->rec, 0);
+  if (rc) return rc;
+  GQ_CHECK_HIP(hipStreamSynchronize(0));  // the kernel reads the scratch buffers
+  *out = ms.release();
   return GQ_OK;
 }
 
 // Occupancy grid of every mesh (setup-time).  Voxel (ix,iy,iz) of the 32^3 grid over the mesh AABB is marked when
 // (a) the bounding box of some face overlaps it (+- one voxel), or (b) its centre or one of its corners is inside the mesh
 // (sign of the closest face).  An unmarked voxel does not touch the surface and nine probes of it are outside.
+// The data is built aside and handed to the mesh set only when it is complete: after a failure the set has none, and the
+// next call builds it again.
 int gq_meshset_build_occupancy(gqMeshSet* ms) {
   GQ_REQUIRE(ms, "meshset_build_occupancy: null");
   if (ms->occ_dev) return GQ_OK;
   const int n = ms->n_mesh;
-  std::vector<float> bb((size_t)n * 8), invz(n);
-  GQ_CHECK_HIP(hipMemcpy(bb.data(), ms->aabb_dev, sizeof(float) * n * 8, hipMemcpyDeviceToHost));
+  std::vector<float> bb(ms->aabb_host, ms->aabb_host + (size_t)n * 8), invz(n);
   for (int m = 0; m < n; ++m) {
     // grow the box a little so that surface points are strictly inside the grid, then store 32/extent
     for (int c = 0; c < 3; ++c) {
@@ -584,65 +547,65 @@ int gq_meshset_build_occupancy(gqMeshSet* ms) {
     bb[m * 8 + 7] = 32.0f / (bb[m * 8 + 5] - bb[m * 8 + 1]);
     invz[m] = 32.0f / (bb[m * 8 + 6] - bb[m * 8 + 2]);
   }
-  GQ_CHECK_HIP(hipMemcpy(ms->aabb_dev, bb.data(), sizeof(float) * n * 8, hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMalloc(&ms->occ_invz_dev, sizeof(float) * n));
-  GQ_CHECK_HIP(hipMemcpy(ms->occ_invz_dev, invz.data(), sizeof(float) * n, hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMalloc(&ms->occ_dev, sizeof(uint32_t) * n * 1024));
-  GQ_CHECK_HIP(hipMemset(ms->occ_dev, 0, sizeof(uint32_t) * n * 1024));
+  GqOwner part;
+  GQ_CHECK_HIP(hipMemcpy(ms->aabb_dev, bb.data(), sizeof(float) * n * 8, hipMemcpyHostToDevice));  // the same box on a retry
+  float* invz_dev = part.upload(invz.data(), (size_t)n);
+  uint32_t* occ = part.alloc<uint32_t>((size_t)n * 1024);
+  if (part.rc) return part.rc;
+  GQ_CHECK_HIP(hipMemsetAsync(occ, 0, sizeof(uint32_t) * n * 1024, 0));
   hipLaunchKernelGGL(gq_occ_faces_kernel, dim3((unsigned)((ms->n_faces + 255) / 256)), dim3(256), 0, 0, ms->rec,
-                     ms->off_dev, n, ms->aabb_dev, ms->occ_invz_dev, ms->occ_dev);
+                     ms->off_dev, n, ms->aabb_dev, invz_dev, occ);
   GQ_LAUNCH_CHECK();
   hipLaunchKernelGGL(gq_occ_centres_kernel, dim3(128, (unsigned)n), dim3(256), 0, 0, ms->rec, ms->off_dev, ms->aabb_dev,
-                     ms->occ_invz_dev, ms->occ_dev);
+                     invz_dev, occ);
   GQ_LAUNCH_CHECK();
-  GQ_CHECK_HIP(hipDeviceSynchronize());
   // per-voxel candidate faces (only when 16-bit local face indices suffice)
   bool small = true;
   for (int m = 0; m < n; ++m) small = small && (ms->off_host[m + 1] - ms->off_host[m] < 65536);
+  uint32_t* cand_off = nullptr;
+  uint16_t* cand_idx = nullptr;
+  uint64_t run = 0;
   if (small) {
     const size_t nv = (size_t)n * 32768;
-    uint32_t* cnt_dev = nullptr;
-    GQ_CHECK_HIP(hipMalloc(&cnt_dev, sizeof(uint32_t) * nv));
+    GqOwner scratch;
+    uint32_t* cnt_dev = scratch.alloc<uint32_t>(nv);
+    if (scratch.rc) return scratch.rc;
     hipLaunchKernelGGL(gq_cand_kernel<false>, dim3(128, (unsigned)n), dim3(256), 0, 0, ms->rec, ms->off_dev, ms->aabb_dev,
-                       ms->occ_invz_dev, ms->occ_dev, cnt_dev, nullptr, nullptr);
+                       invz_dev, occ, cnt_dev, nullptr, nullptr);
     GQ_LAUNCH_CHECK();
     std::vector<uint32_t> cnt(nv), offs(nv + 1);
-    GQ_CHECK_HIP(hipMemcpy(cnt.data(), cnt_dev, sizeof(uint32_t) * nv, hipMemcpyDeviceToHost));
-    GQ_CHECK_HIP(hipFree(cnt_dev));
-    uint64_t run = 0;
+    GQ_CHECK_HIP(hipMemcpy(cnt.data(), cnt_dev, sizeof(uint32_t) * nv, hipMemcpyDeviceToHost));  // in order behind the kernel
     for (size_t i = 0; i < nv; ++i) {
       offs[i] = (uint32_t)run;
       run += cnt[i];
     }
     GQ_REQUIRE(run < (1ull << 32), "meshset_build_occupancy: candidate lists too long");
     offs[nv] = (uint32_t)run;
-    ms->n_cand = (int64_t)run;
-    GQ_CHECK_HIP(hipMalloc(&ms->cand_off_dev, sizeof(uint32_t) * (nv + 1)));
-    GQ_CHECK_HIP(hipMalloc(&ms->cand_idx_dev, sizeof(uint16_t) * (run + 1)));
-    GQ_CHECK_HIP(hipMemcpy(ms->cand_off_dev, offs.data(), sizeof(uint32_t) * (nv + 1), hipMemcpyHostToDevice));
+    cand_off = part.upload(offs.data(), nv + 1);
+    cand_idx = part.alloc<uint16_t>(run + 1);
+    if (part.rc) return part.rc;
     hipLaunchKernelGGL(gq_cand_kernel<true>, dim3(128, (unsigned)n), dim3(256), 0, 0, ms->rec, ms->off_dev, ms->aabb_dev,
-                       ms->occ_invz_dev, ms->occ_dev, nullptr, ms->cand_off_dev, ms->cand_idx_dev);
+                       invz_dev, occ, nullptr, cand_off, cand_idx);
     GQ_LAUNCH_CHECK();
-    GQ_CHECK_HIP(hipDeviceSynchronize());
   }
+  GQ_CHECK_HIP(hipStreamSynchronize(0));  // complete before any other stream reads it
+  ms->mem.adopt(part);
+  ms->occ_invz_dev = invz_dev;
+  ms->occ_dev = occ;
+  ms->cand_off_dev = cand_off;
+  ms->cand_idx_dev = cand_idx;
+  ms->n_cand = (int64_t)run;
   return GQ_OK;
 }
 
 int gq_meshset_destroy(gqMeshSet* ms) {
-  if (!ms) return GQ_OK;
-  (void)hipFree(ms->rec);
-  (void)hipFree(ms->off_dev);
-  (void)hipFree(ms->aabb_dev);
-  (void)hipFree(ms->sub_aabb_dev);
-  (void)hipFree(ms->cl_aabb_dev);
-  (void)hipFree(ms->sub_off_dev);
-  (void)hipFree(ms->cl_off_dev);
-  if (ms->occ_dev) (void)hipFree(ms->occ_dev);
-  if (ms->occ_invz_dev) (void)hipFree(ms->occ_invz_dev);
-  if (ms->cand_off_dev) (void)hipFree(ms->cand_off_dev);
-  if (ms->cand_idx_dev) (void)hipFree(ms->cand_idx_dev);
-  delete[] ms->off_host;
   delete ms;
+  return GQ_OK;
+}
+
+int gq_setup_live_allocations(int64_t* n) {
+  GQ_REQUIRE(n, "setup_live_allocations: null");
+  *n = gq_setup_live_.load();
   return GQ_OK;
 }
 
@@ -669,9 +632,8 @@ int gq_sdf_forward(const float* points, int64_t n_points, const float* face_vert
              (long long)n_points, (long long)n_faces);
   GQ_REQUIRE(workspace_bytes >= (size_t)n_faces * sizeof(GqFace) + 256, "sdf_forward: workspace too small");
   GqFace* rec = (GqFace*)workspace;
-  hipLaunchKernelGGL(gq_face_prep_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, st, face_verts,
-                     (const int32_t*)nullptr, rec, n_faces);
-  GQ_LAUNCH_CHECK();
+  int rc = gq_face_records_(face_verts, nullptr, n_faces, n_faces, rec, st);
+  if (rc) return rc;
   if (n_points >= 131072) {
     hipLaunchKernelGGL(gq_sdf_points_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, st, points,
                        n_points, rec, (int)n_faces, dist_sq, sign, normal, closest);
@@ -846,28 +808,19 @@ int gq_pointgrid_create(const float* surface_points_host, int64_t n_obj, int64_t
     uint16_t* pp = pts.data() + (size_t)o * P;
     for (int i = 0; i < P; ++i) pp[fill[cell[i]]++] = (uint16_t)i;  // points of a cell in index order
   }
-  gqPointGrid* g = new gqPointGrid();
+  auto g = std::make_unique<gqPointGrid>();
   g->n_obj = (int)n_obj;
   g->P = P;
   g->G = G;
-  g->box_dev = nullptr;
-  g->start_dev = nullptr;
-  g->pts_dev = nullptr;
-  GQ_CHECK_HIP(hipMalloc(&g->box_dev, box.size() * sizeof(float)));
-  GQ_CHECK_HIP(hipMalloc(&g->start_dev, start.size() * sizeof(int32_t)));
-  GQ_CHECK_HIP(hipMalloc(&g->pts_dev, pts.size() * sizeof(uint16_t)));
-  GQ_CHECK_HIP(hipMemcpy(g->box_dev, box.data(), box.size() * sizeof(float), hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(g->start_dev, start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  GQ_CHECK_HIP(hipMemcpy(g->pts_dev, pts.data(), pts.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  *out = g;
+  g->box_dev = g->mem.upload(box.data(), box.size());
+  g->start_dev = g->mem.upload(start.data(), start.size());
+  g->pts_dev = g->mem.upload(pts.data(), pts.size());
+  if (g->mem.rc) return g->mem.rc;
+  *out = g.release();
   return GQ_OK;
 }
 
 int gq_pointgrid_destroy(gqPointGrid* g) {
-  if (!g) return GQ_OK;
-  if (g->box_dev) (void)hipFree(g->box_dev);
-  if (g->start_dev) (void)hipFree(g->start_dev);
-  if (g->pts_dev) (void)hipFree(g->pts_dev);
   delete g;
   return GQ_OK;
 }

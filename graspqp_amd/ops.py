@@ -109,57 +109,58 @@ def _c(t: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------------------------
 # mesh sets (device-resident triangle soups)
 # ----------------------------------------------------------------------------------------------------------
-class MeshSet:
+class _DeviceObject:
+    """An opaque object of the C ABI, created on ``device`` and destroyed once: by ``close()`` or with the wrapper."""
+
+    def __init__(self, create, destroy, device, *args):
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._destroy = destroy
+        self.handle = None
+        h = ctypes.c_void_p(0)
+        with torch.cuda.device(self.device):
+            _C.call(create, *args, ctypes.byref(h))
+        self.handle = h
+
+    def close(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            getattr(_C.lib(), self._destroy)(h)
+        hid = getattr(self, "hid", None)
+        if hid is not None:
+            _HANDLES.pop(hid, None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MeshSet(_DeviceObject):
     """n_mesh triangle soups on the device (face records precomputed once)."""
 
-    def __init__(self, face_verts_list):
+    def __init__(self, face_verts_list, device=None):
         fvs = [np.ascontiguousarray(np.asarray(f, dtype=np.float32).reshape(-1, 3, 3)) for f in face_verts_list]
         self.n_mesh = len(fvs)
         self.offsets = np.zeros(self.n_mesh + 1, dtype=np.int32)
         self.offsets[1:] = np.cumsum([len(f) for f in fvs])
         allf = np.ascontiguousarray(np.concatenate(fvs, 0))
         self.n_faces = int(self.offsets[-1])
-        h = ctypes.c_void_p(0)
-        torch.cuda.current_device()  # make sure the HIP context exists
-        _C.call(
-            "gq_meshset_create",
-            allf.ctypes.data_as(ctypes.c_void_p),
-            self.offsets.ctypes.data_as(ctypes.c_void_p),
-            self.n_mesh,
-            ctypes.byref(h),
-        )
-        self.handle = h
+        super().__init__("gq_meshset_create", "gq_meshset_destroy", device, allf.ctypes.data_as(ctypes.c_void_p),
+                         self.offsets.ctypes.data_as(ctypes.c_void_p), self.n_mesh)
         self.hid = _register_handle(self)
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _C.lib().gq_meshset_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
-
-class Bvh:
+class Bvh(_DeviceObject):
     """Implicit 4-ary box hierarchy over one mesh (csrc/bvh.hip): the acceleration data of compute_sdf for large query
     counts."""
 
-    def __init__(self, face_verts):
+    def __init__(self, face_verts, device=None):
         fv = np.ascontiguousarray(np.asarray(face_verts, dtype=np.float32).reshape(-1, 3, 3))
         self.n_faces = int(fv.shape[0])
-        h = ctypes.c_void_p(0)
-        torch.cuda.current_device()
-        _C.call("gq_bvh_create", fv.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(self.n_faces), ctypes.byref(h))
-        self.handle = h
+        super().__init__("gq_bvh_create", "gq_bvh_destroy", device, fv.ctypes.data_as(ctypes.c_void_p),
+                         ctypes.c_int64(self.n_faces))
         self.hid = _register_handle(self)
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _C.lib().gq_bvh_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 def surface_fps(face_verts_list, n_keep: int, oversample: int = 100, generator=None, draws=None, device="cuda") -> torch.Tensor:
@@ -201,27 +202,18 @@ def morton_sort_points(points: torch.Tensor, bits: int = 10) -> torch.Tensor:
     return torch.gather(points, 1, order.unsqueeze(-1).expand(-1, -1, 3)).contiguous()
 
 
-class PointGrid:
+class PointGrid(_DeviceObject):
     """Coarse uniform grid over the surface points of every object (n_obj,P,3): set-up data of the link-driven
     penetration query (gq_hand_pen_forward_cells)."""
 
-    def __init__(self, surface_points, cells_per_axis: int = 0):
+    def __init__(self, surface_points, cells_per_axis: int = 0, device=None):
+        if device is None and torch.is_tensor(surface_points) and surface_points.is_cuda:
+            device = surface_points.device
         sp = np.ascontiguousarray(np.asarray(surface_points.detach().cpu() if torch.is_tensor(surface_points) else surface_points,
                                              dtype=np.float32))
         self.n_obj, self.P = int(sp.shape[0]), int(sp.shape[1])
-        h = ctypes.c_void_p(0)
-        torch.cuda.current_device()
-        _C.call("gq_pointgrid_create", sp.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(self.n_obj), ctypes.c_int64(self.P),
-                int(cells_per_axis), ctypes.byref(h))
-        self.handle = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _C.lib().gq_pointgrid_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+        super().__init__("gq_pointgrid_create", "gq_pointgrid_destroy", device, sp.ctypes.data_as(ctypes.c_void_p),
+                         ctypes.c_int64(self.n_obj), ctypes.c_int64(self.P), int(cells_per_axis))
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -298,8 +290,10 @@ def _cached(face_verts, kind):
     ent = _MESH_CACHE.get(key)
     if ent is not None and ent[0]() is face_verts and ent[1] == face_verts.data_ptr() and ent[2] == face_verts._version:
         return ent[3]
+    if torch.cuda.is_current_stream_capturing():  # the build copies to the host and synchronises
+        raise RuntimeError("graspqp_amd: first call per mesh must happen outside graph capture")
     fv = face_verts.detach().to(torch.float32).cpu().numpy()  # one device->host copy, once per mesh and kind
-    obj = MeshSet([fv]) if kind == "clusters" else Bvh(fv)
+    obj = MeshSet([fv], face_verts.device) if kind == "clusters" else Bvh(fv, face_verts.device)
     ref = weakref.ref(face_verts, lambda _r, k=key: _MESH_CACHE.pop(k, None))
     _MESH_CACHE[key] = (ref, face_verts.data_ptr(), face_verts._version, obj)
     return obj
@@ -324,6 +318,9 @@ def compute_sdf(points: torch.Tensor, face_verts: torch.Tensor):
         raise ValueError(f"compute_sdf: face_verts must be (F,3,3), got {tuple(face_verts.shape)}")
     if not points.is_cuda:
         raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if points.device.index != torch.cuda.current_device():  # launches go to the current device's stream
+        with torch.cuda.device(points.device):
+            return compute_sdf(points, face_verts)
     N, F = points.shape[0], face_verts.shape[0]
     if N > 0 and not face_verts.requires_grad:
         if N >= _BVH_MIN_QUERIES and _BVH_MIN_FACES <= F <= _BVH_MAX_FACES:
@@ -454,6 +451,9 @@ torch.library.register_autograd("graspqp_amd::box_qp", _box_qp_bwd, setup_contex
 
 def box_qp(Q, p, lower, upper, eps=5e-2, max_iter=12, not_improved_lim=3):
     """argmin 1/2 x'Qx + p'x, lower <= x <= upper -> (x, lam, slack); differentiable (qpth semantics)."""
+    if Q.is_cuda and Q.device.index != torch.cuda.current_device():  # launches go to the current device's stream
+        with torch.cuda.device(Q.device):
+            return box_qp(Q, p, lower, upper, eps, max_iter, not_improved_lim)
     x, lam, slack, _ = _Eager.box_qp(Q, p, lower, upper, float(eps), int(max_iter), int(not_improved_lim))
     return x, lam, slack
 
@@ -743,12 +743,15 @@ def fc_peek(ws, B, n, k):
 # ----------------------------------------------------------------------------------------------------------
 # hand handle + kinematics
 # ----------------------------------------------------------------------------------------------------------
-class HandHandle:
+class HandHandle(_DeviceObject):
     """Device copy of a HandSpec's reduced kinematic tree + its link meshes."""
 
-    def __init__(self, spec):
+    def __init__(self, spec, device=None):
+        if isinstance(spec, str):
+            from .hands import get_hand_spec
+
+            spec = get_hand_spec(spec)
         self.spec = spec
-        torch.cuda.current_device()
         keep = []
 
         def arr(a, dt):
@@ -776,11 +779,10 @@ class HandHandle:
             d.n_actuated = spec.n_dofs
             d.coupling = arr(spec.coupling, np.float32)
             d.coupling_offset = arr(spec.coupling_offset, np.float32)
-        h = ctypes.c_void_p(0)
-        _C.call("gq_hand_create", ctypes.byref(d), ctypes.byref(h))
-        self.handle = h
-        self.links = MeshSet([spec.link_faces(l) for l in range(spec.n_links)])
-        _C.call("gq_meshset_build_occupancy", self.links.handle)
+        super().__init__("gq_hand_create", "gq_hand_destroy", device, ctypes.byref(d))
+        self.links = MeshSet([spec.link_faces(l) for l in range(spec.n_links)], self.device)
+        with torch.cuda.device(self.device):
+            _C.call("gq_meshset_build_occupancy", self.links.handle)
         self.J, self.L, self.S = spec.n_dofs, spec.n_links, spec.n_spheres
         self.hid = _register_handle(self)
 
@@ -788,13 +790,11 @@ class HandHandle:
         nb = _size_call("gq_fk_workspace_bytes", self.handle, ctypes.c_int64(B))
         return _ws(nb, dev), nb
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                _C.lib().gq_hand_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
+    def close(self):
+        links = getattr(self, "links", None)
+        if links is not None:
+            links.close()
+        super().close()
 
 
 @_custom_op("graspqp_amd::fk_contacts", mutates_args=(), device_types="cuda")

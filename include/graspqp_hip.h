@@ -38,6 +38,9 @@ typedef struct gqMeshSet gqMeshSet; /* n_mesh triangle soups resident on the dev
 int gq_meshset_create(const float* face_verts_host /* (sumF,3,3) */, const int32_t* face_offset_host /* (n_mesh+1) */,
                       int n_mesh, gqMeshSet** out);
 int gq_meshset_destroy(gqMeshSet* ms);
+/* Device and host allocations currently held by all set-up objects of the process (gqMeshSet, gqBvh, gqPointGrid, gqHand):
+ * an exact measure of their lifetime -- every create raises it, the matching destroy takes it back.                        */
+int gq_setup_live_allocations(int64_t* n);
 /* setup-time 32^3 occupancy grid + per-voxel candidate faces per mesh; required by penetration_only = 1 and the fused steps */
 int gq_meshset_build_occupancy(gqMeshSet* ms);
 int gq_meshset_num_faces(const gqMeshSet* ms, int mesh /* -1 = all */, int64_t* n);
@@ -56,8 +59,6 @@ int gq_sdf_forward_meshset(const gqMeshSet* ms, const float* points, int64_t n_p
 typedef struct gqBvh gqBvh;
 int gq_bvh_create(const float* face_verts_host, int64_t n_faces, gqBvh** out);
 int gq_bvh_destroy(gqBvh* bvh);
-int gq_debug_set_bvh_sorted(int on); /* 1: the queries of a 2048-point chunk are ordered by direction inside the block before
-                                        the traversal (coherent wavefronts; measured slower, A/B runs); 0 (default): plain order */
 int gq_sdf_forward_bvh(const gqBvh* bvh, const float* points, int64_t n_points, float* dist_sq, int32_t* sign,
                        float* normal /* or NULL */, float* closest, void* stream);
 int gq_sdf_backward(const float* grad_dist_sq, const float* points, const float* closest, int64_t n_points,

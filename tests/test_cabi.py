@@ -34,6 +34,37 @@ def test_argument_validation_without_gpu():
     assert b"bad arguments" in lib.gq_last_error()
     assert lib.gq_fc_workspace_bytes(4, 4, 4, 12, ctypes.byref(out)) == 0 and out.value > 0
     assert lib.gq_sdf_workspace_bytes(1000, ctypes.byref(out)) == 0 and out.value >= 64000
+    # the create functions check their arguments before the first allocation: an error code and a message, *out untouched,
+    # nothing held (no device object exists yet in a process that starts with this module)
+    live = ctypes.c_int64(-1)
+    fv = np.zeros((65537, 3, 3), dtype=np.float32)
+    fvp = fv.ctypes.data_as(ctypes.c_void_p)
+    offsets = np.array([0, 5, 3], dtype=np.int32)
+    points = np.zeros((1, 64, 3), dtype=np.float32)
+    for name, args in (("gq_bvh_create", (fvp, 0)), ("gq_bvh_create", (fvp, 65537)),
+                       ("gq_meshset_create", (fvp, offsets.ctypes.data_as(ctypes.c_void_p), 2)),
+                       ("gq_pointgrid_create", (points.ctypes.data_as(ctypes.c_void_p), 1, 64, 33))):
+        handle = ctypes.c_void_p(0)
+        assert getattr(lib, name)(*args, ctypes.byref(handle)) != 0, (name, args[1:])
+        assert handle.value is None, name
+        assert name[3:].encode() in lib.gq_last_error(), name  # "bvh_create: ..."
+        assert lib.gq_setup_live_allocations(ctypes.byref(live)) == 0 and live.value == 0, name
+
+
+def test_first_call_per_mesh_is_refused_during_graph_capture(monkeypatch):
+    """_cached builds acceleration data with a host copy and a synchronisation: refused, before any device call, while the
+    current stream is capturing; a mesh that already has its entry is served."""
+    from graspqp_amd import ops
+
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    fv = torch.zeros(40, 3, 3)
+    before = dict(ops._MESH_CACHE)
+    with pytest.raises(RuntimeError, match="first call per mesh must happen outside graph capture"):
+        ops._cached(fv, "bvh")
+    assert ops._MESH_CACHE == before
+    entry = object()
+    monkeypatch.setitem(ops._MESH_CACHE, (id(fv), "bvh"), (lambda: fv, fv.data_ptr(), fv._version, entry))
+    assert ops._cached(fv, "bvh") is entry
 
 
 def test_no_cpu_fallback():
