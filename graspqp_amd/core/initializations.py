@@ -73,7 +73,8 @@ def initialize_convex_hull(hand_model, object_model, args=None, env_mask=None, e
                            generator=None):
     """Reference signature (initializations.py:15).  ``args`` carries the ranges of scripts/fit.py:59-71 and ``n_contact``
     (a Namespace or dict; missing entries take the reference defaults)."""
-    n_obj = len(object_model.object_mesh_list)
+    meshes = object_model.object_mesh_list  # None: the objects are point clouds
+    n_obj = len(meshes if meshes is not None else object_model.object_code_list)
     be = object_model.batch_size_each
     pose = convex_hull_poses(hand_model.spec, object_model.convex_hulls(), n_obj, be, args, generator, hand_model.device)
     if not init_contacts:  # initializations.py:183-184

@@ -16,6 +16,19 @@ from ..hands.spec import load_obj_triangles
 from ..utils import meshes as mesh_utils
 
 
+def _fps_points(points: torch.Tensor, k: int) -> torch.Tensor:
+    """``k`` of the (N,3) device points by farthest-point sampling from point 0 (set-up time; the arg-max of every round stays
+    on the device)."""
+    dist = torch.full((points.shape[0],), float("inf"), device=points.device)
+    sel = torch.zeros(k, dtype=torch.long, device=points.device)
+    cur = torch.zeros((), dtype=torch.long, device=points.device)
+    for i in range(k):
+        sel[i] = cur
+        dist = torch.minimum(dist, ((points - points[cur]) ** 2).sum(-1))
+        cur = torch.argmax(dist)
+    return points[sel]
+
+
 class ObjectModel:
     def __init__(self, data_root_path=None, batch_size_each=1, scale=1.0, num_samples=2000, device="cuda"):
         if not str(device).startswith("cuda"):
@@ -32,6 +45,8 @@ class ObjectModel:
         self.surface_points_tensor = None
         self.surface_points_each = None  # (n_obj, P, 3), un-expanded
         self._meshset = None
+        self._cloudset = None  # ops.PointCloudSet of an object given as oriented point clouds (initialize_from_point_clouds)
+        self.cloud_points_list = None
         self._cog = None
         self._hull = None  # (face_verts (sumF,3,3), area cdf (sumF), offsets (n_obj+1)) on the device, built on demand
         self.sdf_library = "HIP"
@@ -72,6 +87,7 @@ class ObjectModel:
         self.object_mesh_list = [np.asarray(f, dtype=np.float32) for f in face_verts_list]
         self.object_face_verts_list = [torch.tensor(f, device=self.device) for f in self.object_mesh_list]
         self._meshset = ops.MeshSet(self.object_mesh_list)
+        self._cloudset, self.cloud_points_list = None, None
         n_obj = len(face_verts_list)
         self.object_scale_tensor = torch.ones(n_obj, self.batch_size_each, device=self.device)  # scale_choice = [1.0]
         if self.num_samples != 0:
@@ -84,12 +100,43 @@ class ObjectModel:
         self._cog = None
         self._hull = None
 
+    def initialize_from_point_clouds(self, points_list, normals_list, object_code_list=None, radius=None, surface_points_list=None):
+        """Objects as oriented point clouds (points with unit outward normals; scans, open shells, unions of parts): the
+        contact query of ``cal_distance`` becomes the surfel signed distance of ``ops.sdf_cloud`` with disc radius ``radius``
+        (None: per cloud 2 x the median nearest-neighbour distance).  ``surface_points_list`` None: ``num_samples`` of the
+        cloud's own points by farthest-point sampling from point 0, Morton-ordered.  There is no mesh: ``object_mesh_list``
+        and ``object_face_verts_list`` are None, and ``convex_hulls`` takes the cloud's points."""
+        pts = [np.ascontiguousarray(np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, dtype=np.float32).reshape(-1, 3))
+               for p in points_list]
+        if self.num_samples != 0 and surface_points_list is None:
+            for i, p in enumerate(pts):
+                if len(p) < self.num_samples:
+                    raise ValueError(f"initialize_from_point_clouds: cloud {i} has {len(p)} points, fewer than num_samples = "
+                                     f"{self.num_samples}")
+        self.object_code_list = object_code_list or [f"obj{i}" for i in range(len(pts))]
+        self.object_mesh_list = None
+        self.object_face_verts_list = None
+        self._meshset = None
+        self._cloudset = ops.PointCloudSet(pts, normals_list, radius, device=self.device)
+        self.cloud_points_list = pts
+        self.object_scale_tensor = torch.ones(len(pts), self.batch_size_each, device=self.device)
+        if self.num_samples != 0:
+            if surface_points_list is None:
+                sp = torch.stack([_fps_points(torch.tensor(p, device=self.device), self.num_samples) for p in pts])
+                sp = ops.morton_sort_points(sp)
+            else:
+                sp = torch.tensor(np.stack(surface_points_list), dtype=torch.float32, device=self.device)
+            self.surface_points_each = sp.contiguous()
+            self.surface_points_tensor = sp.repeat_interleave(self.batch_size_each, dim=0)
+        self._cog = None
+        self._hull = None
+
     def convex_hulls(self):
         """Convex hull of every object (scaled like initializations.py:42-46) as device arrays for
         ``initialize_convex_hull``: triangles oriented outward, per-object cumulative area table, offsets."""
         if self._hull is None:
             fvs, cdfs, off = [], [], [0]
-            for i, f in enumerate(self.object_mesh_list):
+            for i, f in enumerate(self.object_mesh_list if self._cloudset is None else self.cloud_points_list):
                 h = mesh_utils.convex_hull_faces(f.reshape(-1, 3) * float(self.object_scale_tensor[i].max().item()))
                 fvs.append(h)
                 cdfs.append(mesh_utils.area_cdf(h))
@@ -106,7 +153,10 @@ class ObjectModel:
     # object_model.py:186-255
     def cal_distance(self, x, with_closest_points=False):
         _, n_points, _ = x.shape
-        d2, sgn, nrm, cls = ops.sdf_meshset(x.reshape(-1, 3), self._meshset, self.batch_size_each * n_points)
+        if self._cloudset is not None:
+            d2, sgn, nrm, cls = ops.sdf_cloud(x.reshape(-1, 3), self._cloudset, self.batch_size_each * n_points)
+        else:
+            d2, sgn, nrm, cls = ops.sdf_meshset(x.reshape(-1, 3), self._meshset, self.batch_size_each * n_points)
         dis, normals = ops.signed_distance(d2, sgn, nrm)  # sqrt(d2 + 1e-8) * (-sgn), nrm * sgn
         distance = dis.reshape(-1, n_points)
         normals = normals.reshape(-1, n_points, 3)

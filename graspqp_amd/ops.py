@@ -151,6 +151,40 @@ class MeshSet(_DeviceObject):
         self.hid = _register_handle(self)
 
 
+class PointCloudSet(_DeviceObject):
+    """n_obj oriented point clouds on the device (csrc/cloud.hip): points with outward normals and one disc radius per cloud,
+    sorted into a uniform grid at set-up.  ``radius`` None: per cloud 2 x the median nearest-neighbour distance
+    (``utils.meshes.cloud_radius``); a number, or one number per cloud, sets it (a cloud of one point needs it).  Normals are
+    normalised in double by the library; zero / non-finite normals, non-finite points, empty clouds and radii <= 0 raise."""
+
+    def __init__(self, points_list, normals_list, radius=None, device=None):
+        pts = [np.ascontiguousarray(np.asarray(p.detach().cpu() if torch.is_tensor(p) else p, dtype=np.float32).reshape(-1, 3))
+               for p in points_list]
+        nrm = [np.ascontiguousarray(np.asarray(n.detach().cpu() if torch.is_tensor(n) else n, dtype=np.float32).reshape(-1, 3))
+               for n in normals_list]
+        if len(pts) != len(nrm) or any(len(p) != len(n) for p, n in zip(pts, nrm)):
+            raise ValueError("PointCloudSet: every cloud needs as many normals as points")
+        self.n_obj = len(pts)
+        if radius is None:
+            from .utils.meshes import cloud_radius
+
+            radius = [cloud_radius(p) for p in pts]
+        elif np.ndim(radius) == 0:
+            radius = [float(radius)] * self.n_obj
+        self.radius = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+        if len(self.radius) != self.n_obj:
+            raise ValueError(f"PointCloudSet: {len(self.radius)} radii for {self.n_obj} clouds")
+        self.offsets = np.zeros(self.n_obj + 1, dtype=np.int32)
+        self.offsets[1:] = np.cumsum([len(p) for p in pts])
+        self.n_points = int(self.offsets[-1])
+        allp = np.ascontiguousarray(np.concatenate(pts, 0)) if pts else np.zeros((0, 3), np.float32)
+        alln = np.ascontiguousarray(np.concatenate(nrm, 0)) if nrm else np.zeros((0, 3), np.float32)
+        as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        super().__init__("gq_cloudset_create", "gq_cloudset_destroy", device, as_p(allp), as_p(alln), as_p(self.offsets),
+                         as_p(self.radius), self.n_obj)
+        self.hid = _register_handle(self)
+
+
 class Bvh(_DeviceObject):
     """Implicit 4-ary box hierarchy over one mesh (csrc/bvh.hip): the acceleration data of compute_sdf for large query
     counts."""
@@ -384,6 +418,36 @@ torch.library.register_autograd("graspqp_amd::sdf_bvh", _sdf_bvh_bwd, setup_cont
 
 def sdf_meshset(points, meshset: MeshSet, queries_per_mesh: int):
     return _Eager.sdf_meshset(points, meshset.hid, int(queries_per_mesh))
+
+
+@_custom_op("graspqp_amd::sdf_cloud", mutates_args=(), device_types="cuda")
+def _sdf_cloud_op(points: Tensor, cloudset: int, queries_per_object: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The contact query against a PointCloudSet (surfel signed distance, include/graspqp_hip.h): the outputs of sdf_meshset."""
+    pts = _c(points).reshape(-1, 3)
+    d2, sgn, nrm, cls = _sdf_outputs(pts)
+    cs = _handle(cloudset)
+    if cs.handle is None:
+        raise RuntimeError(f"graspqp_amd: point cloud set {cloudset} has been closed")
+    if pts.shape[0] > 0:
+        _C.call("gq_cloud_forward", cs.handle, _C.f32(pts), pts.shape[0], int(queries_per_object), _C.f32(d2), _C.i32(sgn),
+                _C.f32(nrm), _C.f32(cls), _C.stream_ptr())
+    return d2, sgn, nrm, cls
+
+
+@_sdf_cloud_op.register_fake
+def _(points, cloudset, queries_per_object):
+    return _sdf_outputs(points.reshape(-1, 3))
+
+
+torch.library.register_autograd("graspqp_amd::sdf_cloud", _sdf_ms_bwd, setup_context=_sdf_ms_setup)
+
+
+def sdf_cloud(points, cloudset: PointCloudSet, queries_per_object: int):
+    """(dist_sq, sign int32, normal, closest) of the queries against the clouds of ``cloudset``: query q uses cloud
+    q // queries_per_object.  Only dist_sq is differentiable, w.r.t. points (sdf_backward)."""
+    if cloudset.handle is None:
+        raise RuntimeError("graspqp_amd: this PointCloudSet has been closed")
+    return _Eager.sdf_cloud(points, cloudset.hid, int(queries_per_object))
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -1347,6 +1411,7 @@ _eager("sdf_backward", _sdf_backward)
 _eager("compute_sdf", _compute_sdf_op, _sdf_bwd, _sdf_setup)
 _eager("sdf_meshset", _sdf_meshset_op, _sdf_ms_bwd, _sdf_ms_setup)
 _eager("sdf_bvh", _sdf_bvh_op, _sdf_bvh_bwd, _sdf_ms_setup)
+_eager("sdf_cloud", _sdf_cloud_op, _sdf_ms_bwd, _sdf_ms_setup)
 _eager("box_qp", _box_qp_op, _box_qp_bwd, _box_qp_setup)
 _eager("box_qp_backward", _box_qp_bwd_op)
 _eager("lsq_box_qp", _lsq_box_qp_op, _lsq_bwd, _lsq_setup)

@@ -14,6 +14,9 @@ Tabletop mode (a weight on "E_prior" or "E_wall", scripts/fit.py:77-78,369-373; 
 more launch (gq_tabletop_terms) between the joined branches and the FK backward, which adds their link wrenches and
 global-pose gradients to the penetration branch's; ``terms`` is then (7,B) with [E_prior, E_wall] appended, and the
 proposal and the accept step are the stand-alone launches.
+
+Objects as oriented point clouds (an ``ops.PointCloudSet`` in the place of the ``ops.MeshSet``): the object SDF of the contacts is
+gq_cloud_forward, always a launch of its own; it fills the same four buffers, so every other launch is the one of a mesh object.
 """
 
 from __future__ import annotations
@@ -44,12 +47,15 @@ def merge_weights(weights=None):
 
 
 class GraspStepper:
-    def __init__(self, hand: ops.HandHandle, object_meshes: ops.MeshSet, surface_points: torch.Tensor, batch_each: int,
+    def __init__(self, hand: ops.HandHandle, object_meshes, surface_points: torch.Tensor, batch_each: int,
                  n_contact: int, weights=None, fc_cfg=None, mala_cfg=None, device="cuda", seed=1,
                  penetration_only: bool = True, energy_type: str = "graspqp", optimizer: str = "mala_star",
                  tdg_directions=None, point_grid: int = 0, split_self_pen: bool = True, n_surface_points: int = 512,
                  surface_samples=None, table_z: float = 0.0):
-        """energy_type: "graspqp" (default) | "dexgrasp" | "tdg" (scripts/fit.py:343-347); every type has the fused four-
+        """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
+        contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
+        everything downstream reads the same four buffers.
+        energy_type: "graspqp" (default) | "dexgrasp" | "tdg" (scripts/fit.py:343-347); every type has the fused four-
         launch form (the force-closure role of the first stage launch is the contact terms + that energy) and the per-role
         form on two graph branches.  optimizer: "mala_star" | "dexgraspnet"
         (AnnealingDexGraspNet, core/optimizer.py:11-149: no z-score in the temperature, no re-initialisation).
@@ -62,6 +68,7 @@ class GraspStepper:
         self.penetration_only = ops.pen_mode(penetration_only)  # 1: E_pen only needs dis > 0 (energy.py:59-61)
         self.split_self_pen = bool(split_self_pen)  # False: A/B switch, self penetration stays in the FK forward launch
         self.hand, self.objs = hand, object_meshes
+        self.cloud = isinstance(object_meshes, ops.PointCloudSet)
         self.dev = torch.device(device)
         self.surf = surface_points.to(self.dev, torch.float32).contiguous()  # (n_obj,P,3)
         self.n_obj, self.P = self.surf.shape[0], self.surf.shape[1]
@@ -234,10 +241,12 @@ class GraspStepper:
         ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
         self._propose_desc, self._accept_desc = pr, ac
-        sd = _C.SdfDesc()
-        sd.meshes, sd.queries_per_mesh = self.objs.handle, self.be * n
-        sd.dist_sq, sd.sign, sd.obj_dir, sd.closest = (t.data_ptr() for t in (self.d2, self.sgn, self.onrm, self.closest))
-        self._sdf_desc = sd
+        self._sdf_desc = None  # clouds: the query is never attached to the FK forward launch
+        if not self.cloud:
+            sd = _C.SdfDesc()
+            sd.meshes, sd.queries_per_mesh = self.objs.handle, self.be * n
+            sd.dist_sq, sd.sign, sd.obj_dir, sd.closest = (t.data_ptr() for t in (self.d2, self.sgn, self.onrm, self.closest))
+            self._sdf_desc = sd
 
     # ---- energy + gradient of the pose in (pose, idx) -> terms_new (5,B), total_new (B), grad_new (B,D) ----------
     # Four pieces: FK (+ self penetration), then two independent branches (contacts -> object SDF -> E_fc fwd+bwd |
@@ -251,15 +260,20 @@ class GraspStepper:
                 float(self.w["E_spen"]), _C.f32(self.terms_new[3]) if sph else None,
                 _C.f32(self.g_sph_w) if sph else None, ctypes.byref(self._propose_desc) if loop else None,
                 ctypes.byref(self._sdf_desc) if sdf else None, _C.ptr(self.fk_ws), self.fk_nb, st)
+        self._fk_sdf_attached = bool(sdf)  # whether the last FK forward launch carried the object query
         if self.S == 0:
             _C.call("gq_fill", _C.f32(self.terms_new[3]), 0.0, self.B, st)
+
+    def _eval_object_query(self, st):
+        """dist_sq / sign / direction / closest point of the B n contact points on their objects: mesh set or point clouds."""
+        _C.call("gq_cloud_forward" if self.cloud else "gq_sdf_forward_meshset", self.objs.handle, _C.f32(self.cpts),
+                self.B * self.n, self.be * self.n, _C.f32(self.d2), _C.i32(self.sgn), _C.f32(self.onrm), _C.f32(self.closest), st)
 
     def _eval_contacts(self, st):
         B, n, w, fc = self.B, self.n, self.w, self.fc
         C, f32, i32 = _C.call, _C.f32, _C.i32
         e_fc = self.terms_new[1]
-        C("gq_sdf_forward_meshset", self.objs.handle, f32(self.cpts), B * n, self.be * n, f32(self.d2), i32(self.sgn),
-          f32(self.onrm), f32(self.closest), st)
+        self._eval_object_query(st)
         if self.energy_type != "graspqp":
             # E_dis terms (+ outward object normals), then the other force-closure energy adds w_fc dE/dp in one launch
             C("gq_contact_terms", f32(self.d2), i32(self.sgn), f32(self.onrm), f32(self.closest), f32(self.cpts),
@@ -323,7 +337,7 @@ class GraspStepper:
         outputs), the accept step the tail of the FK backward kernel."""
         # small batches: the contact queries ride along with the kinematics (latency); large ones: their own launch
         # (throughput -- query wavefronts should not hold slots while wavefront 0 of their block does the kinematics)
-        attach = fused and self.B <= 512
+        attach = fused and self.B <= 512 and not self.cloud
         # per-role launches, 384..1023 rows: sphere centres + self penetration leave the FK forward launch (which both
         # branches wait for) and ride on the penetration branch, as in the fused form (same device code, same bits):
         # +3.9 % at 512 rows.  From 2048 rows on that branch is the longer one (-1.1 %), and a third graph branch for the
@@ -332,8 +346,7 @@ class GraspStepper:
         self._eval_fk(pose, idx, st, loop, sdf=attach, spheres=not fused and not split_spen)
         if fused:
             if not attach:
-                _C.call("gq_sdf_forward_meshset", self.objs.handle, _C.f32(self.cpts), self.B * self.n, self.be * self.n,
-                        _C.f32(self.d2), _C.i32(self.sgn), _C.f32(self.onrm), _C.f32(self.closest), st)
+                self._eval_object_query(st)
             # both branches side by side in two launches
             self._pen_desc.hand_pose = pose.data_ptr()
             if self._alt_desc is None:

@@ -104,8 +104,8 @@ def box(half=(0.03, 0.04, 0.05)) -> np.ndarray:
     return fv.astype(np.float32)
 
 
-def sample_surface(face_verts: np.ndarray, n: int, seed: int = 42) -> np.ndarray:
-    """Area-weighted uniform samples on a triangle soup -> (n,3) float64."""
+def sample_surface(face_verts: np.ndarray, n: int, seed: int = 42, return_faces: bool = False):
+    """Area-weighted uniform samples on a triangle soup -> (n,3) float64 (``return_faces``: and the face index of each)."""
     rng = np.random.default_rng(seed)
     fv = face_verts.astype(np.float64)
     area = 0.5 * np.linalg.norm(np.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0]), axis=1)
@@ -113,7 +113,33 @@ def sample_surface(face_verts: np.ndarray, n: int, seed: int = 42) -> np.ndarray
     r1, r2 = rng.random(n), rng.random(n)
     s = np.sqrt(r1)
     w0, w1, w2 = 1 - s, s * (1 - r2), s * r2
-    return fv[fi, 0] * w0[:, None] + fv[fi, 1] * w1[:, None] + fv[fi, 2] * w2[:, None]
+    pts = fv[fi, 0] * w0[:, None] + fv[fi, 1] * w1[:, None] + fv[fi, 2] * w2[:, None]
+    return (pts, fi) if return_faces else pts
+
+
+def face_normals(face_verts: np.ndarray) -> np.ndarray:
+    """Unit normals (F,3) float64 of a triangle soup, by the winding of its faces."""
+    fv = np.asarray(face_verts, dtype=np.float64)
+    n = np.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0])
+    return n / np.linalg.norm(n, axis=1, keepdims=True)
+
+
+def mesh_to_cloud(face_verts: np.ndarray, n: int, seed: int = 42):
+    """An oriented point cloud of a mesh: ``n`` area-weighted surface samples (the draws of ``sample_surface`` with the same
+    seed) with the unit normals of the faces they lie on -> (points (n,3), normals (n,3)) float32."""
+    pts, fi = sample_surface(face_verts, n, seed, return_faces=True)
+    return pts.astype(np.float32), face_normals(face_verts)[fi].astype(np.float32)
+
+
+def cloud_radius(points: np.ndarray) -> float:
+    """Default disc radius of an oriented point cloud: 2 x the median distance of a point to its nearest other point."""
+    from scipy.spatial import cKDTree
+
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    if len(p) < 2:
+        raise ValueError("cloud_radius: a cloud of fewer than two points has no neighbour distance; give the radius")
+    d, _ = cKDTree(p).query(p, k=2)
+    return 2.0 * float(np.median(d[:, 1]))
 
 
 def farthest_point_sampling(points: np.ndarray, k: int, start: int = 0) -> np.ndarray:

@@ -38,7 +38,7 @@ typedef struct gqMeshSet gqMeshSet; /* n_mesh triangle soups resident on the dev
 int gq_meshset_create(const float* face_verts_host /* (sumF,3,3) */, const int32_t* face_offset_host /* (n_mesh+1) */,
                       int n_mesh, gqMeshSet** out);
 int gq_meshset_destroy(gqMeshSet* ms);
-/* Device and host allocations currently held by all set-up objects of the process (gqMeshSet, gqBvh, gqPointGrid, gqHand):
+/* Device and host allocations currently held by all set-up objects of the process (gqMeshSet, gqBvh, gqPointGrid, gqHand, gqCloudSet):
  * an exact measure of their lifetime -- every create raises it, the matching destroy takes it back.                        */
 int gq_setup_live_allocations(int64_t* n);
 /* setup-time 32^3 occupancy grid + per-voxel candidate faces per mesh; required by penetration_only = 1 and the fused steps */
@@ -63,6 +63,37 @@ int gq_sdf_forward_bvh(const gqBvh* bvh, const float* points, int64_t n_points, 
                        float* normal /* or NULL */, float* closest, void* stream);
 int gq_sdf_backward(const float* grad_dist_sq, const float* points, const float* closest, int64_t n_points,
                     float* grad_points, void* stream);
+
+/* ---- objects as oriented point clouds: surfel signed distance for the contact query ------------------------------------
+ * For objects that come as points with normals (scans, open shells, unions of parts) instead of watertight meshes; it takes
+ * the place of gq_sdf_forward_meshset (core/object_model.py:186-255) and has no counterpart in the reference.
+ * A cloud is N points p_i with unit outward normals n_i and one radius rho > 0, read as N oriented discs.  For a query x:
+ *   1. nearest sample  j = argmin_i |x - p_i|^2, ties to the smallest index (nearest CENTRE);
+ *   2. v = x - p_j, h = v . n_j, lat = v - h n_j, l = |lat|;
+ *   3. closest = p_j + lat min(1, rho / l): the nearest point of disc j (x - h n_j over the disc, a rim point beyond it);
+ *   4. dist_sq = |x - closest|^2;
+ *   5. sign = +1 if h >= 0 else -1 (int32, +1 outside);
+ *   6. normal = sign n_j for l <= rho (no division; a query on the disc gets n_j), (x - closest)/|x - closest| beyond the rim.
+ * Only dist_sq is differentiable, w.r.t. x, as 2 (x - closest) -- exact for the distance to a disc: gq_sdf_backward applies.
+ * dist_sq (N), sign (N), normal (N,3) (may be NULL), closest (N,3): layout and meaning of gq_sdf_forward_meshset.
+ * gq_cloudset_create takes HOST arrays: points / normals (sumN,3), offsets (n_obj+1) starting at 0, radius (n_obj); normals are
+ * normalised in double; 1 <= N <= 2^20 per cloud.  A zero or non-finite normal, a non-finite point, N = 0 or rho <= 0 is
+ * refused before anything touches the device.  The set counts in gq_setup_live_allocations.
+ * gq_cloud_forward: query q uses cloud q / queries_per_object; one wavefront per query walks the cloud's uniform grid outward
+ * from the query's (clamped) cell and returns the brute-force winner (csrc/cloud.hip); no workspace, no atomics, bitwise
+ * reproducible.  A non-finite query, or one so far away that d^2 overflows float32, gives NaN outputs with sign +1.
+ * gq_cloud_check is the argument check of both on its own (host only, no GPU): gq_cloudset_create calls it with n_points =
+ * n_obj and queries_per_object = 1, gq_cloud_forward with the set's own offsets and radii.                               */
+typedef struct gqCloudSet gqCloudSet;
+int gq_cloud_check(int64_t n_obj, const int32_t* offsets_host /* (n_obj+1) */, const float* radius_host /* (n_obj) */,
+                   int64_t n_points, int64_t queries_per_object);
+int gq_cloudset_create(const float* points_host /* (sumN,3) */, const float* normals_host /* (sumN,3) */,
+                       const int32_t* offsets_host /* (n_obj+1) */, const float* radius_host /* (n_obj) */, int n_obj,
+                       gqCloudSet** out);
+int gq_cloudset_destroy(gqCloudSet* cs);
+int gq_cloud_forward(const gqCloudSet* cs, const float* points /* (n_points,3) */, int64_t n_points,
+                     int64_t queries_per_object, float* dist_sq, int32_t* sign, float* normal /* or NULL */, float* closest,
+                     void* stream);
 
 /* ---- box-constrained QP: qpth.qp.QPFunction as used by SQPLsqSolver.solve --------------------------
  * reference: metrics/solver/qp_solver.py:8,60-134 (QPFunction(maxIter=12, eps=5e-2), G = [I;-I], h = [u;-l]).
