@@ -127,6 +127,13 @@ InitDesc = _struct("InitDesc", [
     ("u_face", "p"), ("u_len", "p"), ("u_pose", "p"), ("u_joint", "p"), ("hand_pose", "p"), ("shell_points", "p"),
     ("shell_dirs", "p"), ("workspace", "p"), ("workspace_bytes", "z")])
 
+
+class SceneGrid(ctypes.Structure):
+    """gqSceneGrid: a signed-distance grid of the surroundings (positive outside the obstacles), a plain struct."""
+    _fields_ = [("values", ctypes.c_void_p), ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nz", ctypes.c_int),
+                ("origin", ctypes.c_float * 3), ("voxel", ctypes.c_float)]
+
+
 _lib = None
 _protos = None
 

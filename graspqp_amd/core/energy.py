@@ -131,6 +131,13 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal):
         z_height = hand_model.get_surface_points()[..., -1].clamp(max=0.0)
         losses["E_wall"] = z_height.abs().sum(-1)
 
+    if "E_scene" in energy_names:  # hand surface samples inside the obstacles of a signed-distance grid (HandModel.set_scene)
+        scene = getattr(hand_model, "scene", None)
+        if scene is None:
+            raise ValueError('calculate_energy: "E_scene" needs HandModel.set_scene(ops.SceneSDF(...))')
+        phi = ops.scene_distance(hand_model.get_surface_points(), scene)  # +inf outside the volume: free space
+        losses["E_scene"] = torch.relu(hand_model.scene_margin - phi).sum(-1)
+
     if "E_manipulativity" in energy_names:
         # energy.py:80-87: mean squared contact velocity the joints cannot produce when the contacts move along
         # normal * max(|distance|, 5 mm); differentiable (ops.joint_velocity_residuals: analytic kinematic Hessian)

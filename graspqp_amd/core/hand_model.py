@@ -210,6 +210,15 @@ class HandModel:
         s2.cand_nrm = np.tile(np.array([[0, 0, 1.0]], dtype=np.float32), (len(pts), 1))
         self._surface = (ops.HandHandle(s2), pts, s2.cand_link)
 
+    def set_scene(self, scene, margin=0.0):
+        """The surroundings as an ``ops.SceneSDF`` (None removes it): calculate_energy(..., energy_names=[..., "E_scene"]) is then
+        the sum over the surface samples of relu(margin - phi); ``margin`` >= 0 is a clearance in metres."""
+        if scene is not None and not isinstance(scene, ops.SceneSDF):
+            raise ValueError("HandModel.set_scene: scene must be an ops.SceneSDF or None")
+        if not float(margin) >= 0.0:
+            raise ValueError(f"HandModel.set_scene: margin = {margin!r} must be >= 0")
+        self.scene, self.scene_margin = scene, float(margin)
+
     def get_surface_points(self):
         """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose."""
         h, pts, _ = self._surface_handle()

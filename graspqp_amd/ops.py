@@ -1230,6 +1230,210 @@ def tabletop_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg
                                 _axis3(grasp_axis), float(table_z))
 
 
+# ----------------------------------------------------------------------------------------------------------
+# scene obstacles: E_scene on a signed-distance grid of the surroundings (csrc/scene.hip, include/graspqp_hip.h)
+# ----------------------------------------------------------------------------------------------------------
+_SCENE_CHUNK = 1 << 20  # nodes per set-up query of from_meshes / from_point_clouds
+
+
+def _scene_grid(values, origin, voxel) -> "_C.SceneGrid":
+    g = _C.SceneGrid()
+    g.values = values.data_ptr()
+    g.nx, g.ny, g.nz = (int(s) for s in values.shape)
+    g.origin = (ctypes.c_float * 3)(*(float(o) for o in origin))
+    g.voxel = float(voxel)
+    return g
+
+
+class SceneSDF:
+    """A signed-distance grid of the hand's surroundings (an ESDF / TSDF volume): ``values`` (nx,ny,nz) float32 on the
+    device, phi at the nodes in metres, POSITIVE OUTSIDE the obstacles; ``origin`` = world position of node (0,0,0);
+    ``voxel`` = the node spacing of all axes.  A CUDA float32 contiguous tensor is used without a copy (anything else is
+    converted once), so overwriting ``values`` in place moves the obstacles, also under a captured graph.  Between the nodes
+    phi is the trilinear interpolant; outside the volume is free space (include/graspqp_hip.h)."""
+
+    def __init__(self, values, origin, voxel, device="cuda"):
+        v = values if torch.is_tensor(values) else torch.as_tensor(np.asarray(values, dtype=np.float32))
+        if v.dim() != 3:
+            raise ValueError(f"SceneSDF: values must be (nx,ny,nz), got {tuple(v.shape)}")
+        origin = [float(o) for o in (origin.detach().cpu().tolist() if torch.is_tensor(origin) else origin)]
+        if len(origin) != 3:
+            raise ValueError(f"SceneSDF: origin must have 3 entries, got {len(origin)}")
+        if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
+            v = v.detach().to(device, torch.float32).contiguous()
+        self.values, self.origin, self.voxel = v, tuple(origin), float(voxel)
+        self.shape = tuple(int(s) for s in v.shape)
+        self.grid = _scene_grid(v, self.origin, self.voxel)
+        self.check()
+
+    def check(self, batch=1, n_links=1, n_samples=1):
+        """gq_scene_check (host only) of the grid and of a launch's shapes; raises ValueError with the library's message."""
+        try:
+            _C.call("gq_scene_check", ctypes.byref(self.grid), ctypes.c_int64(int(batch)), int(n_links), ctypes.c_int64(int(n_samples)))
+        except RuntimeError as e:
+            raise ValueError(f"SceneSDF: {e}") from None
+
+    @staticmethod
+    def _nodes(origin, shape, voxel, device):
+        ax = [float(o) + float(voxel) * torch.arange(int(n), dtype=torch.float64, device=device) for o, n in zip(origin, shape)]
+        return torch.stack(torch.meshgrid(*ax, indexing="ij"), -1).to(torch.float32)
+
+    def node_positions(self):
+        """World positions of the nodes, (nx,ny,nz,3) float32 on the device of ``values``."""
+        return self._nodes(self.origin, self.shape, self.voxel, self.values.device)
+
+    @classmethod
+    def _filled(cls, query, n_obj, origin, shape, voxel, device):
+        """phi = min over the objects of sign * sqrt(dist_sq) at the nodes, in chunks of at most 2^20 nodes."""
+        pts = cls._nodes(origin, shape, voxel, device).reshape(-1, 3)
+        phi = torch.full((pts.shape[0],), float("inf"), device=device)
+        with torch.no_grad():
+            for k in range(n_obj):
+                for a in range(0, pts.shape[0], _SCENE_CHUNK):
+                    d2, sgn = query(k, pts[a:a + _SCENE_CHUNK])
+                    phi[a:a + _SCENE_CHUNK] = torch.minimum(phi[a:a + _SCENE_CHUNK], sgn.to(torch.float32) * d2.sqrt())
+        return cls(phi.reshape(tuple(int(n) for n in shape)), origin, voxel, device)
+
+    @classmethod
+    def from_meshes(cls, face_verts_list, origin, shape, voxel, device="cuda"):
+        """The grid of the union of triangle meshes (each (F,3,3)): phi = min over the meshes of sign * sqrt(dist_sq) of
+        ``compute_sdf`` at the node positions.  Set-up code.  A mesh must be CLOSED for its sign to mean anything: the sign is
+        that of the nearest face's side, which for an open sheet flips across the sheet's plane far from it."""
+        fvs = [torch.as_tensor(np.asarray(f.detach().cpu() if torch.is_tensor(f) else f, dtype=np.float32).reshape(-1, 3, 3)).to(device)
+               for f in face_verts_list]
+        return cls._filled(lambda k, p: compute_sdf(p, fvs[k])[:2], len(fvs), origin, shape, voxel, device)
+
+    @classmethod
+    def from_point_clouds(cls, points_list, normals_list, origin, shape, voxel, radius=None, device="cuda"):
+        """The same from oriented point clouds (``PointCloudSet`` / ``sdf_cloud``, the surfel signed distance of DESIGN 13);
+        a cloud must sample a CLOSED surface with outward normals for its sign to mean anything."""
+        n = len(points_list)
+        rad = [None] * n if radius is None else [float(radius)] * n if np.ndim(radius) == 0 else [float(r) for r in radius]
+        if len(rad) != n or len(normals_list) != n:
+            raise ValueError(f"SceneSDF.from_point_clouds: {n} clouds, {len(normals_list)} normal sets, {len(rad)} radii")
+        sets = [PointCloudSet([p], [nr], r, device) for p, nr, r in zip(points_list, normals_list, rad)]
+        return cls._filled(lambda k, p: sdf_cloud(p, sets[k], p.shape[0])[:2], len(sets), origin, shape, voxel, device)
+
+
+def _scene_call(grid, margin, hp, points, link, n_links, Rg, LT, up_scene, w_scene, e_scene, accumulate, wrench, gRt, st=None):
+    _C.call("gq_scene_terms", ctypes.byref(grid), float(margin), _C.f32(points), _C.i32(link), ctypes.c_int64(points.shape[0]),
+            int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT), ctypes.c_int64(hp.shape[0]), _C.f32(up_scene),
+            float(w_scene), _C.f32(e_scene), int(accumulate), _C.f32(wrench), _C.f32(gRt), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::scene_distance", mutates_args=(), device_types="cuda")
+def _scene_distance_op(points: Tensor, values: Tensor, origin: List[float], voxel: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (phi (...), grad phi (...,3), inside (...) uint8) of the grid at world points (...,3); outside the volume
+    phi = +inf, grad = 0, inside = 0."""
+    pts, v = _c(points), _c(values)
+    flat = pts.reshape(-1, 3)
+    N, dev = flat.shape[0], pts.device
+    phi, grad, inside = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
+    grid = _scene_grid(v, origin, voxel)
+    _C.call("gq_scene_query", ctypes.byref(grid), _C.f32(flat), ctypes.c_int64(N), _C.f32(phi), _C.f32(grad), _C.u8(inside),
+            _C.stream_ptr())
+    return phi.reshape(pts.shape[:-1]), grad.reshape(pts.shape), inside.reshape(pts.shape[:-1])
+
+
+@_scene_distance_op.register_fake
+def _(points, values, origin, voxel):
+    return (points.new_empty(points.shape[:-1]), points.new_empty(points.shape),
+            points.new_empty(points.shape[:-1], dtype=torch.uint8))
+
+
+def _scene_distance_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.mark_non_differentiable(output[1], output[2])
+
+
+def _scene_distance_bwd(ctx, g_phi, g_grad, g_inside):
+    (grad,) = ctx.saved_tensors
+    return grad * g_phi.unsqueeze(-1), None, None, None
+
+
+torch.library.register_autograd("graspqp_amd::scene_distance", _scene_distance_bwd, setup_context=_scene_distance_setup)
+
+
+def scene_distance(points, scene: SceneSDF):
+    """phi (...) of the scene's grid at world points (...,3): the trilinear interpolant, +inf outside the volume (free
+    space).  Differentiable w.r.t. ``points``: the backward is grad phi * upstream, zero outside the volume."""
+    if not points.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if points.dim() < 1 or points.shape[-1] != 3:
+        raise ValueError(f"scene_distance: points must be (...,3), got {tuple(points.shape)}")
+    return _Eager.scene_distance(points, scene.values, list(scene.origin), scene.voxel)[0]
+
+
+@_custom_op("graspqp_amd::scene_terms", mutates_args=(), device_types="cuda")
+def _scene_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+              origin: List[float], voxel: float, margin: float) -> Tensor:
+    """-> E_scene (B), unweighted: sum over the hand's surface samples of max(margin - phi, 0).  The kinematic state (Rg,
+    link_T) is the one of ``hand_pose``, passed in detached, as for hand_pen."""
+    hp, v = _c(hand_pose), _c(values)
+    e = torch.empty(hp.shape[0], device=hp.device)
+    _scene_call(_scene_grid(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT), None, 0.0,
+                e, 0, None, None)
+    return e
+
+
+@_scene_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin):
+    return hand_pose.new_empty(hand_pose.shape[0])
+
+
+@_custom_op("graspqp_amd::scene_terms_backward", mutates_args=(), device_types="cuda")
+def _scene_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                  origin: List[float], voxel: float, margin: float, g_scene: Tensor) -> Tuple[Tensor, Tensor]:
+    """Upstream row gradients (B) on E_scene -> (link wrench (B,L,6), gRt (B,12)) for fk_backward."""
+    hp, v = _c(hand_pose), _c(values)
+    B, dev = hp.shape[0], hp.device
+    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
+    _scene_call(_scene_grid(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT),
+                _c(g_scene), 0.0, None, 0, wrench, gRt)
+    return wrench, gRt
+
+
+@_scene_bwd_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin, g_scene):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+
+
+class _SceneTerms(torch.autograd.Function):
+    """Glue between two registered ops (scene_terms + fk_backward), as _TabletopTerms."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, samples, idx, Rg, LT, ws, scene, margin):
+        hp = _c(hand_pose.detach())
+        e = _Eager.scene_terms(hp, samples.points, samples.link, hand.L, Rg, LT, scene.values, list(scene.origin), scene.voxel,
+                               margin)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, samples.points, samples.link, scene.values)
+        ctx.hand, ctx.origin, ctx.voxel, ctx.margin = hand, list(scene.origin), scene.voxel, margin
+        return e
+
+    @staticmethod
+    def backward(ctx, g_scene):
+        hp, idx, Rg, LT, ws, points, link, values = ctx.saved_tensors
+        hand = ctx.hand
+        wrench, gRt = _Eager.scene_terms_backward(hp, points, link, hand.L, Rg, LT, values, ctx.origin, ctx.voxel, ctx.margin,
+                                                  g_scene)
+        gp = _fk_backward(hand, hp, idx, Rg, LT, ws, None, None, None, wrench, gRt, None)
+        return gp, None, None, None, None, None, None, None, None
+
+
+def scene_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, LT, ws, scene: SceneSDF, margin=0.0):
+    """-> E_scene (B) = sum over ``samples`` of max(margin - phi(x_w), 0) on the scene's grid, unweighted, differentiable
+    w.r.t. ``hand_pose``.  ``idx``, ``Rg``, ``LT``, ``ws`` are the kinematic state of ``hand_pose`` (fk_contacts); ``margin``
+    >= 0 is a clearance in metres."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if samples.n_links != hand.L:
+        raise ValueError(f"scene_terms: the samples refer to {samples.n_links} links, the hand has {hand.L}")
+    if not float(margin) >= 0.0:
+        raise ValueError(f"scene_terms: margin = {margin!r} must be >= 0")
+    return _SceneTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws, scene, float(margin))
+
+
 @_custom_op("graspqp_amd::self_pen", mutates_args=(), device_types="cuda")
 def _self_pen_op(centers: Tensor, hand: int) -> Tuple[Tensor, Tensor]:
     """E_spen (B,) of world sphere centres (B,S,3) and dE/dcentres (hand_model.py:989-1040)."""
@@ -1428,6 +1632,9 @@ _eager("hand_pen", _hand_pen_op)
 _eager("hand_pen_backward", _hand_pen_bwd_op)
 _eager("tabletop_terms", _tabletop_op)
 _eager("tabletop_terms_backward", _tabletop_bwd_op)
+_eager("scene_distance", _scene_distance_op, _scene_distance_bwd, _scene_distance_setup)
+_eager("scene_terms", _scene_op)
+_eager("scene_terms_backward", _scene_bwd_op)
 _eager("self_pen", _self_pen_op, _self_pen_bwd, _self_pen_setup)
 _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_distance_setup)
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)

@@ -104,6 +104,22 @@ def box(half=(0.03, 0.04, 0.05)) -> np.ndarray:
     return fv.astype(np.float32)
 
 
+def open_bin(center=(0.0, 0.0, 0.0), inner_half=(0.15, 0.15), floor_z=-0.08, height=0.12, wall=0.02):
+    """An open-topped bin around ``center`` as five closed slabs (a floor and four walls of thickness ``wall``), each 12
+    outward-oriented triangles: the ``box`` scene preset of the tools (``ops.SceneSDF.from_meshes`` needs closed meshes).
+    ``inner_half`` = half extents of the free space in x and y, ``floor_z`` = top of the floor relative to the centre,
+    ``height`` = height of the walls above it."""
+    cx, cy, cz = (float(c) for c in center)
+    hx, hy = (float(h) for h in inner_half)
+    z0, z1 = cz + floor_z, cz + floor_z + height
+    slabs = [((cx, cy, z0 - 0.5 * wall), (hx + wall, hy + wall, 0.5 * wall))]  # floor, under the walls too
+    for sx in (-1.0, 1.0):
+        slabs.append(((cx + sx * (hx + 0.5 * wall), cy, 0.5 * (z0 + z1)), (0.5 * wall, hy + wall, 0.5 * height)))
+    for sy in (-1.0, 1.0):
+        slabs.append(((cx, cy + sy * (hy + 0.5 * wall), 0.5 * (z0 + z1)), (hx, 0.5 * wall, 0.5 * height)))
+    return [(box(half).astype(np.float64) + np.asarray(c)).astype(np.float32) for c, half in slabs]
+
+
 def sample_surface(face_verts: np.ndarray, n: int, seed: int = 42, return_faces: bool = False):
     """Area-weighted uniform samples on a triangle soup -> (n,3) float64 (``return_faces``: and the face index of each)."""
     rng = np.random.default_rng(seed)

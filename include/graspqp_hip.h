@@ -499,6 +499,54 @@ int gq_tabletop_terms(const float* samples /* (Ns,3) link frame, device */, cons
 int gq_tabletop_total(float* total /* (B) in/out */, const float* e_prior, float w_prior, const float* e_wall, float w_wall,
                       int64_t batch, void* stream);
 
+/* ---- scene obstacles of the stepper: E_scene on a signed-distance grid of the surroundings (ESDF / TSDF volume) -----
+ * The grid is a plain struct.  values is phi at the nodes in metres, POSITIVE OUTSIDE the obstacles, fp32 on the device,
+ * (nx,ny,nz) row-major with z fastest; origin is the world position of node (0,0,0); voxel is the one node spacing h of
+ * all axes.  The memory belongs to the caller, who may overwrite values in place between launches (moving obstacles; a
+ * captured graph reads the new numbers).  Limits: 2 <= nx, ny, nz, nx ny nz <= 2^28, h finite and > 0, origin finite.
+ *   phi at a world point x: u = (x - origin) / h per axis.  x is INSIDE the volume iff every u_a is finite and
+ *   0 <= u_a <= n_a - 1 (both ends inclusive); the cell is i_a = min(floor(u_a), n_a - 2), the weights f_a = u_a - i_a in
+ *   [0,1]; phi(x) is the trilinear interpolant of the 8 nodes of the cell and grad phi(x) its own gradient, e.g.
+ *   d phi / dx = (1/h) sum_jk w_j(f_y) w_k(f_z) (v_1jk - v_0jk).  A point outside the volume is free space and contributes
+ *   nothing.  A point with a non-finite coordinate gives NaN and never becomes an index: the finiteness test and the clamp
+ *   to [0, n_a - 2] come before the float -> int conversion and before any load.  The inside test is made on exact
+ *   quantities (x_a >= origin_a, and x_a - origin_a <= h (n_a - 1) in double): one ulp beyond the last node plane is outside.
+ * gq_scene_terms: one launch for the energy and its gradient, in the form gq_fk_backward takes.  Per hand surface sample
+ * (link-frame point p of link sample_link): x_h = T_link p, x_w = R x_h + t with t = hand_pose[:, :3].
+ *   E_scene = sum_s max(margin - phi(x_w), 0)       margin >= 0: a clearance in metres
+ * (phi = z - table_z and margin 0 make it E_wall).  e_scene is written UNWEIGHTED.  The gradient carries the upstream
+ * factor of the row: up_scene[row] if the pointer is given, else w_scene.  With g_w = -up grad phi(x_w) and g_h = R' g_w
+ * for the samples with phi < margin:
+ *   link_wrench (B,L,6): f_l = sum g_h, m_l = sum x_h x g_h (about the hand origin, hand frame)
+ *   gRt (B,12) = [gsum(3), K(9)]: gsum = -sum g_h, K = sum g_h (x) x_h, row-major K[a][j] = g_h[a] x_h[j]
+ *   (grad_t = -R gsum, grad_R = R K); there is no g_R.
+ * accumulate = 1 adds to the two gradient buffers (a plain rounded add of the finished value: the bits of buffer + the
+ * overwriting launch's value), 0 overwrites them; links without samples get a zero wrench when overwriting and are left
+ * alone when accumulating.  Fixed-order sums, no atomics: bitwise reproducible run to run (the sums follow the order of the
+ * samples).  n_links <= 64; n_samples need not be a multiple of 64; a link id outside the hand is ignored.  A row with a
+ * non-finite sample position gets a NaN energy and gradient; the other rows are unaffected.
+ * gq_scene_check is the argument check of the launch on its own (host only, no GPU); its message names the argument.
+ * gq_scene_query: phi (N), grad phi (N,3) and inside (N) at arbitrary world points (N,3), one point per lane, by the same
+ * device body (csrc/scene_dev.h): bit for bit the fused launch's numbers at the same point.  Outside the volume
+ * phi = +inf, grad = 0, inside = 0; a non-finite point gives NaN phi and grad, inside = 0.                            */
+typedef struct gqSceneGrid {
+  const float* values;  /* (nx,ny,nz) device, fp32, z fastest: phi at the nodes, positive outside the obstacles */
+  int nx, ny, nz;
+  float origin[3];      /* world position of node (0,0,0) */
+  float voxel;          /* node spacing h > 0, all axes */
+} gqSceneGrid;
+int gq_scene_check(const gqSceneGrid* grid, int64_t batch, int n_links, int64_t n_samples);
+int gq_scene_terms(const gqSceneGrid* grid, float margin, const float* samples /* (Ns,3) link frame, device */,
+                   const int32_t* sample_link /* (Ns) */, int64_t n_samples, int n_links, const float* hand_pose, int pose_dim,
+                   const float* Rg /* (B,9) */, const float* link_T /* (B,L,12) */, int64_t batch,
+                   const float* up_scene /* (B) or NULL */, float w_scene, float* e_scene /* (B) or NULL, unweighted */,
+                   int accumulate /* 1: add to the two gradient buffers, 0: overwrite */,
+                   float* link_wrench /* (B,L,6) or NULL */, float* gRt /* (B,12) or NULL */, void* stream);
+int gq_scene_query(const gqSceneGrid* grid, const float* points /* (N,3) world, device */, int64_t n_points,
+                   float* phi /* (N) */, float* grad /* (N,3) or NULL */, uint8_t* inside /* (N) or NULL */, void* stream);
+/* total[row] += w_scene * e_scene[row]: the row total that gq_fk_backward writes holds the five terms of its own tail. */
+int gq_scene_total(float* total /* (B) in/out */, const float* e_scene, float w_scene, int64_t batch, void* stream);
+
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
  * Per object: samples_per_object points on its convex hull (area-weighted), pushed out by `inflate` (0.01 in the
  * reference) along the face normal; farthest-point sampling of batch_each of them (start = sample 0); per row the look-at

@@ -13,6 +13,8 @@ Evidence run, not a test: writes one JSON record (default gpurun_out/fit_end_to_
 usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_iter 7000] [--out file.json]
        [--w_wall 0] [--w_prior 0]   (scripts/fit.py:77-78: tabletop synthesis; the class surface and the oracle then carry
        E_wall / E_prior on the stepper's surface samples, st.samples)
+       [--w_scene 0] [--scene_margin 0] [--scene box]   (scene obstacles: the ``box`` preset is an open-topped bin of five slabs
+       around the first object, voxelised on an 80^3 grid of 5 mm by ops.SceneSDF.from_meshes; the class surface carries E_scene)
 """
 import argparse
 import json
@@ -37,6 +39,9 @@ ap.add_argument("--reset_epochs", type=int, default=600)
 ap.add_argument("--oracle_rows", type=int, default=6)
 ap.add_argument("--w_wall", type=float, default=0.0)
 ap.add_argument("--w_prior", type=float, default=0.0)
+ap.add_argument("--w_scene", type=float, default=0.0)
+ap.add_argument("--scene_margin", type=float, default=0.0)
+ap.add_argument("--scene", choices=("box",), default="box")
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "fit_end_to_end.json"))
 args = ap.parse_args()
 
@@ -54,6 +59,9 @@ W = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.
 TABLETOP = args.w_wall > 0 or args.w_prior > 0
 if TABLETOP:
     W.update({"E_prior": args.w_prior, "E_wall": args.w_wall})  # fit.py:369-370
+SCENE = args.w_scene > 0
+if SCENE:
+    W["E_scene"] = args.w_scene
 spec = get_hand_spec(args.hand)
 n_obj, be, n = args.n_objects, args.batch_size, args.n_contact
 B = n_obj * be
@@ -63,8 +71,14 @@ sps = [meshes.surface_points(f, 2500, oversample=4, seed=42) for f in fvs]
 om = ObjectModel(batch_size_each=be, num_samples=2500)
 om.initialize_from_meshes(fvs, codes, surface_points_list=sps)
 hand = ops.HandHandle(spec)
-st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1,
-                  weights={"E_prior": args.w_prior, "E_wall": args.w_wall} if TABLETOP else None)
+weights = {"E_prior": args.w_prior, "E_wall": args.w_wall} if TABLETOP else {}
+scene = None
+if SCENE:  # the ``box`` preset: an open-topped bin around the first object
+    center = 0.5 * (fvs[0].reshape(-1, 3).min(0) + fvs[0].reshape(-1, 3).max(0))
+    scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), [float(c) - 0.5 * 0.005 * 79 for c in center], (80, 80, 80), 0.005)
+    weights["E_scene"] = args.w_scene
+st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1, weights=weights or None, scene=scene,
+                  scene_margin=args.scene_margin)
 st.set_hulls(om.convex_hulls())
 st.initialize()  # on-device initialize_convex_hull + the first evaluation
 e0, t0_terms = st.energy.clone(), st.terms.clone()
@@ -90,11 +104,13 @@ assert torch.isfinite(st.energy).all() and torch.isfinite(st.hand_pose).all()
 hm = HandModel(spec, "cuda")
 hp = st.hand_pose.clone().requires_grad_()
 hm.set_parameters(hp, st.contact_idx.clone())
-if TABLETOP:
+if TABLETOP or SCENE:
     hm.set_surface_points(st.samples.points.cpu().numpy(), st.samples.link.cpu().numpy())
+if SCENE:
+    hm.set_scene(scene, args.scene_margin)
 metric = GraspSpanMetricFactory.create(GraspSpanMetricFactory.MetricType.GRASPQP, {"friction": 0.2, "max_limit": 20.0, "n_cone_vecs": 4})
 losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1,
-                          energy_names=["E_prior", "E_wall"] if TABLETOP else [])
+                          energy_names=(["E_prior", "E_wall"] if TABLETOP else []) + (["E_scene"] if SCENE else []))
 total_cls = sum(W[k] * losses[k] for k in W)
 rel_cls = ((total_cls.detach() - st.energy).abs() / st.energy.abs().clamp_min(1e-6))
 

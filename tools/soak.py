@@ -2,10 +2,13 @@
 every `reset_epochs`) on the bench scene, at one or several batch sizes: energies must stay finite and fall, the debug
 counters must not show inline-ranked overflow growing, the stop iteration is histogrammed.  Development aid, not a test.
 
-usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--out file.json]
+usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--w_scene W] [--scene_margin M]
+       [--scene box] [--out file.json]
        (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
        schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
-       hand surface samples left below the plane; --out writes the records as JSON.
+       hand surface samples left below the plane; --w_scene > 0 runs it in scene mode against the ``box`` preset (an open-topped
+       bin of five slabs around the first object, 80^3 grid of 5 mm, ops.SceneSDF.from_meshes) and reports the mean E_scene at
+       the start and at the end; --out writes the records as JSON.
 """
 import argparse
 import json
@@ -29,11 +32,17 @@ ap.add_argument("n_objects", type=int, nargs="*", default=[1, 8])
 ap.add_argument("--w_wall", type=float, default=0.0)
 ap.add_argument("--w_prior", type=float, default=0.0)
 ap.add_argument("--table_z", type=float, default=0.0)
+ap.add_argument("--w_scene", type=float, default=0.0)
+ap.add_argument("--scene_margin", type=float, default=0.0)
+ap.add_argument("--scene", choices=("box",), default="box")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
 TABLETOP = args.w_wall > 0 or args.w_prior > 0
-weights = {"E_wall": args.w_wall, "E_prior": args.w_prior} if TABLETOP else None
+SCENE = args.w_scene > 0
+weights = {"E_wall": args.w_wall, "E_prior": args.w_prior} if TABLETOP else {}
+if SCENE:
+    weights["E_scene"] = args.w_scene
 records = []
 
 
@@ -54,12 +63,17 @@ for n_obj in args.n_objects:
     sps = [meshes.surface_points(f, 2500, oversample=4, seed=42) for f in fvs]
     om = ObjectModel(batch_size_each=256, num_samples=2500)
     om.initialize_from_meshes(fvs, surface_points_list=sps)
-    st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3, weights=weights,
-                      table_z=args.table_z)
+    scene = None
+    if SCENE:
+        center = 0.5 * (fvs[0].reshape(-1, 3).min(0) + fvs[0].reshape(-1, 3).max(0))
+        scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), [float(c) - 0.5 * 0.005 * 79 for c in center], (80, 80, 80), 0.005)
+    st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3, weights=weights or None,
+                      table_z=args.table_z, scene=scene, scene_margin=args.scene_margin)
     st.set_hulls(om.convex_hulls())
     st.initialize()
     e0 = st.energy.clone()
     wall0 = float(st.terms[6].mean()) if TABLETOP else None
+    scene0 = float(st.terms[-1].mean()) if SCENE else None
     st.capture(iters=8)
     hist = {}
     acc = []
@@ -96,6 +110,11 @@ for n_obj in args.n_objects:
         print(f"  tabletop: mean E_wall {wall0:.4f} -> {rec['E_wall_mean_final']:.6f}, mean E_prior {rec['E_prior_mean_final']:.4f}, "
               f"{rec['samples_below_plane_final_total']} samples below the plane in {rec['rows_with_samples_below_plane_final']} "
               f"of {st.B} rows", flush=True)
+    if SCENE:
+        rec.update({"w_scene": args.w_scene, "scene_margin": args.scene_margin, "scene": args.scene, "E_scene_mean_initial": scene0,
+                    "E_scene_mean_final": float(st.terms[-1].mean()), "rows_with_E_scene_final": int((st.terms[-1] > 0).sum())})
+        print(f"  scene: mean E_scene {scene0:.4f} -> {rec['E_scene_mean_final']:.6f}, {rec['rows_with_E_scene_final']} of {st.B} rows "
+              "still touch an obstacle", flush=True)
     records.append(rec)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
