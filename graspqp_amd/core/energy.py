@@ -138,6 +138,19 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal):
         phi = ops.scene_distance(hand_model.get_surface_points(), scene)  # +inf outside the volume: free space
         losses["E_scene"] = torch.relu(hand_model.scene_margin - phi).sum(-1)
 
+    if "E_approach" in energy_names:  # the same hinge along the approach corridor (HandModel.set_approach): the whole hand moved
+        scene, corridor = getattr(hand_model, "scene", None), getattr(hand_model, "approach", None)  # back by d_k = D k / K
+        if scene is None or corridor is None:
+            raise ValueError('calculate_energy: "E_approach" needs HandModel.set_scene(...) and HandModel.set_approach(...)')
+        D, K, margin = corridor
+        margin = hand_model.scene_margin if margin is None else margin
+        x = hand_model.get_surface_points()
+        back = (hand_model.global_rotation @ hand_model.grasp_axis.view(1, -1, 1)).view(-1, 3)  # R a
+        e = 0
+        for k in range(1, K + 1):
+            e = e + torch.relu(margin - ops.scene_distance(x - (D * k / K) * back.unsqueeze(1), scene)).sum(-1)
+        losses["E_approach"] = e * (1.0 / K)
+
     if "E_manipulativity" in energy_names:
         # energy.py:80-87: mean squared contact velocity the joints cannot produce when the contacts move along
         # normal * max(|distance|, 5 mm); differentiable (ops.joint_velocity_residuals: analytic kinematic Hessian)

@@ -219,6 +219,22 @@ class HandModel:
             raise ValueError(f"HandModel.set_scene: margin = {margin!r} must be >= 0")
         self.scene, self.scene_margin = scene, float(margin)
 
+    def set_approach(self, distance, stations, margin=None):
+        """The approach corridor of calculate_energy(..., energy_names=[..., "E_approach"]): the mean over the stations
+        d_k = distance k / stations, k = 1..stations <= 32, of the scene hinge with the whole hand moved back by d_k along the
+        spec's grasp_axis.  Needs ``set_scene`` first; ``margin`` = None follows the scene's margin, also one set by a later
+        ``set_scene``."""
+        if getattr(self, "scene", None) is None:
+            raise ValueError("HandModel.set_approach: call set_scene(ops.SceneSDF(...)) first")
+        margin = None if margin is None else float(margin)
+        if margin is not None and not margin >= 0.0:
+            raise ValueError(f"HandModel.set_approach: margin = {margin!r} must be >= 0")
+        if not 0.0 < float(distance) < float("inf"):
+            raise ValueError(f"HandModel.set_approach: distance = {distance!r} must be finite and > 0")
+        if int(stations) != stations or not 1 <= int(stations) <= 32:
+            raise ValueError(f"HandModel.set_approach: stations = {stations!r} must be an integer in 1..32")
+        self.approach = (float(distance), int(stations), margin)
+
     def get_surface_points(self):
         """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose."""
         h, pts, _ = self._surface_handle()

@@ -1434,6 +1434,107 @@ def scene_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, L
     return _SceneTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws, scene, float(margin))
 
 
+# ----------------------------------------------------------------------------------------------------------
+# approach clearance: E_approach, the scene grid along the hand's approach corridor (csrc/approach.hip)
+# ----------------------------------------------------------------------------------------------------------
+def approach_check(scene: SceneSDF, batch, n_links, n_samples, distance, stations, grasp_axis):
+    """gq_approach_check (host only) of the grid, a launch's shapes and the corridor; raises ValueError with the library's
+    message."""
+    ax = (ctypes.c_float * 3)(*(float(a) for a in grasp_axis))
+    try:
+        _C.call("gq_approach_check", ctypes.byref(scene.grid), ctypes.c_int64(int(batch)), int(n_links),
+                ctypes.c_int64(int(n_samples)), float(distance), int(stations), ctypes.cast(ax, ctypes.c_void_p))
+    except RuntimeError as e:
+        raise ValueError(f"approach: {e}") from None
+
+
+def _approach_call(grid, margin, distance, stations, hp, points, link, n_links, Rg, LT, axis, up_approach, w_approach, e_approach,
+                   accumulate, wrench, gRt, st=None):
+    ax = (ctypes.c_float * 3)(*(float(a) for a in axis))
+    _C.call("gq_approach_terms", ctypes.byref(grid), float(margin), float(distance), int(stations), _C.f32(points), _C.i32(link),
+            ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT),
+            ctypes.c_int64(hp.shape[0]), ctypes.cast(ax, ctypes.c_void_p), _C.f32(up_approach), float(w_approach),
+            _C.f32(e_approach), int(accumulate), _C.f32(wrench), _C.f32(gRt), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::approach_terms", mutates_args=(), device_types="cuda")
+def _approach_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                 origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int,
+                 margin: float) -> Tensor:
+    """-> E_approach (B), unweighted: the mean over the stations d_k = distance k / stations of the hinge sum of the hand's
+    surface samples moved back by d_k along grasp_axis.  The kinematic state (Rg, link_T) is the one of ``hand_pose``."""
+    hp, v = _c(hand_pose), _c(values)
+    e = torch.empty(hp.shape[0], device=hp.device)
+    _approach_call(_scene_grid(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
+                   _c(Rg), _c(LT), grasp_axis, None, 0.0, e, 0, None, None)
+    return e
+
+
+@_approach_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin):
+    return hand_pose.new_empty(hand_pose.shape[0])
+
+
+@_custom_op("graspqp_amd::approach_terms_backward", mutates_args=(), device_types="cuda")
+def _approach_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                     origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int, margin: float,
+                     g_approach: Tensor) -> Tuple[Tensor, Tensor]:
+    """Upstream row gradients (B) on E_approach -> (link wrench (B,L,6), gRt (B,12)) for fk_backward."""
+    hp, v = _c(hand_pose), _c(values)
+    B, dev = hp.shape[0], hp.device
+    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
+    _approach_call(_scene_grid(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
+                   _c(Rg), _c(LT), grasp_axis, _c(g_approach), 0.0, None, 0, wrench, gRt)
+    return wrench, gRt
+
+
+@_approach_bwd_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin, g_approach):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+
+
+class _ApproachTerms(torch.autograd.Function):
+    """Glue between two registered ops (approach_terms + fk_backward), as _SceneTerms."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, samples, idx, Rg, LT, ws, scene, axis, distance, stations, margin):
+        hp = _c(hand_pose.detach())
+        e = _Eager.approach_terms(hp, samples.points, samples.link, hand.L, Rg, LT, scene.values, list(scene.origin), scene.voxel,
+                                  axis, distance, stations, margin)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, samples.points, samples.link, scene.values)
+        ctx.hand, ctx.origin, ctx.voxel = hand, list(scene.origin), scene.voxel
+        ctx.corridor = (axis, distance, stations, margin)
+        return e
+
+    @staticmethod
+    def backward(ctx, g_approach):
+        hp, idx, Rg, LT, ws, points, link, values = ctx.saved_tensors
+        hand = ctx.hand
+        wrench, gRt = _Eager.approach_terms_backward(hp, points, link, hand.L, Rg, LT, values, ctx.origin, ctx.voxel,
+                                                     *ctx.corridor, g_approach)
+        gp = _fk_backward(hand, hp, idx, Rg, LT, ws, None, None, None, wrench, gRt, None)
+        return (gp,) + (None,) * 11
+
+
+def approach_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, LT, ws, scene: SceneSDF, grasp_axis, distance,
+                   stations, margin=0.0):
+    """-> E_approach (B) = (1/K) sum over the stations k = 1..K and over ``samples`` of max(margin - phi(x_w^k), 0) on the
+    scene's grid, x_w^k the sample with the whole hand moved back by ``distance`` k / K along ``grasp_axis`` (hand frame);
+    unweighted, differentiable w.r.t. ``hand_pose``.  ``idx``, ``Rg``, ``LT``, ``ws`` are the kinematic state of ``hand_pose``
+    (fk_contacts); K = ``stations`` in 1..32, ``distance`` > 0 and ``margin`` >= 0 in metres."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if samples.n_links != hand.L:
+        raise ValueError(f"approach_terms: the samples refer to {samples.n_links} links, the hand has {hand.L}")
+    if not float(margin) >= 0.0:
+        raise ValueError(f"approach_terms: margin = {margin!r} must be >= 0")
+    axis = [float(a) for a in _axis3(grasp_axis)]
+    approach_check(scene, hand_pose.shape[0], hand.L, samples.Ns, distance, stations, axis)
+    return _ApproachTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws, scene, axis,
+                                float(distance), int(stations), float(margin))
+
+
 @_custom_op("graspqp_amd::self_pen", mutates_args=(), device_types="cuda")
 def _self_pen_op(centers: Tensor, hand: int) -> Tuple[Tensor, Tensor]:
     """E_spen (B,) of world sphere centres (B,S,3) and dE/dcentres (hand_model.py:989-1040)."""
@@ -1635,6 +1736,8 @@ _eager("tabletop_terms_backward", _tabletop_bwd_op)
 _eager("scene_distance", _scene_distance_op, _scene_distance_bwd, _scene_distance_setup)
 _eager("scene_terms", _scene_op)
 _eager("scene_terms_backward", _scene_bwd_op)
+_eager("approach_terms", _approach_op)
+_eager("approach_terms_backward", _approach_bwd_op)
 _eager("self_pen", _self_pen_op, _self_pen_bwd, _self_pen_setup)
 _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_distance_setup)
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)

@@ -21,6 +21,11 @@ on -- adds its link wrenches and gRt the same way; ``terms`` gets [E_scene] appe
 are the stand-alone launches.  The grid's values may be overwritten in place between iterations (moving obstacles), also
 between replays of a captured graph.
 
+Approach mode (a weight on "E_approach" and an ``ops.SceneSDF``, with or without a weight on "E_scene"): the corridor the hand
+travels along its approach axis must be free of the same grid.  One more launch (gq_approach_terms) after gq_scene_terms adds
+its link wrenches and gRt the same way; ``terms`` gets [E_approach] appended last, after E_scene; its share of the row total is
+one more gq_scene_total launch, and the proposal and the accept step are the stand-alone launches.
+
 Objects as oriented point clouds (an ``ops.PointCloudSet`` in the place of the ``ops.MeshSet``): the object SDF of the contacts is
 gq_cloud_forward, always a launch of its own; it fills the same four buffers, so every other launch is the one of a mesh object.
 """
@@ -36,20 +41,22 @@ from . import _C, ops
 TERM_NAMES = ("E_dis", "E_fc", "E_pen", "E_spen", "E_joints")
 TABLETOP_TERMS = ("E_prior", "E_wall")
 SCENE_TERMS = ("E_scene",)
+APPROACH_TERMS = ("E_approach",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
 def merge_weights(weights=None):
-    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms and of the scene term) updated with ``weights``; a key that
-    names no term of the stepper raises (it would otherwise be accepted and never used), and so does a negative weight of a
-    tabletop term or of the scene term."""
+    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term and of the approach term) updated with
+    ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and so does a
+    negative weight of a tabletop term, of the scene term or of the approach term."""
+    switched = TABLETOP_TERMS + SCENE_TERMS + APPROACH_TERMS
     w = dict(DEFAULT_WEIGHTS)
-    w.update({k: 0.0 for k in TABLETOP_TERMS + SCENE_TERMS})
+    w.update({k: 0.0 for k in switched})
     for k, v in (weights or {}).items():
         if k not in w:
             raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
         w[k] = float(v)
-        if k in TABLETOP_TERMS + SCENE_TERMS and not w[k] >= 0.0:  # these terms are switched by their weight: > 0 on, 0 off
+        if k in switched and not w[k] >= 0.0:  # these terms are switched by their weight: > 0 on, 0 off
             raise ValueError(f"GraspStepper: weights[{k!r}] = {v!r} must be >= 0")
     return w
 
@@ -59,7 +66,8 @@ class GraspStepper:
                  n_contact: int, weights=None, fc_cfg=None, mala_cfg=None, device="cuda", seed=1,
                  penetration_only: bool = True, energy_type: str = "graspqp", optimizer: str = "mala_star",
                  tdg_directions=None, point_grid: int = 0, split_self_pen: bool = True, n_surface_points: int = 512,
-                 surface_samples=None, table_z: float = 0.0, scene=None, scene_margin: float = 0.0):
+                 surface_samples=None, table_z: float = 0.0, scene=None, scene_margin: float = 0.0,
+                 approach_distance: float = 0.10, approach_stations: int = 4, approach_margin=None):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -71,7 +79,11 @@ class GraspStepper:
         with ``n_surface_points`` (as HandModel does) unless ``surface_samples`` = (points (Ns,3) in the link frames, link ids
         (Ns)) is given; ``table_z`` is the height of the table plane.
         weights["E_scene"] > 0 selects the scene mode (module docstring) and needs ``scene``, an ``ops.SceneSDF``; the term is
-        sum over the same surface samples of max(scene_margin - phi, 0).  With weight 0 a scene changes nothing."""
+        sum over the same surface samples of max(scene_margin - phi, 0).  With weight 0 a scene changes nothing.
+        weights["E_approach"] > 0 selects the approach mode (module docstring) and needs ``scene`` too, with or without a weight
+        on "E_scene": the mean over the stations d_k = approach_distance k / approach_stations (k = 1..approach_stations <= 32)
+        of the same hinge sum with the whole hand moved back by d_k along the spec's grasp_axis; ``approach_margin`` = None
+        takes ``scene_margin``.  With weight 0 the three arguments change nothing."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -93,7 +105,19 @@ class GraspStepper:
             raise ValueError('GraspStepper: weights["E_scene"] > 0 needs scene=ops.SceneSDF(...)')
         if not float(scene_margin) >= 0.0:
             raise ValueError(f"GraspStepper: scene_margin = {scene_margin!r} must be >= 0")
-        self.term_names = TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
+        self.approach_mode = self.w["E_approach"] > 0
+        if self.approach_mode:
+            if not isinstance(scene, ops.SceneSDF):
+                raise ValueError('GraspStepper: weights["E_approach"] > 0 needs scene=ops.SceneSDF(...)')
+            approach_margin = scene_margin if approach_margin is None else approach_margin
+            if not float(approach_margin) >= 0.0:
+                raise ValueError(f"GraspStepper: approach_margin = {approach_margin!r} must be >= 0")
+            if not 0.0 < float(approach_distance) < float("inf"):
+                raise ValueError(f"GraspStepper: approach_distance = {approach_distance!r} must be finite and > 0")
+            if int(approach_stations) != approach_stations or not 1 <= int(approach_stations) <= 32:
+                raise ValueError(f"GraspStepper: approach_stations = {approach_stations!r} must be an integer in 1..32")
+        self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
+                           + (APPROACH_TERMS if self.approach_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -219,18 +243,25 @@ class GraspStepper:
             ad.e_fc = self.terms_new[1].data_ptr()
             self._alt_desc = ad
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
-        self._fuse_loop = not (self.tabletop or self.scene_mode)
+        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode)
         self.samples, self.g_R = None, None
-        self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode else (None, 0.0)
-        if self.tabletop or self.scene_mode:  # one set of surface samples for both modes
+        self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode or self.approach_mode else (None, 0.0)
+        if self.tabletop or self.scene_mode or self.approach_mode:  # one set of surface samples for all modes
             if surface_samples is None:
                 from .utils import meshes as mesh_utils
 
                 surface_samples = mesh_utils.hand_surface_samples(hand.spec, int(n_surface_points))
             self.samples = ops.SurfaceSamples(hand, surface_samples[0], surface_samples[1], device=self.dev)
         if self.scene_mode:
-            self._i_scene = nT - 1
+            self._i_scene = nT - 2 if self.approach_mode else nT - 1
             scene.check(B, L, self.samples.Ns)
+        if self.approach_mode:
+            self._i_approach = nT - 1
+            self.approach_distance, self.approach_stations = float(approach_distance), int(approach_stations)
+            self.approach_margin = float(approach_margin)
+            self._approach_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
+            ops.approach_check(scene, B, L, self.samples.Ns, self.approach_distance, self.approach_stations,
+                               hand.spec.grasp_axis)
         if self.tabletop:
             self.g_R = f(B, 9)
             self.table_z = float(table_z)
@@ -255,8 +286,8 @@ class GraspStepper:
                                                                   int(m["annealing_period"]))
         ac.energy, ac.pose, ac.idx, ac.grad = (t.data_ptr() for t in (self.energy, self.hand_pose, self.contact_idx, self.grad))
         ac.accept, ac.temperature = self.accept.data_ptr(), self.temperature.data_ptr()
-        # the fused accept tail merges the five terms of the FK backward's own total; tabletop and scene mode (six to eight terms)
-        # never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
+        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene and approach mode (six to nine
+        # terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
         assert self._fuse_loop == (nT == len(TERM_NAMES))
         ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
@@ -352,6 +383,15 @@ class GraspStepper:
                 ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D, f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), None,
                 float(self.w["E_scene"]), f32(self.terms_new[self._i_scene]), 1, f32(self.wrench), f32(self.gRt), st)
 
+    def _eval_approach(self, pose, st):
+        """E_approach -> terms_new[-1]; the gradient of w_approach E_approach is added to the link wrenches and gRt that the
+        FK backward reads."""
+        f32, sm = _C.f32, self.samples
+        _C.call("gq_approach_terms", ctypes.byref(self.scene.grid), self.approach_margin, self.approach_distance,
+                self.approach_stations, f32(sm.points), _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D,
+                f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), ctypes.cast(self._approach_axis, ctypes.c_void_p), None,
+                float(self.w["E_approach"]), f32(self.terms_new[self._i_approach]), 1, f32(self.wrench), f32(self.gRt), st)
+
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
         f32 = _C.f32
@@ -399,6 +439,8 @@ class GraspStepper:
             self._eval_tabletop(pose, st)
         if self.scene_mode:
             self._eval_scene(pose, st)
+        if self.approach_mode:
+            self._eval_approach(pose, st)
         self._eval_tail(pose, idx, st, loop)
         if self.tabletop:  # the FK backward's total holds the five terms
             _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
@@ -406,6 +448,9 @@ class GraspStepper:
         if self.scene_mode:
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_scene]), float(self.w["E_scene"]),
                     ctypes.c_int64(self.B), st)
+        if self.approach_mode:  # the generic total += w e
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_approach]),
+                    float(self.w["E_approach"]), ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):
         """Energy terms, total and d total / d pose at an arbitrary (pose, idx); returns clones."""

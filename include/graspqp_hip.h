@@ -547,6 +547,38 @@ int gq_scene_query(const gqSceneGrid* grid, const float* points /* (N,3) world, 
 /* total[row] += w_scene * e_scene[row]: the row total that gq_fk_backward writes holds the five terms of its own tail. */
 int gq_scene_total(float* total /* (B) in/out */, const float* e_scene, float w_scene, int64_t batch, void* stream);
 
+/* ---- approach clearance of the stepper: E_approach, the scene grid along the hand's approach corridor ---------------
+ * E_scene asks that the hand is free of the surroundings at the grasp pose; this term asks the same of the way there.
+ * With a = grasp_axis (hand frame, used as given), D = distance > 0 in metres, K = n_stations in 1..32 and
+ * d_k = D k / K for k = 1..K, station k is the whole hand, joints unchanged, moved back by d_k against its approach
+ * direction (-d_k R a in the world).  Per hand surface sample with x_h = T_link p:
+ *   y_k = x_h - d_k a (hand frame)      x_w^k = R y_k + t
+ *   E_approach = (1/K) sum_k sum_s max(margin - phi(x_w^k), 0)
+ * phi is the trilinear interpolant of the gqSceneGrid under exactly the contract of "scene obstacles" above: a station
+ * point outside the volume is free space, a non-finite one makes the row's energy and gradient NaN and touches no memory.
+ * d = 0 is not a station (that is E_scene).  e_approach is written UNWEIGHTED.  The gradient carries the upstream factor
+ * of the row: up_approach[row] if the pointer is given, else w_approach.  With g_w = -up (1/K) grad phi(x_w^k) and
+ * g_h = R' g_w for every (s, k) with phi < margin:
+ *   link_wrench (B,L,6): f_l = sum g_h, m_l = sum x_h x g_h (x_h unshifted: the joints move x_h, not the offset)
+ *   gRt (B,12) = [gsum(3), K9(9)]: gsum = -sum g_h, K9 = sum g_h (x) y_k (the shifted point), row-major; there is no g_R.
+ * accumulate, links without samples, n_samples not a multiple of 64 and link ids outside the hand are as in
+ * gq_scene_terms.  1/K is one 1.0f / K, multiplied into the finished row energy, and into `up` before `up` scales the
+ * finished sums.  Fixed-order sums (stations ascending inside a sample, then the orders of gq_scene_terms), no atomics:
+ * bitwise reproducible run to run.  The row total takes gq_scene_total(total, e_approach, w_approach, B).
+ * gq_approach_check is the argument check of the launch on its own (host only, no GPU): everything gq_scene_check refuses,
+ * a distance that is not finite or <= 0, n_stations outside 1..32, a NULL, non-finite or all-zero grasp_axis; its message
+ * contains "approach" and names the argument.                                                                         */
+int gq_approach_check(const gqSceneGrid* grid, int64_t batch, int n_links, int64_t n_samples, float distance, int n_stations,
+                      const float* grasp_axis /* 3 floats, host */);
+int gq_approach_terms(const gqSceneGrid* grid, float margin, float distance, int n_stations,
+                      const float* samples /* (Ns,3) link frame, device */, const int32_t* sample_link /* (Ns) */,
+                      int64_t n_samples, int n_links, const float* hand_pose, int pose_dim, const float* Rg /* (B,9) */,
+                      const float* link_T /* (B,L,12) */, int64_t batch, const float* grasp_axis /* 3 floats, host */,
+                      const float* up_approach /* (B) or NULL */, float w_approach,
+                      float* e_approach /* (B) or NULL, unweighted */,
+                      int accumulate /* 1: add to the two gradient buffers, 0: overwrite */,
+                      float* link_wrench /* (B,L,6) or NULL */, float* gRt /* (B,12) or NULL */, void* stream);
+
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
  * Per object: samples_per_object points on its convex hull (area-weighted), pushed out by `inflate` (0.01 in the
  * reference) along the face normal; farthest-point sampling of batch_each of them (start = sample 0); per row the look-at

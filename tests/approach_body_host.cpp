@@ -1,0 +1,50 @@
+// The device body of the approach term (graspqp_amd/csrc/approach_dev.h, on top of scene_dev.h) compiled for the HOST:
+// tests/test_approach_body_host.py builds this program with the host compiler and sanitizers and compares its float32 results
+// with the fp64 oracle.  No GPU involved.
+// usage: approach_body_host in.bin out.bin
+//   in.bin : int32 nx ny nz, float32 origin[3] voxel, float32 R[9] t[3] a[3] distance margin, int32 K N,
+//            float32 values[nx ny nz], float32 x_h[N][3]
+//   out.bin: per sample float32 e, G[3], K9[9]   (sums over the sample's stations, upstream 1, without 1/K)
+#include <math.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <vector>
+using std::min;
+#define GQ_SCENE_HOST_BUILD
+#define __device__
+#define __forceinline__ inline
+#define GQ_INF_F __builtin_inff()
+#include "../include/graspqp_hip.h"
+struct gq3 {
+  float x, y, z;
+};
+static inline gq3 gq_mk(float x, float y, float z) { return gq3{x, y, z}; }
+#include "../graspqp_amd/csrc/approach_dev.h"
+
+int main(int argc, char** argv) {
+  if (argc != 3) return 2;
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 3;
+  int d[3], kn[2];
+  float oh[4], c[17];
+  if (fread(d, 4, 3, f) != 3 || fread(oh, 4, 4, f) != 4 || fread(c, 4, 17, f) != 17 || fread(kn, 4, 2, f) != 2) return 4;
+  const int K = kn[0], N = kn[1];
+  std::vector<float> v((size_t)d[0] * d[1] * d[2]), p((size_t)N * 3);
+  if (fread(v.data(), 4, v.size(), f) != v.size() || fread(p.data(), 4, p.size(), f) != p.size()) return 5;
+  fclose(f);
+  gqSceneGrid g{v.data(), d[0], d[1], d[2], {oh[0], oh[1], oh[2]}, oh[3]};
+  const gq3 r1 = gq_mk(c[0], c[1], c[2]), r2 = gq_mk(c[3], c[4], c[5]), r3 = gq_mk(c[6], c[7], c[8]);
+  const gq3 t = gq_mk(c[9], c[10], c[11]), a = gq_mk(c[12], c[13], c[14]);
+  FILE* o = fopen(argv[2], "wb");
+  if (!o) return 6;
+  for (int i = 0; i < N; ++i) {
+    float out[13] = {0};
+    gq3 G = gq_mk(0, 0, 0);
+    gq_approach_stations(g, gq_mk(p[3 * i], p[3 * i + 1], p[3 * i + 2]), a, r1, r2, r3, t, c[15], K, c[16], out[0], G, out + 4);
+    out[1] = G.x, out[2] = G.y, out[3] = G.z;
+    fwrite(out, 4, 13, o);
+  }
+  fclose(o);
+  return 0;
+}

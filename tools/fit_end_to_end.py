@@ -15,6 +15,8 @@ usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_it
        E_wall / E_prior on the stepper's surface samples, st.samples)
        [--w_scene 0] [--scene_margin 0] [--scene box]   (scene obstacles: the ``box`` preset is an open-topped bin of five slabs
        around the first object, voxelised on an 80^3 grid of 5 mm by ops.SceneSDF.from_meshes; the class surface carries E_scene)
+       [--w_approach 0] [--approach_distance 0.10] [--approach_stations 4]   (approach corridor against the same preset; the class
+       surface carries E_approach through HandModel.set_approach)
 """
 import argparse
 import json
@@ -42,6 +44,9 @@ ap.add_argument("--w_prior", type=float, default=0.0)
 ap.add_argument("--w_scene", type=float, default=0.0)
 ap.add_argument("--scene_margin", type=float, default=0.0)
 ap.add_argument("--scene", choices=("box",), default="box")
+ap.add_argument("--w_approach", type=float, default=0.0)
+ap.add_argument("--approach_distance", type=float, default=0.10)
+ap.add_argument("--approach_stations", type=int, default=4)
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "fit_end_to_end.json"))
 args = ap.parse_args()
 
@@ -62,6 +67,9 @@ if TABLETOP:
 SCENE = args.w_scene > 0
 if SCENE:
     W["E_scene"] = args.w_scene
+APPROACH = args.w_approach > 0
+if APPROACH:
+    W["E_approach"] = args.w_approach
 spec = get_hand_spec(args.hand)
 n_obj, be, n = args.n_objects, args.batch_size, args.n_contact
 B = n_obj * be
@@ -73,12 +81,15 @@ om.initialize_from_meshes(fvs, codes, surface_points_list=sps)
 hand = ops.HandHandle(spec)
 weights = {"E_prior": args.w_prior, "E_wall": args.w_wall} if TABLETOP else {}
 scene = None
-if SCENE:  # the ``box`` preset: an open-topped bin around the first object
+if SCENE or APPROACH:  # the ``box`` preset: an open-topped bin around the first object
     center = 0.5 * (fvs[0].reshape(-1, 3).min(0) + fvs[0].reshape(-1, 3).max(0))
     scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), [float(c) - 0.5 * 0.005 * 79 for c in center], (80, 80, 80), 0.005)
-    weights["E_scene"] = args.w_scene
+    if SCENE:
+        weights["E_scene"] = args.w_scene
+    if APPROACH:
+        weights["E_approach"] = args.w_approach
 st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1, weights=weights or None, scene=scene,
-                  scene_margin=args.scene_margin)
+                  scene_margin=args.scene_margin, approach_distance=args.approach_distance, approach_stations=args.approach_stations)
 st.set_hulls(om.convex_hulls())
 st.initialize()  # on-device initialize_convex_hull + the first evaluation
 e0, t0_terms = st.energy.clone(), st.terms.clone()
@@ -104,13 +115,16 @@ assert torch.isfinite(st.energy).all() and torch.isfinite(st.hand_pose).all()
 hm = HandModel(spec, "cuda")
 hp = st.hand_pose.clone().requires_grad_()
 hm.set_parameters(hp, st.contact_idx.clone())
-if TABLETOP or SCENE:
+if TABLETOP or SCENE or APPROACH:
     hm.set_surface_points(st.samples.points.cpu().numpy(), st.samples.link.cpu().numpy())
-if SCENE:
+if SCENE or APPROACH:
     hm.set_scene(scene, args.scene_margin)
+if APPROACH:
+    hm.set_approach(args.approach_distance, args.approach_stations)
 metric = GraspSpanMetricFactory.create(GraspSpanMetricFactory.MetricType.GRASPQP, {"friction": 0.2, "max_limit": 20.0, "n_cone_vecs": 4})
 losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1,
-                          energy_names=(["E_prior", "E_wall"] if TABLETOP else []) + (["E_scene"] if SCENE else []))
+                          energy_names=(["E_prior", "E_wall"] if TABLETOP else []) + (["E_scene"] if SCENE else []) +
+                          (["E_approach"] if APPROACH else []))
 total_cls = sum(W[k] * losses[k] for k in W)
 rel_cls = ((total_cls.detach() - st.energy).abs() / st.energy.abs().clamp_min(1e-6))
 

@@ -3,12 +3,13 @@ every `reset_epochs`) on the bench scene, at one or several batch sizes: energie
 counters must not show inline-ranked overflow growing, the stop iteration is histogrammed.  Development aid, not a test.
 
 usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--w_scene W] [--scene_margin M]
-       [--scene box] [--out file.json]
+       [--scene box] [--w_approach W] [--approach_distance D] [--approach_stations K] [--out file.json]
        (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
        schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
        hand surface samples left below the plane; --w_scene > 0 runs it in scene mode against the ``box`` preset (an open-topped
        bin of five slabs around the first object, 80^3 grid of 5 mm, ops.SceneSDF.from_meshes) and reports the mean E_scene at
-       the start and at the end; --out writes the records as JSON.
+       the start and at the end; --w_approach > 0 adds the approach corridor against the same preset (K stations over D metres
+       along the hand's grasp axis) and reports the mean E_approach the same way; --out writes the records as JSON.
 """
 import argparse
 import json
@@ -35,6 +36,9 @@ ap.add_argument("--table_z", type=float, default=0.0)
 ap.add_argument("--w_scene", type=float, default=0.0)
 ap.add_argument("--scene_margin", type=float, default=0.0)
 ap.add_argument("--scene", choices=("box",), default="box")
+ap.add_argument("--w_approach", type=float, default=0.0)
+ap.add_argument("--approach_distance", type=float, default=0.10)
+ap.add_argument("--approach_stations", type=int, default=4)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
@@ -43,6 +47,9 @@ SCENE = args.w_scene > 0
 weights = {"E_wall": args.w_wall, "E_prior": args.w_prior} if TABLETOP else {}
 if SCENE:
     weights["E_scene"] = args.w_scene
+APPROACH = args.w_approach > 0
+if APPROACH:
+    weights["E_approach"] = args.w_approach
 records = []
 
 
@@ -64,16 +71,19 @@ for n_obj in args.n_objects:
     om = ObjectModel(batch_size_each=256, num_samples=2500)
     om.initialize_from_meshes(fvs, surface_points_list=sps)
     scene = None
-    if SCENE:
+    if SCENE or APPROACH:
         center = 0.5 * (fvs[0].reshape(-1, 3).min(0) + fvs[0].reshape(-1, 3).max(0))
         scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), [float(c) - 0.5 * 0.005 * 79 for c in center], (80, 80, 80), 0.005)
     st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3, weights=weights or None,
-                      table_z=args.table_z, scene=scene, scene_margin=args.scene_margin)
+                      table_z=args.table_z, scene=scene, scene_margin=args.scene_margin,
+                      approach_distance=args.approach_distance, approach_stations=args.approach_stations)
     st.set_hulls(om.convex_hulls())
     st.initialize()
     e0 = st.energy.clone()
     wall0 = float(st.terms[6].mean()) if TABLETOP else None
-    scene0 = float(st.terms[-1].mean()) if SCENE else None
+    i_scene = st.term_names.index("E_scene") if SCENE else None
+    scene0 = float(st.terms[i_scene].mean()) if SCENE else None
+    approach0 = float(st.terms[-1].mean()) if APPROACH else None
     st.capture(iters=8)
     hist = {}
     acc = []
@@ -112,9 +122,16 @@ for n_obj in args.n_objects:
               f"of {st.B} rows", flush=True)
     if SCENE:
         rec.update({"w_scene": args.w_scene, "scene_margin": args.scene_margin, "scene": args.scene, "E_scene_mean_initial": scene0,
-                    "E_scene_mean_final": float(st.terms[-1].mean()), "rows_with_E_scene_final": int((st.terms[-1] > 0).sum())})
+                    "E_scene_mean_final": float(st.terms[i_scene].mean()),
+                    "rows_with_E_scene_final": int((st.terms[i_scene] > 0).sum())})
         print(f"  scene: mean E_scene {scene0:.4f} -> {rec['E_scene_mean_final']:.6f}, {rec['rows_with_E_scene_final']} of {st.B} rows "
               "still touch an obstacle", flush=True)
+    if APPROACH:
+        rec.update({"w_approach": args.w_approach, "approach_distance": args.approach_distance,
+                    "approach_stations": args.approach_stations, "E_approach_mean_initial": approach0,
+                    "E_approach_mean_final": float(st.terms[-1].mean()), "rows_with_E_approach_final": int((st.terms[-1] > 0).sum())})
+        print(f"  approach: mean E_approach {approach0:.4f} -> {rec['E_approach_mean_final']:.6f}, {rec['rows_with_E_approach_final']} "
+              f"of {st.B} rows still meet an obstacle on the way in", flush=True)
     records.append(rec)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
