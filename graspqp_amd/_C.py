@@ -134,6 +134,12 @@ class SceneGrid(ctypes.Structure):
                 ("origin", ctypes.c_float * 3), ("voxel", ctypes.c_float)]
 
 
+class ClutterGrids(ctypes.Structure):
+    """gqClutterGrids: a stack of n_grids scene grids that share shape, origin and voxel (one grid per object)."""
+    _fields_ = [("values", ctypes.c_void_p), ("n_grids", ctypes.c_int), ("nx", ctypes.c_int), ("ny", ctypes.c_int),
+                ("nz", ctypes.c_int), ("origin", ctypes.c_float * 3), ("voxel", ctypes.c_float)]
+
+
 _lib = None
 _protos = None
 

@@ -212,9 +212,11 @@ class HandModel:
 
     def set_scene(self, scene, margin=0.0):
         """The surroundings as an ``ops.SceneSDF`` (None removes it): calculate_energy(..., energy_names=[..., "E_scene"]) is then
-        the sum over the surface samples of relu(margin - phi); ``margin`` >= 0 is a clearance in metres."""
-        if scene is not None and not isinstance(scene, ops.SceneSDF):
-            raise ValueError("HandModel.set_scene: scene must be an ops.SceneSDF or None")
+        the sum over the surface samples of relu(margin - phi); ``margin`` >= 0 is a clearance in metres.  With an
+        ``ops.SceneSDFSet`` (one grid per object) the rows are object-major and the batch must be divisible by ``n_grids``: row b
+        reads grid b // (B / n_grids)."""
+        if scene is not None and not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
+            raise ValueError("HandModel.set_scene: scene must be an ops.SceneSDF, an ops.SceneSDFSet or None")
         if not float(margin) >= 0.0:
             raise ValueError(f"HandModel.set_scene: margin = {margin!r} must be >= 0")
         self.scene, self.scene_margin = scene, float(margin)

@@ -18,7 +18,7 @@ asks for the registered route (tests compare the two bit for bit).
 import ctypes
 import os
 import weakref
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1315,7 +1315,104 @@ class SceneSDF:
         return cls._filled(lambda k, p: sdf_cloud(p, sets[k], p.shape[0])[:2], len(sets), origin, shape, voxel, device)
 
 
+def _clutter_grids(values, origin, voxel) -> "_C.ClutterGrids":
+    g = _C.ClutterGrids()
+    g.values = values.data_ptr()
+    g.n_grids, g.nx, g.ny, g.nz = (int(s) for s in values.shape)
+    g.origin = (ctypes.c_float * 3)(*(float(o) for o in origin))
+    g.voxel = float(voxel)
+    return g
+
+
+class SceneSDFSet:
+    """A stack of scene grids, one per object (include/graspqp_hip.h, "clutter scenes"): ``values`` (G,nx,ny,nz) float32 on the
+    device, grid g in the frame of object g; ``origin`` and ``voxel`` are shared by all grids.  A CUDA float32 contiguous
+    tensor is used without a copy, so ``scene_compose`` or an in-place write moves the obstacles, also under a captured graph.
+    Rows are object-major: of B rows, row b reads grid b // (B / G)."""
+
+    def __init__(self, values, origin, voxel, device="cuda"):
+        v = values if torch.is_tensor(values) else torch.as_tensor(np.asarray(values, dtype=np.float32))
+        if v.dim() != 4:
+            raise ValueError(f"SceneSDFSet: values must be (G,nx,ny,nz), got {tuple(v.shape)}")
+        origin = [float(o) for o in (origin.detach().cpu().tolist() if torch.is_tensor(origin) else origin)]
+        if len(origin) != 3:
+            raise ValueError(f"SceneSDFSet: origin must have 3 entries, got {len(origin)}")
+        if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
+            v = v.detach().to(device, torch.float32).contiguous()
+        self.values, self.origin, self.voxel = v, tuple(origin), float(voxel)
+        self.n_grids, self.shape = int(v.shape[0]), tuple(int(s) for s in v.shape[1:])
+        self.grid_set = _clutter_grids(v, self.origin, self.voxel)
+        self.check(self.n_grids, 1)
+
+    @classmethod
+    def empty(cls, n_grids, origin, shape, voxel, device="cuda"):
+        """An uninitialised stack for ``scene_compose`` to fill."""
+        return cls(torch.empty((int(n_grids),) + tuple(int(n) for n in shape), dtype=torch.float32, device=device), origin, voxel, device)
+
+    def check(self, batch, rows_per_grid, n_links=1, n_samples=1):
+        """gq_clutter_check (host only) of the stack and of a launch's shapes; raises ValueError with the library's message."""
+        try:
+            _C.call("gq_clutter_check", ctypes.byref(self.grid_set), ctypes.c_int64(int(batch)), int(rows_per_grid), int(n_links),
+                    ctypes.c_int64(int(n_samples)))
+        except RuntimeError as e:
+            raise ValueError(f"SceneSDFSet: {e}") from None
+
+    def rows_per_grid(self, batch, what="batch"):
+        if batch % self.n_grids:
+            raise ValueError(f"SceneSDFSet: {what} = {batch} is not divisible by n_grids = {self.n_grids}")
+        return batch // self.n_grids
+
+    def scene(self, g) -> "SceneSDF":
+        """Grid ``g`` as an ``ops.SceneSDF`` that shares the stack's memory."""
+        return SceneSDF(self.values[int(g)], self.origin, self.voxel)
+
+
+def scene_compose(out: SceneSDFSet, target_T, parts, part_T, exclude=None, base=None, far=1.0):
+    """Fills ``out`` in place on the device (gq_clutter_compose) and returns it: node (g,i,j,k) = min(``far``, ``base`` at the
+    node's world position, every part but ``exclude[g]`` at its part-frame position), the node being placed in the world by
+    ``target_T[g]``.  ``parts``: a sequence of ``SceneSDF``, each in its own part frame; ``target_T`` (G,3,4) or (G,12) and
+    ``part_T`` (n_parts,3,4) or (n_parts,12): world_from_frame [R|t], float32 CUDA (contiguous float32 CUDA tensors are read
+    in place at launch, so the call can be captured in a graph and replayed after a pose update); ``exclude`` (G) int32 or
+    None; ``base``: a ``SceneSDF`` in the world frame or None.  No allocation, no synchronisation."""
+    parts = list(parts)
+    dev = out.values.device
+
+    def poses(T, n, name):
+        if T is None:
+            T = torch.zeros(0, 12)
+        T = T if torch.is_tensor(T) else torch.as_tensor(np.asarray(T, dtype=np.float32))
+        T = _c(T.to(dev)).reshape(-1, 12) if T.numel() else T.to(dev, torch.float32).reshape(0, 12)
+        if T.shape[0] != n:
+            raise ValueError(f"scene_compose: {name} must hold {n} poses of 12 floats, got {tuple(T.shape)}")
+        return T
+
+    tT, pT = poses(target_T, out.n_grids, "target_T"), poses(part_T, len(parts), "part_T")
+    ex = None
+    if exclude is not None:
+        ex = _c(exclude.to(dev), torch.int32)
+        if ex.shape != (out.n_grids,):
+            raise ValueError(f"scene_compose: exclude must be ({out.n_grids},), got {tuple(ex.shape)}")
+    arr = (_C.SceneGrid * max(len(parts), 1))(*(p.grid for p in parts))
+    try:
+        _C.call("gq_clutter_compose_check", ctypes.byref(out.grid_set), ctypes.cast(arr, ctypes.c_void_p), len(parts),
+                ctypes.byref(base.grid) if base is not None else None, float(far))
+    except RuntimeError as e:
+        raise ValueError(f"scene_compose: {e}") from None
+    _Eager.scene_compose(out.values, list(out.origin), out.voxel, tT, [p.values for p in parts],
+                         [float(o) for p in parts for o in p.origin], [p.voxel for p in parts], pT, ex,
+                         None if base is None else base.values, [0.0, 0.0, 0.0] if base is None else list(base.origin),
+                         0.0 if base is None else base.voxel, float(far))
+    return out
+
+
 def _scene_call(grid, margin, hp, points, link, n_links, Rg, LT, up_scene, w_scene, e_scene, accumulate, wrench, gRt, st=None):
+    if isinstance(grid, _C.ClutterGrids):  # a stack: row b reads grid b // (B / G)
+        B = hp.shape[0]
+        _C.call("gq_clutter_terms", ctypes.byref(grid), B // max(grid.n_grids, 1), float(margin), _C.f32(points), _C.i32(link),
+                ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT), ctypes.c_int64(B),
+                _C.f32(up_scene), float(w_scene), _C.f32(e_scene), int(accumulate), _C.f32(wrench), _C.f32(gRt),
+                _C.stream_ptr() if st is None else st)
+        return
     _C.call("gq_scene_terms", ctypes.byref(grid), float(margin), _C.f32(points), _C.i32(link), ctypes.c_int64(points.shape[0]),
             int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT), ctypes.c_int64(hp.shape[0]), _C.f32(up_scene),
             float(w_scene), _C.f32(e_scene), int(accumulate), _C.f32(wrench), _C.f32(gRt), _C.stream_ptr() if st is None else st)
@@ -1361,6 +1458,11 @@ def scene_distance(points, scene: SceneSDF):
         raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
     if points.dim() < 1 or points.shape[-1] != 3:
         raise ValueError(f"scene_distance: points must be (...,3), got {tuple(points.shape)}")
+    if isinstance(scene, SceneSDFSet):  # points (B,...,3), B divisible by G: row b reads grid b // (B / G)
+        if points.dim() < 2:
+            raise ValueError(f"scene_distance: with a SceneSDFSet points must be (B,...,3), got {tuple(points.shape)}")
+        scene.rows_per_grid(points.shape[0], "the points' leading dimension")
+        return _Eager.scene_distance_set(points, scene.values, list(scene.origin), scene.voxel)[0]
     return _Eager.scene_distance(points, scene.values, list(scene.origin), scene.voxel)[0]
 
 
@@ -1405,8 +1507,9 @@ class _SceneTerms(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hand_pose, hand, samples, idx, Rg, LT, ws, scene, margin):
         hp = _c(hand_pose.detach())
-        e = _Eager.scene_terms(hp, samples.points, samples.link, hand.L, Rg, LT, scene.values, list(scene.origin), scene.voxel,
-                               margin)
+        ctx.is_set = isinstance(scene, SceneSDFSet)
+        fwd = _Eager.scene_terms_set if ctx.is_set else _Eager.scene_terms
+        e = fwd(hp, samples.points, samples.link, hand.L, Rg, LT, scene.values, list(scene.origin), scene.voxel, margin)
         ctx.save_for_backward(hp, idx, Rg, LT, ws, samples.points, samples.link, scene.values)
         ctx.hand, ctx.origin, ctx.voxel, ctx.margin = hand, list(scene.origin), scene.voxel, margin
         return e
@@ -1415,8 +1518,8 @@ class _SceneTerms(torch.autograd.Function):
     def backward(ctx, g_scene):
         hp, idx, Rg, LT, ws, points, link, values = ctx.saved_tensors
         hand = ctx.hand
-        wrench, gRt = _Eager.scene_terms_backward(hp, points, link, hand.L, Rg, LT, values, ctx.origin, ctx.voxel, ctx.margin,
-                                                  g_scene)
+        bwd = _Eager.scene_terms_set_backward if ctx.is_set else _Eager.scene_terms_backward
+        wrench, gRt = bwd(hp, points, link, hand.L, Rg, LT, values, ctx.origin, ctx.voxel, ctx.margin, g_scene)
         gp = _fk_backward(hand, hp, idx, Rg, LT, ws, None, None, None, wrench, gRt, None)
         return gp, None, None, None, None, None, None, None, None
 
@@ -1431,6 +1534,8 @@ def scene_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, L
         raise ValueError(f"scene_terms: the samples refer to {samples.n_links} links, the hand has {hand.L}")
     if not float(margin) >= 0.0:
         raise ValueError(f"scene_terms: margin = {margin!r} must be >= 0")
+    if isinstance(scene, SceneSDFSet):
+        scene.check(hand_pose.shape[0], scene.rows_per_grid(hand_pose.shape[0]), hand.L, samples.Ns)
     return _SceneTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws, scene, float(margin))
 
 
@@ -1441,6 +1546,9 @@ def approach_check(scene: SceneSDF, batch, n_links, n_samples, distance, station
     """gq_approach_check (host only) of the grid, a launch's shapes and the corridor; raises ValueError with the library's
     message."""
     ax = (ctypes.c_float * 3)(*(float(a) for a in grasp_axis))
+    if isinstance(scene, SceneSDFSet):  # the stack's own check, then the corridor's on one of its grids
+        scene.check(batch, scene.rows_per_grid(int(batch)), n_links, n_samples)
+        scene = scene.scene(0)
     try:
         _C.call("gq_approach_check", ctypes.byref(scene.grid), ctypes.c_int64(int(batch)), int(n_links),
                 ctypes.c_int64(int(n_samples)), float(distance), int(stations), ctypes.cast(ax, ctypes.c_void_p))
@@ -1451,6 +1559,14 @@ def approach_check(scene: SceneSDF, batch, n_links, n_samples, distance, station
 def _approach_call(grid, margin, distance, stations, hp, points, link, n_links, Rg, LT, axis, up_approach, w_approach, e_approach,
                    accumulate, wrench, gRt, st=None):
     ax = (ctypes.c_float * 3)(*(float(a) for a in axis))
+    if isinstance(grid, _C.ClutterGrids):  # a stack: row b reads grid b // (B / G)
+        B = hp.shape[0]
+        _C.call("gq_clutter_corridor_terms", ctypes.byref(grid), B // max(grid.n_grids, 1), float(margin), float(distance),
+                int(stations), _C.f32(points), _C.i32(link), ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp), hp.shape[1],
+                _C.f32(Rg), _C.f32(LT), ctypes.c_int64(B), ctypes.cast(ax, ctypes.c_void_p), _C.f32(up_approach),
+                float(w_approach), _C.f32(e_approach), int(accumulate), _C.f32(wrench), _C.f32(gRt),
+                _C.stream_ptr() if st is None else st)
+        return
     _C.call("gq_approach_terms", ctypes.byref(grid), float(margin), float(distance), int(stations), _C.f32(points), _C.i32(link),
             ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT),
             ctypes.c_int64(hp.shape[0]), ctypes.cast(ax, ctypes.c_void_p), _C.f32(up_approach), float(w_approach),
@@ -1500,8 +1616,10 @@ class _ApproachTerms(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hand_pose, hand, samples, idx, Rg, LT, ws, scene, axis, distance, stations, margin):
         hp = _c(hand_pose.detach())
-        e = _Eager.approach_terms(hp, samples.points, samples.link, hand.L, Rg, LT, scene.values, list(scene.origin), scene.voxel,
-                                  axis, distance, stations, margin)
+        ctx.is_set = isinstance(scene, SceneSDFSet)
+        fwd = _Eager.approach_terms_set if ctx.is_set else _Eager.approach_terms
+        e = fwd(hp, samples.points, samples.link, hand.L, Rg, LT, scene.values, list(scene.origin), scene.voxel, axis, distance,
+                stations, margin)
         ctx.save_for_backward(hp, idx, Rg, LT, ws, samples.points, samples.link, scene.values)
         ctx.hand, ctx.origin, ctx.voxel = hand, list(scene.origin), scene.voxel
         ctx.corridor = (axis, distance, stations, margin)
@@ -1511,8 +1629,8 @@ class _ApproachTerms(torch.autograd.Function):
     def backward(ctx, g_approach):
         hp, idx, Rg, LT, ws, points, link, values = ctx.saved_tensors
         hand = ctx.hand
-        wrench, gRt = _Eager.approach_terms_backward(hp, points, link, hand.L, Rg, LT, values, ctx.origin, ctx.voxel,
-                                                     *ctx.corridor, g_approach)
+        bwd = _Eager.approach_terms_set_backward if ctx.is_set else _Eager.approach_terms_backward
+        wrench, gRt = bwd(hp, points, link, hand.L, Rg, LT, values, ctx.origin, ctx.voxel, *ctx.corridor, g_approach)
         gp = _fk_backward(hand, hp, idx, Rg, LT, ws, None, None, None, wrench, gRt, None)
         return (gp,) + (None,) * 11
 
@@ -1533,6 +1651,123 @@ def approach_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg
     approach_check(scene, hand_pose.shape[0], hand.L, samples.Ns, distance, stations, axis)
     return _ApproachTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws, scene, axis,
                                 float(distance), int(stations), float(margin))
+
+
+# ----------------------------------------------------------------------------------------------------------
+# clutter scenes: the same routes on a stack of grids, one per object (csrc/clutter.hip); the stack crosses the dispatcher as
+# (values (G,nx,ny,nz), origin, voxel), and row b reads grid b // (B / G)
+# ----------------------------------------------------------------------------------------------------------
+@_custom_op("graspqp_amd::scene_distance_set", mutates_args=(), device_types="cuda")
+def _scene_distance_set_op(points: Tensor, values: Tensor, origin: List[float], voxel: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """scene_distance with points (B,...,3) and a stack of G grids, B divisible by G."""
+    pts, v = _c(points), _c(values)
+    flat = pts.reshape(-1, 3)
+    N, dev = flat.shape[0], pts.device
+    phi, grad, inside = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
+    grids = _clutter_grids(v, origin, voxel)
+    _C.call("gq_clutter_query", ctypes.byref(grids), _C.f32(flat), ctypes.c_int64(N), ctypes.c_int64(N // max(grids.n_grids, 1)),
+            _C.f32(phi), _C.f32(grad), _C.u8(inside), _C.stream_ptr())
+    return phi.reshape(pts.shape[:-1]), grad.reshape(pts.shape), inside.reshape(pts.shape[:-1])
+
+
+@_scene_distance_set_op.register_fake
+def _(points, values, origin, voxel):
+    return (points.new_empty(points.shape[:-1]), points.new_empty(points.shape),
+            points.new_empty(points.shape[:-1], dtype=torch.uint8))
+
+
+torch.library.register_autograd("graspqp_amd::scene_distance_set", _scene_distance_bwd, setup_context=_scene_distance_setup)
+
+
+@_custom_op("graspqp_amd::scene_terms_set", mutates_args=(), device_types="cuda")
+def _scene_set_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                  origin: List[float], voxel: float, margin: float) -> Tensor:
+    """scene_terms on a stack of grids (G,nx,ny,nz)."""
+    hp, v = _c(hand_pose), _c(values)
+    e = torch.empty(hp.shape[0], device=hp.device)
+    _scene_call(_clutter_grids(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT), None, 0.0,
+                e, 0, None, None)
+    return e
+
+
+@_scene_set_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin):
+    return hand_pose.new_empty(hand_pose.shape[0])
+
+
+@_custom_op("graspqp_amd::scene_terms_set_backward", mutates_args=(), device_types="cuda")
+def _scene_set_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                      origin: List[float], voxel: float, margin: float, g_scene: Tensor) -> Tuple[Tensor, Tensor]:
+    """scene_terms_backward on a stack of grids."""
+    hp, v = _c(hand_pose), _c(values)
+    B, dev = hp.shape[0], hp.device
+    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
+    _scene_call(_clutter_grids(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT),
+                _c(g_scene), 0.0, None, 0, wrench, gRt)
+    return wrench, gRt
+
+
+@_scene_set_bwd_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin, g_scene):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+
+
+@_custom_op("graspqp_amd::approach_terms_set", mutates_args=(), device_types="cuda")
+def _approach_set_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                     origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int,
+                     margin: float) -> Tensor:
+    """approach_terms on a stack of grids (G,nx,ny,nz)."""
+    hp, v = _c(hand_pose), _c(values)
+    e = torch.empty(hp.shape[0], device=hp.device)
+    _approach_call(_clutter_grids(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
+                   _c(Rg), _c(LT), grasp_axis, None, 0.0, e, 0, None, None)
+    return e
+
+
+@_approach_set_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin):
+    return hand_pose.new_empty(hand_pose.shape[0])
+
+
+@_custom_op("graspqp_amd::approach_terms_set_backward", mutates_args=(), device_types="cuda")
+def _approach_set_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                         origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int, margin: float,
+                         g_approach: Tensor) -> Tuple[Tensor, Tensor]:
+    """approach_terms_backward on a stack of grids."""
+    hp, v = _c(hand_pose), _c(values)
+    B, dev = hp.shape[0], hp.device
+    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
+    _approach_call(_clutter_grids(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
+                   _c(Rg), _c(LT), grasp_axis, _c(g_approach), 0.0, None, 0, wrench, gRt)
+    return wrench, gRt
+
+
+@_approach_set_bwd_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin, g_approach):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+
+
+@_custom_op("graspqp_amd::scene_compose", mutates_args=("out_values",), device_types="cuda")
+def _scene_compose_op(out_values: Tensor, origin: List[float], voxel: float, target_T: Tensor, part_values: List[Tensor],
+                      part_origins: List[float], part_voxels: List[float], part_T: Tensor, exclude: Optional[Tensor],
+                      base_values: Optional[Tensor], base_origin: List[float], base_voxel: float, far: float) -> None:
+    """gq_clutter_compose: writes out_values (G,nx,ny,nz) in place.  Part p is (part_values[p], part_origins[3p:3p+3],
+    part_voxels[p]); the poses (G,12) / (n_parts,12) and exclude (G) int32 are read on the device at launch."""
+    n = len(part_values)
+    arr = (_C.SceneGrid * max(n, 1))(*(_scene_grid(v, part_origins[3 * p:3 * p + 3], part_voxels[p]) for p, v in enumerate(part_values)))
+    base = None if base_values is None else _scene_grid(base_values, base_origin, base_voxel)
+    grids = _clutter_grids(out_values, origin, voxel)
+    _C.call("gq_clutter_compose", ctypes.byref(grids), _C.f32(out_values), _C.f32(target_T), ctypes.cast(arr, ctypes.c_void_p), n,
+            _C.f32(part_T) if n else None, _C.i32(exclude), ctypes.byref(base) if base is not None else None, float(far),
+            _C.stream_ptr())
+
+
+@_scene_compose_op.register_fake
+def _(out_values, origin, voxel, target_T, part_values, part_origins, part_voxels, part_T, exclude, base_values, base_origin,
+      base_voxel, far):
+    return None
 
 
 @_custom_op("graspqp_amd::self_pen", mutates_args=(), device_types="cuda")
@@ -1738,6 +1973,12 @@ _eager("scene_terms", _scene_op)
 _eager("scene_terms_backward", _scene_bwd_op)
 _eager("approach_terms", _approach_op)
 _eager("approach_terms_backward", _approach_bwd_op)
+_eager("scene_distance_set", _scene_distance_set_op, _scene_distance_bwd, _scene_distance_setup)
+_eager("scene_terms_set", _scene_set_op)
+_eager("scene_terms_set_backward", _scene_set_bwd_op)
+_eager("approach_terms_set", _approach_set_op)
+_eager("approach_terms_set_backward", _approach_set_bwd_op)
+_eager("scene_compose", _scene_compose_op)
 _eager("self_pen", _self_pen_op, _self_pen_bwd, _self_pen_setup)
 _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_distance_setup)
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)

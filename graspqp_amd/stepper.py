@@ -26,6 +26,10 @@ travels along its approach axis must be free of the same grid.  One more launch 
 its link wrenches and gRt the same way; ``terms`` gets [E_approach] appended last, after E_scene; its share of the row total is
 one more gq_scene_total launch, and the proposal and the accept step are the stand-alone launches.
 
+Clutter (``scene`` is an ``ops.SceneSDFSet`` with one grid per object): the same two launches read a stack of grids and pick the
+grid from the row, row // batch_each (gq_clutter_terms / gq_clutter_corridor_terms, the same row bodies: bit for bit the single-grid
+launch's numbers on that grid).  ``ops.scene_compose`` refills the stack in place, also between replays of a captured graph.
+
 Objects as oriented point clouds (an ``ops.PointCloudSet`` in the place of the ``ops.MeshSet``): the object SDF of the contacts is
 gq_cloud_forward, always a launch of its own; it fills the same four buffers, so every other launch is the one of a mesh object.
 """
@@ -83,7 +87,9 @@ class GraspStepper:
         weights["E_approach"] > 0 selects the approach mode (module docstring) and needs ``scene`` too, with or without a weight
         on "E_scene": the mean over the stations d_k = approach_distance k / approach_stations (k = 1..approach_stations <= 32)
         of the same hinge sum with the whole hand moved back by d_k along the spec's grasp_axis; ``approach_margin`` = None
-        takes ``scene_margin``.  With weight 0 the three arguments change nothing."""
+        takes ``scene_margin``.  With weight 0 the three arguments change nothing.
+        ``scene`` may be an ``ops.SceneSDFSet`` with one grid per object (``n_grids`` == n_obj, rows object-major): row b of both
+        terms then reads grid b // batch_each (module docstring, "Clutter")."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -101,14 +107,18 @@ class GraspStepper:
         self.w = merge_weights(weights)
         self.tabletop = any(self.w[k] > 0 for k in TABLETOP_TERMS)
         self.scene_mode = self.w["E_scene"] > 0
-        if self.scene_mode and not isinstance(scene, ops.SceneSDF):
-            raise ValueError('GraspStepper: weights["E_scene"] > 0 needs scene=ops.SceneSDF(...)')
+        if self.scene_mode and not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
+            raise ValueError('GraspStepper: weights["E_scene"] > 0 needs scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
         if not float(scene_margin) >= 0.0:
             raise ValueError(f"GraspStepper: scene_margin = {scene_margin!r} must be >= 0")
         self.approach_mode = self.w["E_approach"] > 0
+        # clutter: one grid per object, the two launches pick the grid from the row (row // batch_each)
+        self.clutter = (self.scene_mode or self.approach_mode) and isinstance(scene, ops.SceneSDFSet)
+        if self.clutter and scene.n_grids != self.n_obj:
+            raise ValueError(f"GraspStepper: scene has n_grids = {scene.n_grids}, the stepper has n_obj = {self.n_obj} objects")
         if self.approach_mode:
-            if not isinstance(scene, ops.SceneSDF):
-                raise ValueError('GraspStepper: weights["E_approach"] > 0 needs scene=ops.SceneSDF(...)')
+            if not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
+                raise ValueError('GraspStepper: weights["E_approach"] > 0 needs scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
             approach_margin = scene_margin if approach_margin is None else approach_margin
             if not float(approach_margin) >= 0.0:
                 raise ValueError(f"GraspStepper: approach_margin = {approach_margin!r} must be >= 0")
@@ -254,7 +264,7 @@ class GraspStepper:
             self.samples = ops.SurfaceSamples(hand, surface_samples[0], surface_samples[1], device=self.dev)
         if self.scene_mode:
             self._i_scene = nT - 2 if self.approach_mode else nT - 1
-            scene.check(B, L, self.samples.Ns)
+            scene.check(B, self.be, L, self.samples.Ns) if self.clutter else scene.check(B, L, self.samples.Ns)
         if self.approach_mode:
             self._i_approach = nT - 1
             self.approach_distance, self.approach_stations = float(approach_distance), int(approach_stations)
@@ -379,6 +389,12 @@ class GraspStepper:
         """E_scene -> terms_new[-1]; the gradient of w_scene E_scene is added to the link wrenches and gRt that the FK
         backward reads."""
         f32, sm = _C.f32, self.samples
+        if self.clutter:
+            _C.call("gq_clutter_terms", ctypes.byref(self.scene.grid_set), self.be, self.scene_margin, f32(sm.points),
+                    _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D, f32(self.Rg), f32(self.link_T),
+                    ctypes.c_int64(self.B), None, float(self.w["E_scene"]), f32(self.terms_new[self._i_scene]), 1,
+                    f32(self.wrench), f32(self.gRt), st)
+            return
         _C.call("gq_scene_terms", ctypes.byref(self.scene.grid), self.scene_margin, f32(sm.points), _C.i32(sm.link),
                 ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D, f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), None,
                 float(self.w["E_scene"]), f32(self.terms_new[self._i_scene]), 1, f32(self.wrench), f32(self.gRt), st)
@@ -387,6 +403,13 @@ class GraspStepper:
         """E_approach -> terms_new[-1]; the gradient of w_approach E_approach is added to the link wrenches and gRt that the
         FK backward reads."""
         f32, sm = _C.f32, self.samples
+        if self.clutter:
+            _C.call("gq_clutter_corridor_terms", ctypes.byref(self.scene.grid_set), self.be, self.approach_margin,
+                    self.approach_distance, self.approach_stations, f32(sm.points), _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L,
+                    f32(pose), self.D, f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B),
+                    ctypes.cast(self._approach_axis, ctypes.c_void_p), None, float(self.w["E_approach"]),
+                    f32(self.terms_new[self._i_approach]), 1, f32(self.wrench), f32(self.gRt), st)
+            return
         _C.call("gq_approach_terms", ctypes.byref(self.scene.grid), self.approach_margin, self.approach_distance,
                 self.approach_stations, f32(sm.points), _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D,
                 f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), ctypes.cast(self._approach_axis, ctypes.c_void_p), None,

@@ -579,6 +579,77 @@ int gq_approach_terms(const gqSceneGrid* grid, float margin, float distance, int
                       int accumulate /* 1: add to the two gradient buffers, 0: overwrite */,
                       float* link_wrench /* (B,L,6) or NULL */, float* gRt /* (B,12) or NULL */, void* stream);
 
+/* ---- clutter scenes: one scene grid per object, composed on the device from posed part grids ------------------------
+ * The stepper's rows are object-major (n_obj x batch_each), every object's rows in that object's own frame; in a bin with N
+ * objects, grasping object g needs "bin + every object but g" in g's frame.  gqClutterGrids is a stack of n_grids grids
+ * that share shape, origin and voxel: grid g is exactly the gqSceneGrid {values + g nx ny nz, nx, ny, nz, origin, voxel},
+ * under the contract of "scene obstacles" above (phi, the inside rule, free space outside, the NaN rule, the order of the
+ * operations: the same device body, csrc/scene_dev.h).  The memory belongs to the caller.  Limits: those of gqSceneGrid per
+ * grid, 1 <= n_grids <= 65536.
+ * Row-to-grid mapping: row b reads grid b / rows_per_grid; batch == n_grids * rows_per_grid is required exactly.
+ * gq_clutter_terms / gq_clutter_corridor_terms take the arguments of gq_scene_terms / gq_approach_terms behind (grids,
+ * rows_per_grid), one launch each.  Outputs, accumulate, the upstream factor, links without samples, link ids outside the
+ * hand and NaN rows are word for word those of the single-grid entry points, and row b's numbers are BIT FOR BIT those of
+ * the single-grid entry point called on row b with grid b / rows_per_grid (the kernels run the same row body, csrc/
+ * scene_row_dev.h and approach_row_dev.h).  The row totals take gq_scene_total.
+ * gq_clutter_query: point i reads grid i / points_per_grid, n_points == n_grids * points_per_grid; the bits of gq_scene_query
+ * on the same point and grid.
+ * gq_clutter_check is the argument check of the two launches on its own (host only, no GPU): everything gq_scene_check
+ * refuses, n_grids outside 1..65536, rows_per_grid < 1, batch != n_grids * rows_per_grid; its message contains "clutter"
+ * and names the argument (gq_clutter_corridor_terms adds what gq_approach_check refuses).
+ *
+ * gq_clutter_compose fills the stack `out`.  Inputs are what a perception stack holds: one grid per part in the part's own
+ * frame (a HOST array of descriptors, values on the device; copied into the kernel's arguments, nothing is uploaded), a
+ * rigid pose per part and per target as 12 floats row-major [R|t] (world_from_part, world_from_frame_g) ON THE DEVICE, and
+ * optionally a static grid `base` in the world frame.  Node (g,i,j,k) of the output:
+ *   x_f = origin + h (i,j,k)  (one fmaf per axis)      x_w = R_g x_f + t_g      q_p = R_p' (x_w - t_p)
+ *   phi = min over { far; base(x_w) if x_w is inside base's volume; phi_p(q_p) for every part p != exclude[g] whose volume
+ *         contains q_p }
+ * Every phi is the trilinear interpolant of "scene obstacles".  The rotations are used as given, not re-orthonormalised.
+ * A non-finite x_w or q_p, or a NaN among the sampled values, makes the node NaN (the min never drops a NaN).  exclude[g]
+ * outside 0..n_parts-1, or exclude == NULL, leaves no part out.  Parts are visited in ascending order, no atomics: bitwise
+ * reproducible run to run.  A block is a tile of 4 x 4 x 16 nodes of one grid and leaves out the parts whose volume none of
+ * its nodes can reach, by a conservative test that never changes a result.  No allocation and no synchronisation; poses
+ * and exclude are read at launch, so the call can be captured in a graph and a replay after an in-place pose update
+ * recomposes.  out_values is out->values, writable.  n_grids x tiles <= 2^23 per launch.
+ * gq_clutter_compose_check (host only): everything gq_scene_check refuses for out, for base and for every part (the message
+ * names the part's index), n_parts outside 0..32, n_parts == 0 without a base, a non-finite far; the message contains
+ * "clutter".                                                                                                          */
+typedef struct gqClutterGrids {
+  const float* values;   /* (n_grids,nx,ny,nz) device fp32, z fastest; phi at the nodes, positive outside */
+  int n_grids, nx, ny, nz;
+  float origin[3];       /* of node (0,0,0), the same in every grid's own frame */
+  float voxel;
+} gqClutterGrids;
+int gq_clutter_check(const gqClutterGrids* grids, int64_t batch, int rows_per_grid, int n_links, int64_t n_samples);
+int gq_clutter_terms(const gqClutterGrids* grids, int rows_per_grid, float margin,
+                     const float* samples /* (Ns,3) link frame, device */, const int32_t* sample_link /* (Ns) */,
+                     int64_t n_samples, int n_links, const float* hand_pose, int pose_dim, const float* Rg /* (B,9) */,
+                     const float* link_T /* (B,L,12) */, int64_t batch, const float* up_scene /* (B) or NULL */, float w_scene,
+                     float* e_scene /* (B) or NULL, unweighted */,
+                     int accumulate /* 1: add to the two gradient buffers, 0: overwrite */,
+                     float* link_wrench /* (B,L,6) or NULL */, float* gRt /* (B,12) or NULL */, void* stream);
+int gq_clutter_corridor_terms(const gqClutterGrids* grids, int rows_per_grid, float margin, float distance, int n_stations,
+                              const float* samples /* (Ns,3) link frame, device */, const int32_t* sample_link /* (Ns) */,
+                              int64_t n_samples, int n_links, const float* hand_pose, int pose_dim,
+                              const float* Rg /* (B,9) */, const float* link_T /* (B,L,12) */, int64_t batch,
+                              const float* grasp_axis /* 3 floats, host */, const float* up_approach /* (B) or NULL */,
+                              float w_approach, float* e_approach /* (B) or NULL, unweighted */,
+                              int accumulate /* 1: add to the two gradient buffers, 0: overwrite */,
+                              float* link_wrench /* (B,L,6) or NULL */, float* gRt /* (B,12) or NULL */, void* stream);
+int gq_clutter_query(const gqClutterGrids* grids, const float* points /* (N,3) device */, int64_t n_points,
+                     int64_t points_per_grid, float* phi /* (N) */, float* grad /* (N,3) or NULL */,
+                     uint8_t* inside /* (N) or NULL */, void* stream);
+int gq_clutter_compose_check(const gqClutterGrids* out, const gqSceneGrid* parts /* HOST array */, int n_parts,
+                             const gqSceneGrid* base /* or NULL */, float far);
+int gq_clutter_compose(const gqClutterGrids* out, float* out_values /* = out->values, writable */,
+                       const float* target_T /* (G,12) device: world_from_frame_g, row-major [R|t] */,
+                       const gqSceneGrid* parts /* HOST array, n_parts in 0..32, each in its own part frame */, int n_parts,
+                       const float* part_T /* (n_parts,12) device: world_from_part */,
+                       const int32_t* exclude /* (G) device or NULL: the part left out of grid g */,
+                       const gqSceneGrid* base /* static grid in the world frame, or NULL */,
+                       float far /* finite: the value where nothing is known */, void* stream);
+
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
  * Per object: samples_per_object points on its convex hull (area-weighted), pushed out by `inflate` (0.01 in the
  * reference) along the face normal; farthest-point sampling of batch_each of them (start = sample 0); per row the look-at

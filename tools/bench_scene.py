@@ -8,8 +8,16 @@ alternately over windows of --steps iterations that end in a device synchronise.
 launches and of 200 gq_approach_terms launches at K = 1, 4, 8 on the same inputs, beside K x the scene launch's time: what K
 separate launches would cost.
 
+--only clutter measures the clutter scenes instead, --n_obj objects x --batch_size rows each: the stand-alone
+gq_clutter_terms / gq_clutter_corridor_terms launches beside gq_scene_terms / gq_approach_terms on the same rows with one grid, and
+beside --n_obj row-slice launches of the existing entry points (the alternative to the stack); the stepper in scene + approach mode
+with an ops.SceneSDFSet and with one ops.SceneSDF; and gq_clutter_compose (--n_obj targets of --grid^3, --n_obj parts of
+--part_grid^3, a base of --grid^3) beside ops.SceneSDF.from_meshes of the same scenes.  Everything in windows that alternate,
+--rounds of them; the spread of a figure over its windows is its margin.  One JSON line is appended to --out.
+
 usage: python tools/bench_scene.py [--steps 200] [--warmup 24] [--rounds 3] [--w_scene 50] [--scene_margin 0.005]
-       [--w_approach 20] [--approach_distance 0.10] [--approach_stations 4] [--only MODE] [--out file.jsonl]
+       [--w_approach 20] [--approach_distance 0.10] [--approach_stations 4] [--only MODE] [--n_obj 8] [--part_grid 48]
+       [--out file.jsonl]
 """
 import argparse
 import json
@@ -39,7 +47,10 @@ ap.add_argument("--w_prior", type=float, default=1.0)
 ap.add_argument("--w_approach", type=float, default=20.0)
 ap.add_argument("--approach_distance", type=float, default=0.10)
 ap.add_argument("--approach_stations", type=int, default=4)
-ap.add_argument("--only", choices=("all", "default", "tabletop", "scene", "approach"), default="all", help="profiling runs: one mode alone")
+ap.add_argument("--only", choices=("all", "default", "tabletop", "scene", "approach", "clutter"), default="all",
+                help="profiling runs: one mode alone; clutter: the measurements of DESIGN 16")
+ap.add_argument("--n_obj", type=int, default=8, help="--only clutter: objects (= grids of the stack)")
+ap.add_argument("--part_grid", type=int, default=48, help="--only clutter: nodes per axis of a part grid of the compose measurement")
 ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "scene_bench.jsonl"))
 args = ap.parse_args()
 
@@ -60,6 +71,119 @@ t0 = time.perf_counter()
 scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), origin, (args.grid,) * 3, args.voxel)
 torch.cuda.synchronize()
 t_setup = time.perf_counter() - t0
+
+
+def clutter_bench():
+    """--only clutter (module docstring)."""
+    G, be, K = args.n_obj, args.batch_size, args.approach_stations
+    B, shape = G * be, (args.grid,) * 3
+    hpB, idxB = make_initial_state(spec, fv, B, args.n_contact, 1000)
+    hpB, idxB = hpB.cuda(), idxB.cuda()
+    stack = ops.SceneSDFSet(scene.values[None].repeat(G, 1, 1, 1).contiguous(), scene.origin, scene.voxel)
+    surf = torch.tensor(sp)[None].repeat(G, 1, 1)
+    kw = dict(weights={"E_scene": args.w_scene, "E_approach": args.w_approach}, scene_margin=args.scene_margin,
+              approach_distance=args.approach_distance, approach_stations=K)
+    sts = {}
+    for name, sc in (("set", stack), ("single", scene)):
+        st = GraspStepper(hand, ops.MeshSet([fv] * G), surf, be, args.n_contact, seed=1, scene=sc, **kw)
+        st.reset(hpB, idxB)
+        st.capture()
+        for _ in range(args.warmup):
+            st.step()
+        st.realign_draws()
+        sts[name] = st
+    torch.cuda.synchronize()
+
+    def window(fn, n):
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        ev0.record()
+        for _ in range(n):
+            fn()
+        ev1.record()
+        torch.cuda.synchronize()
+        return 1e3 * ev0.elapsed_time(ev1) / n  # us
+
+    def alternate(fns, n, warm=20):
+        for fn in fns.values():
+            for _ in range(warm):
+                fn()
+        out = {k: [] for k in fns}
+        for _ in range(args.rounds):
+            for k, fn in fns.items():
+                out[k].append(window(fn, n))
+        return {k: {"median_us": float(np.median(v)), "min_us": min(v), "max_us": max(v)} for k, v in out.items()}
+
+    rec = {"clutter": True, "hand": args.hand, "n_obj": G, "batch_each": be, "rows": B, "grid": list(shape), "voxel": args.voxel,
+           "stations": K, "rounds": args.rounds, "lib": os.environ.get("GRASPQP_HIP_LIB", "default build")}
+    # the stepper: a window is --steps replays of the captured iteration
+    rec["stepper_us_per_iteration"] = alternate({k: st.step for k, st in sts.items()}, args.steps, warm=0)
+    assert all(torch.isfinite(st.energy).all() for st in sts.values())
+    # the launches on their own, on the final state of the stack's stepper (accumulate = 1 into the live buffers, as in an iteration)
+    st, one = sts["set"], sts["single"]
+    st.evaluate(st.hand_pose.clone(), st.contact_idx.clone())
+    one.evaluate(st.hand_pose.clone(), st.contact_idx.clone())
+    ptr, sm, f32 = ops._C.stream_ptr, st.samples, ops._C.f32
+    e, wr, gr = torch.empty(B, device="cuda"), torch.zeros(B, st.L, 6, device="cuda"), torch.zeros(B, 12, device="cuda")
+    Rg, LT, pose = st.Rg.reshape(B, 9), st.link_T.reshape(B, st.L, 12), st.pose_new
+
+    def sliced(call):
+        for g in range(G):
+            r = slice(g * be, (g + 1) * be)
+            call(grids[g], pose[r], Rg[r], LT[r], e[r], wr[r], gr[r])
+
+    grids = [stack.scene(g).grid for g in range(G)]
+    sc_slice = lambda grid, p, R, T, ee, w6, g12: ops._scene_call(grid, args.scene_margin, p, sm.points, sm.link, st.L, R, T, None,
+                                                                  args.w_scene, ee, 1, w6, g12)
+    ap_slice = lambda grid, p, R, T, ee, w6, g12: ops._approach_call(grid, args.scene_margin, args.approach_distance, K, p, sm.points,
+                                                                     sm.link, st.L, R, T, spec.grasp_axis, None, args.w_approach,
+                                                                     ee, 1, w6, g12)
+    rec["scene_launch"] = alternate({"gq_clutter_terms": lambda: st._eval_scene(pose, ptr()),
+                                     "gq_scene_terms": lambda: one._eval_scene(one.pose_new, ptr()),
+                                     f"{G} row-slice gq_scene_terms": lambda: sliced(sc_slice)}, 200)
+    rec["corridor_launch"] = alternate({"gq_clutter_corridor_terms": lambda: st._eval_approach(pose, ptr()),
+                                        "gq_approach_terms": lambda: one._eval_approach(one.pose_new, ptr()),
+                                        f"{G} row-slice gq_approach_terms": lambda: sliced(ap_slice)}, 200)
+    # compose: G targets around the object, G parts (the object's own grid, posed around the bin), the bin as the base
+    pn = args.part_grid
+    part_origin = [float(c) - 0.5 * args.voxel * (pn - 1) for c in center]
+    t0 = time.perf_counter()
+    part = ops.SceneSDF.from_meshes([fv], part_origin, (pn,) * 3, args.voxel)
+    torch.cuda.synchronize()
+    rec["part_grid"], rec["part_setup_s"] = [pn] * 3, time.perf_counter() - t0
+    gen = torch.Generator().manual_seed(7)
+    T = torch.zeros(G, 3, 4)
+    for g in range(G):
+        q = torch.nn.functional.normalize(torch.randn(4, generator=gen), dim=0)
+        w, x, y, z = (float(v) for v in q)
+        T[g, :, :3] = torch.tensor([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                                    [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                                    [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        T[g, :, 3] = 0.12 * (torch.rand(3, generator=gen) * 2 - 1)
+    Td, ex = T.cuda().contiguous(), torch.arange(G, dtype=torch.int32, device="cuda")
+    out = ops.SceneSDFSet.empty(G, scene.origin, shape, args.voxel)
+    far = 0.5 * args.voxel * (pn - 1) * 0.25
+    rec["compose_launch"] = alternate({"gq_clutter_compose": lambda: ops.scene_compose(out, Td, [part] * G, Td, ex, scene, far)}, 50, warm=5)
+    rec["compose_nodes"], rec["compose_below_far_fraction"] = int(out.values.numel()), float((out.values < far).float().mean())
+    # what a user does today: re-voxelise "bin + every object but g" per target, in the target's frame
+    fvt = torch.tensor(fv, dtype=torch.float32)
+    binm = [torch.tensor(np.asarray(m), dtype=torch.float32) for m in meshes.open_bin(center)]
+    t0 = time.perf_counter()
+    for g in range(G):
+        Rg_, tg = T[g, :, :3], T[g, :, 3]
+        world = binm + [fvt @ T[p, :, :3].T + T[p, :, 3] for p in range(G) if p != g]
+        ops.SceneSDF.from_meshes([(m - tg) @ Rg_ for m in world], scene.origin, shape, args.voxel)
+    torch.cuda.synchronize()
+    rec["from_meshes_same_scenes_s"] = time.perf_counter() - t0
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(rec) + "\n")
+    print(json.dumps(rec), flush=True)
+
+
+if args.only == "clutter":
+    clutter_bench()
+    sys.exit(0)
 modes = {"default": {}, "tabletop": dict(weights={"E_wall": args.w_wall, "E_prior": args.w_prior}),
          "scene": dict(weights={"E_scene": args.w_scene}, scene=scene, scene_margin=args.scene_margin),
          "approach": dict(weights={"E_scene": args.w_scene, "E_approach": args.w_approach}, scene=scene, scene_margin=args.scene_margin,
