@@ -140,6 +140,13 @@ class ClutterGrids(ctypes.Structure):
                 ("nz", ctypes.c_int), ("origin", ctypes.c_float * 3), ("voxel", ctypes.c_float)]
 
 
+class DepthViews(ctypes.Structure):
+    """gqDepthViews: V depth images of one pinhole camera model, optional per-pixel labels, a pose per view."""
+    _fields_ = [("depth", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("cam_T", ctypes.c_void_p), ("n_views", ctypes.c_int),
+                ("width", ctypes.c_int), ("height", ctypes.c_int), ("fx", ctypes.c_float), ("fy", ctypes.c_float),
+                ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("depth_min", ctypes.c_float), ("depth_max", ctypes.c_float)]
+
+
 _lib = None
 _protos = None
 

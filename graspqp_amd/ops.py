@@ -1405,6 +1405,114 @@ def scene_compose(out: SceneSDFSet, target_T, parts, part_T, exclude=None, base=
     return out
 
 
+def _depth_views(depth, labels, cam_T, intrinsics, depth_range) -> "_C.DepthViews":
+    v = _C.DepthViews()
+    v.depth, v.labels, v.cam_T = depth.data_ptr(), (labels.data_ptr() if labels is not None else None), cam_T.data_ptr()
+    v.n_views, v.height, v.width = (int(s) for s in depth.shape)
+    v.fx, v.fy, v.cx, v.cy = (float(x) for x in intrinsics)
+    v.depth_min, v.depth_max = (float(x) for x in depth_range)
+    return v
+
+
+class SceneTSDF:
+    """A scene volume fused from depth images on the device (include/graspqp_hip.h, "scenes from depth images").
+
+    ``.scene`` is an ``ops.SceneSDF`` (``n_grids`` None: one grid in the world frame) or an ``ops.SceneSDFSet`` (``n_grids``
+    grids, grid g in the frame of object g) over ``shape`` nodes at ``voxel`` spacing from ``origin``; it goes wherever a scene
+    goes (``GraspStepper(scene=...)``, ``HandModel.set_scene``, the ``base`` of ``scene_compose``) and shares ``.values``, the
+    running truncated signed distance in metres, positive in seen free space, clamped to +-``trunc``.  ``.weight`` is the number
+    of views that updated each node, capped at ``max_weight``.  ``integrate`` writes both in place with one launch per batch of
+    frames, so a stepper's captured graph reads the new volume at its next replay.
+
+    ``unknown`` is the value of a node no view has updated.  The default ``-trunc`` makes unobserved space OCCUPIED: the
+    conservative choice for a hand that must stay in seen free space (occluded regions, the space behind surfaces and outside
+    every frustum push the hand out).  ``+trunc`` makes unobserved space FREE instead: only surfaces that were actually seen are
+    obstacles, and the hand may enter space no camera has looked at.
+
+    The distance is truncated: ``E_scene`` / ``E_approach`` are hinges at ``scene_margin``, and a margin at or above ``trunc``
+    would be active everywhere in free space -- keep ``scene_margin`` below ``trunc``.  With a skipped label (``skip``), every
+    ray through the target's pixels is taken as free in that grid, so a table hidden under the target is carved away with it:
+    keep the table by ``E_wall`` or by a second view that sees it beside the target."""
+
+    def __init__(self, origin, shape, voxel, trunc, n_grids=None, unknown=None, max_weight=64.0, device="cuda"):
+        self.trunc, self.max_weight = float(trunc), float(max_weight)
+        self.unknown = -self.trunc if unknown is None else float(unknown)
+        fin = lambda v: abs(v) < float("inf")  # False for a NaN
+        if not (fin(self.trunc) and self.trunc > 0.0):
+            raise ValueError(f"SceneTSDF: trunc must be finite and > 0, got {trunc!r}")
+        if not (fin(self.max_weight) and self.max_weight >= 1.0):
+            raise ValueError(f"SceneTSDF: max_weight must be finite and >= 1, got {max_weight!r}")
+        if not fin(self.unknown):
+            raise ValueError(f"SceneTSDF: unknown must be finite, got {unknown!r}")
+        G = 1 if n_grids is None else int(n_grids)
+        self._stack = torch.empty((G,) + tuple(int(n) for n in shape), dtype=torch.float32, device=device)
+        self.weight = torch.empty_like(self._stack) if n_grids is not None else torch.empty_like(self._stack)[0]
+        self.scene = SceneSDFSet(self._stack, origin, voxel, device) if n_grids is not None else SceneSDF(self._stack[0], origin, voxel, device)
+        self.values, self.origin, self.voxel = self.scene.values, self.scene.origin, self.scene.voxel
+        self.n_grids, self.shape = G, tuple(self._stack.shape[1:])
+        self._weight = self.weight.view(self._stack.shape)
+        self._grids = _clutter_grids(self._stack, self.origin, self.voxel)
+        self.reset()
+
+    def reset(self):
+        """A fresh volume: ``values = unknown``, ``weight = 0`` (two fills, no synchronisation)."""
+        self._stack.fill_(self.unknown)
+        self._weight.zero_()
+        return self
+
+    def integrate(self, depth, intrinsics, cam_T, labels=None, target_T=None, skip=None, depth_range=(0.05, 5.0)):
+        """Fuses depth frames into the volume in place (gq_tsdf_integrate, one launch) and returns ``self``.  ``depth`` (H,W) or
+        (V,H,W): metres along the optical axis; ``intrinsics`` = (fx, fy, cx, cy) of the pinhole, pixel centres at integer
+        (col,row); ``cam_T`` (V,12) or (V,3,4): world_from_camera [R|t]; ``labels`` like ``depth``, int32: a segmentation id per
+        pixel; ``target_T`` (G,12) or (G,3,4): world_from_frame of every grid, None = the grids' frame is the world; ``skip`` (G)
+        int32: the label grid g takes as free space (its own target), negative = none; ``depth_range`` = (depth_min, depth_max),
+        a pixel outside it is no measurement.  Contiguous float32 / int32 CUDA tensors are read in place at launch, so the call
+        can be captured in a graph and replayed after the images, poses or ``skip`` were overwritten.  No allocation, no
+        synchronisation.  Views are fused in ascending order; V views in one call give the bits of V calls."""
+        dev = self._stack.device
+
+        def tensor(t, dtype):
+            t = t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))
+            return _c(t.to(dev), dtype)
+
+        d = tensor(depth, torch.float32)
+        d = d[None] if d.dim() == 2 else d
+        if d.dim() != 3:
+            raise ValueError(f"SceneTSDF.integrate: depth must be (H,W) or (V,H,W), got {tuple(d.shape)}")
+        V = int(d.shape[0])
+        lab = None
+        if labels is not None:
+            lab = tensor(labels, torch.int32)
+            lab = lab[None] if lab.dim() == 2 else lab
+            if lab.shape != d.shape:
+                raise ValueError(f"SceneTSDF.integrate: labels must have depth's shape {tuple(d.shape)}, got {tuple(lab.shape)}")
+
+        def poses(T, n, name):
+            T = tensor(T, torch.float32)
+            if T.numel() != 12 * n:
+                raise ValueError(f"SceneTSDF.integrate: {name} must hold {n} poses of 12 floats, got {tuple(T.shape)}")
+            return T.reshape(n, 12)
+
+        cT = poses(cam_T, V, "cam_T")
+        tT = None if target_T is None else poses(target_T, self.n_grids, "target_T")
+        sk = None
+        if skip is not None:
+            sk = tensor(skip, torch.int32)
+            if sk.shape != (self.n_grids,):
+                raise ValueError(f"SceneTSDF.integrate: skip must be ({self.n_grids},), got {tuple(sk.shape)}")
+        intrinsics, depth_range = [float(x) for x in intrinsics], [float(x) for x in depth_range]
+        if len(intrinsics) != 4 or len(depth_range) != 2:
+            raise ValueError("SceneTSDF.integrate: intrinsics must be (fx, fy, cx, cy) and depth_range (depth_min, depth_max)")
+        views = _depth_views(d, lab, cT, intrinsics, depth_range)
+        try:
+            _C.call("gq_tsdf_check", ctypes.byref(self._grids), ctypes.byref(views), self.trunc, self.max_weight, self.unknown)
+        except RuntimeError as e:
+            raise ValueError(f"SceneTSDF.integrate: {e}") from None
+        _Eager.tsdf_integrate(self._stack, self._weight, list(self.origin), self.voxel, d, lab, cT, intrinsics, depth_range, tT, sk,
+                              self.trunc, self.max_weight)
+        return self
+
+
 def _scene_call(grid, margin, hp, points, link, n_links, Rg, LT, up_scene, w_scene, e_scene, accumulate, wrench, gRt, st=None):
     if isinstance(grid, _C.ClutterGrids):  # a stack: row b reads grid b // (B / G)
         B = hp.shape[0]
@@ -1770,6 +1878,32 @@ def _(out_values, origin, voxel, target_T, part_values, part_origins, part_voxel
     return None
 
 
+@_custom_op("graspqp_amd::tsdf_integrate", mutates_args=("values", "weight"), device_types="cuda")
+def _tsdf_integrate_op(values: Tensor, weight: Tensor, origin: List[float], voxel: float, depth: Tensor, labels: Optional[Tensor],
+                       cam_T: Tensor, intrinsics: List[float], depth_range: List[float], target_T: Optional[Tensor],
+                       skip: Optional[Tensor], trunc: float, max_weight: float) -> None:
+    """gq_tsdf_integrate: updates values and weight (G,nx,ny,nz) in place from depth (V,H,W), labels (V,H,W) int32 or None and
+    cam_T (V,12); intrinsics = [fx, fy, cx, cy], depth_range = [depth_min, depth_max]; target_T (G,12) or None and skip (G) int32
+    or None are read on the device at launch."""
+    G, V = values.shape[0], depth.shape[0]
+    for t, dtype in ((depth, torch.float32), (labels, torch.int32), (cam_T, torch.float32)):
+        _C.ptr(t, dtype)  # CUDA, contiguous, the element type the kernel reads
+    if not (values.dim() == 4 and weight.shape == values.shape and depth.dim() == 3 and cam_T.numel() == 12 * V
+            and (labels is None or labels.shape == depth.shape) and (target_T is None or target_T.numel() == 12 * G)
+            and (skip is None or skip.numel() == G)):
+        raise RuntimeError("tsdf_integrate: weight must have values' shape (G,nx,ny,nz), labels depth's (V,H,W), cam_T 12 V floats, "
+                           "target_T 12 G floats and skip G entries")
+    grids = _clutter_grids(values, origin, voxel)
+    views = _depth_views(depth, labels, cam_T, intrinsics, depth_range)
+    _C.call("gq_tsdf_integrate", ctypes.byref(grids), _C.f32(values), _C.f32(weight), _C.f32(target_T), ctypes.byref(views),
+            _C.i32(skip), float(trunc), float(max_weight), _C.stream_ptr())
+
+
+@_tsdf_integrate_op.register_fake
+def _(values, weight, origin, voxel, depth, labels, cam_T, intrinsics, depth_range, target_T, skip, trunc, max_weight):
+    return None
+
+
 @_custom_op("graspqp_amd::self_pen", mutates_args=(), device_types="cuda")
 def _self_pen_op(centers: Tensor, hand: int) -> Tuple[Tensor, Tensor]:
     """E_spen (B,) of world sphere centres (B,S,3) and dE/dcentres (hand_model.py:989-1040)."""
@@ -1979,6 +2113,7 @@ _eager("scene_terms_set_backward", _scene_set_bwd_op)
 _eager("approach_terms_set", _approach_set_op)
 _eager("approach_terms_set_backward", _approach_set_bwd_op)
 _eager("scene_compose", _scene_compose_op)
+_eager("tsdf_integrate", _tsdf_integrate_op)
 _eager("self_pen", _self_pen_op, _self_pen_bwd, _self_pen_setup)
 _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_distance_setup)
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)

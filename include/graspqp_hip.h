@@ -650,6 +650,53 @@ int gq_clutter_compose(const gqClutterGrids* out, float* out_values /* = out->va
                        const gqSceneGrid* base /* static grid in the world frame, or NULL */,
                        float far /* finite: the value where nothing is known */, void* stream);
 
+/* ---- scenes from depth images: TSDF fusion on the device into scene grids ---------------------------------------------
+ * What a robot has is depth images, not a signed-distance volume.  gq_tsdf_integrate fuses a batch of depth frames into a
+ * gqClutterGrids stack IN PLACE, one launch per batch (n_grids = 1 is the single world grid).  State: `values` of the stack IS
+ * the running truncated signed distance D in metres, positive in seen free space -- the memory gq_scene_terms /
+ * gq_clutter_terms and their corridor siblings read, there is no extraction pass -- and beside it `weight` (n_grids,nx,ny,nz)
+ * fp32, the number of views that updated the node, capped.  A fresh volume is values = unknown, weight = 0; -trunc (unobserved
+ * space is occupied) is the conservative unknown for a hand that must stay in seen free space, +trunc makes it free.
+ * Views: V depth images of one camera model (pinhole, pixel centres at integer (col,row)), metres along the optical axis,
+ * an optional segmentation id per pixel, and a pose per view, world_from_camera as 12 floats row-major [R|t], used as given.
+ * Node (g,i,j,k) carries D and W in registers and visits the views in ascending order.  Per view:
+ *   x_f = origin + h (i,j,k), x_w = R_g x_f + t_g   exactly as gq_clutter_compose (x_w = x_f when target_T is NULL)
+ *   x_c = R_c' (x_w - t_c)                          exactly as its part-frame point
+ *   z = x_c.z; the view is skipped unless z >= depth_min (tested before any division)
+ *   u = fmaf(fx, x_c.x / z, cx), v = fmaf(fy, x_c.y / z, cy), true divisions; the node is in the image iff
+ *   u >= -0.5 && u < width - 0.5 && v >= -0.5 && v < height - 0.5, tested on the floats before the float -> int conversion;
+ *   col = (int)floorf(u + 0.5f), row = (int)floorf(v + 0.5f) (held to width - 1 / height - 1 when the sum rounds up to the
+ *   bound), d = depth[view][row][col], valid iff depth_min <= d <= depth_max (0, negative, NaN, inf: the view is skipped)
+ *   if labels and skip are given, skip[g] >= 0 and labels[pix] == skip[g]:  s = trunc (the target is no obstacle of its own
+ *   grid: this view takes the whole ray through the pixel as free); otherwise sdf = d - z, the view is skipped if
+ *   sdf < -trunc (occluded), else s = min(sdf, trunc)
+ *   D = fmaf(W, D, s) / (W + 1.0f), then W = min(W + 1.0f, max_weight)
+ * After the loop both are stored.  A non-finite x_w makes the node NaN and leaves its weight alone; a non-finite x_c does the
+ * same in that view (the NaN is sticky: every later mean keeps it).  A node no view updates keeps D and W bit for bit.  No
+ * atomics, views ascending: bitwise reproducible, and one launch with V views gives the bits of V launches with one view each.
+ * No allocation, no synchronisation, no upload: poses, skip, images and labels are read at launch, so the call can sit in a
+ * captured graph and a replay after in-place writes re-integrates.  A block is a tile of 4 x 4 x 16 nodes of one grid;
+ * n_grids x tiles <= 2^23 per launch.  values is grids->values, writable.
+ * gq_tsdf_check (host only, no GPU): everything gq_clutter_check refuses for the stack (called with batch = n_grids,
+ * rows_per_grid = 1), a NULL views, depth or cam_T, n_views outside 1..64, width or height outside 1..8192, fx or fy
+ * non-finite or <= 0, non-finite cx or cy, depth_min not finite or not > 0, depth_max not finite or < depth_min, trunc not
+ * finite or not > 0, max_weight not finite or < 1, a non-finite unknown; its message contains "tsdf" and names the
+ * argument.                                                                                                            */
+typedef struct gqDepthViews {
+  const float*   depth;    /* (V,H,W) device, metres along the optical axis (z of the camera frame), row-major, W fastest */
+  const int32_t* labels;   /* (V,H,W) device or NULL: a segmentation id per pixel */
+  const float*   cam_T;    /* (V,12) device: world_from_camera, row-major [R|t], read at launch, used as given */
+  int n_views, width, height;
+  float fx, fy, cx, cy;    /* pinhole; pixel centres at integer (col,row) */
+  float depth_min, depth_max;
+} gqDepthViews;
+int gq_tsdf_check(const gqClutterGrids* grids, const gqDepthViews* views, float trunc, float max_weight, float unknown);
+int gq_tsdf_integrate(const gqClutterGrids* grids, float* values /* = grids->values, writable */,
+                      float* weight /* (n_grids,nx,ny,nz) device */,
+                      const float* target_T /* (G,12) device world_from_frame_g, or NULL = identity */,
+                      const gqDepthViews* views, const int32_t* skip /* (G) device or NULL */,
+                      float trunc, float max_weight, void* stream);
+
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
  * Per object: samples_per_object points on its convex hull (area-weighted), pushed out by `inflate` (0.01 in the
  * reference) along the face normal; farthest-point sampling of batch_each of them (start = sample 0); per row the look-at
