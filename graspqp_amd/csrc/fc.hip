@@ -217,14 +217,15 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_fc_grad_kernel(GqFcBwdArgs g) {
 
 extern "C" {
 
-// workspace = F (B,6,nz) + x,lam,slack + Ftr + dl_dx + dx + dlam + val + svd + QP workspace
+// workspace = F (B,6,nz) + x,lam,slack + Ftr + dl_dx + dx + dlam + val + svd + best-iterate slot (B,nz,5) + QP workspace
 int gq_fc_workspace_bytes(int64_t batch, int n_contact, int n_cone, int max_iter, size_t* bytes) {
   GQ_REQUIRE(bytes && batch >= 0 && n_contact > 0 && n_cone > 0, "fc_workspace_bytes: bad arguments");
   const size_t nz = (size_t)n_contact * n_cone, B = (size_t)batch;
   size_t qp = 0;
   int rc = gq_boxqp_workspace_bytes(batch, (int)nz, max_iter, &qp);
   if (rc) return rc;
-  *bytes = gq_al(B * 6 * nz * 4) + gq_al(B * nz * 4) * 4 + gq_al(B * 2 * nz * 4) * 3 + gq_al(B * 4) * 2 + qp + 512;
+  *bytes = gq_al(B * 6 * nz * 4) + gq_al(B * nz * 4) * 4 + gq_al(B * 2 * nz * 4) * 3 + gq_al(B * 4) * 2 + gq_al(B * 5 * nz * 4) +
+           qp + 512;
   return GQ_OK;
 }
 

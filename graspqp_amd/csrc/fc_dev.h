@@ -99,6 +99,7 @@ __device__ __forceinline__ void gq_contact_term_store(const GqContactTerm& c, si
 static inline size_t gq_al(size_t v) { return (v + 255) & ~(size_t)255; }
 struct GqFcWs {
   float *F, *x, *lam, *slack, *Ftr, *dldx, *dx, *dlam, *val, *svd;
+  float* slot;  // (B,nz,5) best iterate of every row, kept current by the fused step's head (GqQpArgs.slot)
   void* qp;
   size_t qp_bytes;
 };
@@ -116,6 +117,7 @@ static inline GqFcWs gq_fc_carve(void* base, size_t B, size_t nz, size_t total) 
   w.dlam = (float*)(c + o); o += gq_al(B * 2 * nz * 4);
   w.val = (float*)(c + o); o += gq_al(B * 4);
   w.svd = (float*)(c + o); o += gq_al(B * 4);
+  w.slot = (float*)(c + o); o += gq_al(B * 5 * nz * 4);
   w.qp = (void*)(c + o);
   w.qp_bytes = total > o ? total - o : 0;
   return w;

@@ -20,6 +20,7 @@ struct GqFcStepArgs {
   float* resid;       // (B,max_iter)
   float* mu_tab;      // (B,max_iter)
   float* snap;        // (B,max_iter,5,nz)
+  float* slot;        // (B,nz,5) the row's best iterate among iterations 0 .. max_iter - 2: head stores it, tail asks for it at once
   int* kstar;         // [stop iteration, iterations]
   int32_t* n_iter;    // or null
   float* e_fc;        // (B)
@@ -97,7 +98,8 @@ __device__ __forceinline__ void gq_fc_head_body(const GqFcStepArgs& g, int row, 
   q.resid = g.resid;
   q.mu = g.mu_tab;
   q.snap = g.snap;
-  gq_qp_lr_iterate(q, row, lane, S, live, p, hu, hl, hist_resid, hist_mu);
+  q.slot = g.slot;
+  gq_qp_lr_iterate<true>(q, row, lane, S, live, p, hu, hl, hist_resid, hist_mu);
 }
 
 // qpth's batch-global stop rule without a launch of its own, for any batch size (max_iter <= 16).  Called by every
@@ -242,11 +244,15 @@ __device__ __forceinline__ void gq_fc_head_epilogue(const GqFcStepArgs& g, int b
   }
 }
 
-// qpth's batch-global stop rule (qp.hip::gq_qp_stop_wave_kernel) evaluated by one wavefront from registers: lane l owns
-// rows l, l+64, ... (RPL of them); returns the last iteration whose record counts.  B <= 64*RPL, max_iter <= 16.
+// qpth's batch-global stop rule (qp.hip::gq_qp_stop_wave_kernel) in two steps, so that several wavefronts can share it.
+// Step 1, gq_qp_stop_reduce: a wavefront holds the whole (B, max_iter) tables in registers (lane l owns rows l, l+64, ...,
+// RPL of them; B <= 64*RPL, max_iter <= 16), follows every row's running best residual, and for the iterations
+// first, first + stride, ... folds the rows into one record of three words in `red` (LDS, 16 x 3 words): max of the
+// running bests, min of mu -- both NaN-propagating like torch -- and whether any row improved.  The cross-lane folds
+// are the expensive part (two DPP trees and a ballot per iteration), and they are what the wavefronts divide.
 template <int RPL>
-__device__ __forceinline__ int gq_qp_stop_rows(const float* __restrict__ resid, const float* __restrict__ mu, int B,
-                                               int max_iter, float eps, int lim, int lane) {
+__device__ __forceinline__ void gq_qp_stop_reduce(const float* __restrict__ resid, const float* __restrict__ mu, int B,
+                                                  int max_iter, int lane, int first, int stride, float* red) {
   float rs[RPL][16], ms[RPL][16];
   if ((max_iter & 3) == 0) {  // rows are 16-byte aligned: four iterations per load
 #pragma unroll
@@ -274,11 +280,10 @@ __device__ __forceinline__ int gq_qp_stop_rows(const float* __restrict__ resid, 
     }
   }
   float run[RPL];
-  int not_improved = 0, stop_at = max_iter - 1;
-  bool done = false;
+  int next = __builtin_amdgcn_readfirstlane(first);  // wave-uniform: the folds below run under a scalar branch
 #pragma unroll
   for (int it = 0; it < 16; ++it) {
-    if (it < max_iter && !done) {  // wave-uniform
+    if (it < max_iter) {  // wave-uniform
       float mx = -GQ_INF, mn = GQ_INF;
       bool any = false;
 #pragma unroll
@@ -297,9 +302,29 @@ __device__ __forceinline__ int gq_qp_stop_rows(const float* __restrict__ resid, 
           mn = gq_nanmin(mn, ms[k][it]);
         }
       }
-      const bool any_w = __ballot(any) != 0ull;
-      const float mxw = -gq_dpp_nanmin(-mx);  // NaN-propagating max
-      const float mnw = gq_dpp_nanmin(mn);
+      if (it == next) {
+        next += stride;
+        const bool any_w = __ballot(any) != 0ull;
+        const float mxw = -gq_dpp_nanmin(-mx);  // NaN-propagating max
+        const float mnw = gq_dpp_nanmin(mn);
+        if (lane == 0) {
+          red[it * 3] = mxw;
+          red[it * 3 + 1] = mnw;
+          red[it * 3 + 2] = any_w ? 1.0f : 0.0f;
+        }
+      }
+    }
+  }
+}
+// Step 2: the sequential rule on the records; returns the last iteration whose record counts.
+__device__ __forceinline__ int gq_qp_stop_apply(const float* red, int max_iter, float eps, int lim) {
+  int not_improved = 0, stop_at = max_iter - 1;
+  bool done = false;
+#pragma unroll
+  for (int it = 0; it < 16; ++it) {
+    if (it < max_iter && !done) {  // wave-uniform
+      const float mxw = red[it * 3], mnw = red[it * 3 + 1];
+      const bool any_w = red[it * 3 + 2] != 0.0f;
       not_improved = (it == 0) ? 0 : (any_w ? 0 : not_improved + 1);
       if ((not_improved == lim) || (mxw < eps) || (mnw > 1e32f)) {
         stop_at = it;
@@ -310,59 +335,140 @@ __device__ __forceinline__ int gq_qp_stop_rows(const float* __restrict__ resid, 
   return stop_at;
 }
 
-// RPL > 0: the stop rule is replayed here (B <= 64*RPL, max_iter <= 16); RPL == 0: k* was written by a stop launch.
-// one wavefront = one row; sh: nz*3 floats of LDS (per-column gradient contributions | x for x_sum)
+// LDS of one tail row (bytes): nz x 3 floats (x for x_sum, then the per-column gradient contributions) | 16 x 3 words of
+// stop-rule records
+__host__ __device__ inline size_t gq_fc_tail_lds_bytes(int nz) { return ((size_t)nz * 3 + 48) * sizeof(float); }
+
+// One block = one row, called by every thread of the block; wavefront 0 does the row's work.
+// RPL > 0: the stop rule is replayed here (B <= 64*RPL, max_iter <= 16) by the block's OTHER wavefronts (at least one),
+// which divide its iterations among themselves (gq_qp_stop_reduce) and hand their records over through LDS and one block
+// barrier; wavefront 0 applies the rule to them (gq_qp_stop_apply).  RPL == 0: k* was written by the head epilogue or a
+// stop launch and the block's other wavefronts leave.
+// The row does not wait for k* to ask for its iterate.  Two candidates have fixed addresses and are requested with the
+// first loads: the slot in which the head keeps the row's best iterate among iterations 0 .. max_iter - 2
+// (GqQpArgs.slot), and the snapshot of the last iteration.  In the regime of the MALA* loop the rule stops at the last
+// iteration or the one before in all but a few per cent of the launches, and then one of the two IS the best iterate
+// among 0..k*; only when the rule stops before the slot's iteration does the row go back to memory for the snapshot of
+// the true best.  What does not depend on the iterate (F F', its factor, the svd term) is computed while the stop
+// rule runs.  Nothing of the row is stored before k* is known.
+// sh: gq_fc_tail_lds_bytes(nz) of LDS; rec: -DGQ_BLOCK_TIMES record of the block or null.
 template <int NC, int RPL>
-__device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, float* sh) {
-  const int lane = gq_lane();
+__device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, float* sh, uint64_t* rec = nullptr) {
+  const int lane = gq_lane(), wv = (int)threadIdx.x / GQ_WAVE;
   const int nz = g.nz;
-  // loads that depend on nothing computed here go first: the row's columns of F and the E_dis part of the contact
-  // gradient that the E_fc part is added to at the very end
+  float* s_red = sh + (size_t)nz * 3;
+  if (wv > 0) {
+    if (RPL == 0) return;
+    gq_qp_stop_reduce<(RPL > 0 ? RPL : 1)>(g.resid, g.mu_tab, g.B, g.max_iter, lane, wv - 1, (int)blockDim.x / GQ_WAVE - 1, s_red);
+#ifdef GQ_BLOCK_TIMES
+    if (rec && wv == 1 && lane == 0) rec[2] = __builtin_amdgcn_s_memrealtime();
+#endif
+    __syncthreads();
+    return;
+  }
+  // loads that depend on nothing computed here go first: the row's columns of F, the E_dis part of the contact gradient
+  // that the E_fc part is added to at the very end, the row's residuals (lane it holds iteration it), both candidates
   GqLr<6, NC> S;
   S.ridge = g.ridge;
   bool live[NC];
+  const int last = g.max_iter - 1;
+  const float* sl_a = g.slot + ((size_t)row * nz) * 5;
+  const float* sn_l = g.snap + (((size_t)row * g.max_iter + last) * 5) * nz;
+  float ca[NC][5], cl[NC][5];  // candidates: slot | last snapshot (x, z_u, z_l, s_u, s_l)
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     const int i = lane + GQ_WAVE * c;
     live[c] = i < nz;
 #pragma unroll
     for (int q = 0; q < 6; ++q) S.a[c][q] = live[c] ? g.F[((size_t)row * 6 + q) * nz + i] : 0.0f;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      ca[c][q] = live[c] ? sl_a[(size_t)i * 5 + q] : 0.0f;
+      cl[c][q] = live[c] ? sn_l[(size_t)q * nz + i] : 0.0f;
+    }
   }
   gq3 gc0 = gq_mk(0, 0, 0);
   if (lane < g.n) {
     const float* o = g.g_cpts + ((size_t)row * g.n + lane) * 3;
     gc0 = gq_mk(o[0], o[1], o[2]);
   }
-  int ks;
-  if (RPL > 0) {
-    ks = gq_qp_stop_rows<(RPL > 0 ? RPL : 1)>(g.resid, g.mu_tab, g.B, g.max_iter, g.eps, g.not_improved_lim, lane);
+  int ks = 0;
+  if (RPL == 0) ks = g.kstar[0];
+  const float mine = (lane < g.max_iter) ? g.resid[(size_t)row * g.max_iter + lane] : 0.0f;  // max_iter <= 64
+  // ---- what does not depend on the iterate: F F' and its Cholesky factor -------------------------------------------
+  double part[21];
+#pragma unroll
+  for (int i = 0; i < 21; ++i) part[i] = 0.0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = 0; b <= a; ++b) part[a * (a + 1) / 2 + b] += (double)S.a[c][a] * (double)S.a[c][b];
+  gq_wave_sums_d<21>(part);  // F F'
+  double Lm[21], inv[6];
+  const bool ok = gq_chol6(part, Lm, inv);
+  double lp = 1.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) lp *= Lm[i * (i + 1) / 2 + i];
+  const float svd = ok ? powf((float)lp, 1.0f / 6.0f) : 0.0f;  // (prod sigma)^(1/6) = det(F F')^(1/12)
+  const float ex = expf(-g.svd_gain * svd);
+  // the slot's iteration: the last one among 0 .. last - 1 that improved the row's residual (the head's recording rule)
+  int bi_a = 0;
+  float bst_a = 0.0f;
+  for (int it = 0; it < last; ++it) {
+    const float rs = gq_readlane(mine, it);
+    if (it == 0 || rs < bst_a) {
+      bst_a = rs;
+      bi_a = it;
+    }
+  }
+  const float r_last = gq_readlane(mine, last);
+#ifdef GQ_BLOCK_TIMES
+  if (rec && lane == 0) rec[3] = __builtin_amdgcn_s_memrealtime();
+#endif
+  if (RPL > 0) {  // the only wait for the stop wavefronts
+    __syncthreads();
+    ks = gq_qp_stop_apply(s_red, g.max_iter, g.eps, g.not_improved_lim);
     if (row == 0 && lane == 0) {
       g.kstar[0] = ks;
       g.kstar[1] = ks + 1;
       if (g.n_iter) *g.n_iter = ks + 1;
     }
-  } else {
-    ks = g.kstar[0];
   }
-  // best iterate of this row among iterations 0..k* (qpth returns the per-row best, not the last): the row's
-  // residuals are fetched together (lane it holds iteration it), then scanned from registers
-  int bi = 0;
-  {
-    const float mine = (lane < g.max_iter && lane < 64) ? g.resid[(size_t)row * g.max_iter + lane] : 0.0f;
+  ks = __builtin_amdgcn_readfirstlane(ks);
+  // best iterate of this row among iterations 0..k* (qpth returns the per-row best, not the last)
+  const bool use_last = ks == last && (last == 0 || r_last < bst_a);  // false for NaN: a NaN iterate never becomes best
+  const bool redo = !use_last && bi_a > ks;  // the rule stopped before the slot's iteration
+#ifdef GQ_BLOCK_TIMES
+  if (rec && lane == 0) {  // k* known | running counts over the launches: rows that went back to memory, launches
+    rec[7] = __builtin_amdgcn_s_memrealtime();
+    rec[4] += redo ? 1u : 0u;
+    rec[5] += 1u;
+  }
+#endif
+  float it5[NC][5];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int q = 0; q < 5; ++q) it5[c][q] = use_last ? cl[c][q] : ca[c][q];
+  if (redo) {  // wave-uniform, rare
+    int bi = 0;
     float bst = 0.0f;
     for (int it = 0; it <= ks; ++it) {
-      const float rs = it < 64 ? gq_readlane(mine, it) : g.resid[(size_t)row * g.max_iter + it];
+      const float rs = gq_readlane(mine, it);
       if (it == 0 || rs < bst) {
         bst = rs;
         bi = it;
       }
     }
-  }
-  const float* sn = g.snap + (((size_t)row * g.max_iter + bi) * 5) * nz;
-  float x[NC], du[NC], dl[NC], lam[NC];
-  double part[21];
+    const float* sn = g.snap + (((size_t)row * g.max_iter + bi) * 5) * nz;
 #pragma unroll
-  for (int i = 0; i < 21; ++i) part[i] = 0.0;
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int q = 0; q < 5; ++q) it5[c][q] = live[c] ? sn[(size_t)q * nz + lane + GQ_WAVE * c] : 0.0f;
+  }
+  float x[NC], du[NC], dl[NC], lam[NC];
   float r[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -370,34 +476,22 @@ __device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, 
     x[c] = 0.0f;
     du[c] = dl[c] = 1.0f;
     if (live[c]) {
-      x[c] = sn[i];
-      const float zu = sn[nz + i], zl = sn[2 * nz + i], su = sn[3 * nz + i], sl = sn[4 * nz + i];
+      x[c] = it5[c][0];
+      const float zu = it5[c][1], zl = it5[c][2], su = it5[c][3], sl = it5[c][4];
       du[c] = fmaxf(zu, 1e-8f) / fmaxf(su, 1e-8f);
       dl[c] = fmaxf(zl, 1e-8f) / fmaxf(sl, 1e-8f);
       g.x[(size_t)row * nz + i] = x[c];
     }
     lam[c] = g.ridge + du[c] + dl[c];
 #pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      r[a] = fmaf(S.a[c][a], x[c], r[a]);
-#pragma unroll
-      for (int b = 0; b <= a; ++b) part[a * (a + 1) / 2 + b] += (double)S.a[c][a] * (double)S.a[c][b];
-    }
+    for (int a = 0; a < 6; ++a) r[a] = fmaf(S.a[c][a], x[c], r[a]);
   }
 #pragma unroll
   for (int a = 0; a < 6; ++a) r[a] = gq_dpp_sum(r[a]);  // F x
-  gq_wave_sums_d<21>(part);                             // F F'
-  double Lm[21], inv[6];
-  const bool ok = gq_chol6(part, Lm, inv);
-  double lp = 1.0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) lp *= Lm[i * (i + 1) / 2 + i];
-  const float svd = ok ? powf((float)lp, 1.0f / 6.0f) : 0.0f;  // (prod sigma)^(1/6) = det(F F')^(1/12)
   float val = 0.0f;
 #pragma unroll
   for (int a = 0; a < 6; ++a) val = fmaf(r[a], r[a], val);
   val *= 0.5f;
-  const float ex = expf(-g.svd_gain * svd);
   if (lane == 0) {
     g.val[row] = val;
     g.svd[row] = svd;
@@ -458,10 +552,12 @@ __device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, 
         w[a] *= inv[a];
       }
       // gradient wrt the torque rows of column i (rows 3..5); tau = tw (r x f) -> d/dr = tw (f x g_tau)
+      //   g_tau = (gval r + F dx) x + r dx + s6 w, with the roundings spelled out (the sums of two products leave the
+      //   compiler a choice of which product to fuse, and it depends on the code around them)
       gq3 gt;
-      gt.x = (gval * r[3] + fd[3]) * x[c] + r[3] * dx[c] + s6 * (float)w[3];
-      gt.y = (gval * r[4] + fd[4]) * x[c] + r[4] * dx[c] + s6 * (float)w[4];
-      gt.z = (gval * r[5] + fd[5]) * x[c] + r[5] * dx[c] + s6 * (float)w[5];
+      gt.x = fmaf(s6, (float)w[3], fmaf(fmaf(gval, r[3], fd[3]), x[c], r[3] * dx[c]));
+      gt.y = fmaf(s6, (float)w[4], fmaf(fmaf(gval, r[4], fd[4]), x[c], r[4] * dx[c]));
+      gt.z = fmaf(s6, (float)w[5], fmaf(fmaf(gval, r[5], fd[5]), x[c], r[5] * dx[c]));
       const gq3 gp = g.tw * gq_cross(gq_mk(S.a[c][0], S.a[c][1], S.a[c][2]), gt);
       sh[i * 3] = gp.x;
       sh[i * 3 + 1] = gp.y;
@@ -489,7 +585,6 @@ __device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, 
   }
 }
 
-
 // ---- host side: argument block of the fused step (fields of gqFcStepDesc = parameters of gq_fc_step) ----------------------------------------
 int gq_qp_tables_(void* workspace, size_t workspace_bytes, int B, int nz, int max_iter, float** resid, float** mu,
                   float** snap, float** runmin, int** kstar, unsigned** agg);
@@ -506,6 +601,7 @@ static inline int gq_fc_step_fill(const gqFcStepDesc& d, GqFcStepArgs* out, floa
   const int nz = d.n_contact * d.n_cone;
   GQ_REQUIRE(nz <= 128, "fc_step: n_contact * n_cone = %d exceeds 128", nz);
   GQ_REQUIRE(d.max_iter >= 1 && d.max_iter <= 64, "fc_step: max_iter=%d out of range", d.max_iter);
+  GQ_REQUIRE(d.batch * 5 * nz < ((int64_t)1 << 32), "fc_step: batch=%lld exceeds the 32-bit index of the best-iterate slot", (long long)d.batch);
   size_t need = 0;
   int rc = gq_fc_workspace_bytes(d.batch, d.n_contact, d.n_cone, d.max_iter, &need);
   if (rc) return rc;
@@ -546,6 +642,7 @@ static inline int gq_fc_step_fill(const gqFcStepDesc& d, GqFcStepArgs* out, floa
   a.g_cpts = d.g_contact_pts;
   a.g_cnrm = d.g_hand_normals;
   a.F = w.F;
+  a.slot = w.slot;
   a.n_iter = d.n_iter;
   a.e_fc = d.e_fc;
   a.val = w.val;

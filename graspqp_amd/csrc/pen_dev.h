@@ -79,7 +79,8 @@ struct GqPenArgs {
 // launch time span in 100 MHz s_memrealtime ticks, sharded 64 ways so the atomics of 1e3 blocks do not pile up on one
 // address: span[2*s] = min start, span[2*s+1] = max end of the blocks with (linear block id % 64) == s
 // -DGQ_BLOCK_TIMES (development builds only, tools/block_timeline.py): the span buffer is followed by eight words per
-// block -- start, end, end of scan / ranking / finish, entries | items << 32 -- so the caller passes 128 + 8 * blocks words
+// block -- start, end, end of scan / ranking / finish, entries | items << 32 -- so the caller passes 128 + 8 * blocks words;
+// in a fused step `blocks` counts BOTH launches (the blocks of stage B record behind those of stage A, stage.hip)
 #ifdef GQ_BLOCK_TIMES
 __device__ __forceinline__ uint64_t gq_hw_id() {  // HW_ID (wave / SIMD / CU / SH / SE of gfx9) | XCC_ID << 32
   return (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | ((uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
@@ -706,6 +707,9 @@ struct GqPenBwdArgs {
   float* e_pen;
   uint64_t* span;      // optional: the forward query's 64 x {min start, max end} shards ...
   uint64_t* span_acc;  // ... folded into {sum of spans, launches} and re-armed here (the query is over by now)
+#ifdef GQ_BLOCK_TIMES
+  int rec0;            // block records of the first launch in front of those of stage B (stage.hip)
+#endif
 };
 
 // One block per row, surface points in rounds of up to 4096.  Phase A: every thread reads the weights of its 16 points

@@ -18,6 +18,8 @@ struct GqQpArgs {
   float* resid;  // (B, max_iter)
   float* mu;     // (B, max_iter)
   float* snap;   // (B, max_iter, 5, nz): x, lam_u, lam_l, slack_u, slack_l
+  float* slot;   // (B, nz, 5), gq_qp_lr_iterate<true> only: the row's best iterate among iterations 0 .. max_iter - 2, five words per column
+                 // (the last iteration's snapshot has a fixed address in `snap` anyway)
 };
 
 // ---- backward: (dx, _, dlam) = solve_kkt(d, grad_x, 0, 0), d = clamp(lam,1e-8)/clamp(slack,1e-8) ---------------
@@ -80,7 +82,9 @@ __device__ __forceinline__ void gq_lr_kkt(const SOLVER& S, const float (&du)[NC]
 // All PDIPM iterations of one problem (qpth 0.0.18 semantics, oracle/ref_cpu/qp.py::pdipm_forward_box), recording
 // resid / mu of every iteration and a snapshot of every iterate that improves the row's best residual.  S: the solver,
 // its matrix loaded by the caller.
-template <int NC, class SOLVER>
+// SLOT: the recorded iterates of iterations 0 .. max_iter - 2 also go into g.slot (the fused force-closure head only; the
+// generic solvers are compiled without the branch and keep their registers).
+template <bool SLOT = false, int NC, class SOLVER>
 __device__ __forceinline__ void gq_qp_lr_iterate(const GqQpArgs& g, int row, int lane, SOLVER& S,
                                                  const bool (&live)[NC], const float (&p)[NC], const float (&hu)[NC],
                                                  const float (&hl)[NC], float* hist_resid = nullptr,
@@ -163,6 +167,19 @@ __device__ __forceinline__ void gq_qp_lr_iterate(const GqQpArgs& g, int row, int
           s[2 * nz] = zl[c];
           s[3 * nz] = su[c];
           s[4 * nz] = sl[c];
+          if (SLOT && it < g.max_iter - 1) {  // fixed address per row: a reader can ask for it before it knows k*
+            // Five adjacent words per column, so that one address serves the five stores, and that address is formed
+            // here, every time: left to itself the compiler keeps loop-invariant 64-bit addresses in registers across
+            // all iterations (ten VGPRs with a (5, nz) layout, which the fused head does not have).
+            unsigned r = (unsigned)row;
+            asm volatile("" : "+v"(r));
+            float* b = g.slot + (r * (unsigned)nz + (unsigned)(lane + GQ_WAVE * c)) * 5u;  // B * 5 * nz < 2^32
+            b[0] = x[c];
+            b[1] = zu[c];
+            b[2] = zl[c];
+            b[3] = su[c];
+            b[4] = sl[c];
+          }
         }
       }
     }

@@ -4,7 +4,8 @@
 //   stage A   blocks [0, B/4)        fc head   contact terms + cone matrix + all QP iterations; 4 rows per block,
 //                                              one wavefront (SIMD) each
 //             blocks [B/4, .. + gx B) pen query penetration-only hand query of 256 surface points of one row
-//   stage B   blocks [0, B)          fc tail   stop rule + E_fc + QP backward + contact gradient (wave 0 only)
+//   stage B   blocks [0, B)          fc tail   E_fc + QP backward + contact gradient (wave 0) beside the stop rule (waves
+//                                              1..3 share its iterations); the row's iterate is requested before k* is known
 //             blocks [B, 2B)         pen bwd   link wrenches + E_pen of one row
 //             blocks [2B, 2B + B/4)  spheres   world sphere centres + self penetration (optional; 4 rows per block)
 //
@@ -111,17 +112,29 @@ template <int NC, int RPL>
 __global__ __launch_bounds__(256) void gq_stage_b_kernel(GqFcStepArgs f, GqPenBwdArgs p, GqSpenRole sp) {
   extern __shared__ char gq_lds[];
   const int b = (int)blockIdx.x;
+#ifdef GQ_BLOCK_TIMES  // one record per block of the three roles, behind the records of the first launch (p.rec0 of them)
+  uint64_t* rec = p.span ? p.span + 128 + 8 * ((size_t)p.rec0 + b) : nullptr;
+  if (rec && threadIdx.x == 0) {
+    rec[0] = __builtin_amdgcn_s_memrealtime();
+    rec[6] = gq_hw_id();
+  }
+#endif
   if (b >= 2 * f.B) {
     gq_spen_role_body(sp, b - 2 * f.B, f.B, gq_lds);
-    return;
-  }
-  if (b < f.B) {  // one row per block here: 2B blocks = two per CU at B = 256, every tail wavefront has a CU's L1 to itself
-    if (threadIdx.x >= GQ_WAVE) return;
-    __builtin_amdgcn_s_setprio(3);  // the longest role of this launch: one dependent instruction stream per row
+  } else if (b < f.B) {  // one row per block here: 2B blocks = two per CU at B = 256, every tail wavefront has a CU's L1 to itself
+    // wavefront 0 = the row, wavefronts 1..3 = the stop rule beside it (RPL > 0)
+    __builtin_amdgcn_s_setprio(3);  // the longest role of this launch: dependent instruction streams
+#ifdef GQ_BLOCK_TIMES
+    gq_fc_tail_body<NC, RPL>(f, b, reinterpret_cast<float*>(gq_lds), rec);
+#else
     gq_fc_tail_body<NC, RPL>(f, b, reinterpret_cast<float*>(gq_lds));
+#endif
   } else {
     gq_pen_bwd_body(p, b - f.B, gq_lds);
   }
+#ifdef GQ_BLOCK_TIMES
+  if (rec && threadIdx.x == 0) rec[1] = __builtin_amdgcn_s_memrealtime();
+#endif
 }
 
 // ---- the same two launches for the reference's other force-closure energies (scripts/fit.py:343-347) ---------------------
@@ -299,8 +312,11 @@ int gq_fc_pen_step(const gqFcStepDesc* fc, const gqPenStepDesc* pen, void* strea
   const bool two = f.nz > GQ_WAVE;
   const int nfc = (f.B + GQ_HEAD_ROWS - 1) / GQ_HEAD_ROWS;
   const size_t lds_a = std::max(ps.lds_q, (size_t)GQ_HEAD_ROWS * f.n * 6 * sizeof(float) + GQ_HEAD_LDS_WORDS * sizeof(unsigned));
-  const size_t lds_b = std::max(std::max(gq_pen_bwd_lds_bytes(), (size_t)f.nz * 3 * sizeof(float)), ps.lds_sp);
+  const size_t lds_b = std::max(std::max(gq_pen_bwd_lds_bytes(), gq_fc_tail_lds_bytes(f.nz)), ps.lds_sp);
   const dim3 grid_a((unsigned)(nfc + ps.n_q)), grid_b((unsigned)(2 * f.B + ps.n_sp)), block(256);
+#ifdef GQ_BLOCK_TIMES
+  ps.pb.rec0 = (int)grid_a.x;
+#endif
 #define GQ_STAGE_A(NCV, STOPV)                                                                                               \
   do {                                                                                                                       \
     if (ps.ppt == 2) hipLaunchKernelGGL((gq_stage_a_kernel<NCV, STOPV, 2>), grid_a, block, lds_a, st, f, ps.p, ps.gx, nfc);  \

@@ -141,11 +141,14 @@ int gq_fc_peek(void* workspace, size_t workspace_bytes, int64_t batch, int n_con
 /* Fused form of gq_contact_terms + gq_fc_forward + gq_fc_backward for constant upstream weights (the MALA* loop,
  * scripts/fit.py:434-438: w_dis on E_dis, w_fc on E_fc): two launches per iteration instead of nine, the grasp matrix
  * stays in registers between the cone construction and the QP iterations, and qpth's batch-global stop rule is
- * replayed inside the second kernel (batches <= 256 rows) or applied by the first kernel's last block to per-block
- * aggregates (larger batches) -- no launch of its own either way.  Inputs as gq_contact_terms; g_contact_pts receives
- * w_dis dE_dis/dp + w_fc dE_fc/dp, g_hand_normals w_dis dE_dis/dnH.  Workspace: gq_fc_workspace_bytes; gq_fc_peek
- * works afterwards.  ZERO-FILL THE WORKSPACE ONCE after allocating it (hipMemset): the block counter of the
- * large-batch stop rule lives in it and wraps back to zero at the end of every launch.                            */
+ * replayed inside the second kernel (batches <= 256 rows: by three wavefronts beside the one that does the row's work)
+ * or applied by the first kernel's last block to per-block aggregates (larger batches) -- no launch of its own either
+ * way.  Inputs as gq_contact_terms; g_contact_pts receives w_dis dE_dis/dp + w_fc dE_fc/dp, g_hand_normals
+ * w_dis dE_dis/dnH.  Workspace: gq_fc_workspace_bytes (it includes, per row, a slot of n_contact * n_cone * 5 floats in
+ * which the first kernel keeps the row's best iterate among all iterations but the last, so that the second kernel can
+ * ask for its iterate before the stop iteration is known); gq_fc_peek works afterwards.  ZERO-FILL THE WORKSPACE ONCE
+ * after allocating it (hipMemset): the block counter of the large-batch stop rule lives in it and wraps back to zero
+ * at the end of every launch.                                                                                       */
 int gq_fc_step(const float* dist_sq, const int32_t* sign, const float* obj_dir, const float* closest,
                const float* contact_pts, const float* hand_normals, const float* cog, int64_t batch, int n_contact,
                int n_cone, float friction, float torque_weight, float max_limit, float svd_gain, float values_gain,

@@ -21,7 +21,7 @@ st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, 
 # the instrumented library writes one (start, end) pair per block BEHIND the 64 span pairs: the stepper's own span buffer
 # has to be that large too, or its launches write out of bounds
 assert "libgraspqp_hip_A" in os.environ.get("GRASPQP_HIP_LIB", ""), "run with the -DGQ_BLOCK_TIMES build (tools/block_timeline.sh)"
-st._span = torch.zeros(64 + 4 * (st.B * 10 + 16), 2, dtype=torch.int64, device="cuda")
+st._span = torch.zeros(64 + 4 * (st.B * 13 + 32), 2, dtype=torch.int64, device="cuda")  # a fused step also records its stage-B blocks (2.25 B behind <= 10.25 B)
 st._span[:64, 0] = -1
 st._pen_desc.span = st._span.data_ptr()
 hps, idxs = zip(*[make_initial_state(spec, f, 256, 12, 1000 + o) for o, f in enumerate(fvs)])

@@ -20,7 +20,7 @@ hand = ops.HandHandle(spec)
 st = GraspStepper(hand, ops.MeshSet([fv]), torch.tensor(sp)[None], 256, 12, seed=1)
 B = st.B
 nq, nfc = B * 5, B // 4  # two points per thread: five query blocks per row; four fc rows per block
-st._span = torch.zeros(64 + 4 * (B * 10 + nfc + 16), 2, dtype=torch.int64, device="cuda")  # room for either block count
+st._span = torch.zeros(64 + 4 * (B * 13 + 32), 2, dtype=torch.int64, device="cuda")  # room for either block count and for the stage-B records behind
 st._span[:64, 0] = -1
 st._pen_desc.span = st._span.data_ptr()
 hp, idx = make_initial_state(spec, fv, 256, 12, 1000)
