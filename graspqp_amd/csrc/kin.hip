@@ -251,24 +251,44 @@ struct GqFkBwdArgs {
   const float* g_theta;    // (B,J) direct joint-angle gradient (E_joints) or null
   const float* g_R;        // (B,9) direct gradient on the global rotation matrix or null
   int B, n, D;
-  float* reserved;   // unread (once a (B, J, 6) workspace; the kernel folds in LDS): keeps the kernel-argument offsets of
-                     // the members below, and with them the instructions of this timed kernel, as they were
   float* grad_pose;  // (B, D)
   gqRowEnergyDesc en;  // en.total != nullptr: E_dis, E_joints (+ its gradient) and the weighted total ride along
-  int has_accept;      // MalaStar.accept_step runs last in the same wavefront (needs en.total)
+  int has_accept;      // MalaStar.accept_step runs last in the same block (needs en.total)
   GqAcceptArgs ac;
+#ifdef GQ_BLOCK_TIMES
+  uint64_t* rec;  // eight words per block (tools/block_timeline_fk_backward.py) or null
+#endif
 };
+#ifdef GQ_BLOCK_TIMES
+static uint64_t* gq_fkb_rec = nullptr;
+#define GQ_FKB_STAMP(k, who) do { if (g.rec && (who)) g.rec[8 * (size_t)blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
+#define GQ_FKB_STAMP(k, who) do { } while (0)
+#endif
 
 __device__ __forceinline__ void gq_add6(float* a, gq3 f, gq3 m) {
   a[0] += f.x; a[1] += f.y; a[2] += f.z;
   a[3] += m.x; a[4] += m.y; a[5] += m.z;
 }
 
-// one wavefront per row.  Items (contacts, spheres) are processed one per lane into (f, m, node) records in LDS; lane j
-// then folds, in item order, the records and link wrenches that ride on node j; children are folded into parents level
-// by level; the twelve global-pose sums use the fixed DPP tree.  Every sum has a fixed order -> reproducible.
+// One block per row, its three chains side by side: NW = GQ_FKB_WAVES wavefronts up to GQ_FKB_MAX_BATCH rows, where the launch
+// is latency; beyond that NW = 1 (gq_fk_backward_wave_kernel: every role on the one wavefront, lane j folds the six components
+// of node j) -- four wavefronts per row then only take slots from each other (-1.5 % at 2048 rows).  Same bits either way.
+//   wavefront 0       items (contacts, spheres), one per lane, into (f, m, node) records in LDS + its per-lane global-pose
+//                     sums; after the tree sweep the joint gradient on lanes < J
+//   all wavefronts    node fold and tree sweep, one task per (node, component): task j*6+k adds, in index order, the link
+//                     wrenches and then the records that ride on node j; children are folded into parents level by level
+//   pose wavefront    the twelve global-pose sums (fixed DPP tree over wavefront 0's lane values) and the Gram-Schmidt
+//                     backward on its lane 0, beside the fold
+//   energy wavefront  accept-step operands and energy-tail loads at the top; E_dis, E_joints and the total beside the item
+//                     loop; the accept step after the last barrier
+// Every hand-over goes through LDS and a block barrier.  Every sum has a fixed order -> reproducible, and the same bits at
+// any block size.
 #define GQ_FK_MAX_ITEMS 320
-__global__ __launch_bounds__(GQ_WAVE) void gq_fk_backward_kernel(GqFkBwdArgs g) {
+#define GQ_FKB_WAVES 4
+#define GQ_FKB_MAX_BATCH 512
+template <int NW>
+__device__ __forceinline__ void gq_fk_backward_body(const GqFkBwdArgs g) {
   __shared__ float sI[GQ_FK_MAX_ITEMS * 6];
   __shared__ int sIn[GQ_FK_MAX_ITEMS];
   __shared__ float sNF[64 * 6];
@@ -276,8 +296,16 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_fk_backward_kernel(GqFkBwdArgs g) 
   __shared__ float sWr[64 * 6];    // link wrenches of this row
   __shared__ int sLN[64];          // link -> node
   __shared__ int sCh[64];          // child lists
+  __shared__ int sCo[65];          // node -> its range of the child lists
+  __shared__ int sDep[64];         // node -> depth
   __shared__ float sG[128];        // the row's new gradient (accept step)
-  const int row = blockIdx.x, lane = gq_lane();
+  __shared__ float sAcc[12 * GQ_WAVE];  // wavefront 0's per-lane global-pose sums, [sum][lane]
+  constexpr int nw = NW, nt = NW * GQ_WAVE;
+  const int row = blockIdx.x, lane = gq_lane(), tid = (int)threadIdx.x;
+  const int wv = NW > 1 ? __builtin_amdgcn_readfirstlane(tid) / GQ_WAVE : 0;
+  constexpr int w_pose = nw > 1 ? 1 : 0, w_en = nw > 2 ? 2 : nw - 1, w_tab = nw - 1;
+  // fold / sweep tasks go to the wavefronts in the order 0, 2, 3, .., pose wavefront: it has the longest chain beside them
+  const int vt = GQ_WAVE * ((nw > 1 && wv == w_pose) ? nw - 1 : (wv > w_pose ? wv - 1 : wv)) + lane;
   const gqHand& h = g.h;
   const float* hp = g.hand_pose + (size_t)row * g.D;
   const float* R = g.Rg + (size_t)row * 9;
@@ -286,250 +314,318 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_fk_backward_kernel(GqFkBwdArgs g) 
   const int n_c = (g.g_cpts || g.g_cnrm) ? g.n : 0;
   const int n_s = g.g_spheres ? h.S : 0;
   const int n_items = n_c + n_s;
-  // ---- everything that does not depend on another load is requested first (a single wavefront hides no latency) ----
-  for (int i = lane; i < h.L * 12; i += GQ_WAVE) sLT[i] = LT[i];
+  const int n_tasks = h.J * 6;
+  GQ_FKB_STAMP(0, tid == 0);
+  // ---- everything that does not depend on another load is requested first, spread over the block -----------------------
+  for (int i = tid; i < h.L * 12; i += nt) sLT[i] = LT[i];
   if (g.g_wrench)
-    for (int i = lane; i < h.L * 6; i += GQ_WAVE) sWr[i] = g.g_wrench[(size_t)row * h.L * 6 + i];
-  if (lane < h.L) sLN[lane] = h.link_node[lane];
-  int depth = -1, ch0 = 0, ch1 = 0, ntype = 0;
+    for (int i = tid; i < h.L * 6; i += nt) sWr[i] = g.g_wrench[(size_t)row * h.L * 6 + i];
+  if (wv == w_tab) {
+    if (lane < h.L) sLN[lane] = h.link_node[lane];
+    if (lane < h.J) {
+      sDep[lane] = h.node_depth[lane];
+      sCo[lane] = h.child_off[lane];
+    }
+    const int n_ch = h.child_off[h.J];  // J - (number of roots) entries
+    if (lane == 0) sCo[h.J] = n_ch;
+    if (lane < n_ch) sCh[lane] = h.child_idx[lane];
+  }
+  int ntype = 0, depth = -1, ch0 = 0, ch1 = 0;
   gq3 axj = gq_mk(0, 0, 0);
   GqT Wj = gq_t_identity();
-  if (lane < h.J) {
+  if (NW == 1 && lane < h.J) {
     depth = h.node_depth[lane];
     ch0 = h.child_off[lane];
     ch1 = h.child_off[lane + 1];
+  }
+  float en_jhi = 0.0f, en_jlo = 0.0f, en_th = 0.0f;
+  if (wv == 0 && lane < h.J) {
     ntype = h.node_type[lane];
     axj = gq_mk(h.node_axis[lane * 3], h.node_axis[lane * 3 + 1], h.node_axis[lane * 3 + 2]);
     Wj = gq_t_load(W + lane * 12);
   }
-  if (lane < h.child_off[h.J]) sCh[lane] = h.child_idx[lane];  // J - (number of roots) entries
-  // inputs of the energy tail and of the accept step (independent of everything computed here)
-  float en_d2 = 0.0f, en_sg = 0.0f, en_jhi = 0.0f, en_jlo = 0.0f, en_th = 0.0f, en_efc = 0.0f, en_epen = 0.0f, en_espen = 0.0f;
-  gq3 en_on = gq_mk(0, 0, 0), en_nh = gq_mk(0, 0, 0);
-  if (g.en.total) {
-    if (lane < g.en.n) {
-      const size_t t = (size_t)row * g.en.n + lane;
-      en_d2 = g.en.dist_sq[t];
-      en_sg = (float)g.en.sign[t];
-      en_on = gq_mk(g.en.obj_dir[t * 3], g.en.obj_dir[t * 3 + 1], g.en.obj_dir[t * 3 + 2]);
-      en_nh = gq_mk(g.en.hand_normals[t * 3], g.en.hand_normals[t * 3 + 1], g.en.hand_normals[t * 3 + 2]);
-    }
-    if (lane < h.JA) {
-      en_jhi = g.en.joints_upper[lane];
-      en_jlo = g.en.joints_lower[lane];
-      en_th = hp[9 + lane];
-    }
-    en_efc = g.en.e_fc[row];
-    en_epen = g.en.e_pen[row];
-    en_espen = g.en.e_spen[row];
+  if ((wv == 0 || wv == w_en) && g.en.total && lane < h.JA) {  // E_joints: its gradient on wavefront 0, its sum on the energy one
+    en_jhi = g.en.joints_upper[lane];
+    en_jlo = g.en.joints_lower[lane];
+    en_th = hp[9 + lane];
   }
-  // what lane 0 needs at the very end (global-pose part): fetched now, one value per lane, handed over by readlane
-  float rt_l = 0.0f, pose_l = 0.0f;
-  if (g.g_Rt && lane < 12) rt_l = g.g_Rt[(size_t)row * 12 + lane];
-  if (lane < 9) pose_l = hp[lane];
+  // inputs of the energy tail and of the accept step (independent of everything computed here)
+  float en_d2 = 0.0f, en_sg = 0.0f, en_efc = 0.0f, en_epen = 0.0f, en_espen = 0.0f;
+  gq3 en_on = gq_mk(0, 0, 0), en_nh = gq_mk(0, 0, 0);
   GqAcceptPre ap{};
-  if (g.has_accept) ap = gq_accept_prefetch(g.ac, row, lane);
+  if (wv == w_en) {
+    if (g.has_accept) ap = gq_accept_prefetch_loads(g.ac, row, lane);
+    if (g.en.total) {
+      if (lane < g.en.n) {
+        const size_t t = (size_t)row * g.en.n + lane;
+        en_d2 = g.en.dist_sq[t];
+        en_sg = (float)g.en.sign[t];
+        en_on = gq_mk(g.en.obj_dir[t * 3], g.en.obj_dir[t * 3 + 1], g.en.obj_dir[t * 3 + 2]);
+        en_nh = gq_mk(g.en.hand_normals[t * 3], g.en.hand_normals[t * 3 + 1], g.en.hand_normals[t * 3 + 2]);
+      }
+      en_efc = g.en.e_fc[row];
+      en_epen = g.en.e_pen[row];
+      en_espen = g.en.e_spen[row];
+    }
+  }
+  // what lane 0 of the pose wavefront needs at its end: fetched now, one value per lane, handed over by readlane
+  float rt_l = 0.0f, pose_l = 0.0f;
+  if (wv == w_pose) {
+    if (g.g_Rt && lane < 12) rt_l = g.g_Rt[(size_t)row * 12 + lane];
+    if (lane < 9) pose_l = hp[lane];
+  }
   __syncthreads();
+  GQ_FKB_STAMP(2, tid == 0);
   // ---- items: per-lane contribution to the global pose + (f, m) on the carrying node -----------------------------
-  float acc[12];  // gt (3), gR (9) partial sums of this lane
+  if (wv == 0) {
+    float acc[12];  // gt (3), gR (9) partial sums of this lane
 #pragma unroll
-  for (int i = 0; i < 12; ++i) acc[i] = 0.0f;
-  for (int it = lane; it < n_items; it += GQ_WAVE) {
-    gq3 f = gq_mk(0, 0, 0), m = gq_mk(0, 0, 0);
-    int l;
-    if (it < n_c) {
-      const int ci = (int)g.idx[(size_t)row * g.n + it];
-      l = h.cand_link[ci];
-      const GqT T = gq_t_load(sLT + l * 12);
-      const gq3 ph = gq_t_apply(T, gq_mk(h.cand_pos[ci * 3], h.cand_pos[ci * 3 + 1], h.cand_pos[ci * 3 + 2]));
-      const gq3 nh = gq_t_rot(T, gq_mk(h.cand_nrm[ci * 3], h.cand_nrm[ci * 3 + 1], h.cand_nrm[ci * 3 + 2]));
-      if (g.g_cpts) {
-        const float* q = g.g_cpts + ((size_t)row * g.n + it) * 3;
+    for (int i = 0; i < 12; ++i) acc[i] = 0.0f;
+    for (int it = lane; it < n_items; it += GQ_WAVE) {
+      gq3 f = gq_mk(0, 0, 0), m = gq_mk(0, 0, 0);
+      int l;
+      if (it < n_c) {
+        const int ci = (int)g.idx[(size_t)row * g.n + it];
+        l = h.cand_link[ci];
+        const GqT T = gq_t_load(sLT + l * 12);
+        const gq3 ph = gq_t_apply(T, gq_mk(h.cand_pos[ci * 3], h.cand_pos[ci * 3 + 1], h.cand_pos[ci * 3 + 2]));
+        const gq3 nh = gq_t_rot(T, gq_mk(h.cand_nrm[ci * 3], h.cand_nrm[ci * 3 + 1], h.cand_nrm[ci * 3 + 2]));
+        if (g.g_cpts) {
+          const float* q = g.g_cpts + ((size_t)row * g.n + it) * 3;
+          const gq3 gp = gq_mk(q[0], q[1], q[2]);
+          acc[0] += gp.x; acc[1] += gp.y; acc[2] += gp.z;
+          acc[3] += gp.x * ph.x; acc[4] += gp.x * ph.y; acc[5] += gp.x * ph.z;
+          acc[6] += gp.y * ph.x; acc[7] += gp.y * ph.y; acc[8] += gp.y * ph.z;
+          acc[9] += gp.z * ph.x; acc[10] += gp.z * ph.y; acc[11] += gp.z * ph.z;
+          const gq3 gph = gq_mtv(R, gp);
+          f = f + gph;
+          m = m + gq_cross(ph, gph);
+        }
+        if (g.g_cnrm) {
+          const float* q = g.g_cnrm + ((size_t)row * g.n + it) * 3;
+          const gq3 gn = gq_mk(q[0], q[1], q[2]);
+          acc[3] += gn.x * nh.x; acc[4] += gn.x * nh.y; acc[5] += gn.x * nh.z;
+          acc[6] += gn.y * nh.x; acc[7] += gn.y * nh.y; acc[8] += gn.y * nh.z;
+          acc[9] += gn.z * nh.x; acc[10] += gn.z * nh.y; acc[11] += gn.z * nh.z;
+          m = m + gq_cross(nh, gq_mtv(R, gn));
+        }
+      } else {
+        const int sidx = it - n_c;
+        l = h.sphere_link[sidx];
+        const float* q = g.g_spheres + ((size_t)row * h.S + sidx) * 3;
         const gq3 gp = gq_mk(q[0], q[1], q[2]);
+        const GqT T = gq_t_load(sLT + l * 12);
+        const gq3 ph = gq_t_apply(T, gq_mk(h.sphere[sidx * 4], h.sphere[sidx * 4 + 1], h.sphere[sidx * 4 + 2]));
         acc[0] += gp.x; acc[1] += gp.y; acc[2] += gp.z;
         acc[3] += gp.x * ph.x; acc[4] += gp.x * ph.y; acc[5] += gp.x * ph.z;
         acc[6] += gp.y * ph.x; acc[7] += gp.y * ph.y; acc[8] += gp.y * ph.z;
         acc[9] += gp.z * ph.x; acc[10] += gp.z * ph.y; acc[11] += gp.z * ph.z;
         const gq3 gph = gq_mtv(R, gp);
-        f = f + gph;
-        m = m + gq_cross(ph, gph);
+        f = gph;
+        m = gq_cross(ph, gph);
       }
-      if (g.g_cnrm) {
-        const float* q = g.g_cnrm + ((size_t)row * g.n + it) * 3;
-        const gq3 gn = gq_mk(q[0], q[1], q[2]);
-        acc[3] += gn.x * nh.x; acc[4] += gn.x * nh.y; acc[5] += gn.x * nh.z;
-        acc[6] += gn.y * nh.x; acc[7] += gn.y * nh.y; acc[8] += gn.y * nh.z;
-        acc[9] += gn.z * nh.x; acc[10] += gn.z * nh.y; acc[11] += gn.z * nh.z;
-        m = m + gq_cross(nh, gq_mtv(R, gn));
+      if (it < GQ_FK_MAX_ITEMS) {
+        sI[it * 6 + 0] = f.x; sI[it * 6 + 1] = f.y; sI[it * 6 + 2] = f.z;
+        sI[it * 6 + 3] = m.x; sI[it * 6 + 4] = m.y; sI[it * 6 + 5] = m.z;
+        sIn[it] = sLN[l];
       }
-    } else {
-      const int sidx = it - n_c;
-      l = h.sphere_link[sidx];
-      const float* q = g.g_spheres + ((size_t)row * h.S + sidx) * 3;
-      const gq3 gp = gq_mk(q[0], q[1], q[2]);
-      const GqT T = gq_t_load(sLT + l * 12);
-      const gq3 ph = gq_t_apply(T, gq_mk(h.sphere[sidx * 4], h.sphere[sidx * 4 + 1], h.sphere[sidx * 4 + 2]));
-      acc[0] += gp.x; acc[1] += gp.y; acc[2] += gp.z;
-      acc[3] += gp.x * ph.x; acc[4] += gp.x * ph.y; acc[5] += gp.x * ph.z;
-      acc[6] += gp.y * ph.x; acc[7] += gp.y * ph.y; acc[8] += gp.y * ph.z;
-      acc[9] += gp.z * ph.x; acc[10] += gp.z * ph.y; acc[11] += gp.z * ph.z;
-      const gq3 gph = gq_mtv(R, gp);
-      f = gph;
-      m = gq_cross(ph, gph);
     }
-    if (it < GQ_FK_MAX_ITEMS) {
-      sI[it * 6 + 0] = f.x; sI[it * 6 + 1] = f.y; sI[it * 6 + 2] = f.z;
-      sI[it * 6 + 3] = m.x; sI[it * 6 + 4] = m.y; sI[it * 6 + 5] = m.z;
-      sIn[it] = sLN[l];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) sAcc[i * GQ_WAVE + lane] = acc[i];
+  }
+  // ---- energy chain, beside the items: E_dis, E_joints (the sum; its gradient joins gth below) and the total ------------
+  float e_dis = 0.0f, e_joints = 0.0f, total = 0.0f;
+  if (wv == w_en) {
+    if (g.has_accept) gq_accept_temperature(g.ac, ap);
+    if (g.en.total) {
+      float ej = 0.0f;
+      if (lane < h.JA) {  // E_joints = sum relu(theta - hi) + relu(lo - theta)  (energy.py:47-54)
+        const float th = en_th, hi = en_jhi, lo = en_jlo;
+        if (th > hi) ej += th - hi;
+        if (th < lo) ej += lo - th;
+      }
+      float ed = 0.0f;  // E_dis = sum_i exp(1 + vC_i . nH_i) |d_i|  (energy.py:25-28)
+      if (lane < g.en.n) {
+        const float root = sqrtf(en_d2 + 1e-8f);
+        const float dt = en_sg * (en_on.x * en_nh.x + en_on.y * en_nh.y + en_on.z * en_nh.z);
+        ed += expf(1.0f + dt) * root;
+      }
+      for (int c = lane + GQ_WAVE; c < g.en.n; c += GQ_WAVE) {
+        const size_t t = (size_t)row * g.en.n + c;
+        const float root = sqrtf(g.en.dist_sq[t] + 1e-8f);
+        const float sg = (float)g.en.sign[t];
+        const float dt = sg * (g.en.obj_dir[t * 3] * g.en.hand_normals[t * 3] + g.en.obj_dir[t * 3 + 1] * g.en.hand_normals[t * 3 + 1] +
+                               g.en.obj_dir[t * 3 + 2] * g.en.hand_normals[t * 3 + 2]);
+        ed += expf(1.0f + dt) * root;
+      }
+      e_dis = gq_dpp_sum(ed);
+      e_joints = gq_dpp_sum(ej);
+      total = g.en.w_dis * e_dis + g.en.w_fc * en_efc + g.en.w_pen * en_epen + g.en.w_spen * en_espen + g.en.w_joints * e_joints;
+      if (lane == 0) {
+        g.en.e_dis[row] = e_dis;
+        g.en.e_joints[row] = e_joints;
+        g.en.total[row] = total;
+      }
     }
+    GQ_FKB_STAMP(7, lane == 0);
   }
   __syncthreads();
-  // ---- node accumulators: link wrenches (E_pen) then items, each in index order ---------------------------------------
-  float nf[6] = {0, 0, 0, 0, 0, 0};
-  if (lane < h.J) {
-    if (g.g_wrench) {
+  GQ_FKB_STAMP(3, tid == 0);
+  // ---- node accumulators, one task per (node, component): link wrenches (E_pen) then items, each in index order ---------
+  float nf6[6] = {0, 0, 0, 0, 0, 0};  // NW == 1: lane j holds node j
+  if constexpr (NW == 1) {
+    if (lane < h.J) {
+      if (g.g_wrench) {
 #pragma unroll 4
-      for (int l = 0; l < h.L; ++l) {
-        const float mine = (sLN[l] == lane) ? 1.0f : 0.0f;
+        for (int l = 0; l < h.L; ++l) {
+          const float mine = (sLN[l] == lane) ? 1.0f : 0.0f;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) nf[k] = fmaf(mine, sWr[l * 6 + k], nf[k]);
+          for (int k = 0; k < 6; ++k) nf6[k] = fmaf(mine, sWr[l * 6 + k], nf6[k]);
+        }
       }
-    }
 #pragma unroll 4
-    for (int it = 0; it < n_items; ++it) {  // branch-free: every lane reads the (broadcast) record, the owner adds it
-      // (a multiply, not a select: the compiler turns a select back into a branch around the LDS reads.  A non-finite
-      // record then reaches every node of the row -- harmless, a row with any NaN is zeroed by the proposal anyway)
-      const float mine = (sIn[it] == lane) ? 1.0f : 0.0f;
+      for (int it = 0; it < n_items; ++it) {
+        const float mine = (sIn[it] == lane) ? 1.0f : 0.0f;
 #pragma unroll
-      for (int k = 0; k < 6; ++k) nf[k] = fmaf(mine, sI[it * 6 + k], nf[k]);
+        for (int k = 0; k < 6; ++k) nf6[k] = fmaf(mine, sI[it * 6 + k], nf6[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 6; ++k) sNF[lane * 6 + k] = nf6[k];
     }
+  } else {
+    for (int t = vt; t < n_tasks; t += nt) {
+      const int j = t / 6, k = t - j * 6;
+      float nf = 0.0f;
+      if (g.g_wrench) {
+#pragma unroll 4
+        for (int l = 0; l < h.L; ++l) {
+          const float mine = (sLN[l] == j) ? 1.0f : 0.0f;
+          nf = fmaf(mine, sWr[l * 6 + k], nf);
+        }
+      }
+#pragma unroll 4
+      for (int it = 0; it < n_items; ++it) {  // branch-free: every task reads the record, the owner adds it
+        // (a multiply, not a select: the compiler turns a select back into a branch around the LDS reads.  A non-finite
+        // record then reaches every node of the row -- harmless, a row with any NaN is zeroed by the proposal anyway)
+        const float mine = (sIn[it] == j) ? 1.0f : 0.0f;
+        nf = fmaf(mine, sI[it * 6 + k], nf);
+      }
+      sNF[t] = nf;
+    }
+  }
+  float* go = g.grad_pose + (size_t)row * g.D;
+  // ---- global pose, beside the fold: fixed-tree sums over wavefront 0's lanes ----------------------------------------------
+  if (wv == w_pose) {
+    float tot[12];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) sNF[lane * 6 + k] = nf[k];
+    for (int i = 0; i < 12; ++i) tot[i] = sAcc[i * GQ_WAVE + lane];
+    gq_wave_sums_f<12>(tot);  // all twelve lane sums at once (pairwise folding, fixed order)
+    if (lane == 0) {
+      gq3 gt = gq_mk(tot[0], tot[1], tot[2]);
+      float gR[9];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) gR[i] = tot[3 + i] + (g.g_R ? g.g_R[(size_t)row * 9 + i] : 0.0f);
+      if (g.g_Rt) {  // grad_t = -R gsum ; grad_R = R K
+        float e[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) e[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rt_l), i));
+        gt = gt - gq_mv(R, gq_mk(e[0], e[1], e[2]));
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            gR[i * 3 + j] += R[i * 3 + 0] * e[3 + 0 * 3 + j] + R[i * 3 + 1] * e[3 + 1 * 3 + j] + R[i * 3 + 2] * e[3 + 2 * 3 + j];
+      }
+      go[0] = gt.x; go[1] = gt.y; go[2] = gt.z;
+      sG[0] = gt.x; sG[1] = gt.y; sG[2] = gt.z;
+      // Gram-Schmidt backward: columns of gR are the gradients of x, y, z
+      float pz[9];
+#pragma unroll
+      for (int i = 3; i < 9; ++i) pz[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pose_l), i));
+      const gq3 a = gq_mk(pz[3], pz[4], pz[5]), b = gq_mk(pz[6], pz[7], pz[8]);
+      const float na = sqrtf(gq_dot(a, a));
+      const gq3 x = (1.0f / na) * a;
+      const gq3 yp = b - gq_dot(x, b) * x;
+      const float ny = sqrtf(gq_dot(yp, yp));
+      const gq3 y = (1.0f / ny) * yp;
+      gq3 gx = gq_mk(gR[0], gR[3], gR[6]), gy = gq_mk(gR[1], gR[4], gR[7]);
+      const gq3 gz = gq_mk(gR[2], gR[5], gR[8]);
+      gx = gx + gq_cross(y, gz);
+      gy = gy + gq_cross(gz, x);
+      const gq3 gyp = (1.0f / ny) * (gy - gq_dot(gy, y) * y);
+      const gq3 gb = gyp - gq_dot(gyp, x) * x;
+      gx = gx - gq_dot(x, b) * gyp - gq_dot(gyp, x) * b;
+      const gq3 ga = (1.0f / na) * (gx - gq_dot(gx, x) * x);
+      go[3] = ga.x; go[4] = ga.y; go[5] = ga.z;
+      go[6] = gb.x; go[7] = gb.y; go[8] = gb.z;
+      sG[3] = ga.x; sG[4] = ga.y; sG[5] = ga.z;
+      sG[6] = gb.x; sG[7] = gb.y; sG[8] = gb.z;
+    }
+    GQ_FKB_STAMP(6, lane == 0);
   }
   __syncthreads();
+  GQ_FKB_STAMP(4, tid == 0);
   // ---- fold children into parents, deepest level first ----------------------------------------------------------------
   for (int d = h.max_depth - 1; d >= 0; --d) {
-    if (depth == d) {
-      for (int k = ch0; k < ch1; ++k) {
-        const int c = sCh[k];
+    if constexpr (NW == 1) {
+      if (depth == d) {
+        for (int k = ch0; k < ch1; ++k) {
+          const int c = sCh[k];
 #pragma unroll
-        for (int q = 0; q < 6; ++q) nf[q] += sNF[c * 6 + q];
+          for (int q = 0; q < 6; ++q) nf6[q] += sNF[c * 6 + q];
+        }
+#pragma unroll
+        for (int q = 0; q < 6; ++q) sNF[lane * 6 + q] = nf6[q];
       }
-#pragma unroll
-      for (int q = 0; q < 6; ++q) sNF[lane * 6 + q] = nf[q];
+    } else {
+      for (int t = vt; t < n_tasks; t += nt) {
+        const int j = t / 6, k = t - j * 6;
+        if (sDep[j] == d) {
+          float nf = sNF[t];
+          for (int c = sCo[j]; c < sCo[j + 1]; ++c) nf += sNF[sCh[c] * 6 + k];
+          sNF[t] = nf;
+        }
+      }
     }
     __syncthreads();
   }
-  float* go = g.grad_pose + (size_t)row * g.D;
-  float ej = 0.0f;
+  GQ_FKB_STAMP(5, tid == 0);
   float gth = 0.0f;
-  if (lane < h.J) {  // d E / d theta_j = axis_w . (m - o x f)  (revolute) | axis_w . f (prismatic)
-    const gq3 f = gq_mk(nf[0], nf[1], nf[2]), m = gq_mk(nf[3], nf[4], nf[5]);
+  if (wv == 0 && lane < h.J) {  // d E / d theta_j = axis_w . (m - o x f)  (revolute) | axis_w . f (prismatic)
+    const gq3 f = gq_mk(sNF[lane * 6 + 0], sNF[lane * 6 + 1], sNF[lane * 6 + 2]);
+    const gq3 m = gq_mk(sNF[lane * 6 + 3], sNF[lane * 6 + 4], sNF[lane * 6 + 5]);
     const gq3 aw = gq_t_rot(Wj, axj);
     const gq3 o = gq_t_pos(Wj);
     gth = (ntype == 1) ? gq_dot(aw, m - gq_cross(o, f)) : gq_dot(aw, f);
   }
   if (h.coup) {  // coupled hand: d / d theta_act = C' (d / d theta_tree)  (the jacobian_fnc of the reference's hand files)
     __syncthreads();
-    if (lane < h.J) sNF[lane] = gth;
+    if (wv == 0 && lane < h.J) sNF[lane] = gth;
     __syncthreads();
     gth = 0.0f;
-    if (lane < h.JA)
+    if (wv == 0 && lane < h.JA)
       for (int j = 0; j < h.J; ++j) gth = fmaf(h.coup[j * h.JA + lane], sNF[j], gth);
   }
-  if (lane < h.JA) {
+  if (wv == 0 && lane < h.JA) {
     if (g.g_theta) gth += g.g_theta[(size_t)row * h.JA + lane];
-    if (g.en.total) {  // E_joints = sum relu(theta - hi) + relu(lo - theta)  (energy.py:47-54)
-      const float th = en_th, hi = en_jhi, lo = en_jlo;
-      if (th > hi) {
-        ej += th - hi;
-        gth += g.en.w_joints;
-      }
-      if (th < lo) {
-        ej += lo - th;
-        gth -= g.en.w_joints;
-      }
+    if (g.en.total) {  // gradient of w_joints E_joints
+      if (en_th > en_jhi) gth += g.en.w_joints;
+      if (en_th < en_jlo) gth -= g.en.w_joints;
     }
     go[9 + lane] = gth;
     sG[9 + lane] = gth;
   }
-  float e_dis = 0.0f, e_joints = 0.0f, total = 0.0f;
-  if (g.en.total) {
-    float ed = 0.0f;  // E_dis = sum_i exp(1 + vC_i . nH_i) |d_i|  (energy.py:25-28)
-    if (lane < g.en.n) {
-      const float root = sqrtf(en_d2 + 1e-8f);
-      const float dt = en_sg * (en_on.x * en_nh.x + en_on.y * en_nh.y + en_on.z * en_nh.z);
-      ed += expf(1.0f + dt) * root;
-    }
-    for (int c = lane + GQ_WAVE; c < g.en.n; c += GQ_WAVE) {
-      const size_t t = (size_t)row * g.en.n + c;
-      const float root = sqrtf(g.en.dist_sq[t] + 1e-8f);
-      const float sg = (float)g.en.sign[t];
-      const float dt = sg * (g.en.obj_dir[t * 3] * g.en.hand_normals[t * 3] + g.en.obj_dir[t * 3 + 1] * g.en.hand_normals[t * 3 + 1] +
-                             g.en.obj_dir[t * 3 + 2] * g.en.hand_normals[t * 3 + 2]);
-      ed += expf(1.0f + dt) * root;
-    }
-    e_dis = gq_dpp_sum(ed);
-    e_joints = gq_dpp_sum(ej);
-    total = g.en.w_dis * e_dis + g.en.w_fc * en_efc + g.en.w_pen * en_epen + g.en.w_spen * en_espen + g.en.w_joints * e_joints;
-    if (lane == 0) {
-      g.en.e_dis[row] = e_dis;
-      g.en.e_joints[row] = e_joints;
-      g.en.total[row] = total;
-    }
-  }
-  // ---- global pose: fixed-tree sums over the lanes ---------------------------------------------------------------------
-  float tot[12];
-#pragma unroll
-  for (int i = 0; i < 12; ++i) tot[i] = acc[i];
-  gq_wave_sums_f<12>(tot);  // all twelve lane sums at once (pairwise folding, fixed order)
-  if (lane == 0) {
-    gq3 gt = gq_mk(tot[0], tot[1], tot[2]);
-    float gR[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gR[i] = tot[3 + i] + (g.g_R ? g.g_R[(size_t)row * 9 + i] : 0.0f);
-    if (g.g_Rt) {  // grad_t = -R gsum ; grad_R = R K
-      float e[12];
-#pragma unroll
-      for (int i = 0; i < 12; ++i) e[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rt_l), i));
-      gt = gt - gq_mv(R, gq_mk(e[0], e[1], e[2]));
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          gR[i * 3 + j] += R[i * 3 + 0] * e[3 + 0 * 3 + j] + R[i * 3 + 1] * e[3 + 1 * 3 + j] + R[i * 3 + 2] * e[3 + 2 * 3 + j];
-    }
-    go[0] = gt.x; go[1] = gt.y; go[2] = gt.z;
-    sG[0] = gt.x; sG[1] = gt.y; sG[2] = gt.z;
-    // Gram-Schmidt backward: columns of gR are the gradients of x, y, z
-    float pz[9];
-#pragma unroll
-    for (int i = 3; i < 9; ++i) pz[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pose_l), i));
-    const gq3 a = gq_mk(pz[3], pz[4], pz[5]), b = gq_mk(pz[6], pz[7], pz[8]);
-    const float na = sqrtf(gq_dot(a, a));
-    const gq3 x = (1.0f / na) * a;
-    const gq3 yp = b - gq_dot(x, b) * x;
-    const float ny = sqrtf(gq_dot(yp, yp));
-    const gq3 y = (1.0f / ny) * yp;
-    gq3 gx = gq_mk(gR[0], gR[3], gR[6]), gy = gq_mk(gR[1], gR[4], gR[7]);
-    const gq3 gz = gq_mk(gR[2], gR[5], gR[8]);
-    gx = gx + gq_cross(y, gz);
-    gy = gy + gq_cross(gz, x);
-    const gq3 gyp = (1.0f / ny) * (gy - gq_dot(gy, y) * y);
-    const gq3 gb = gyp - gq_dot(gyp, x) * x;
-    gx = gx - gq_dot(x, b) * gyp - gq_dot(gyp, x) * b;
-    const gq3 ga = (1.0f / na) * (gx - gq_dot(gx, x) * x);
-    go[3] = ga.x; go[4] = ga.y; go[5] = ga.z;
-    go[6] = gb.x; go[7] = gb.y; go[8] = gb.z;
-    sG[3] = ga.x; sG[4] = ga.y; sG[5] = ga.z;
-    sG[6] = gb.x; sG[7] = gb.y; sG[8] = gb.z;
-  }
   if (g.has_accept) {  // Metropolis test on the new total, state merge of this row -- from registers / LDS
     __syncthreads();
-    const float term = lane == 0 ? e_dis : lane == 1 ? en_efc : lane == 2 ? en_epen : lane == 3 ? en_espen : e_joints;
-    gq_accept_finish(g.ac, ap, row, lane, total, sG, term);
+    if (wv == w_en) {
+      const float term = lane == 0 ? e_dis : lane == 1 ? en_efc : lane == 2 ? en_epen : lane == 3 ? en_espen : e_joints;
+      gq_accept_finish(g.ac, ap, row, lane, total, sG, term);
+    }
   }
+  GQ_FKB_STAMP(1, wv == w_en && lane == 0);
 }
+__global__ __launch_bounds__(GQ_WAVE * GQ_FKB_WAVES) void gq_fk_backward_kernel(GqFkBwdArgs g) { gq_fk_backward_body<GQ_FKB_WAVES>(g); }
+__global__ __launch_bounds__(GQ_WAVE) void gq_fk_backward_wave_kernel(GqFkBwdArgs g) { gq_fk_backward_body<1>(g); }
 
 // ---- self penetration (hand_model.py:989-1040) on given world centres ----------------------------------------------
 // one wavefront per row stages the centres and the radii in LDS and runs the scan of the fused forms (kin_dev.h)
@@ -753,12 +849,26 @@ int gq_fk_backward(const gqHand* h, const float* hand_pose, const int64_t* conta
     if (rc) return rc;
     a.has_accept = 1;
   }
+#ifdef GQ_BLOCK_TIMES
+  a.rec = gq_fkb_rec;
+#endif
   GQ_REQUIRE(a.n + h->S <= GQ_FK_MAX_ITEMS, "fk_backward: n_contact + n_spheres = %d exceeds %d", a.n + h->S,
              GQ_FK_MAX_ITEMS);
-  hipLaunchKernelGGL(gq_fk_backward_kernel, dim3((unsigned)batch), dim3(GQ_WAVE), 0, (hipStream_t)stream, a);
+  if (batch <= GQ_FKB_MAX_BATCH)
+    hipLaunchKernelGGL(gq_fk_backward_kernel, dim3((unsigned)batch), dim3(GQ_WAVE * GQ_FKB_WAVES), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(gq_fk_backward_wave_kernel, dim3((unsigned)batch), dim3(GQ_WAVE), 0, (hipStream_t)stream, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }
+
+#ifdef GQ_BLOCK_TIMES
+// development builds only: (batch, 8) words that every later gq_fk_backward launch stamps (100 MHz ticks), or null
+int gq_debug_fk_backward_times(uint64_t* rec) {
+  gq_fkb_rec = rec;
+  return GQ_OK;
+}
+#endif
 
 int gq_self_pen_forward(const gqHand* h, const float* sphere_centers, int64_t batch, float grad_scale, float* e_spen,
                         float* g_centers, void* stream) {

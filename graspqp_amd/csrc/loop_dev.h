@@ -199,8 +199,11 @@ struct GqAcceptPre {
   bool reset;
   float pose_new[2];
   int64_t idx_new;
+  int64_t st;  // post-propose step counter and z-score of the row: operands of the temperature
+  float zv;
 };
-__device__ __forceinline__ GqAcceptPre gq_accept_prefetch(const GqAcceptArgs& g, int row, int lane) {
+// the loads alone (the FK backward block issues them ahead of its first barrier) ...
+__device__ __forceinline__ GqAcceptPre gq_accept_prefetch_loads(const GqAcceptArgs& g, int row, int lane) {
   GqAcceptPre p;
   const size_t draw0 = g.slot_ctr ? (size_t)((g.slot_ctr[1] - 1) % g.slots) * g.B : 0;
   p.u = g.u_accept[draw0 + row];
@@ -209,12 +212,23 @@ __device__ __forceinline__ GqAcceptPre gq_accept_prefetch(const GqAcceptArgs& g,
   p.pose_new[0] = lane < g.D ? g.pose_new[(size_t)row * g.D + lane] : 0.0f;
   p.pose_new[1] = lane + GQ_WAVE < g.D ? g.pose_new[(size_t)row * g.D + lane + GQ_WAVE] : 0.0f;
   p.idx_new = lane < g.n ? g.idx_new[(size_t)row * g.n + lane] : 0;
-  float T = g.T0 * powf(g.decay, (float)((int)g.step[row] / g.annealing_period));
+  p.st = g.step[row];
+  p.zv = g.z ? g.z[row] : 0.0f;
+  p.T = 0.0f;
+  return p;
+}
+// ... and the temperature from them
+__device__ __forceinline__ void gq_accept_temperature(const GqAcceptArgs& g, GqAcceptPre& p) {
+  float T = g.T0 * powf(g.decay, (float)((int)p.st / g.annealing_period));
   if (g.z) {
-    const float proba = 0.5f * (1.0f + erff(g.z[row] * 0.70710678118654752f));
+    const float proba = 0.5f * (1.0f + erff(p.zv * 0.70710678118654752f));
     T = T * (1.0f + proba);
   }
   p.T = T;
+}
+__device__ __forceinline__ GqAcceptPre gq_accept_prefetch(const GqAcceptArgs& g, int row, int lane) {
+  GqAcceptPre p = gq_accept_prefetch_loads(g, row, lane);
+  gq_accept_temperature(g, p);
   return p;
 }
 // e_new: the row's new total (wave-uniform); sG: the row's new gradient (D <= 128 floats, LDS or global); term: lane

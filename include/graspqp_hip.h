@@ -273,8 +273,9 @@ typedef struct gqHand gqHand;
 int gq_hand_create(const gqHandDesc* desc, gqHand** out);
 int gq_hand_destroy(gqHand* h);
 /* Optional head of gq_fk_forward / tail of gq_fk_backward: MalaStar.try_step and MalaStar.accept_step
- * (core/optimizer.py:199-273, 289-340; parameters as gq_mala_propose / gq_mala_accept) run in the same wavefront as
- * the row's kinematics, so an iteration needs no launch of its own for them.  u_switch / new_idx / u_accept hold
+ * (core/optimizer.py:199-273, 289-340; parameters as gq_mala_propose / gq_mala_accept) run in the row's block of the
+ * kinematics launch (the proposal in the kinematics wavefront, the accept step in the energy wavefront of the FK
+ * backward's four), so an iteration needs no launch of its own for them.  u_switch / new_idx / u_accept hold
  * `slots` iterations of random draws, (slots,B,n) / (slots,B,n) / (slots,B); slot_ctr (2 x int32, device, zeroed
  * once) selects the current slot and is advanced on the device, so that the whole iteration can be replayed from a
  * hipGraph: the host refills the buffers every `slots` iterations.                                               */
@@ -330,7 +331,9 @@ typedef struct gqRowEnergyDesc {
 } gqRowEnergyDesc;
 /* analytic backward (replaces autograd through pytorch_kinematics); the workspace must be the one written by
  * gq_fk_forward for the same hand_pose.  Any gradient input may be NULL.  g_link_wrench (B,L,6) = (f, m about the
- * hand origin) in the hand frame and g_Rt (B,12) come from gq_hand_pen_backward.  energy: NULL or see above.    */
+ * hand origin) in the hand frame and g_Rt (B,12) come from gq_hand_pen_backward.  energy: NULL or see above.
+ * One block of four wavefronts per row: wrench chain, global-pose chain and energy / accept chain side by side,
+ * every sum in a fixed order (the same bits as one wavefront per row would give).                                */
 int gq_fk_backward(const gqHand* h, const float* hand_pose, const int64_t* contact_idx, int64_t batch, int n_contact,
                    const float* Rg, const float* link_T, const float* g_contact_points, const float* g_contact_normals,
                    const float* g_sphere_centers, const float* g_link_wrench, const float* g_Rt, const float* g_theta,

@@ -1,0 +1,112 @@
+"""Seeded inputs of one gq_fk_backward call and the call itself through the C ABI, shared by
+tests/test_gpu_fk_backward_block.py and tools/make_golden_fk_backward.py (which records the outputs of a given library).
+
+Inputs are numpy arrays from np.random.RandomState (a frozen stream); the kinematic state (Rg, link_T, node frames) comes
+from gq_fk_forward on the same pose, or from the fixture.  Every gradient input and the energy / accept tail are optional,
+as in the C ABI."""
+import ctypes
+
+import numpy as np
+import torch
+
+GRAD_INPUTS = ("g_cpts", "g_cnrm", "g_spheres", "g_wrench", "g_Rt", "g_theta", "g_R")
+WEIGHTS = dict(w_dis=100.0, w_fc=1.0, w_pen=100.0, w_spen=10.0, w_joints=1.0)
+N_TERMS = 5
+
+
+def make_inputs(spec, B, n, seed):
+    """Pose near the default state with some joints beyond their limits (E_joints and its gradient are non-zero), contact
+    indices, all seven gradient inputs, the contact records of the energy tail and the accepted state of the accept step."""
+    r = np.random.RandomState(seed)
+    f = lambda *s: r.standard_normal(s).astype(np.float32)
+    JA = spec.n_dofs  # actuated joints = pose dimension - 9
+    L, S, D = spec.n_links, spec.n_spheres, 9 + JA
+    t = f(B, 3)
+    t = 0.12 * t / np.linalg.norm(t, axis=1, keepdims=True)
+    lo, hi = np.asarray(spec.joints_lower, np.float32), np.asarray(spec.joints_upper, np.float32)
+    th = np.clip(np.asarray(spec.default_state, np.float32)[None, :JA] + 0.3 * f(B, JA), lo - 0.2, hi + 0.2)
+    inp = dict(hand_pose=np.concatenate([t, f(B, 6), th], 1).astype(np.float32),
+               idx=r.randint(0, spec.n_contact_candidates, (B, n)).astype(np.int64),
+               g_cpts=f(B, n, 3), g_cnrm=f(B, n, 3), g_spheres=f(B, max(S, 1), 3)[:, :S], g_wrench=f(B, L, 6), g_Rt=f(B, 12),
+               g_theta=f(B, JA), g_R=f(B, 9),
+               dist_sq=(1e-3 * r.rand(B, n)).astype(np.float32), sign=(2 * r.randint(0, 2, (B, n)) - 1).astype(np.int32),
+               e_fc=r.rand(B).astype(np.float32), e_pen=r.rand(B).astype(np.float32), e_spen=r.rand(B).astype(np.float32),
+               u_accept=r.rand(B).astype(np.float32), z=f(B), step=r.randint(1, 400, B).astype(np.int64),
+               energy_old=(40.0 + 80.0 * r.rand(B)).astype(np.float32), pose_old=f(B, D), grad_old=f(B, D),
+               idx_old=r.randint(0, spec.n_contact_candidates, (B, n)).astype(np.int64), terms_old=f(N_TERMS, B))
+    # the Metropolis test must go both ways in every fixture: rows 0 and 1 come from far above any new total, row 2 from zero,
+    # the others from the range of the totals (about 8 per contact at these weights)
+    inp["energy_old"] = (n * (7.5 + 2.5 * r.rand(B))).astype(np.float32)
+    inp["energy_old"][:2], inp["energy_old"][2] = 1e4, 0.0
+    for k in ("obj_dir", "hand_normals"):
+        v = f(B, n, 3)
+        inp[k] = (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(np.float32)
+    return inp
+
+
+def forward_state(C, hand, inp):
+    """Rg (B,9), link_T (B,L,12) and the node frames (B,J,12) of gq_fk_forward on the inputs' pose, as numpy arrays."""
+    hp, ix = torch.tensor(inp["hand_pose"]).cuda(), torch.tensor(inp["idx"]).cuda()
+    B, n = ix.shape
+    dev = hp.device
+    Rg, LT = torch.empty(B, 9, device=dev), torch.empty(B, hand.L, 12, device=dev)
+    cp, cn = torch.empty(B, n, 3, device=dev), torch.empty(B, n, 3, device=dev)
+    ws, nb = hand.fk_ws(B, dev)
+    C.call("gq_fk_forward", hand.handle, C.f32(hp), C.i64(ix), B, n, C.f32(Rg), C.f32(LT), C.f32(cp), C.f32(cn), None, 0.0,
+           None, None, None, None, C.ptr(ws), nb, C.stream_ptr())
+    torch.cuda.synchronize()
+    N = hand.spec.n_nodes  # tree joints (coupled hands: more than the pose carries)
+    W = ws[: B * N * 48].view(torch.float32).view(B, N, 12)
+    return dict(Rg=Rg.cpu().numpy(), link_T=LT.cpu().numpy(), node_W=W.cpu().numpy().copy())
+
+
+def run_backward(C, hand, inp, present=GRAD_INPUTS, tail=True):
+    """One gq_fk_backward launch on `inp` (make_inputs + forward_state).  present: the gradient inputs that are handed over;
+    tail: with the fused energy and accept tail.  -> dict of numpy outputs."""
+    cu = {k: torch.tensor(np.ascontiguousarray(v)).cuda() for k, v in inp.items()}
+    B, n = inp["idx"].shape
+    D = inp["hand_pose"].shape[1]
+    ws, nb = hand.fk_ws(B, cu["hand_pose"].device)
+    ws.zero_()
+    ws[: B * hand.spec.n_nodes * 48].view(torch.float32).copy_(cu["node_W"].reshape(-1))
+    opt = lambda k: C.f32(cu[k]) if (k in present and cu[k].numel() > 0) else None
+    gp = torch.full((B, D), float("nan"), device="cuda")
+    keep = []
+    en = ac = None
+    if tail:
+        jlo = torch.tensor(np.asarray(hand.spec.joints_lower, np.float32)).cuda()
+        jhi = torch.tensor(np.asarray(hand.spec.joints_upper, np.float32)).cuda()
+        terms_new = torch.zeros(N_TERMS, B, device="cuda")
+        terms_new[1], terms_new[2], terms_new[3] = cu["e_fc"], cu["e_pen"], cu["e_spen"]
+        total = torch.zeros(B, device="cuda")
+        en = C.RowEnergyDesc()
+        en.dist_sq, en.sign, en.obj_dir, en.hand_normals = (cu[k].data_ptr() for k in ("dist_sq", "sign", "obj_dir", "hand_normals"))
+        en.joints_lower, en.joints_upper = jlo.data_ptr(), jhi.data_ptr()
+        en.e_fc, en.e_pen, en.e_spen = (terms_new[i].data_ptr() for i in (1, 2, 3))
+        en.n = n
+        for k, v in WEIGHTS.items():
+            setattr(en, k, v)
+        en.e_dis, en.e_joints, en.total = terms_new[0].data_ptr(), terms_new[4].data_ptr(), total.data_ptr()
+        accept = torch.full((B,), 7, dtype=torch.uint8, device="cuda")
+        temperature = torch.zeros(B, device="cuda")
+        energy, pose, grad, idx, terms = (cu[k].clone() for k in ("energy_old", "pose_old", "grad_old", "idx_old", "terms_old"))
+        ac = C.AcceptDesc()
+        ac.u_accept, ac.z, ac.reset_mask, ac.step = cu["u_accept"].data_ptr(), cu["z"].data_ptr(), None, cu["step"].data_ptr()
+        ac.starting_temperature, ac.decay, ac.annealing_period = 18.0, 0.95, 30
+        ac.energy, ac.pose, ac.idx, ac.grad = energy.data_ptr(), pose.data_ptr(), idx.data_ptr(), grad.data_ptr()
+        ac.accept, ac.temperature = accept.data_ptr(), temperature.data_ptr()
+        ac.n_terms, ac.terms_new, ac.terms = N_TERMS, terms_new.data_ptr(), terms.data_ptr()
+        slot_ctr = torch.tensor([0, 1], dtype=torch.int32, device="cuda")  # one slot of draws, the proposal has advanced [1]
+        ac.slot_ctr, ac.slots = slot_ctr.data_ptr(), 1
+        keep = [jlo, jhi, slot_ctr]
+    C.call("gq_fk_backward", hand.handle, C.f32(cu["hand_pose"]), C.i64(cu["idx"]), B, n, C.f32(cu["Rg"]), C.f32(cu["link_T"]),
+           opt("g_cpts"), opt("g_cnrm"), opt("g_spheres"), opt("g_wrench"), opt("g_Rt"), opt("g_theta"), opt("g_R"), C.f32(gp),
+           ctypes.byref(en) if tail else None, ctypes.byref(ac) if tail else None, C.ptr(ws), nb, C.stream_ptr())
+    torch.cuda.synchronize()
+    del keep
+    out = dict(grad_pose=gp.cpu().numpy())
+    if tail:
+        out.update(e_dis=terms_new[0].cpu().numpy(), e_joints=terms_new[4].cpu().numpy(), total=total.cpu().numpy(),
+                   accept=accept.cpu().numpy(), pose=pose.cpu().numpy(), grad=grad.cpu().numpy(), idx=idx.cpu().numpy(),
+                   terms=terms.cpu().numpy(), energy=energy.cpu().numpy(), temperature=temperature.cpu().numpy())
+    return out
