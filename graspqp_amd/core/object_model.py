@@ -131,6 +131,18 @@ class ObjectModel:
         self._cog = None
         self._hull = None
 
+    def initialize_from_tsdf(self, tsdf, min_weight=1.0, bounds=None, radius=None, object_code_list=None):
+        """Objects from depth images: one object per grid of ``tsdf`` (an ``ops.SceneTSDF`` fused from frames that hold the target
+        alone, ``ops.keep_label``), each in its grid's frame.  ``tsdf.extract_clouds(min_weight, bounds)`` turns the volume's
+        zero level set into surfels on the device (one synchronisation, to learn their number), ``initialize_from_point_clouds``
+        takes them from there: a single-view volume gives an open shell, which is what the cloud route is for."""
+        clouds = tsdf.extract_clouds(min_weight, bounds)
+        for g, (p, _) in enumerate(clouds):
+            if len(p) == 0 or len(p) < self.num_samples:
+                raise ValueError(f"initialize_from_tsdf: grid {g} yields {len(p)} surfels, num_samples = {self.num_samples} "
+                                 f"(min_weight = {min_weight}, bounds = {bounds!r})")
+        self.initialize_from_point_clouds([p for p, _ in clouds], [n for _, n in clouds], object_code_list, radius)
+
     def convex_hulls(self):
         """Convex hull of every object (scaled like initializations.py:42-46) as device arrays for
         ``initialize_convex_hull``: triangles oriented outward, per-object cumulative area table, offsets."""

@@ -1512,6 +1512,82 @@ class SceneTSDF:
                               self.trunc, self.max_weight)
         return self
 
+    def _region(self, bounds):
+        """The half-open node region [i0,i1,j0,j1,k0,k1] of the nodes inside ``bounds`` = (lo, hi), two points of the grid frame."""
+        if bounds is None:
+            return []
+        lo, hi = (np.asarray(b, dtype=np.float64).reshape(3) for b in bounds)
+        region = []
+        for a in range(3):
+            u0, u1 = (lo[a] - self.origin[a]) / self.voxel, (hi[a] - self.origin[a]) / self.voxel
+            if not (abs(u0) < float("inf") and abs(u1) < float("inf")):
+                raise ValueError(f"SceneTSDF.surfels: bounds must be finite, got {bounds!r}")
+            i0, i1 = max(int(np.ceil(u0 - 1e-6)), 0), min(int(np.floor(u1 + 1e-6)) + 1, self.shape[a])
+            if i0 >= i1:
+                raise ValueError(f"SceneTSDF.surfels: bounds {bounds!r} hold no node of the grid on axis {a}")
+            region += [i0, i1]
+        return region
+
+    def surfels(self, capacity, min_weight=1.0, bounds=None, out=None):
+        """The zero level set of every grid as an oriented point cloud (gq_tsdf_surfels, three launches): -> ``(points
+        (G,capacity,3), normals (G,capacity,3), count (G,2) int32)`` on the device, in the grid's frame.  A surfel sits where D
+        changes sign along a grid edge whose two nodes carry ``weight >= min_weight`` and |D| < ``trunc``; its normal is the
+        normalised smoothed gradient of D (outward: D is positive in free space).  ``count[g] = (found, written)`` with
+        ``written = min(found, capacity)``; rows at and beyond ``written`` are not touched.  ``bounds`` = (lo, hi), two points of
+        the grid frame: only edges between nodes inside that box.  ``out`` = an earlier result, whose buffers are written again.
+        No synchronisation, and with ``out`` no allocation: the call can be captured in a graph behind ``integrate``.  The order
+        of the surfels is fixed (tile, node, axis), so two calls agree bit for bit.  With ``min_weight=2`` only surfaces two views
+        agree on remain, which trims the silhouette tails of a projective TSDF: on the sphere check of DESIGN 18 the radial error
+        falls from median 0.41 mm / max 0.67 voxel to 0.28 mm / 0.63 voxel."""
+        capacity = int(capacity)
+        region = self._region(bounds)
+        self._surfels_check(region, min_weight, True, capacity)
+        dev, G = self._stack.device, self.n_grids
+        if out is None:
+            out = (torch.empty(G, capacity, 3, device=dev), torch.empty(G, capacity, 3, device=dev),
+                   torch.empty(G, 2, dtype=torch.int32, device=dev))
+        P, N, count = out
+        if not (tuple(P.shape) == tuple(N.shape) == (G, capacity, 3) and tuple(count.shape) == (G, 2)):
+            raise ValueError(f"SceneTSDF.surfels: out must be ((G,capacity,3), (G,capacity,3), (G,2)) with G = {G}, capacity = {capacity}")
+        _Eager.tsdf_surfels(self._stack, self._weight, list(self.origin), self.voxel, region, float(min_weight), self.trunc, P, N, count,
+                            self._surfel_workspace())
+        return P, N, count
+
+    def _surfels_check(self, region, min_weight, has_outputs, capacity):
+        reg = (ctypes.c_int32 * 6)(*region) if region else None
+        try:
+            _C.call("gq_tsdf_surfels_check", ctypes.byref(self._grids), reg, float(min_weight), self.trunc, int(has_outputs),
+                    ctypes.c_int64(capacity))
+        except RuntimeError as e:
+            raise ValueError(f"SceneTSDF.surfels: {e}") from None
+
+    def _surfel_workspace(self):
+        if getattr(self, "_surfel_ws", None) is None:
+            self._surfel_ws = _ws(_size_call("gq_tsdf_surfels_workspace_bytes", ctypes.byref(self._grids)), self._stack.device)
+        return self._surfel_ws
+
+    def extract_clouds(self, min_weight=1.0, bounds=None):
+        """-> a list of G ``(points (n_g,3), normals (n_g,3))`` pairs on the device, every grid's surfels trimmed to their number: a
+        counting call, ONE read of ``count`` on the host (the only synchronisation), then a call of exactly the largest size."""
+        region = self._region(bounds)
+        self._surfels_check(region, min_weight, False, 0)
+        count = torch.empty(self.n_grids, 2, dtype=torch.int32, device=self._stack.device)
+        _Eager.tsdf_surfels(self._stack, self._weight, list(self.origin), self.voxel, region, float(min_weight), self.trunc, None, None,
+                            count, self._surfel_workspace())
+        found = count[:, 0].cpu().tolist()
+        P, N, _ = self.surfels(max(max(found), 1), min_weight, bounds)
+        return [(P[g, :n], N[g, :n]) for g, n in enumerate(found)]
+
+
+def keep_label(depth, labels, label):
+    """``depth`` with 0 (no measurement) wherever the pixel's label differs from ``label``: frames masked this way fuse into a
+    volume that holds the labelled object alone (``SceneTSDF.integrate`` ignores a pixel outside ``depth_range``)."""
+    depth = depth if torch.is_tensor(depth) else torch.as_tensor(np.asarray(depth))
+    labels = labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels))
+    if depth.shape != labels.shape:
+        raise ValueError(f"keep_label: labels must have depth's shape {tuple(depth.shape)}, got {tuple(labels.shape)}")
+    return torch.where(labels.to(depth.device) == int(label), depth, torch.zeros((), dtype=depth.dtype, device=depth.device))
+
 
 def _scene_call(grid, margin, hp, points, link, n_links, Rg, LT, up_scene, w_scene, e_scene, accumulate, wrench, gRt, st=None):
     if isinstance(grid, _C.ClutterGrids):  # a stack: row b reads grid b // (B / G)
@@ -1904,6 +1980,32 @@ def _(values, weight, origin, voxel, depth, labels, cam_T, intrinsics, depth_ran
     return None
 
 
+@_custom_op("graspqp_amd::tsdf_surfels", mutates_args=("points", "normals", "count", "workspace"), device_types="cuda")
+def _tsdf_surfels_op(values: Tensor, weight: Optional[Tensor], origin: List[float], voxel: float, region: List[int], min_weight: float,
+                     trunc: float, points: Optional[Tensor], normals: Optional[Tensor], count: Tensor, workspace: Tensor) -> None:
+    """gq_tsdf_surfels: the surfels of values / weight (G,nx,ny,nz) into points, normals (G,capacity,3) and count (G,2) int32;
+    region = [i0,i1,j0,j1,k0,k1] or [] for the whole grid; points = normals = None runs the count only.  No gradient."""
+    G = values.shape[0]
+    if not (values.dim() == 4 and (weight is None or weight.shape == values.shape) and len(region) in (0, 6)
+            and (points is None) == (normals is None) and tuple(count.shape) == (G, 2)
+            and (points is None or (points.dim() == 3 and points.shape[0] == G and points.shape[2] == 3 and normals.shape == points.shape))):
+        raise RuntimeError("tsdf_surfels: weight must have values' shape (G,nx,ny,nz), region 0 or 6 entries, points and normals "
+                           "(G,capacity,3) or both None, count (G,2)")
+    grids = _clutter_grids(values, origin, voxel)
+    need = _size_call("gq_tsdf_surfels_workspace_bytes", ctypes.byref(grids))
+    if workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError(f"tsdf_surfels: workspace holds {workspace.numel() * workspace.element_size()} bytes, {need} are needed")
+    reg = (ctypes.c_int32 * 6)(*(int(r) for r in region)) if len(region) else None
+    capacity = 0 if points is None else int(points.shape[1])
+    _C.call("gq_tsdf_surfels", ctypes.byref(grids), _C.f32(values), _C.f32(weight), reg, float(min_weight), float(trunc), _C.f32(points),
+            _C.f32(normals), ctypes.c_int64(capacity), _C.i32(count), _C.ptr(workspace), _C.stream_ptr())
+
+
+@_tsdf_surfels_op.register_fake
+def _(values, weight, origin, voxel, region, min_weight, trunc, points, normals, count, workspace):
+    return None
+
+
 @_custom_op("graspqp_amd::self_pen", mutates_args=(), device_types="cuda")
 def _self_pen_op(centers: Tensor, hand: int) -> Tuple[Tensor, Tensor]:
     """E_spen (B,) of world sphere centres (B,S,3) and dE/dcentres (hand_model.py:989-1040)."""
@@ -2114,6 +2216,7 @@ _eager("approach_terms_set", _approach_set_op)
 _eager("approach_terms_set_backward", _approach_set_bwd_op)
 _eager("scene_compose", _scene_compose_op)
 _eager("tsdf_integrate", _tsdf_integrate_op)
+_eager("tsdf_surfels", _tsdf_surfels_op)
 _eager("self_pen", _self_pen_op, _self_pen_bwd, _self_pen_setup)
 _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_distance_setup)
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)

@@ -703,6 +703,38 @@ int gq_tsdf_integrate(const gqClutterGrids* grids, float* values /* = grids->val
                       const gqDepthViews* views, const int32_t* skip /* (G) device or NULL */,
                       float trunc, float max_weight, void* stream);
 
+/* ---- target objects from depth images: the zero level set of a fused stack as oriented point clouds -------------------
+ * gq_tsdf_surfels turns every grid of a gqClutterGrids stack that gq_tsdf_integrate has fused (values = D, positive in free
+ * space; weight = W or NULL = every node observed) into surfels: positions and unit outward normals in the grid's frame, the
+ * input of gq_cloudset_create.  Per grid, inside the half-open node region [i0,i1) x [j0,j1) x [k0,k1) (region = 6 ints on the
+ * HOST in that order, NULL = the whole grid):
+ *   node n is OBSERVED iff it lies in the grid, D(n) is finite and W(n) >= min_weight
+ *   node a owns the edges to b = a + e_c, c = x, y, z; an edge is a CROSSING iff a and b are in the region, both are observed,
+ *   (D_a >= 0) != (D_b >= 0), |D_a| < trunc and |D_b| < trunc -- exact tests on the fp32 inputs
+ *   t = D_a / (D_a - D_b) in [0,1];  p = x_a + t voxel e_c,  x_a = fmaf(voxel, (i,j,k), origin) as gq_clutter_compose's x_f
+ *   d_c(m) = (D(m + e_c) - D(m - e_c)) / 2 if both neighbours are observed, the one-sided difference if one is, 0 if none
+ *   g_c(n) = sum w d_c(m) / sum w over the OBSERVED nodes m of the 3 x 3 neighbourhood of n transverse to c,
+ *            w = (1,2,1) x (1,2,1) (n itself is observed: the sum of the weights is >= 4); the stencils read the whole grid
+ *   v = (1 - t) g(a) + t g(b);  normal = v / |v| if |v|^2 > 1e-20, else e_c sign(D_b - D_a): the number of surfels never
+ *   depends on a floating-point decision.
+ * Outputs: points, normals (G,capacity,3) fp32; count (G,2) int32 = (crossings found, min(found, capacity) written; 0 written
+ * when points is NULL).  Slots at and beyond the written count are not touched.  points == normals == NULL runs the count only.
+ * Order: (tile of 4 x 4 x 16 nodes as gq_tsdf_integrate's blocks, x slowest; node within the tile, z fastest; axis), fixed: two
+ * runs agree bit for bit.  Three launches (count per tile, one block per grid scans the tile counts, emit) and nothing else: no
+ * atomics, no block waits for another, no allocation, synchronisation or upload -- the call can sit in a captured graph
+ * behind gq_tsdf_integrate.  workspace: gq_tsdf_surfels_workspace_bytes(grids) bytes on the device, contents irrelevant.
+ * gq_tsdf_surfels_check (host only, no GPU): a NULL grids, everything gq_clutter_check refuses for the stack, more than 2^23
+ * tiles, trunc not finite or not > 0, a non-finite min_weight, a region that is empty on an axis or leaves the grid,
+ * capacity < 1 when has_outputs, capacity > 2^24; the message starts with "surfels:" and names the argument.            */
+int gq_tsdf_surfels_check(const gqClutterGrids* grids, const int32_t* region /* 6 ints, HOST, or NULL */, float min_weight,
+                          float trunc, int has_outputs, int64_t capacity);
+int gq_tsdf_surfels_workspace_bytes(const gqClutterGrids* grids, size_t* bytes);
+int gq_tsdf_surfels(const gqClutterGrids* grids, const float* values /* = grids->values */,
+                    const float* weight /* (n_grids,nx,ny,nz) device or NULL */, const int32_t* region /* 6 ints, HOST, or NULL */,
+                    float min_weight, float trunc, float* points /* (G,capacity,3) device or NULL */,
+                    float* normals /* (G,capacity,3) device or NULL */, int64_t capacity, int32_t* count /* (G,2) device */,
+                    void* workspace, void* stream);
+
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
  * Per object: samples_per_object points on its convex hull (area-weighted), pushed out by `inflate` (0.01 in the
  * reference) along the face normal; farthest-point sampling of batch_each of them (start = sample 0); per row the look-at
