@@ -17,18 +17,18 @@ deps() {  # headers each translation unit includes
     qp_lr) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h" ;;
     fcstep) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h fc_dev.h fcstep_dev.h" ;;
     qp|qp_dense|qp_nz*) echo "common.h qp_core.h qp_kernels.h wave.h" ;;
-    stage) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h fc_dev.h fcstep_dev.h pen_dev.h setup.h tri.h kin_dev.h metric_dev.h" ;;
-    sdf) echo "common.h setup.h tri.h pen_dev.h sdf_dev.h wave.h" ;;
-    bvh) echo "common.h setup.h tri.h" ;;
+    stage) echo "common.h qp_core.h qp_kernels.h qp_lr.h wave.h fc_dev.h fcstep_dev.h pen_dev.h setup.h cluster_bound.h tri.h kin_dev.h metric_dev.h" ;;
+    sdf) echo "common.h setup.h cluster_bound.h tri.h pen_dev.h sdf_dev.h wave.h" ;;
+    bvh) echo "common.h setup.h cluster_bound.h tri.h" ;;
     fc) echo "common.h fc_dev.h qp_core.h wave.h" ;;
     loop) echo "common.h fc_dev.h loop_dev.h wave.h" ;;
     metric) echo "common.h wave.h metric_dev.h" ;;
     init) echo "common.h wave.h" ;;
     export) echo "common.h kin_dev.h wave.h" ;;
     exact) echo "common.h wave.h exact_dev.h fc_dev.h" ;;
-    kin) echo "common.h setup.h loop_dev.h sdf_dev.h tri.h kin_dev.h wave.h" ;;
+    kin) echo "common.h setup.h cluster_bound.h loop_dev.h sdf_dev.h tri.h kin_dev.h wave.h" ;;
     tabletop) echo "common.h" ;;
-    cloud) echo "common.h setup.h" ;;
+    cloud) echo "common.h setup.h cluster_bound.h" ;;
     scene) echo "common.h scene_dev.h scene_row_dev.h" ;;
     approach) echo "common.h scene_dev.h approach_dev.h approach_row_dev.h" ;;
     clutter) echo "common.h scene_dev.h approach_dev.h scene_row_dev.h approach_row_dev.h clutter_dev.h" ;;

@@ -360,95 +360,7 @@ __global__ __launch_bounds__(256) void gq_occ_centres_kernel(const GqFace* __res
   if (inside) atomicOr(&occ[(size_t)m * 1024 + iz * 32 + iy], 1u << ix);
 }
 
-#include <cmath>
 #include <memory>
-
-// Bound of a 64-face cluster: an oriented box, 16 floats = [centre.xyz, h_u][u.xyz, h_v][v.xyz, h_n][n.xyz, 0].
-// n = area-weighted mean normal of the patch, u = principal direction of its vertices in the plane orthogonal to n,
-// v = n x u.  A Morton patch of a surface mesh is nearly planar, so the box is ~1 mm thick along n and hugs the patch
-// laterally -- for a query point several centimetres away the neighbouring patches are only millimetres farther than
-// the nearest one, and an axis-aligned box around a tilted patch is too loose to tell them apart.
-static void gq_cluster_bound(const float* fv, const int32_t* perm, int64_t a, int64_t b, float* out16) {
-  double n[3] = {0, 0, 0}, c0[3] = {0, 0, 0};
-  for (int64_t i = a; i < b; ++i) {
-    const float* v = fv + (int64_t)perm[i] * 9;
-    const double e1[3] = {(double)v[3] - v[0], (double)v[4] - v[1], (double)v[5] - v[2]};
-    const double e2[3] = {(double)v[6] - v[0], (double)v[7] - v[1], (double)v[8] - v[2]};
-    n[0] += e1[1] * e2[2] - e1[2] * e2[1];
-    n[1] += e1[2] * e2[0] - e1[0] * e2[2];
-    n[2] += e1[0] * e2[1] - e1[1] * e2[0];
-    for (int k = 0; k < 9; ++k) c0[k % 3] += v[k];
-  }
-  const double cnt = 3.0 * (double)(b - a);
-  for (int k = 0; k < 3; ++k) c0[k] /= cnt;
-  double len = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
-  if (len > 1e-30) {
-    for (int k = 0; k < 3; ++k) n[k] /= len;
-  } else {
-    n[0] = 0; n[1] = 0; n[2] = 1;
-  }
-  // t1 orthogonal to n (drop the smallest component), t2 = n x t1
-  double t1[3], t2[3];
-  {
-    const int m = (std::fabs(n[0]) <= std::fabs(n[1]) && std::fabs(n[0]) <= std::fabs(n[2])) ? 0
-                  : (std::fabs(n[1]) <= std::fabs(n[2]) ? 1 : 2);
-    double e[3] = {0, 0, 0};
-    e[m] = 1.0;
-    const double d = n[m];
-    for (int k = 0; k < 3; ++k) t1[k] = e[k] - d * n[k];
-    const double l = std::sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
-    for (int k = 0; k < 3; ++k) t1[k] /= l;
-    t2[0] = n[1] * t1[2] - n[2] * t1[1];
-    t2[1] = n[2] * t1[0] - n[0] * t1[2];
-    t2[2] = n[0] * t1[1] - n[1] * t1[0];
-  }
-  double cxx = 0, cxy = 0, cyy = 0;
-  for (int64_t i = a; i < b; ++i) {
-    const float* v = fv + (int64_t)perm[i] * 9;
-    for (int c = 0; c < 3; ++c) {
-      const double q[3] = {v[c * 3] - c0[0], v[c * 3 + 1] - c0[1], v[c * 3 + 2] - c0[2]};
-      const double x = q[0] * t1[0] + q[1] * t1[1] + q[2] * t1[2], y = q[0] * t2[0] + q[1] * t2[1] + q[2] * t2[2];
-      cxx += x * x;
-      cxy += x * y;
-      cyy += y * y;
-    }
-  }
-  const double th = 0.5 * std::atan2(2.0 * cxy, cxx - cyy);
-  float ax[3][3];  // u, v, n rounded to fp32 (the extents below are taken along the ROUNDED axes)
-  for (int k = 0; k < 3; ++k) {
-    ax[0][k] = (float)(std::cos(th) * t1[k] + std::sin(th) * t2[k]);
-    ax[1][k] = (float)(-std::sin(th) * t1[k] + std::cos(th) * t2[k]);
-    ax[2][k] = (float)n[k];
-  }
-  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, mag = 0.0;
-  for (int64_t i = a; i < b; ++i) {
-    const float* v = fv + (int64_t)perm[i] * 9;
-    for (int c = 0; c < 3; ++c) {
-      const double q[3] = {v[c * 3] - c0[0], v[c * 3 + 1] - c0[1], v[c * 3 + 2] - c0[2]};
-      for (int k = 0; k < 3; ++k) {
-        const double s = q[0] * ax[k][0] + q[1] * ax[k][1] + q[2] * ax[k][2];
-        lo[k] = s < lo[k] ? s : lo[k];
-        hi[k] = s > hi[k] ? s : hi[k];
-      }
-      const double m = std::fabs((double)v[c * 3]) + std::fabs((double)v[c * 3 + 1]) + std::fabs((double)v[c * 3 + 2]);
-      mag = m > mag ? m : mag;
-    }
-  }
-  double ctr[3] = {c0[0], c0[1], c0[2]};
-  for (int k = 0; k < 3; ++k)
-    for (int j = 0; j < 3; ++j) ctr[j] += 0.5 * (lo[k] + hi[k]) * ax[k][j];
-  const double pad = 1e-6 * mag + 1e-12;  // fp32 evaluation on the device + rounding of the centre
-  for (int k = 0; k < 3; ++k) {
-    out16[k] = (float)ctr[k];
-    out16[4 + k] = ax[0][k];
-    out16[8 + k] = ax[1][k];
-    out16[12 + k] = ax[2][k];
-  }
-  out16[3] = (float)(0.5 * (hi[0] - lo[0]) + pad);
-  out16[7] = (float)(0.5 * (hi[1] - lo[1]) + pad);
-  out16[11] = (float)(0.5 * (hi[2] - lo[2]) + pad);
-  out16[15] = 0.0f;
-}
 
 // internal (kin.hip): argument block of the wave-per-query kernel for a mesh set; `points` is left to the caller
 int gq_sdf_wave_args_(const gqMeshSet* ms, int64_t n_points, int64_t queries_per_mesh, float* dist_sq, int32_t* sign,

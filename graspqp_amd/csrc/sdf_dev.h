@@ -3,6 +3,8 @@
 #pragma once
 #include "tri.h"
 
+#include "cluster_bound.h"  // gq_cluster_lb, gq_cluster_lb4: the lower bound of a cluster's box
+
 // ---- wave per query -------------------------------------------------------------------------------------------
 // queries are grouped: query q uses mesh (q / queries_per_mesh); mesh m's records are rec[off[m] .. off[m+1]).
 // With a mesh set the faces of every mesh are Morton-sorted and grouped in clusters of 64 (one face per lane) with an
@@ -28,17 +30,6 @@ struct GqWaveArgs {
   float* normal;
   float* closest;
 };
-
-// lower bound of the squared distance from p to any face of a cluster (oriented box of gq_cluster_bound)
-__device__ __forceinline__ float gq_cluster_lb(const float* __restrict__ r, gq3 p) {
-  const float4 c = *reinterpret_cast<const float4*>(r), u = *reinterpret_cast<const float4*>(r + 4),
-               v = *reinterpret_cast<const float4*>(r + 8), n = *reinterpret_cast<const float4*>(r + 12);
-  const gq3 d = gq_mk(p.x - c.x, p.y - c.y, p.z - c.z);
-  const float eu = fmaxf(fabsf(fmaf(d.x, u.x, fmaf(d.y, u.y, d.z * u.z))) - c.w, 0.0f);
-  const float ev = fmaxf(fabsf(fmaf(d.x, v.x, fmaf(d.y, v.y, d.z * v.z))) - u.w, 0.0f);
-  const float en = fmaxf(fabsf(fmaf(d.x, n.x, fmaf(d.y, n.y, d.z * n.z))) - v.w, 0.0f);
-  return fmaf(eu, eu, fmaf(ev, ev, en * en));
-}
 
 __device__ __forceinline__ void gq_wave_eval_cluster(const GqFace* __restrict__ rec, int f, int f1, gq3 p, float& best,
                                                      unsigned& borig, int& bi) {
@@ -81,13 +72,6 @@ __device__ __forceinline__ GqSdfPre gq_sdf_wave_prefetch(const GqWaveArgs& g, in
     }
   }
   return s;
-}
-__device__ __forceinline__ float gq_cluster_lb4(const float4 (&r)[4], gq3 p) {
-  const gq3 d = gq_mk(p.x - r[0].x, p.y - r[0].y, p.z - r[0].z);
-  const float eu = fmaxf(fabsf(fmaf(d.x, r[1].x, fmaf(d.y, r[1].y, d.z * r[1].z))) - r[0].w, 0.0f);
-  const float ev = fmaxf(fabsf(fmaf(d.x, r[2].x, fmaf(d.y, r[2].y, d.z * r[2].z))) - r[1].w, 0.0f);
-  const float en = fmaxf(fabsf(fmaf(d.x, r[3].x, fmaf(d.y, r[3].y, d.z * r[3].z))) - r[2].w, 0.0f);
-  return fmaf(eu, eu, fmaf(ev, ev, en * en));
 }
 
 // one wavefront answers query q at point p (all lanes pass the same q, p).  GQ_TOPK = clusters taken up per round: four
