@@ -1430,7 +1430,8 @@ class SceneTSDF:
     obstacles, and the hand may enter space no camera has looked at.
 
     The distance is truncated: ``E_scene`` / ``E_approach`` are hinges at ``scene_margin``, and a margin at or above ``trunc``
-    would be active everywhere in free space -- keep ``scene_margin`` below ``trunc``.  With a skipped label (``skip``), every
+    would be active everywhere in free space -- keep ``scene_margin`` below ``trunc``, or run the stepper on ``esdf(max_distance)``,
+    the Euclidean distance field of the volume, which also has a gradient deep inside obstacles.  With a skipped label (``skip``), every
     ray through the target's pixels is taken as free in that grid, so a table hidden under the target is carved away with it:
     keep the table by ``E_wall`` or by a second view that sees it beside the target."""
 
@@ -1577,6 +1578,62 @@ class SceneTSDF:
         found = count[:, 0].cpu().tolist()
         P, N, _ = self.surfels(max(max(found), 1), min_weight, bounds)
         return [(P[g, :n], N[g, :n]) for g, n in enumerate(found)]
+
+    def esdf(self, max_distance, out=None):
+        """The Euclidean distance field of the volume (gq_esdf, eight launches): -> a scene of the kind of ``.scene``
+        with the same geometry, which goes wherever a scene goes.  Outside the band it holds the signed distance to the zero
+        crossings of the volume, up to +-``max_distance``: it has a gradient deep inside obstacles and unobserved space, where
+        the fused value is flat, and ``scene_margin`` / ``approach_margin`` may now go up to ``max_distance`` instead of staying
+        below ``trunc``.  Inside the band (|D| < ``trunc``) the values remain the fused ones, bit for bit, and so remain
+        projective.  A grid knows only its own crossings: near the grid's border the distance to a surface outside it is
+        overestimated.  The volume is not written.  The output scene and the workspace are made at the first call, owned by the
+        volume and returned on every call (``out``: a scene of the same kind and geometry to write instead); after that no
+        allocation and no synchronisation, so the call can be captured in a graph behind ``integrate`` and a stepper built on
+        the returned scene reads the new field at its next replay."""
+        if out is None:
+            if getattr(self, "_esdf_scene", None) is None:
+                v = torch.empty_like(self._stack)
+                self._esdf_scene = (SceneSDFSet(v, self.origin, self.voxel, v.device) if isinstance(self.scene, SceneSDFSet)
+                                    else SceneSDF(v[0], self.origin, self.voxel, v.device))
+            out = self._esdf_scene
+        try:
+            return scene_esdf(self.scene, self.trunc, max_distance, out)
+        except ValueError as e:
+            raise ValueError(f"SceneTSDF.esdf: {e}") from None
+
+
+def scene_esdf(src, trunc, max_distance, out=None):
+    """The Euclidean distance field of a TSDF (gq_esdf, eight launches; include/graspqp_hip.h): ``src`` is an
+    ``ops.SceneSDF`` or an ``ops.SceneSDFSet`` whose values are a truncated signed distance, positive in free space, clamped to
+    +-``trunc`` (a ``SceneTSDF``'s ``.scene``, or the TSDF of a perception stack); -> a scene of the same kind and geometry.  A
+    node with |D| < ``trunc`` keeps D bit for bit, a non-finite node too; every other node gets the signed distance to the
+    nearest zero crossing of its grid along the grid edges' crossing points, held to [``trunc``, ``max_distance``], with the
+    sign of D.  ``src`` is not written.  ``out``: a scene of the same kind and geometry to write (not ``src``); it keeps the
+    workspace of its first call, so a further call with ``out`` allocates nothing and does not synchronise."""
+    if not isinstance(src, (SceneSDF, SceneSDFSet)):
+        raise ValueError(f"scene_esdf: src must be an ops.SceneSDF or an ops.SceneSDFSet, got {type(src).__name__}")
+    single = isinstance(src, SceneSDF)
+    stack = lambda s: s.values[None] if single else s.values
+    sg = _clutter_grids(stack(src), src.origin, src.voxel)
+    try:
+        need = _size_call("gq_esdf_workspace_bytes", ctypes.byref(sg))
+    except RuntimeError as e:
+        raise ValueError(f"scene_esdf: {e}") from None
+    if out is None:
+        v = torch.empty_like(src.values)
+        out = SceneSDF(v, src.origin, src.voxel, v.device) if single else SceneSDFSet(v, src.origin, src.voxel, v.device)
+    if type(out) is not type(src):
+        raise ValueError(f"scene_esdf: out must be an ops.{type(src).__name__} like src, got {type(out).__name__}")
+    ws = getattr(out, "_esdf_ws", None)
+    if ws is None or ws.numel() < need or ws.device != out.values.device:
+        ws = out._esdf_ws = _ws(need, out.values.device)
+    dg = _clutter_grids(stack(out), out.origin, out.voxel)
+    try:
+        _C.call("gq_esdf_check", ctypes.byref(sg), ctypes.byref(dg), float(trunc), float(max_distance), ctypes.c_void_p(ws.data_ptr()))
+    except RuntimeError as e:
+        raise ValueError(f"scene_esdf: {e}") from None
+    _Eager.scene_esdf(stack(src), list(src.origin), src.voxel, float(trunc), float(max_distance), stack(out), ws)
+    return out
 
 
 def keep_label(depth, labels, label):
@@ -2006,6 +2063,27 @@ def _(values, weight, origin, voxel, region, min_weight, trunc, points, normals,
     return None
 
 
+@_custom_op("graspqp_amd::scene_esdf", mutates_args=("out_values", "workspace"), device_types="cuda")
+def _scene_esdf_op(values: Tensor, origin: List[float], voxel: float, trunc: float, max_distance: float, out_values: Tensor,
+                   workspace: Tensor) -> None:
+    """gq_esdf: the Euclidean distance field of the TSDF stack values (G,nx,ny,nz) into out_values of the same shape (not values'
+    memory); workspace holds gq_esdf_workspace_bytes.  No gradient."""
+    if not (values.dim() == 4 and out_values.shape == values.shape):
+        raise RuntimeError("scene_esdf: values and out_values must be (G,nx,ny,nz) of one shape")
+    src, dst = _clutter_grids(values, origin, voxel), _clutter_grids(out_values, origin, voxel)
+    need = _size_call("gq_esdf_workspace_bytes", ctypes.byref(src))
+    if workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError(f"scene_esdf: workspace holds {workspace.numel() * workspace.element_size()} bytes, {need} are needed")
+    _C.f32(values)  # CUDA, contiguous, the element type the kernels read
+    _C.call("gq_esdf", ctypes.byref(src), ctypes.byref(dst), _C.f32(out_values), float(trunc), float(max_distance), _C.ptr(workspace),
+            _C.stream_ptr())
+
+
+@_scene_esdf_op.register_fake
+def _(values, origin, voxel, trunc, max_distance, out_values, workspace):
+    return None
+
+
 @_custom_op("graspqp_amd::self_pen", mutates_args=(), device_types="cuda")
 def _self_pen_op(centers: Tensor, hand: int) -> Tuple[Tensor, Tensor]:
     """E_spen (B,) of world sphere centres (B,S,3) and dE/dcentres (hand_model.py:989-1040)."""
@@ -2217,6 +2295,7 @@ _eager("approach_terms_set_backward", _approach_set_bwd_op)
 _eager("scene_compose", _scene_compose_op)
 _eager("tsdf_integrate", _tsdf_integrate_op)
 _eager("tsdf_surfels", _tsdf_surfels_op)
+_eager("scene_esdf", _scene_esdf_op)
 _eager("self_pen", _self_pen_op, _self_pen_bwd, _self_pen_setup)
 _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_distance_setup)
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)

@@ -735,6 +735,44 @@ int gq_tsdf_surfels(const gqClutterGrids* grids, const float* values /* = grids-
                     float* normals /* (G,capacity,3) device or NULL */, int64_t capacity, int32_t* count /* (G,2) device */,
                     void* workspace, void* stream);
 
+/* ---- Euclidean distance field from a fused TSDF (ESDF) ------------------------------------------------------------------
+ * A fused volume holds a truncated, projective distance: deeper than trunc inside an obstacle or inside unobserved space every
+ * node holds -trunc, the interpolant is flat there and E_scene / E_approach have no gradient; margins must stay below trunc.
+ * gq_esdf turns a gqClutterGrids stack `src` (values = D, positive in free space; n_grids = 1 is the single grid) into a second
+ * stack `dst` of the same n_grids, shape, origin and voxel that holds phi, a Euclidean signed distance up to max_distance.  src
+ * is not written; dst is memory the scene launches read unchanged.  Every test on D is an exact test on the fp32 inputs, trunc
+ * is compared as an fp32 value.  Per grid, h = voxel:
+ *   a node is VOID iff D is not finite: phi = D bit for bit (a NaN stays a NaN), and no edge with a void end is a crossing
+ *   a finite node is FREE iff D >= 0 (0.0 and -0.0 are free, as in gq_tsdf_surfels), else OCCUPIED
+ *   node a owns the edges to b = a + e_c, c = x, y, z; an edge is a CROSSING iff both ends are finite and exactly one is free --
+ *   unlike the surfel rule there is no |D| < trunc condition and no weight: the boundary between seen free space and unknown
+ *   (+.. | -trunc) is a crossing, and an edge between +trunc and -trunc crosses at t = 1/2
+ *   crossing point p = a + t e_c in node units, t = D_a / (D_a - D_b) in [0,1]
+ *   e(n) = h min over all crossing points p of the grid of |n - p|, +inf if the grid has no crossing
+ *   a node is IN BAND iff it is finite and |D| < trunc: phi = D bit for bit (the sub-voxel accuracy of the fused value is kept)
+ *   any other finite node: phi = s min(max(e, trunc), max_distance), s = +1 if free, -1 if occupied
+ * A grid knows only its own crossings: next to the grid's border, where the nearest surface point lies outside the grid, e is
+ * the distance to the nearest crossing inside it, which is larger.
+ * The computation separates exactly.  With g_c(n) = the distance along axis c from n to the nearest crossing on n's own c-line
+ * and env_a(f)(n) = min over m of f(n + m e_a) + m^2:
+ *   (e / h)^2 = min( env_x( min( env_y(g_z^2), env_z(g_y^2) ) ), env_y( env_z(g_x^2) ) )
+ * Because the output is clamped at max_distance, every 1-D pass looks at offsets |m| <= R = ceil(max_distance / h) only (seeds:
+ * crossings on edges within R + 1 nodes).  Eight launches (three seed passes, five envelope passes, the last of which finishes),
+ * windowed minima in a fixed order: no atomics, no block waits for another, no allocation, synchronisation or upload, bitwise
+ * reproducible, and a grid of a stack gets the bits of the single-grid call.  The call can sit in a captured graph behind
+ * gq_tsdf_integrate.  A block holds 16 whole lines of the pass axis in LDS, so an axis may have at most 1024 nodes; R <= 4096;
+ * n_grids x tiles of 16 lines <= 2^23 per launch.  workspace: gq_esdf_workspace_bytes(src) bytes on the device (three times the
+ * stack), contents irrelevant.  dst_values is dst->values, writable.
+ * gq_esdf_check (host only, no GPU) refuses: a NULL src, dst, values pointer or workspace; everything gq_clutter_check refuses
+ * for either stack; dst differing from src in n_grids, shape, origin or voxel; dst values aliasing src values; an axis longer
+ * than 1024 nodes; more than 2^23 tiles; trunc not finite or <= 0; max_distance not finite or < trunc; a window R > 4096.  The
+ * message starts with "esdf:" and names the argument.                                                                   */
+int gq_esdf_check(const gqClutterGrids* src, const gqClutterGrids* dst, float trunc, float max_distance,
+                  const void* workspace /* only tested against NULL */);
+int gq_esdf_workspace_bytes(const gqClutterGrids* src, size_t* bytes);
+int gq_esdf(const gqClutterGrids* src, const gqClutterGrids* dst, float* dst_values /* = dst->values, writable */, float trunc,
+            float max_distance, void* workspace, void* stream);
+
 /* ---- (re-)initialisation: initialize_convex_hull, core/initializations.py:15-193 (scripts/fit.py:315,408-422) --------
  * Per object: samples_per_object points on its convex hull (area-weighted), pushed out by `inflate` (0.01 in the
  * reference) along the face normal; farthest-point sampling of batch_each of them (start = sample 0); per row the look-at
