@@ -1,5 +1,6 @@
-"""Seeded inputs of one gq_fk_backward call and the call itself through the C ABI, shared by
-tests/test_gpu_fk_backward_block.py and tools/make_golden_fk_backward.py (which records the outputs of a given library).
+"""Seeded inputs of one gq_fk_backward call, the call itself through the C ABI and its check against the oracle, shared by
+tests/test_gpu_fk_backward_block.py, tests/test_gpu_kinematics_limits.py and tools/make_golden_fk_backward.py (which records
+the outputs of a given library).
 
 Inputs are numpy arrays from np.random.RandomState (a frozen stream); the kinematic state (Rg, link_T, node frames) comes
 from gq_fk_forward on the same pose, or from the fixture.  Every gradient input and the energy / accept tail are optional,
@@ -14,9 +15,11 @@ WEIGHTS = dict(w_dis=100.0, w_fc=1.0, w_pen=100.0, w_spen=10.0, w_joints=1.0)
 N_TERMS = 5
 
 
-def make_inputs(spec, B, n, seed):
+def make_inputs(spec, B, n, seed, joint_scale=None):
     """Pose near the default state with some joints beyond their limits (E_joints and its gradient are non-zero), contact
-    indices, all seven gradient inputs, the contact records of the energy tail and the accepted state of the accept step."""
+    indices, all seven gradient inputs, the contact records of the energy tail and the accepted state of the accept step.
+    joint_scale (JA,): the joint noise and the excursion beyond the limits in units of a +-0.3 rad joint (hands with
+    millimetre prismatic joints); None = 1, the stream of draws is the same either way."""
     r = np.random.RandomState(seed)
     f = lambda *s: r.standard_normal(s).astype(np.float32)
     JA = spec.n_dofs  # actuated joints = pose dimension - 9
@@ -24,7 +27,8 @@ def make_inputs(spec, B, n, seed):
     t = f(B, 3)
     t = 0.12 * t / np.linalg.norm(t, axis=1, keepdims=True)
     lo, hi = np.asarray(spec.joints_lower, np.float32), np.asarray(spec.joints_upper, np.float32)
-    th = np.clip(np.asarray(spec.default_state, np.float32)[None, :JA] + 0.3 * f(B, JA), lo - 0.2, hi + 0.2)
+    sc = np.ones(JA, np.float32) if joint_scale is None else np.asarray(joint_scale, np.float32)
+    th = np.clip(np.asarray(spec.default_state, np.float32)[None, :JA] + 0.3 * (sc * f(B, JA)), lo - 0.2 * sc, hi + 0.2 * sc)
     inp = dict(hand_pose=np.concatenate([t, f(B, 6), th], 1).astype(np.float32),
                idx=r.randint(0, spec.n_contact_candidates, (B, n)).astype(np.int64),
                g_cpts=f(B, n, 3), g_cnrm=f(B, n, 3), g_spheres=f(B, max(S, 1), 3)[:, :S], g_wrench=f(B, L, 6), g_Rt=f(B, 12),
@@ -110,3 +114,80 @@ def run_backward(C, hand, inp, present=GRAD_INPUTS, tail=True):
                    accept=accept.cpu().numpy(), pose=pose.cpu().numpy(), grad=grad.cpu().numpy(), idx=idx.cpu().numpy(),
                    terms=terms.cpu().numpy(), energy=energy.cpu().numpy(), temperature=temperature.cpu().numpy())
     return out
+
+
+def oracle_grad(spec, inp, present, tail, seed, dtype=torch.float64):
+    """-> (d loss / d hand_pose by autograd through oracle/ref_cpu in `dtype`, the inputs with g_wrench / g_Rt replaced by those
+    of the loss).  Loss: sum(cp . g_cpts) + sum(cn . g_cnrm) + sum(spheres . g_spheres) + sum(R . g_R) + sum(theta . g_theta) +
+    a linear energy on link-fixed points (its hand-frame link wrenches (f, x cross f) are the kernel's g_wrench) + a linear
+    energy on world points seen from the hand frame (its [gsum, K] is the kernel's g_Rt) + w_joints E_joints with the tail.
+    The random constants of the loss are drawn in fp64 and cast, so every dtype differentiates the same loss."""
+    from ref_cpu import kin as okin
+    from ref_cpu import models as omodels
+
+    B, n = inp["idx"].shape
+    L = spec.n_links
+    td = lambda k: torch.tensor(inp[k], dtype=dtype)
+    hp = td("hand_pose").requires_grad_()
+    oh = omodels.OracleHand(spec, dtype)
+    oh.set_parameters(hp, torch.tensor(inp["idx"]))
+    T, R, t = oh.current_status, oh.global_rotation, oh.global_translation
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64).to(dtype)
+    q, w = 0.02 * rn(L, 3, 3), rn(B, L, 3, 3)  # three link-fixed points per link, a constant force on each
+    x = (T[:, :, None, :3, :3] @ q[None, :, :, :, None]).squeeze(-1) + T[:, :, None, :3, 3]
+    P, d = 0.1 * rn(B, 8, 3), rn(B, 8, 3)      # world points, constant hand-frame gradients
+    xh = (P - t[:, None]) @ R
+    inp = dict(inp)
+    inp["g_wrench"] = torch.cat([w.sum(2), torch.cross(x.detach(), w, dim=-1).sum(2)], -1).float().numpy()
+    inp["g_Rt"] = torch.cat([d.sum(1), torch.einsum("bpk,bpj->bkj", xh.detach(), d).reshape(B, 9)], 1).float().numpy()
+    sph = okin.sphere_centers_world(spec, T, R, t)
+    terms = dict(g_cpts=lambda: (oh.contact_points * td("g_cpts")).sum(), g_cnrm=lambda: (oh.contact_normals * td("g_cnrm")).sum(),
+                 g_spheres=lambda: (sph * td("g_spheres")).sum() if spec.n_spheres else hp.sum() * 0.0,
+                 g_wrench=lambda: (x * w).sum(), g_Rt=lambda: (xh * d).sum(), g_theta=lambda: (hp[:, 9:] * td("g_theta")).sum(),
+                 g_R=lambda: (R.reshape(B, 9) * td("g_R")).sum())
+    loss = hp.sum() * 0.0
+    for k in present:
+        loss = loss + terms[k]()
+    if tail:
+        lo, hi = (torch.tensor(np.asarray(a, np.float64)).to(dtype) for a in (spec.joints_lower, spec.joints_upper))
+        loss = loss + WEIGHTS["w_joints"] * (torch.relu(hp[:, 9:] - hi) + torch.relu(lo - hp[:, 9:])).sum()
+    loss.backward()
+    return hp.grad.numpy(), inp
+
+
+def check(C, spec, hand, B, n, seed, present=GRAD_INPUTS, tail=True, joint_scale=None, fp32_floor=False):
+    """gq_fk_backward on make_inputs against the fp64 oracle: 1e-4 on the norm, rtol 2e-3 / atol 2e-4 per element, E_joints,
+    the accept flags.  fp32_floor: the same oracle in float32 on the same inputs gives the noise floor of an fp32 evaluation
+    (its error against the fp64 run); the kernel is allowed the larger of the tolerances above and 4 x that floor -- 2 x because
+    two independent fp32 evaluations can sit on opposite sides of the truth, 2 x for another association order and fused
+    multiply-adds.  -> the inputs (with the forward state), the outputs and the measured errors."""
+    from _parity import rel_err
+
+    inp0 = make_inputs(spec, B, n, seed, joint_scale)
+    go, inp = oracle_grad(spec, inp0, present, tail, seed + 1000)
+    inp.update(forward_state(C, hand, inp))
+    out = run_backward(C, hand, inp, present=present, tail=tail)
+    gg = out["grad_pose"]
+    nrm = np.linalg.norm(gg - go) / np.linalg.norm(go)
+    print(f"{spec.name} B={B} n={n} present={present} tail={tail}: norm-wise {nrm:.3g}, max abs {np.abs(gg - go).max():.3g}, "
+          f"max rel {rel_err(gg, go, 1e-2).max():.3g}")
+    err = dict(norm=nrm, max_abs=np.abs(gg - go).max(), floor_norm=0.0, floor_abs=0.0)
+    if not fp32_floor:
+        assert nrm < 1e-4
+        np.testing.assert_allclose(gg, go, rtol=2e-3, atol=2e-4)
+    else:
+        g32, _ = oracle_grad(spec, inp0, present, tail, seed + 1000, dtype=torch.float32)
+        err["floor_norm"] = np.linalg.norm(g32 - go) / np.linalg.norm(go)
+        err["floor_abs"] = np.abs(g32 - go).max()
+        print(f"{spec.name}: fp32 oracle against its fp64 self: norm-wise {err['floor_norm']:.3g}, max abs {err['floor_abs']:.3g}")
+        assert nrm < max(1e-4, 4 * err["floor_norm"])
+        allowed = np.maximum(2e-4 + 2e-3 * np.abs(go), 4 * err["floor_abs"])
+        bad = np.abs(gg - go) > allowed
+        assert not bad.any(), f"{bad.sum()} elements beyond max(rtol 2e-3 / atol 2e-4, 4 x fp32 floor {err['floor_abs']:.3g})"
+    if tail:
+        assert set(out["accept"].tolist()) <= {0, 1} and np.isfinite(out["total"]).all()
+        th = inp["hand_pose"][:, 9:].astype(np.float64)
+        ej = np.maximum(th - np.asarray(spec.joints_upper, np.float64), 0) + np.maximum(np.asarray(spec.joints_lower, np.float64) - th, 0)
+        np.testing.assert_allclose(out["e_joints"], ej.sum(1), rtol=1e-5, atol=1e-6)
+    return inp, out, err

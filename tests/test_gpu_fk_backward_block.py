@@ -3,7 +3,7 @@ block takes another path (one / many / more than 64 items, more than 128 fold ta
 absent, the glue route of ops._HandPen), and bit for bit against the outputs the parent commit's single-wavefront kernel
 gave on the same inputs (tests/golden/fk_backward_parent_bits.npz, written by tools/make_golden_fk_backward.py).
 
-Oracle loss, fp64 autograd through oracle/ref_cpu: sum(cp . g_cpts) + sum(cn . g_cnrm) + sum(spheres . g_spheres) + sum(R . g_R)
+Oracle loss (fkb.oracle_grad), fp64 autograd through oracle/ref_cpu: sum(cp . g_cpts) + sum(cn . g_cnrm) + sum(spheres . g_spheres) + sum(R . g_R)
 + sum(theta . g_theta) + a linear energy on link-fixed points (its hand-frame link wrenches (f, x cross f) are the kernel's
 g_wrench) + a linear energy on world points seen from the hand frame (its [gsum, K] is the kernel's g_Rt) + w_joints E_joints
 when the energy tail rides along.  Tolerances: those of test_gpu_parity.py::test_fk_contacts_forward_backward (1e-4 on the
@@ -16,11 +16,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from ref_cpu import kin as okin  # noqa: E402
 from ref_cpu import models as omodels  # noqa: E402
 
 import _fk_backward_case as fkb  # noqa: E402
-from _parity import rel_err  # noqa: E402
 from graspqp_amd.hands import get_hand_spec  # noqa: E402
 from graspqp_amd.utils import meshes  # noqa: E402
 
@@ -43,56 +41,10 @@ def _hand(gq, name):
     return _hands[name]
 
 
-def _oracle_grad(spec, inp, present, tail, seed):
-    """-> (fp64 d loss / d hand_pose, the inputs with g_wrench / g_Rt replaced by those of the loss)."""
-    B, n = inp["idx"].shape
-    L = spec.n_links
-    t64 = lambda k: torch.tensor(inp[k], dtype=torch.float64)
-    hp = t64("hand_pose").requires_grad_()
-    oh = omodels.OracleHand(spec, torch.float64)
-    oh.set_parameters(hp, torch.tensor(inp["idx"]))
-    T, R, t = oh.current_status, oh.global_rotation, oh.global_translation
-    g = torch.Generator().manual_seed(seed)
-    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
-    q, w = 0.02 * rn(L, 3, 3), rn(B, L, 3, 3)  # three link-fixed points per link, a constant force on each
-    x = (T[:, :, None, :3, :3] @ q[None, :, :, :, None]).squeeze(-1) + T[:, :, None, :3, 3]
-    P, d = 0.1 * rn(B, 8, 3), rn(B, 8, 3)      # world points, constant hand-frame gradients
-    xh = (P - t[:, None]) @ R
-    inp = dict(inp)
-    inp["g_wrench"] = torch.cat([w.sum(2), torch.cross(x.detach(), w, dim=-1).sum(2)], -1).float().numpy()
-    inp["g_Rt"] = torch.cat([d.sum(1), torch.einsum("bpk,bpj->bkj", xh.detach(), d).reshape(B, 9)], 1).float().numpy()
-    sph = okin.sphere_centers_world(spec, T, R, t)
-    terms = dict(g_cpts=lambda: (oh.contact_points * t64("g_cpts")).sum(), g_cnrm=lambda: (oh.contact_normals * t64("g_cnrm")).sum(),
-                 g_spheres=lambda: (sph * t64("g_spheres")).sum() if spec.n_spheres else hp.sum() * 0.0,
-                 g_wrench=lambda: (x * w).sum(), g_Rt=lambda: (xh * d).sum(), g_theta=lambda: (hp[:, 9:] * t64("g_theta")).sum(),
-                 g_R=lambda: (R.reshape(B, 9) * t64("g_R")).sum())
-    loss = hp.sum() * 0.0
-    for k in present:
-        loss = loss + terms[k]()
-    if tail:
-        lo, hi = (torch.tensor(np.asarray(a, np.float64)) for a in (spec.joints_lower, spec.joints_upper))
-        loss = loss + fkb.WEIGHTS["w_joints"] * (torch.relu(hp[:, 9:] - hi) + torch.relu(lo - hp[:, 9:])).sum()
-    loss.backward()
-    return hp.grad.numpy(), inp
-
-
 def _check(gq, hand_name, B, n, seed, present=fkb.GRAD_INPUTS, tail=True):
-    spec = get_hand_spec(hand_name)
-    hand = _hand(gq, hand_name)
-    go, inp = _oracle_grad(spec, fkb.make_inputs(spec, B, n, seed), present, tail, seed + 1000)
-    inp.update(fkb.forward_state(gq.C, hand, inp))
-    out = fkb.run_backward(gq.C, hand, inp, present=present, tail=tail)
-    gg = out["grad_pose"]
-    nrm = np.linalg.norm(gg - go) / np.linalg.norm(go)
-    print(f"{hand_name} B={B} n={n} present={present} tail={tail}: norm-wise {nrm:.3g}, max abs {np.abs(gg - go).max():.3g}, "
-          f"max rel {rel_err(gg, go, 1e-2).max():.3g}")
-    assert nrm < 1e-4
-    np.testing.assert_allclose(gg, go, rtol=2e-3, atol=2e-4)
-    if tail:
-        assert set(out["accept"].tolist()) <= {0, 1} and np.isfinite(out["total"]).all()
-        th = inp["hand_pose"][:, 9:].astype(np.float64)
-        ej = np.maximum(th - np.asarray(spec.joints_upper, np.float64), 0) + np.maximum(np.asarray(spec.joints_lower, np.float64) - th, 0)
-        np.testing.assert_allclose(out["e_joints"], ej.sum(1), rtol=1e-5, atol=1e-6)
+    """fkb.check (tests/_fk_backward_case.py, shared with the synthetic hands of test_gpu_kinematics_limits.py) on a shipped
+    hand, with the fixed tolerances."""
+    fkb.check(gq.C, get_hand_spec(hand_name), _hand(gq, hand_name), B, n, seed, present=present, tail=tail)
 
 
 @pytest.mark.parametrize("n", [1, 12, 70])  # 70 contacts + the spheres: more than 64 items, the second pass of the item loop
