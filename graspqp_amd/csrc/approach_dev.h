@@ -5,7 +5,7 @@
 //  - the default calls gq_scene_sample (scene_dev.h) once per station: it locates, loads and interpolates in one body, so a lane
 //    waits for a station's gathers before it can address the next;
 //  - with -DGQ_APPROACH_ROTATED (a variant build: GQ_EXTRA_FLAGS / GQ_OUT_DIR of build.sh) the same steps are three pieces --
-//    gq_ap_locate (the tests and the cell, by scene_dev.h's own gq_scene_finite / gq_scene_axis_in / gq_scene_axis), gq_ap_load
+//    gq_ap_locate (the tests and the cell, by gq_finite and scene_dev.h's own gq_scene_axis_in / gq_scene_axis), gq_ap_load
 //    (the 8 nodes) and gq_ap_interp (the fmaf chains of gq_scene_sample, copied term for term) -- and the loop is rotated: the
 //    loads of station k + 1 are issued before station k's are interpolated and consumed.  DESIGN 15 has both code objects'
 //    figures and the launch times.
@@ -26,7 +26,7 @@ struct GqApNodes {
 __device__ __forceinline__ GqApCell gq_ap_locate(const gqSceneGrid& g, gq3 x) {
   GqApCell c;
   c.v = g.values, c.fx = c.fy = c.fz = 0.0f;
-  if (!(gq_scene_finite(x.x) && gq_scene_finite(x.y) && gq_scene_finite(x.z))) {
+  if (!(gq_finite(x.x) && gq_finite(x.y) && gq_finite(x.z))) {
     c.where = GQ_SCENE_NONFINITE;
     return c;
   }

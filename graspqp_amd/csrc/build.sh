@@ -29,12 +29,12 @@ deps() {  # headers each translation unit includes
     kin) echo "common.h setup.h cluster_bound.h loop_dev.h sdf_dev.h tri.h kin_dev.h wave.h" ;;
     tabletop) echo "common.h" ;;
     cloud) echo "common.h setup.h cluster_bound.h" ;;
-    scene) echo "common.h scene_dev.h scene_row_dev.h" ;;
-    approach) echo "common.h scene_dev.h approach_dev.h approach_row_dev.h" ;;
-    clutter) echo "common.h scene_dev.h approach_dev.h scene_row_dev.h approach_row_dev.h clutter_dev.h" ;;
-    tsdf) echo "common.h scene_dev.h clutter_dev.h tsdf_dev.h" ;;
-    surfel) echo "common.h scene_dev.h clutter_dev.h surfel_dev.h" ;;
-    edt) echo "common.h edt_dev.h" ;;
+    scene) echo "common.h grid_stack.h scene_dev.h scene_row_dev.h" ;;
+    approach) echo "common.h grid_stack.h scene_dev.h approach_dev.h approach_row_dev.h" ;;
+    clutter) echo "common.h grid_stack.h scene_dev.h approach_dev.h scene_row_dev.h approach_row_dev.h clutter_dev.h" ;;
+    tsdf) echo "common.h grid_stack.h scene_dev.h clutter_dev.h tsdf_dev.h" ;;
+    surfel) echo "common.h grid_stack.h scene_dev.h clutter_dev.h surfel_dev.h" ;;
+    edt) echo "common.h grid_stack.h edt_dev.h" ;;
     *) echo "common.h" ;;
   esac
 }

@@ -10,9 +10,9 @@
 //    costs a launch per object and iteration.
 //  - gq_clutter_query_kernel is gq_scene_query_kernel with the grid picked per point.
 //  - gq_clutter_compose_kernel writes the stack: node (g,i,j,k) = min(far, base, every part but exclude[g]) resampled at the
-//    node's world position (clutter_dev.h).  One thread per node, a block is a 4 x 4 x 16 tile of one grid with the lane along
-//    z.  Lane p < n_parts of wavefront 0 first tests part p against the tile (gq_clutter_culled); a part that no node of the
-//    tile can reach costs the block no loads.  Poses and exclude are read from device memory at launch: no upload, no
+//    node's world position (clutter_dev.h).  One thread per node, a block is a tile of one grid (grid_stack.h: the stack, the
+//    tile and the decode).  Lane p < n_parts of wavefront 0 first tests part p against the tile (gq_clutter_culled); a part
+//    that no node of the tile can reach costs the block no loads.  Poses and exclude are read from device memory at launch: no upload, no
 //    allocation, no synchronisation, so the launch can sit in a captured graph and a replay recomposes after an in-place
 //    pose update.  Parts in ascending order, no atomics: bitwise reproducible run to run.
 #include "approach_row_dev.h"
@@ -21,19 +21,13 @@
 
 #define GQ_CL_MAX_GRIDS 65536
 
-__device__ __forceinline__ gqSceneGrid gq_clutter_pick(const gqSceneGrid& first, size_t g) {
-  gqSceneGrid grid = first;
-  grid.values += g * ((size_t)first.nx * (size_t)first.ny * (size_t)first.nz);
-  return grid;
-}
-
 struct GqClutterArgs {
   GqSceneArgs a;  // a.grid is grid 0 of the stack
   int rows_per_grid;
 };
 
 __global__ __launch_bounds__(GQ_SC_WAVES * GQ_WAVE) void gq_clutter_kernel(const GqClutterArgs c) {
-  const gqSceneGrid grid = gq_clutter_pick(c.a.grid, blockIdx.x / (unsigned)c.rows_per_grid);
+  const gqSceneGrid grid = gq_stack_grid(c.a.grid, blockIdx.x / (unsigned)c.rows_per_grid);
   gq_scene_row(c.a, grid);
 }
 
@@ -43,7 +37,7 @@ struct GqCorridorArgs {
 };
 
 __global__ __launch_bounds__(GQ_AP_WAVES * GQ_WAVE) void gq_clutter_corridor_kernel(const GqCorridorArgs c) {
-  const gqSceneGrid grid = gq_clutter_pick(c.a.grid, blockIdx.x / (unsigned)c.rows_per_grid);
+  const gqSceneGrid grid = gq_stack_grid(c.a.grid, blockIdx.x / (unsigned)c.rows_per_grid);
   gq_approach_row(c.a, grid);
 }
 
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(256) void gq_clutter_query_kernel(const gqSceneGrid
                                                                float* __restrict__ grad, uint8_t* __restrict__ inside) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  const gqSceneGrid grid = gq_clutter_pick(first, (size_t)(i / points_per_grid));
+  const gqSceneGrid grid = gq_stack_grid(first, (size_t)(i / points_per_grid));
   const gq3 x = gq_mk(points[i * 3], points[i * 3 + 1], points[i * 3 + 2]);
   float f = GQ_INF_F;  // outside the volume: free space
   gq3 gp = gq_mk(0, 0, 0);
@@ -73,21 +67,15 @@ struct GqComposeArgs {
   gqSceneGrid parts[GQ_CL_MAX_PARTS];
   gqSceneGrid base;
   int n_parts, has_base;
-  int tiles_x, tiles_y, tiles_z;
+  GqTiling tiling;
   float far;
 };
 
-__global__ __launch_bounds__(GQ_CL_TX* GQ_CL_TY* GQ_CL_TZ) void gq_clutter_compose_kernel(const GqComposeArgs c) {
-  // block -> (grid, tile): all of it block-uniform
-  unsigned b = blockIdx.x;
-  const int tk = (int)(b % (unsigned)c.tiles_z);
-  b /= (unsigned)c.tiles_z;
-  const int tj = (int)(b % (unsigned)c.tiles_y);
-  b /= (unsigned)c.tiles_y;
-  const int ti = (int)(b % (unsigned)c.tiles_x);
-  const size_t g = b / (unsigned)c.tiles_x;
+__global__ __launch_bounds__(GQ_CL_THREADS) void gq_clutter_compose_kernel(const GqComposeArgs c) {
+  const GqTile t = gq_tile_of(blockIdx.x, c.tiling);  // block-uniform
+  const size_t g = t.g;
   const float* Tg = c.target_T + g * 12;
-  const int i0 = ti * GQ_CL_TX, j0 = tj * GQ_CL_TY, k0 = tk * GQ_CL_TZ;
+  const int i0 = t.i0, j0 = t.j0, k0 = t.k0;
   const int tid = threadIdx.x;
   const int exclude = c.exclude ? c.exclude[g] : -1;
 #ifndef GQ_CLUTTER_NO_CULL
@@ -102,40 +90,26 @@ __global__ __launch_bounds__(GQ_CL_TX* GQ_CL_TY* GQ_CL_TZ) void gq_clutter_compo
 #else  // a variant build for measurements and for the equality test: every part is sampled by every tile
   const unsigned live = 0xffffffffu;
 #endif
-  const int i = i0 + tid / (GQ_CL_TY * GQ_CL_TZ), j = j0 + (tid / GQ_CL_TZ) % GQ_CL_TY, k = k0 + tid % GQ_CL_TZ;
-  if (i >= c.out.nx || j >= c.out.ny || k >= c.out.nz) return;
+  int i, j, k;
+  if (!gq_tile_node(t, tid, c.out.nx, c.out.ny, c.out.nz, i, j, k)) return;
   const float v = gq_clutter_node(c.out, Tg, i, j, k, c.parts, c.n_parts, c.part_T, exclude, live, c.has_base ? &c.base : nullptr, c.far);
   c.out_values[((g * c.out.nx + i) * c.out.ny + j) * c.out.nz + k] = v;
-}
-
-// gq_scene_check's refusal, retold under this unit's name (and with `what` naming the grid it was about)
-static int gq_clutter_retell(const char* what) {
-  char why[400];
-  snprintf(why, sizeof(why), "%s", gq_last_error());
-  GQ_FAIL(GQ_ERR_ARG, "clutter: %s: %s", what, why);
-}
-
-static gqSceneGrid gq_clutter_first(const gqClutterGrids* grids) {
-  gqSceneGrid g{};
-  g.values = grids->values, g.nx = grids->nx, g.ny = grids->ny, g.nz = grids->nz, g.voxel = grids->voxel;
-  for (int a = 0; a < 3; ++a) g.origin[a] = grids->origin[a];
-  return g;
 }
 
 static int gq_clutter_check_grids(const gqClutterGrids* grids) {
   GQ_REQUIRE(grids, "clutter: grids is NULL");
   GQ_REQUIRE(grids->n_grids >= 1 && grids->n_grids <= GQ_CL_MAX_GRIDS, "clutter: n_grids must be in 1..%d, got %d", GQ_CL_MAX_GRIDS,
              grids->n_grids);
-  const gqSceneGrid first = gq_clutter_first(grids);  // shape, origin and voxel are shared: one check holds for every grid
-  if (gq_scene_check(&first, 1, 1, 1) != GQ_OK) return gq_clutter_retell("grids");
+  const gqSceneGrid first = gq_stack_grid(grids);  // shape, origin and voxel are shared: one check holds for every grid
+  if (gq_scene_check(&first, 1, 1, 1) != GQ_OK) return gq_retell("clutter", "grids");
   return GQ_OK;
 }
 
 int gq_clutter_check(const gqClutterGrids* grids, int64_t batch, int rows_per_grid, int n_links, int64_t n_samples) {
   const int rc = gq_clutter_check_grids(grids);
   if (rc != GQ_OK) return rc;
-  const gqSceneGrid first = gq_clutter_first(grids);
-  if (gq_scene_check(&first, batch, n_links, n_samples) != GQ_OK) return gq_clutter_retell("launch");
+  const gqSceneGrid first = gq_stack_grid(grids);
+  if (gq_scene_check(&first, batch, n_links, n_samples) != GQ_OK) return gq_retell("clutter", "launch");
   GQ_REQUIRE(rows_per_grid >= 1, "clutter: rows_per_grid must be >= 1, got %d", rows_per_grid);
   GQ_REQUIRE(batch == (int64_t)grids->n_grids * rows_per_grid, "clutter: batch must be n_grids * rows_per_grid = %d * %d, got %lld",
              grids->n_grids, rows_per_grid, (long long)batch);
@@ -152,7 +126,7 @@ int gq_clutter_terms(const gqClutterGrids* grids, int rows_per_grid, float margi
   GQ_REQUIRE(margin >= 0.0f && margin < GQ_INF_F, "clutter: margin must be finite and >= 0, got %g", (double)margin);
   GqClutterArgs c{};
   GqSceneArgs& a = c.a;
-  a.grid = gq_clutter_first(grids);
+  a.grid = gq_stack_grid(grids);
   a.samples = samples, a.sample_link = sample_link, a.hand_pose = hand_pose, a.Rg = Rg, a.link_T = link_T;
   a.up_scene = up_scene;
   a.Ns = (int)n_samples, a.L = n_links, a.D = pose_dim;
@@ -172,9 +146,9 @@ int gq_clutter_corridor_terms(const gqClutterGrids* grids, int rows_per_grid, fl
                               float* link_wrench, float* gRt, void* stream) {
   const int rc = gq_clutter_check(grids, batch, rows_per_grid, n_links, n_samples);
   if (rc != GQ_OK) return rc;
-  const gqSceneGrid first = gq_clutter_first(grids);
+  const gqSceneGrid first = gq_stack_grid(grids);
   if (gq_approach_check(&first, batch, n_links, n_samples, distance, n_stations, grasp_axis) != GQ_OK)
-    return gq_clutter_retell("corridor");
+    return gq_retell("clutter", "corridor");
   GQ_REQUIRE(samples && sample_link && hand_pose && Rg && link_T && pose_dim >= 9, "clutter: bad arguments");
   GQ_REQUIRE(margin >= 0.0f && margin < GQ_INF_F, "clutter: margin must be finite and >= 0, got %g", (double)margin);
   GqCorridorArgs c{};
@@ -204,33 +178,28 @@ int gq_clutter_query(const gqClutterGrids* grids, const float* points, int64_t n
   if (n_points == 0) return GQ_OK;
   GQ_REQUIRE(points && phi, "clutter: points / phi is NULL");
   hipLaunchKernelGGL(gq_clutter_query_kernel, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     gq_clutter_first(grids), points_per_grid, points, n_points, phi, grad, inside);
+                     gq_stack_grid(grids), points_per_grid, points, n_points, phi, grad, inside);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }
-
-static long long gq_clutter_tiles(int n, int t) { return ((long long)n + t - 1) / t; }
 
 int gq_clutter_compose_check(const gqClutterGrids* out, const gqSceneGrid* parts, int n_parts, const gqSceneGrid* base, float far) {
   GQ_REQUIRE(out, "clutter: compose: out is NULL");
   GQ_REQUIRE(out->n_grids >= 1 && out->n_grids <= GQ_CL_MAX_GRIDS, "clutter: compose: out n_grids must be in 1..%d, got %d",
              GQ_CL_MAX_GRIDS, out->n_grids);
-  const gqSceneGrid first = gq_clutter_first(out);
-  if (gq_scene_check(&first, 1, 1, 1) != GQ_OK) return gq_clutter_retell("compose: out");
-  const long long blocks = out->n_grids * gq_clutter_tiles(out->nx, GQ_CL_TX) * gq_clutter_tiles(out->ny, GQ_CL_TY) *
-                           gq_clutter_tiles(out->nz, GQ_CL_TZ);
-  GQ_REQUIRE(blocks <= (1ll << 23), "clutter: compose: out has %lld tiles of %d x %d x %d nodes, at most 2^23 per launch", blocks,
-             GQ_CL_TX, GQ_CL_TY, GQ_CL_TZ);
+  const gqSceneGrid first = gq_stack_grid(out);
+  if (gq_scene_check(&first, 1, 1, 1) != GQ_OK) return gq_retell("clutter", "compose: out");
+  if (gq_tiling_check(out, "clutter: compose: out") != GQ_OK) return GQ_ERR_ARG;
   GQ_REQUIRE(n_parts >= 0 && n_parts <= GQ_CL_MAX_PARTS, "clutter: compose: n_parts must be in 0..%d, got %d", GQ_CL_MAX_PARTS,
              n_parts);
   GQ_REQUIRE(n_parts == 0 || parts, "clutter: compose: parts is NULL");
   GQ_REQUIRE(n_parts > 0 || base, "clutter: compose: n_parts == 0 needs a base");
-  if (base && gq_scene_check(base, 1, 1, 1) != GQ_OK) return gq_clutter_retell("compose: base");
+  if (base && gq_scene_check(base, 1, 1, 1) != GQ_OK) return gq_retell("clutter", "compose: base");
   for (int p = 0; p < n_parts; ++p)
     if (gq_scene_check(parts + p, 1, 1, 1) != GQ_OK) {
       char what[48];
       snprintf(what, sizeof(what), "compose: parts[%d]", p);
-      return gq_clutter_retell(what);
+      return gq_retell("clutter", what);
     }
   GQ_REQUIRE(far > -GQ_INF_F && far < GQ_INF_F, "clutter: compose: far must be finite, got %g", (double)far);
   return GQ_OK;
@@ -244,18 +213,17 @@ int gq_clutter_compose(const gqClutterGrids* out, float* out_values, const float
   GQ_REQUIRE(target_T, "clutter: compose: target_T is NULL");
   GQ_REQUIRE(n_parts == 0 || part_T, "clutter: compose: part_T is NULL");
   GqComposeArgs c{};
-  c.out = gq_clutter_first(out);
+  c.out = gq_stack_grid(out);
   c.out_values = out_values;
   c.target_T = target_T, c.part_T = part_T, c.exclude = exclude;
   for (int p = 0; p < n_parts; ++p) c.parts[p] = parts[p];
   c.n_parts = n_parts;
   c.has_base = base != nullptr;
   if (base) c.base = *base;
-  c.tiles_x = (int)gq_clutter_tiles(out->nx, GQ_CL_TX), c.tiles_y = (int)gq_clutter_tiles(out->ny, GQ_CL_TY);
-  c.tiles_z = (int)gq_clutter_tiles(out->nz, GQ_CL_TZ);
+  c.tiling = gq_tiling(out->nx, out->ny, out->nz);
   c.far = far;
-  const long long blocks = (long long)out->n_grids * c.tiles_x * c.tiles_y * c.tiles_z;
-  hipLaunchKernelGGL(gq_clutter_compose_kernel, dim3((unsigned)blocks), dim3(GQ_CL_TX * GQ_CL_TY * GQ_CL_TZ), 0, (hipStream_t)stream, c);
+  const long long blocks = gq_tiling_blocks(c.tiling, out->n_grids);  // <= 2^23: gq_tiling_check
+  hipLaunchKernelGGL(gq_clutter_compose_kernel, dim3((unsigned)blocks), dim3(GQ_CL_THREADS), 0, (hipStream_t)stream, c);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

@@ -11,11 +11,7 @@
 #pragma once
 #include "scene_dev.h"
 
-#define GQ_CL_MAX_PARTS 32
-// a block is a tile of 4 x 4 x 16 nodes of one grid: lane along z (64-byte store segments), a wavefront is one x slab
-#define GQ_CL_TX 4
-#define GQ_CL_TY 4
-#define GQ_CL_TZ 16
+#define GQ_CL_MAX_PARTS 32  // a block is a tile of one grid: GQ_CL_TX/TY/TZ and its decode are grid_stack.h's
 
 __device__ __forceinline__ gq3 gq_clutter_world(const gqSceneGrid& out, const float* Tg, float fi, float fj, float fk) {
   const gq3 xf = gq_mk(fmaf(out.voxel, fi, out.origin[0]), fmaf(out.voxel, fj, out.origin[1]), fmaf(out.voxel, fk, out.origin[2]));
@@ -73,7 +69,7 @@ __device__ __forceinline__ float gq_clutter_node(const gqSceneGrid& out, const f
                                                  int n_parts, const float* part_T, int exclude, unsigned live, const gqSceneGrid* base,
                                                  float far) {
   const gq3 xw = gq_clutter_world(out, Tg, (float)i, (float)j, (float)k);
-  if (!(gq_scene_finite(xw.x) && gq_scene_finite(xw.y) && gq_scene_finite(xw.z))) return __builtin_nanf("");
+  if (!(gq_finite(xw.x) && gq_finite(xw.y) && gq_finite(xw.z))) return __builtin_nanf("");
   float m = far;
   bool bad = false;
   gq3 unused = gq_mk(0, 0, 0);

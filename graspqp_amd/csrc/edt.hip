@@ -25,10 +25,10 @@ struct GqEdtArgs {
 // block -> (grid, tile of the grid): block-uniform; the pointers move to the block's grid
 __device__ __forceinline__ int gq_edt_block(GqEdtArgs& c) {
   const unsigned b = blockIdx.x;
-  const size_t at = (size_t)(b / (unsigned)c.tiles) * c.nodes;  // grid < n_grids
-  c.in += at, c.out += at;
-  if (c.other) c.other += at;
-  if (c.src) c.src += at;
+  const size_t g = b / (unsigned)c.tiles;  // < n_grids
+  c.in = gq_stack_plane(c.in, c.nodes, g), c.out = gq_stack_plane(c.out, c.nodes, g);
+  if (c.other) c.other = gq_stack_plane(c.other, c.nodes, g);
+  if (c.src) c.src = gq_stack_plane(c.src, c.nodes, g);
   return (int)(b % (unsigned)c.tiles);
 }
 
@@ -78,31 +78,10 @@ __global__ __launch_bounds__(GQ_EDT_THREADS) void gq_edt_env_kernel(GqEdtArgs c)
   }
 }
 
-static bool gq_esdf_finite(float v) { return v > -GQ_INF_F && v < GQ_INF_F; }  // false for NaN and +-inf
-static long long gq_esdf_ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-
-// tiles of one grid in the x, y and z passes
-static void gq_esdf_tiles(const gqClutterGrids* g, long long t[3]) {
-  t[0] = gq_esdf_ceil_div((long long)g->ny * g->nz, GQ_EDT_LINES);
-  t[1] = (long long)g->nx * gq_esdf_ceil_div(g->nz, GQ_EDT_LINES);
-  t[2] = gq_esdf_ceil_div((long long)g->nx * g->ny, GQ_EDT_LINES);
-}
-
-static int gq_esdf_check_stack(const gqClutterGrids* g, const char* name) {
-  GQ_REQUIRE(g, "esdf: %s is NULL", name);
-  GQ_REQUIRE(g->values, "esdf: %s values is NULL", name);
-  if (gq_clutter_check(g, g->n_grids, 1, 1, 1) != GQ_OK) {  // retold under this unit's name
-    char why[400];
-    snprintf(why, sizeof(why), "%s", gq_last_error());
-    GQ_FAIL(GQ_ERR_ARG, "esdf: %s: %s", name, why);
-  }
-  return GQ_OK;
-}
-
 int gq_esdf_check(const gqClutterGrids* src, const gqClutterGrids* dst, float trunc, float max_distance, const void* workspace) {
-  int rc = gq_esdf_check_stack(src, "src");
+  int rc = gq_stack_check(src, "esdf", "src", true);
   if (rc != GQ_OK) return rc;
-  rc = gq_esdf_check_stack(dst, "dst");
+  rc = gq_stack_check(dst, "esdf", "dst", true);
   if (rc != GQ_OK) return rc;
   GQ_REQUIRE(workspace, "esdf: workspace is NULL");
   GQ_REQUIRE(dst->n_grids == src->n_grids, "esdf: dst n_grids must be src's %d, got %d", src->n_grids, dst->n_grids);
@@ -119,12 +98,13 @@ int gq_esdf_check(const gqClutterGrids* src, const gqClutterGrids* dst, float tr
   for (int a = 0; a < 3; ++a)
     GQ_REQUIRE(n[a] <= GQ_EDT_MAX_LINE, "esdf: src n%c = %d, at most %d nodes along an axis (a whole line lives in LDS)", "xyz"[a], n[a],
                GQ_EDT_MAX_LINE);
-  long long t[3];
-  gq_esdf_tiles(src, t);
-  const long long tiles = src->n_grids * (t[0] > t[1] ? (t[0] > t[2] ? t[0] : t[2]) : (t[1] > t[2] ? t[1] : t[2]));
+  // tiles of one grid in the x, y and z passes (every axis <= GQ_EDT_MAX_LINE: the products fit an int)
+  const int t[3] = {gq_edt_tiles<true>({1, n[0], n[1] * n[2], 0}), gq_edt_tiles<true>({n[0], n[1], n[2], 0}),
+                    gq_edt_tiles<false>({n[0] * n[1], n[2], 1, 0})};
+  const long long tiles = (long long)src->n_grids * (t[0] > t[1] ? (t[0] > t[2] ? t[0] : t[2]) : (t[1] > t[2] ? t[1] : t[2]));
   GQ_REQUIRE(tiles <= (1ll << 23), "esdf: src has %lld tiles of %d lines, at most 2^23 per launch", tiles, GQ_EDT_LINES);
-  GQ_REQUIRE(gq_esdf_finite(trunc) && trunc > 0.0f, "esdf: trunc must be finite and > 0, got %g", (double)trunc);
-  GQ_REQUIRE(gq_esdf_finite(max_distance) && max_distance >= trunc, "esdf: max_distance must be finite and >= trunc = %g, got %g",
+  GQ_REQUIRE(gq_finite(trunc) && trunc > 0.0f, "esdf: trunc must be finite and > 0, got %g", (double)trunc);
+  GQ_REQUIRE(gq_finite(max_distance) && max_distance >= trunc, "esdf: max_distance must be finite and >= trunc = %g, got %g",
              (double)trunc, (double)max_distance);
   const double window = ceil((double)max_distance / (double)src->voxel);
   GQ_REQUIRE(window <= (double)GQ_EDT_MAX_WINDOW, "esdf: max_distance / voxel gives a window of %.0f nodes, at most %d", window,
@@ -134,7 +114,7 @@ int gq_esdf_check(const gqClutterGrids* src, const gqClutterGrids* dst, float tr
 
 int gq_esdf_workspace_bytes(const gqClutterGrids* src, size_t* bytes) {
   GQ_REQUIRE(bytes, "esdf: bytes is NULL");
-  const int rc = gq_esdf_check_stack(src, "src");
+  const int rc = gq_stack_check(src, "esdf", "src", true);
   if (rc != GQ_OK) return rc;
   *bytes = 3 * (size_t)src->n_grids * src->nx * src->ny * src->nz * sizeof(float);  // the buffers A, B, C
   return GQ_OK;
@@ -142,7 +122,7 @@ int gq_esdf_workspace_bytes(const gqClutterGrids* src, size_t* bytes) {
 
 template <bool INNER, bool SEED, bool FINISH>
 static int gq_esdf_launch(GqEdtArgs c, int n_grids, hipStream_t stream) {
-  c.tiles = INNER ? c.q.n_outer * (int)gq_esdf_ceil_div(c.q.n_inner, GQ_EDT_LINES) : (int)gq_esdf_ceil_div(c.q.n_outer, GQ_EDT_LINES);
+  c.tiles = gq_edt_tiles<INNER>(c.q);
   const dim3 grid((unsigned)((long long)n_grids * c.tiles)), block(GQ_EDT_THREADS);
   const size_t lds = (size_t)GQ_EDT_LINES * c.q.L * sizeof(float);  // <= 64 KB: L <= GQ_EDT_MAX_LINE
   if (SEED)

@@ -14,9 +14,7 @@
 //   finish:   phi from (e / h)^2 and D by the rules of the contract
 // Every index is formed after its range test.
 #pragma once
-#ifndef GQ_SCENE_HOST_BUILD  // tests/esdf_body_host.cpp compiles this body for the host, with its own qualifiers
-#include "common.h"
-#endif
+#include "grid_stack.h"  // gq_finite, the stack view; common.h unless tests/esdf_body_host.cpp compiles this for the host
 
 #define GQ_EDT_LINES 16
 #define GQ_EDT_THREADS 256
@@ -28,11 +26,9 @@ struct gqEdtPass {
   int R;                    // window, >= 1
 };
 
-__device__ __forceinline__ bool gq_edt_finite(float v) { return fabsf(v) < GQ_INF_F; }  // false for NaN and +-inf
-
-// tiles of one grid
+// tiles of one grid (what the launches ask for, per grid)
 template <bool INNER>
-__device__ __forceinline__ int gq_edt_tiles(const gqEdtPass& q) {
+GQ_HOST_DEVICE int gq_edt_tiles(const gqEdtPass& q) {
   const int per_outer = (q.n_inner + GQ_EDT_LINES - 1) / GQ_EDT_LINES;
   return INNER ? q.n_outer * per_outer : (q.n_outer + GQ_EDT_LINES - 1) / GQ_EDT_LINES;
 }
@@ -70,7 +66,7 @@ __device__ __forceinline__ int gq_edt_stride() {
 // t of the edge from a node with value Da to the next with value Db: in [0,1] where the edge is a crossing (both ends finite,
 // exactly one of them free, free = D >= 0), +inf where it is not.  The signs differ, so the denominator is not 0.
 __device__ __forceinline__ float gq_edt_edge(float Da, float Db) {
-  const bool cross = gq_edt_finite(Da) && gq_edt_finite(Db) && ((Da >= 0.0f) != (Db >= 0.0f));
+  const bool cross = gq_finite(Da) && gq_finite(Db) && ((Da >= 0.0f) != (Db >= 0.0f));
   return cross ? Da / (Da - Db) : GQ_INF_F;
 }
 
@@ -156,7 +152,7 @@ __device__ __forceinline__ float gq_edt_env(const float* line, int stride, int L
 
 // phi of a node from its D and (e / h)^2 (+inf: the grid has no crossing within reach)
 __device__ __forceinline__ float gq_edt_finish(float D, float e2, float voxel, float trunc, float max_distance) {
-  if (!gq_edt_finite(D)) return D;       // void: bit for bit
+  if (!gq_finite(D)) return D;       // void: bit for bit
   if (fabsf(D) < trunc) return D;        // in band: the fused value, bit for bit
   float e = sqrtf(e2) * voxel;
   e = e > trunc ? e : trunc;

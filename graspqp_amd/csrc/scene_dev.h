@@ -3,13 +3,9 @@
 // surface sample) and gq_scene_query_kernel (lane = query point) both call gq_scene_sample, with explicit fmaf, so the two
 // routes agree bit for bit on the same point.
 #pragma once
-#ifndef GQ_SCENE_HOST_BUILD  // tests/scene_body_host.cpp compiles this body for the host, with its own gq3 and qualifiers
-#include "common.h"
-#endif
+#include "grid_stack.h"  // gq_finite; common.h unless tests/scene_body_host.cpp compiles this body for the host (GQ_SCENE_HOST_BUILD)
 
 enum { GQ_SCENE_OUTSIDE = 0, GQ_SCENE_INSIDE = 1, GQ_SCENE_NONFINITE = 2 };
-
-__device__ __forceinline__ bool gq_scene_finite(float v) { return fabsf(v) < GQ_INF_F; }  // false for NaN and +-inf
 
 // The range test 0 <= u <= n - 1 of one axis, made on exact quantities: in float the difference x - origin rounds, and a
 // point one ulp beyond the last node plane would pass as u = n - 1.  x >= origin is exact as it stands; x - origin and
@@ -32,7 +28,7 @@ __device__ __forceinline__ int gq_scene_axis(float u, int n, float& f) {
 // loaded, phi / grad untouched) or GQ_SCENE_NONFINITE (x has a NaN or inf coordinate; nothing is loaded).
 // The tests come first and are written positively: a NaN fails every comparison and so never reaches the conversion.
 __device__ __forceinline__ int gq_scene_sample(const gqSceneGrid& g, gq3 x, float& phi, gq3& grad) {
-  if (!(gq_scene_finite(x.x) && gq_scene_finite(x.y) && gq_scene_finite(x.z))) return GQ_SCENE_NONFINITE;
+  if (!(gq_finite(x.x) && gq_finite(x.y) && gq_finite(x.z))) return GQ_SCENE_NONFINITE;
   if (!(gq_scene_axis_in(x.x, g.origin[0], g.voxel, g.nx) && gq_scene_axis_in(x.y, g.origin[1], g.voxel, g.ny) &&
         gq_scene_axis_in(x.z, g.origin[2], g.voxel, g.nz)))
     return GQ_SCENE_OUTSIDE;

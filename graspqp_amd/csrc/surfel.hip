@@ -1,8 +1,8 @@
 // Target objects from depth images: the zero level set of every grid of a fused TSDF stack as an oriented point cloud
 // (include/graspqp_hip.h, "target objects from depth images"; the body is surfel_dev.h).  Three launches, no atomics, no block
 // waits for another, nothing allocated, synchronised or uploaded: the call can sit in a captured graph behind gq_tsdf_integrate.
-//   1. gq_surfel_count_kernel: a block is a tile of GQ_CL_TX x GQ_CL_TY x GQ_CL_TZ nodes of one grid (the integrate kernel's block ->
-//      (grid, tile) decomposition); D of the tile and of the next node plane on every axis goes to LDS, NaN where the node is not
+//   1. gq_surfel_count_kernel: a block is a tile of GQ_CL_TX x GQ_CL_TY x GQ_CL_TZ nodes of one grid (grid_stack.h's block ->
+//      (grid, tile) decode); D of the tile and of the next node plane on every axis goes to LDS, NaN where the node is not
 //      observed; the block's number of crossing edges (ballot + popcount per wavefront, folded in LDS) goes to workspace[tile].
 //   2. gq_surfel_scan_kernel: one block per grid turns that grid's tile counts into their exclusive prefix (a second array of
 //      the workspace) and writes count[g] = (total, written).
@@ -18,7 +18,7 @@
 
 struct GqSurfelArgs {
   gqSurfelGrid s;  // grid 0 of the stack: values / weight advance by nodes per grid
-  int tiles_x, tiles_y, tiles_z;
+  GqTiling tiling;
   int32_t* tile_count;   // (G tiles)
   int32_t* tile_prefix;  // (G tiles)
   float* points;         // (G,capacity,3) or null
@@ -26,22 +26,6 @@ struct GqSurfelArgs {
   int capacity;
   int32_t* count;  // (G,2)
 };
-
-// block -> (grid, first node of the tile): block-uniform.  Returns the grid's view of the arguments.
-__device__ __forceinline__ gqSurfelGrid gq_surfel_block(const GqSurfelArgs& c, size_t& g, int& i0, int& j0, int& k0) {
-  unsigned b = blockIdx.x;
-  k0 = (int)(b % (unsigned)c.tiles_z) * GQ_CL_TZ;
-  b /= (unsigned)c.tiles_z;
-  j0 = (int)(b % (unsigned)c.tiles_y) * GQ_CL_TY;
-  b /= (unsigned)c.tiles_y;
-  i0 = (int)(b % (unsigned)c.tiles_x) * GQ_CL_TX;
-  g = b / (unsigned)c.tiles_x;
-  gqSurfelGrid s = c.s;
-  const size_t nodes = (size_t)s.grid.nx * (size_t)s.grid.ny * (size_t)s.grid.nz;
-  s.grid.values += g * nodes;  // g < n_grids
-  if (s.weight) s.weight += g * nodes;
-  return s;
-}
 
 // true if no node of the tile lies in the region (block-uniform)
 __device__ __forceinline__ bool gq_surfel_outside(const gqSurfelGrid& s, int i0, int j0, int k0) {
@@ -52,9 +36,9 @@ __device__ __forceinline__ bool gq_surfel_outside(const gqSurfelGrid& s, int i0,
 __global__ __launch_bounds__(GQ_SF_THREADS) void gq_surfel_count_kernel(const GqSurfelArgs c) {
   __shared__ float tile[GQ_SF_TILE];
   __shared__ int wave_n[GQ_SF_WAVES];
-  size_t g;
-  int i0, j0, k0;
-  const gqSurfelGrid s = gq_surfel_block(c, g, i0, j0, k0);
+  const GqTile t = gq_tile_of(blockIdx.x, c.tiling);  // block-uniform
+  const gqSurfelGrid s = gq_surfel_of(c.s, t.g);
+  const int i0 = t.i0, j0 = t.j0, k0 = t.k0;
   const int tid = threadIdx.x;
   if (gq_surfel_outside(s, i0, j0, k0)) {
     if (tid == 0) c.tile_count[blockIdx.x] = 0;
@@ -112,9 +96,9 @@ __global__ __launch_bounds__(GQ_SF_THREADS) void gq_surfel_emit_kernel(const GqS
   if (c.tile_count[blockIdx.x] == 0) return;  // block-uniform: most tiles hold no surface
   const int first = c.tile_prefix[blockIdx.x];
   if (first >= c.capacity) return;
-  size_t g;
-  int i0, j0, k0;
-  const gqSurfelGrid s = gq_surfel_block(c, g, i0, j0, k0);
+  const GqTile t = gq_tile_of(blockIdx.x, c.tiling);  // block-uniform
+  const gqSurfelGrid s = gq_surfel_of(c.s, t.g);
+  const int i0 = t.i0, j0 = t.j0, k0 = t.k0;
   const int tid = threadIdx.x, lane = gq_lane(), wave = tid / GQ_WAVE;
   for (int e = tid; e < GQ_SF_TILE; e += GQ_SF_THREADS) gq_surfel_fill(s, i0, j0, k0, GQ_SF_LO, GQ_SF_HI, e, tile);
   __syncthreads();
@@ -125,8 +109,8 @@ __global__ __launch_bounds__(GQ_SF_THREADS) void gq_surfel_emit_kernel(const GqS
   __syncthreads();
   int slot = first + __popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below);  // crossings of the lower lanes' nodes
   for (int w = 0; w < GQ_SF_WAVES; ++w) slot += w < wave ? wave_n[w] : 0;
-  float* P = c.points + g * (size_t)c.capacity * 3;  // g < n_grids
-  float* N = c.normals + g * (size_t)c.capacity * 3;
+  float* P = c.points + t.g * (size_t)c.capacity * 3;  // g < n_grids
+  float* N = c.normals + t.g * (size_t)c.capacity * 3;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     if (!((flags >> a) & 1u)) continue;
@@ -141,23 +125,13 @@ __global__ __launch_bounds__(GQ_SF_THREADS) void gq_surfel_emit_kernel(const GqS
   }
 }
 
-static long long gq_surfel_tiles(int n, int t) { return ((long long)n + t - 1) / t; }
-static bool gq_surfel_finite(float v) { return v > -GQ_INF_F && v < GQ_INF_F; }  // false for NaN and +-inf
-
 int gq_tsdf_surfels_check(const gqClutterGrids* grids, const int32_t* region, float min_weight, float trunc, int has_outputs,
                           int64_t capacity) {
-  GQ_REQUIRE(grids, "surfels: grids is NULL");
-  if (gq_clutter_check(grids, grids->n_grids, 1, 1, 1) != GQ_OK) {  // retold under this unit's name
-    char why[400];
-    snprintf(why, sizeof(why), "%s", gq_last_error());
-    GQ_FAIL(GQ_ERR_ARG, "surfels: grids: %s", why);
-  }
-  const long long tiles = grids->n_grids * gq_surfel_tiles(grids->nx, GQ_CL_TX) * gq_surfel_tiles(grids->ny, GQ_CL_TY) *
-                          gq_surfel_tiles(grids->nz, GQ_CL_TZ);
-  GQ_REQUIRE(tiles <= (1ll << 23), "surfels: grids has %lld tiles of %d x %d x %d nodes, at most 2^23 per launch", tiles, GQ_CL_TX,
-             GQ_CL_TY, GQ_CL_TZ);
-  GQ_REQUIRE(gq_surfel_finite(trunc) && trunc > 0.0f, "surfels: trunc must be finite and > 0, got %g", (double)trunc);
-  GQ_REQUIRE(gq_surfel_finite(min_weight), "surfels: min_weight must be finite, got %g", (double)min_weight);
+  int rc = gq_stack_check(grids, "surfels", "grids");
+  if (rc == GQ_OK) rc = gq_tiling_check(grids, "surfels: grids");
+  if (rc != GQ_OK) return rc;
+  GQ_REQUIRE(gq_finite(trunc) && trunc > 0.0f, "surfels: trunc must be finite and > 0, got %g", (double)trunc);
+  GQ_REQUIRE(gq_finite(min_weight), "surfels: min_weight must be finite, got %g", (double)min_weight);
   if (region) {
     const int n[3] = {grids->nx, grids->ny, grids->nz};
     for (int a = 0; a < 3; ++a)
@@ -174,8 +148,7 @@ int gq_tsdf_surfels_workspace_bytes(const gqClutterGrids* grids, size_t* bytes) 
   GQ_REQUIRE(bytes, "surfels: bytes is NULL");
   const int rc = gq_tsdf_surfels_check(grids, nullptr, 0.0f, 1.0f, 0, 0);
   if (rc != GQ_OK) return rc;
-  const long long tiles = grids->n_grids * gq_surfel_tiles(grids->nx, GQ_CL_TX) * gq_surfel_tiles(grids->ny, GQ_CL_TY) *
-                          gq_surfel_tiles(grids->nz, GQ_CL_TZ);
+  const long long tiles = gq_tiling_blocks(gq_tiling(grids->nx, grids->ny, grids->nz), grids->n_grids);
   *bytes = (size_t)tiles * 2 * sizeof(int32_t);  // the tiles' counts and their prefix
   return GQ_OK;
 }
@@ -189,15 +162,13 @@ int gq_tsdf_surfels(const gqClutterGrids* grids, const float* values, const floa
   GQ_REQUIRE(count, "surfels: count is NULL");
   GQ_REQUIRE(workspace, "surfels: workspace is NULL");
   GqSurfelArgs c{};
-  c.s.grid.values = values, c.s.grid.nx = grids->nx, c.s.grid.ny = grids->ny, c.s.grid.nz = grids->nz, c.s.grid.voxel = grids->voxel;
-  for (int a = 0; a < 3; ++a) c.s.grid.origin[a] = grids->origin[a];
+  c.s.grid = gq_stack_grid(grids);  // values == grids->values
   c.s.weight = weight, c.s.min_weight = min_weight, c.s.trunc = trunc;
   const int n[3] = {grids->nx, grids->ny, grids->nz};
   for (int a = 0; a < 3; ++a) c.s.region[2 * a] = region ? region[2 * a] : 0, c.s.region[2 * a + 1] = region ? region[2 * a + 1] : n[a];
-  c.tiles_x = (int)gq_surfel_tiles(grids->nx, GQ_CL_TX), c.tiles_y = (int)gq_surfel_tiles(grids->ny, GQ_CL_TY);
-  c.tiles_z = (int)gq_surfel_tiles(grids->nz, GQ_CL_TZ);
-  const int per_grid = c.tiles_x * c.tiles_y * c.tiles_z;  // <= 2^23
-  const long long tiles = (long long)grids->n_grids * per_grid;
+  c.tiling = gq_tiling(grids->nx, grids->ny, grids->nz);
+  const int per_grid = (int)gq_tiling_blocks(c.tiling, 1);  // <= 2^23
+  const long long tiles = gq_tiling_blocks(c.tiling, grids->n_grids);
   c.tile_count = (int32_t*)workspace, c.tile_prefix = (int32_t*)workspace + tiles;
   c.points = points, c.normals = normals, c.capacity = (int)capacity, c.count = count;
   hipLaunchKernelGGL(gq_surfel_count_kernel, dim3((unsigned)tiles), dim3(GQ_SF_THREADS), 0, (hipStream_t)stream, c);

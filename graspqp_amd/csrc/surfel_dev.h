@@ -2,8 +2,8 @@
 // ONE grid of a fused stack as an oriented point cloud.  The kernels of surfel.hip call it on a tile in LDS; tests/
 // surfel_body_host.cpp compiles it for the host, as tsdf_dev.h's body.
 //
-// A block is a tile of GQ_CL_TX x GQ_CL_TY x GQ_CL_TZ nodes, thread tid = (li GQ_CL_TY + lj) GQ_CL_TZ + lk owns node a = tile
-// origin + (li,lj,lk) and its three edges to b = a + e_c.  The tile holds D with a halo of -1 .. +2 nodes on every axis, NaN where
+// A block is a tile of GQ_CL_TX x GQ_CL_TY x GQ_CL_TZ nodes (grid_stack.h), thread tid = (li GQ_CL_TY + lj) GQ_CL_TZ + lk owns node
+// a = tile origin + (li,lj,lk) and its three edges to b = a + e_c.  The tile holds D with a halo of -1 .. +2 nodes on every axis, NaN where
 // the node is not observed (outside the grid, D not finite, W < min_weight), so `observed` is v == v from then on.
 //   crossing: a and b in the region, both observed, (D_a >= 0) != (D_b >= 0), |D_a| < trunc and |D_b| < trunc   (exact tests)
 //   t = D_a / (D_a - D_b) in [0,1]      p = x_a + t voxel e_c, x_a = fmaf(voxel, (i,j,k), origin)
@@ -20,7 +20,7 @@
 #define GQ_SF_NY (GQ_CL_TY + GQ_SF_LO + GQ_SF_HI)
 #define GQ_SF_NZ (GQ_CL_TZ + GQ_SF_LO + GQ_SF_HI)
 #define GQ_SF_TILE (GQ_SF_NX * GQ_SF_NY * GQ_SF_NZ)
-#define GQ_SF_THREADS (GQ_CL_TX * GQ_CL_TY * GQ_CL_TZ)
+#define GQ_SF_THREADS GQ_CL_THREADS
 #define GQ_SF_MIN_NORM2 1e-20f
 
 // what a launch reads of one grid: `values` / `weight` are THIS grid's (weight null: every node observed)
@@ -30,6 +30,13 @@ struct gqSurfelGrid {
   float min_weight, trunc;
   int region[6];  // i0 i1 j0 j1 k0 k1, half-open, inside the grid
 };
+// grid g's view of a launch whose `first` is grid 0's: values and weight advance by the nodes of a grid (g < n_grids)
+__device__ __forceinline__ gqSurfelGrid gq_surfel_of(const gqSurfelGrid& first, size_t g) {
+  gqSurfelGrid s = first;
+  s.grid = gq_stack_grid(first.grid, g);
+  if (s.weight) s.weight = gq_stack_plane(first.weight, gq_stack_nodes(first.grid), g);
+  return s;
+}
 
 // offset in the tile of the node at (li,lj,lk) relative to the tile's first node; each in -GQ_SF_LO .. T + GQ_SF_HI - 1
 __device__ __forceinline__ int gq_surfel_at(int li, int lj, int lk) {
@@ -43,7 +50,7 @@ __device__ __forceinline__ float gq_surfel_node(const gqSurfelGrid& s, int i, in
   if (!(i >= 0 && i < s.grid.nx && j >= 0 && j < s.grid.ny && k >= 0 && k < s.grid.nz)) return __builtin_nanf("");
   const size_t node = ((size_t)i * (size_t)s.grid.ny + (size_t)j) * (size_t)s.grid.nz + (size_t)k;
   const float D = s.grid.values[node];
-  bool seen = gq_scene_finite(D);
+  bool seen = gq_finite(D);
   if (s.weight) seen = seen && s.weight[node] >= s.min_weight;  // false for a NaN weight
   return seen ? D : __builtin_nanf("");
 }
@@ -60,7 +67,8 @@ __device__ __forceinline__ void gq_surfel_fill(const gqSurfelGrid& s, int i0, in
 
 // Bit c set: the edge from the thread's node along axis c is a crossing.  Reads the tile at local 0 .. T on every axis.
 __device__ __forceinline__ unsigned gq_surfel_flags(const gqSurfelGrid& s, const float* tile, int i0, int j0, int k0, int tid) {
-  const int li = tid / (GQ_CL_TY * GQ_CL_TZ), lj = (tid / GQ_CL_TZ) % GQ_CL_TY, lk = tid % GQ_CL_TZ;
+  int li, lj, lk;
+  gq_tile_local(tid, li, lj, lk);
   const int n[3] = {i0 + li, j0 + lj, k0 + lk};
   const int* r = s.region;
   if (!(n[0] >= r[0] && n[0] < r[1] && n[1] >= r[2] && n[1] < r[3] && n[2] >= r[4] && n[2] < r[5])) return 0u;
@@ -111,7 +119,8 @@ __device__ __forceinline__ gq3 gq_surfel_grad(const float* tile, int n) {
 // Position and unit outward normal of the crossing along axis c of the thread's node (bit c of gq_surfel_flags is set).
 __device__ __forceinline__ void gq_surfel_emit(const gqSurfelGrid& s, const float* tile, int i0, int j0, int k0, int tid, int c, float* p,
                                                float* nrm) {
-  const int li = tid / (GQ_CL_TY * GQ_CL_TZ), lj = (tid / GQ_CL_TZ) % GQ_CL_TY, lk = tid % GQ_CL_TZ;
+  int li, lj, lk;
+  gq_tile_local(tid, li, lj, lk);
   const int a = gq_surfel_at(li, lj, lk), b = a + gq_surfel_stride(c);
   const float Da = tile[a], Db = tile[b];
   const float t = Da / (Da - Db);  // the signs differ: the denominator is not 0, t is in [0,1]

@@ -27,7 +27,7 @@ __device__ __forceinline__ int gq_tsdf_pixel(float u, int n) { return min((int)f
 __device__ __forceinline__ void gq_tsdf_view(const gqDepthViews& c, int view, gq3 xw, int skip, float trunc, float max_weight, float& D,
                                              float& W) {
   const gq3 xc = gq_clutter_to_part(c.cam_T + 12 * (size_t)view, xw);
-  if (!(gq_scene_finite(xc.x) && gq_scene_finite(xc.y) && gq_scene_finite(xc.z))) {
+  if (!(gq_finite(xc.x) && gq_finite(xc.y) && gq_finite(xc.z))) {
     D = __builtin_nanf("");  // sticky: every later mean keeps it; the weight is left alone
     return;
   }
@@ -55,7 +55,7 @@ __device__ __forceinline__ void gq_tsdf_view(const gqDepthViews& c, int view, gq
 __device__ __forceinline__ void gq_tsdf_node(const gqSceneGrid& out, const float* Tg, int i, int j, int k, const gqDepthViews& c, int skip,
                                              float trunc, float max_weight, float& D, float& W) {
   const gq3 xw = Tg ? gq_clutter_world(out, Tg, (float)i, (float)j, (float)k) : gq_tsdf_frame(out, (float)i, (float)j, (float)k);
-  if (!(gq_scene_finite(xw.x) && gq_scene_finite(xw.y) && gq_scene_finite(xw.z))) {
+  if (!(gq_finite(xw.x) && gq_finite(xw.y) && gq_finite(xw.z))) {
     D = __builtin_nanf("");
     return;
   }

@@ -1236,13 +1236,40 @@ def tabletop_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg
 _SCENE_CHUNK = 1 << 20  # nodes per set-up query of from_meshes / from_point_clouds
 
 
-def _scene_grid(values, origin, voxel) -> "_C.SceneGrid":
-    g = _C.SceneGrid()
+def _grid_struct(struct, values, origin, voxel):
+    """gqSceneGrid of a (nx,ny,nz) tensor, or gqClutterGrids of a (G,nx,ny,nz) one: the same fields behind a leading n_grids."""
+    g = struct()
     g.values = values.data_ptr()
-    g.nx, g.ny, g.nz = (int(s) for s in values.shape)
+    if struct is _C.ClutterGrids:
+        g.n_grids, g.nx, g.ny, g.nz = (int(s) for s in values.shape)
+    else:
+        g.nx, g.ny, g.nz = (int(s) for s in values.shape)
     g.origin = (ctypes.c_float * 3)(*(float(o) for o in origin))
     g.voxel = float(voxel)
     return g
+
+
+def _scene_grid(values, origin, voxel) -> "_C.SceneGrid":
+    return _grid_struct(_C.SceneGrid, values, origin, voxel)
+
+
+def _clutter_grids(values, origin, voxel) -> "_C.ClutterGrids":
+    return _grid_struct(_C.ClutterGrids, values, origin, voxel)
+
+
+def _grid_fields(stack, values, origin, device):
+    """For SceneSDF and, with ``stack``, SceneSDFSet: ``values`` as the device tensor the grid struct points at (a CUDA float32
+    contiguous tensor as it is, anything else converted once) and ``origin`` as 3 floats."""
+    who, dims = ("SceneSDFSet", "(G,nx,ny,nz)") if stack else ("SceneSDF", "(nx,ny,nz)")
+    v = values if torch.is_tensor(values) else torch.as_tensor(np.asarray(values, dtype=np.float32))
+    if v.dim() != 3 + stack:
+        raise ValueError(f"{who}: values must be {dims}, got {tuple(v.shape)}")
+    origin = [float(o) for o in (origin.detach().cpu().tolist() if torch.is_tensor(origin) else origin)]
+    if len(origin) != 3:
+        raise ValueError(f"{who}: origin must have 3 entries, got {len(origin)}")
+    if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
+        v = v.detach().to(device, torch.float32).contiguous()
+    return v, tuple(origin)
 
 
 class SceneSDF:
@@ -1253,15 +1280,8 @@ class SceneSDF:
     phi is the trilinear interpolant; outside the volume is free space (include/graspqp_hip.h)."""
 
     def __init__(self, values, origin, voxel, device="cuda"):
-        v = values if torch.is_tensor(values) else torch.as_tensor(np.asarray(values, dtype=np.float32))
-        if v.dim() != 3:
-            raise ValueError(f"SceneSDF: values must be (nx,ny,nz), got {tuple(v.shape)}")
-        origin = [float(o) for o in (origin.detach().cpu().tolist() if torch.is_tensor(origin) else origin)]
-        if len(origin) != 3:
-            raise ValueError(f"SceneSDF: origin must have 3 entries, got {len(origin)}")
-        if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
-            v = v.detach().to(device, torch.float32).contiguous()
-        self.values, self.origin, self.voxel = v, tuple(origin), float(voxel)
+        v, origin = _grid_fields(False, values, origin, device)
+        self.values, self.origin, self.voxel = v, origin, float(voxel)
         self.shape = tuple(int(s) for s in v.shape)
         self.grid = _scene_grid(v, self.origin, self.voxel)
         self.check()
@@ -1315,15 +1335,6 @@ class SceneSDF:
         return cls._filled(lambda k, p: sdf_cloud(p, sets[k], p.shape[0])[:2], len(sets), origin, shape, voxel, device)
 
 
-def _clutter_grids(values, origin, voxel) -> "_C.ClutterGrids":
-    g = _C.ClutterGrids()
-    g.values = values.data_ptr()
-    g.n_grids, g.nx, g.ny, g.nz = (int(s) for s in values.shape)
-    g.origin = (ctypes.c_float * 3)(*(float(o) for o in origin))
-    g.voxel = float(voxel)
-    return g
-
-
 class SceneSDFSet:
     """A stack of scene grids, one per object (include/graspqp_hip.h, "clutter scenes"): ``values`` (G,nx,ny,nz) float32 on the
     device, grid g in the frame of object g; ``origin`` and ``voxel`` are shared by all grids.  A CUDA float32 contiguous
@@ -1331,15 +1342,8 @@ class SceneSDFSet:
     Rows are object-major: of B rows, row b reads grid b // (B / G)."""
 
     def __init__(self, values, origin, voxel, device="cuda"):
-        v = values if torch.is_tensor(values) else torch.as_tensor(np.asarray(values, dtype=np.float32))
-        if v.dim() != 4:
-            raise ValueError(f"SceneSDFSet: values must be (G,nx,ny,nz), got {tuple(v.shape)}")
-        origin = [float(o) for o in (origin.detach().cpu().tolist() if torch.is_tensor(origin) else origin)]
-        if len(origin) != 3:
-            raise ValueError(f"SceneSDFSet: origin must have 3 entries, got {len(origin)}")
-        if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
-            v = v.detach().to(device, torch.float32).contiguous()
-        self.values, self.origin, self.voxel = v, tuple(origin), float(voxel)
+        v, origin = _grid_fields(True, values, origin, device)
+        self.values, self.origin, self.voxel = v, origin, float(voxel)
         self.n_grids, self.shape = int(v.shape[0]), tuple(int(s) for s in v.shape[1:])
         self.grid_set = _clutter_grids(v, self.origin, self.voxel)
         self.check(self.n_grids, 1)

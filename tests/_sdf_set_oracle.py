@@ -18,7 +18,6 @@ the queries is allowed to differ:
 
 A face that csrc/tri.h treats as degenerate (gq_make_face: it collapses to a segment) counts as its three edges, sign +1."""
 import os
-import shutil
 import subprocess
 import tempfile
 
@@ -27,10 +26,9 @@ import torch
 
 from ref_cpu import sdf as osdf
 
-from graspqp_amd.utils import meshes
+import _host_program
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+from graspqp_amd.utils import meshes
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -203,16 +201,12 @@ class ClusterTool:
     stand-alone program).  A failure of the program -- a sanitizer report included -- raises."""
 
     def __init__(self, workdir=None, sanitize=False):
-        assert CXX, "a host C++ compiler is needed"
         self._tmp = None
         if workdir is None:
             self._tmp = tempfile.TemporaryDirectory(prefix="gq_cluster_bound_")
             workdir = self._tmp.name
         self.dir = str(workdir)
-        self.exe = os.path.join(self.dir, "cluster_bound_host")
-        flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        subprocess.check_call([CXX, "-O2", "-std=c++17", "-ffp-contract=off", *flags, "-o", self.exe,
-                               os.path.join(HERE, "cluster_bound_host.cpp")])
+        self.exe = _host_program.build("cluster_bound_host", self.dir, sanitize=sanitize)
 
     def _run(self, mode, blob):
         a, b = os.path.join(self.dir, "in.bin"), os.path.join(self.dir, "out.bin")

@@ -5,21 +5,7 @@
 //   in.bin : int32 nx ny nz, float32 origin[3] voxel, float32 R[9] t[3] a[3] distance margin, int32 K N,
 //            float32 values[nx ny nz], float32 x_h[N][3]
 //   out.bin: per sample float32 e, G[3], K9[9]   (sums over the sample's stations, upstream 1, without 1/K)
-#include <math.h>
-#include <stdio.h>
-
-#include <algorithm>
-#include <vector>
-using std::min;
-#define GQ_SCENE_HOST_BUILD
-#define __device__
-#define __forceinline__ inline
-#define GQ_INF_F __builtin_inff()
-#include "../include/graspqp_hip.h"
-struct gq3 {
-  float x, y, z;
-};
-static inline gq3 gq_mk(float x, float y, float z) { return gq3{x, y, z}; }
+#include "host_shim.h"
 #include "../graspqp_amd/csrc/approach_dev.h"
 
 int main(int argc, char** argv) {

@@ -10,21 +10,10 @@
 //        cluster_bound_host lb in.bin out.bin
 //          in.bin : int32 n_clusters, int32 P, float32 box[n_clusters][16], float32 points[n_clusters][P][3]
 //          out.bin: float32 lb[n_clusters][P] = 0.9999f * gq_cluster_lb(box, point)
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-#define __device__
-#define __forceinline__ inline
-struct gq3 {
-  float x, y, z;
-};
+#include "host_shim.h"
 struct alignas(16) float4 {
   float x, y, z, w;
 };
-static inline gq3 gq_mk(float x, float y, float z) { return gq3{x, y, z}; }
 #include "../graspqp_amd/csrc/cluster_bound.h"
 
 template <class T>

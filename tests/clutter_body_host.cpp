@@ -1,6 +1,7 @@
 // The device body of the compose kernel (graspqp_amd/csrc/clutter_dev.h: one output node, and the tile's conservative cull)
 // compiled for the HOST: tests/test_clutter_body_host.py builds this program with the host compiler and sanitizers and compares
-// its float32 results with the fp64 oracle.  Every grid lives in a vector of exactly its size, so a node read outside it ends
+// its float32 results with the fp64 oracle.  The program walks the launch of clutter.hip one block and one thread at a time, by
+// the kernel's own decode (grid_stack.h).  Every grid lives in a vector of exactly its size, so a node read outside it ends
 // the program.  Every node is computed twice -- with every part sampled, and with the parts the tile's cull leaves -- and the
 // program fails (exit 7) if the two differ in a single bit.  No GPU involved.
 // usage: clutter_body_host in.bin out.bin
@@ -8,23 +9,7 @@
 //            float32 part_T[n_parts][12], then per grid (the parts, then the base if has_base):
 //            int32 nx ny nz, float32 origin[3] voxel, float32 values[nx ny nz]
 //   out.bin: float32 phi[G][nx][ny][nz], then int32 culled (tile, part) pairs, int32 all (tile, part) pairs
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-using std::min;
-#define GQ_SCENE_HOST_BUILD
-#define __device__
-#define __forceinline__ inline
-#define GQ_INF_F __builtin_inff()
-#include "../include/graspqp_hip.h"
-struct gq3 {
-  float x, y, z;
-};
-static inline gq3 gq_mk(float x, float y, float z) { return gq3{x, y, z}; }
+#include "host_shim.h"
 #include "../graspqp_amd/csrc/clutter_dev.h"
 
 struct Grid {
@@ -66,31 +51,30 @@ int main(int argc, char** argv) {
   const gqSceneGrid* base = has_base ? &grids[n_parts].g : nullptr;
   const gqSceneGrid out{nullptr, hd[1], hd[2], hd[3], {oh[0], oh[1], oh[2]}, oh[3]};
   const float far = oh[4];
-  std::vector<float> phi((size_t)G * out.nx * out.ny * out.nz);
+  std::vector<float> phi((size_t)G * out.nx * out.ny * out.nz, -7777.0f);  // a node no thread reaches keeps the sentinel
   int culled = 0, pairs = 0;
-  for (int g = 0; g < G; ++g) {
+  const GqTiling tiling = gq_tiling(out.nx, out.ny, out.nz);
+  for (long long block = 0; block < gq_tiling_blocks(tiling, G); ++block) {
+    const GqTile t = gq_tile_of((unsigned)block, tiling);
+    const size_t g = t.g;
     const float* Tg = tT.data() + 12 * g;
-    for (int i0 = 0; i0 < out.nx; i0 += GQ_CL_TX)
-      for (int j0 = 0; j0 < out.ny; j0 += GQ_CL_TY)
-        for (int k0 = 0; k0 < out.nz; k0 += GQ_CL_TZ) {
-          unsigned live = 0;
-          for (int p = 0; p < n_parts; ++p) {
-            const bool c = gq_clutter_culled(out, Tg, i0, j0, k0, parts[p], pT.data() + 12 * p);
-            if (!c) live |= 1u << p;
-            culled += c, ++pairs;
-          }
-          for (int i = i0; i < min(i0 + GQ_CL_TX, out.nx); ++i)
-            for (int j = j0; j < min(j0 + GQ_CL_TY, out.ny); ++j)
-              for (int k = k0; k < min(k0 + GQ_CL_TZ, out.nz); ++k) {
-                const float a = gq_clutter_node(out, Tg, i, j, k, parts.data(), n_parts, pT.data(), excl[g], 0xffffffffu, base, far);
-                const float b = gq_clutter_node(out, Tg, i, j, k, parts.data(), n_parts, pT.data(), excl[g], live, base, far);
-                if (memcmp(&a, &b, 4) != 0 && !(a != a && b != b)) {
-                  fprintf(stderr, "the cull changed node (%d,%d,%d,%d): %a -> %a\n", g, i, j, k, (double)a, (double)b);
-                  return 7;
-                }
-                phi[(((size_t)g * out.nx + i) * out.ny + j) * out.nz + k] = a;
-              }
-        }
+    unsigned live = 0;
+    for (int p = 0; p < n_parts; ++p) {
+      const bool c = gq_clutter_culled(out, Tg, t.i0, t.j0, t.k0, parts[p], pT.data() + 12 * p);
+      if (!c) live |= 1u << p;
+      culled += c, ++pairs;
+    }
+    for (int tid = 0; tid < GQ_CL_THREADS; ++tid) {
+      int i, j, k;
+      if (!gq_tile_node(t, tid, out.nx, out.ny, out.nz, i, j, k)) continue;
+      const float a = gq_clutter_node(out, Tg, i, j, k, parts.data(), n_parts, pT.data(), excl[g], 0xffffffffu, base, far);
+      const float b = gq_clutter_node(out, Tg, i, j, k, parts.data(), n_parts, pT.data(), excl[g], live, base, far);
+      if (memcmp(&a, &b, 4) != 0 && !(a != a && b != b)) {
+        fprintf(stderr, "the cull changed node (%d,%d,%d,%d): %a -> %a\n", (int)g, i, j, k, (double)a, (double)b);
+        return 7;
+      }
+      phi[((g * out.nx + i) * out.ny + j) * out.nz + k] = a;
+    }
   }
   FILE* o = fopen(argv[2], "wb");
   if (!o) return 6;

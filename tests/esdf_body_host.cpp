@@ -6,16 +6,7 @@
 // usage: esdf_body_host in.bin out.bin
 //   in.bin : int32 G nx ny nz, float32 voxel trunc max_distance, float32 D[G][nx][ny][nz]
 //   out.bin: float32 phi[G][nx][ny][nz]
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-#define GQ_SCENE_HOST_BUILD
-#define __device__
-#define __forceinline__ inline
-#define GQ_INF_F __builtin_inff()
+#include "host_shim.h"
 #include "../graspqp_amd/csrc/edt_dev.h"
 
 typedef std::vector<float> Buf;

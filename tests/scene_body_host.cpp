@@ -3,21 +3,7 @@
 // usage: scene_body_host in.bin out.bin
 //   in.bin : int32 nx ny nz, float32 origin[3] voxel, int32 N, float32 values[nx ny nz], float32 points[N][3]
 //   out.bin: per point float32 phi, grad[3], state (0 outside, 1 inside, 2 non-finite)
-#include <math.h>
-#include <stdio.h>
-
-#include <algorithm>
-#include <vector>
-using std::min;
-#define GQ_SCENE_HOST_BUILD
-#define __device__
-#define __forceinline__ inline
-#define GQ_INF_F __builtin_inff()
-#include "../include/graspqp_hip.h"
-struct gq3 {
-  float x, y, z;
-};
-static inline gq3 gq_mk(float x, float y, float z) { return gq3{x, y, z}; }
+#include "host_shim.h"
 #include "../graspqp_amd/csrc/scene_dev.h"
 
 int main(int argc, char** argv) {

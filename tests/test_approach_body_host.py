@@ -2,8 +2,6 @@
 gq_approach_kernel runs) compiled for the HOST with AddressSanitizer and UBSan and compared with the fp64 oracle, at the bounds
 of the GPU tests (values rtol 1e-5 / atol 1e-6, gradients norm-wise 1e-4).  The buffer the program reads is exactly the grid, so
 a node read outside it ends the program.  No GPU involved."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,21 +11,17 @@ import torch
 import ref_cpu  # noqa: F401
 
 import _approach_oracle as ao
+import _host_program
 import _scene_oracle as so
 from graspqp_amd.hands import get_hand_spec
 from graspqp_amd.utils import meshes
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
 G_SHAPE, G_ORIGIN, G_H = (100, 96, 104), (-0.5, -0.48, -0.52), 0.01
 
 
 def _build(tmp_path_factory, name, flags=()):
-    assert CXX, "a host C++ compiler is needed"
     d = tmp_path_factory.mktemp(name)
-    exe = str(d / "approach_body_host")
-    subprocess.check_call([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           *flags, "-o", exe, os.path.join(HERE, "approach_body_host.cpp")])
+    exe = _host_program.build("approach_body_host", d, flags)
 
     def run(field, R, t, a, D, margin, K, xh):
         xh = np.ascontiguousarray(xh, dtype=np.float32).reshape(-1, 3)

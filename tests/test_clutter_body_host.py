@@ -3,28 +3,22 @@ scene_dev.h's interpolant) compiled for the HOST with AddressSanitizer and UBSan
 oracle (tests/_clutter_oracle.py) at the bound of the GPU tests (rtol 1e-5 / atol 1e-6).  Every grid is held in a
 buffer of exactly its size, so a node read outside it, or a float -> int conversion of an out-of-range value, ends the program;
 the program itself fails if the cull changes a single bit.  No GPU involved."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import _host_program
 import _clutter_oracle as co
 import _scene_oracle as so
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
 
 
 @pytest.fixture(scope="module")
 def body(tmp_path_factory):
-    assert CXX, "a host C++ compiler is needed"
     d = tmp_path_factory.mktemp("clutter_body")
-    exe = str(d / "clutter_body_host")
-    subprocess.check_call([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(HERE, "clutter_body_host.cpp")])
+    exe = _host_program.build("clutter_body_host", d)
 
     def grid_bytes(F):
         return (np.array(F.shape, dtype=np.int32).tobytes() + np.array(list(F.origin) + [F.voxel], dtype=np.float32).tobytes()

@@ -3,27 +3,21 @@ AddressSanitizer and UBSan, run as a program of its own and compared with the fp
 under the bound of the GPU test: rtol 1e-5 / atol 1e-6 on every node, in-band and void nodes bit for bit.  The volume, the
 intermediate buffers, the output and every tile are allocations of exactly their size, so a node or an LDS word touched outside one
 ends the program with a non-zero status.  No GPU involved, and nothing is loaded into Python under a sanitizer."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import _host_program
 import _esdf_oracle as eo
 import _surfel_oracle as so
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
 
 
 @pytest.fixture(scope="module")
 def body(tmp_path_factory):
-    assert CXX, "a host C++ compiler is needed"
     d = tmp_path_factory.mktemp("esdf_body")
-    exe = str(d / "esdf_body_host")
-    subprocess.check_call([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(HERE, "esdf_body_host.cpp")])
+    exe = _host_program.build("esdf_body_host", d)
 
     def run(D, voxel, trunc, max_distance):
         """-> phi float32 of D's shape.  A sanitizer report or any other failure of the program raises (check_call)."""

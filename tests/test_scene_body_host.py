@@ -3,27 +3,22 @@ code both scene kernels inline) compiled for the HOST with AddressSanitizer and 
 bounds of the GPU tests (values rtol 1e-5 / atol 1e-6, gradients norm-wise 1e-4).  The vector-holding buffer is exactly the grid,
 so a node read outside it, or a float -> int conversion of an out-of-range value, ends the program.  No GPU involved."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import _host_program
 import _scene_oracle as so
 from graspqp_amd.hands import get_hand_spec
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
 
 
 @pytest.fixture(scope="module")
 def body(tmp_path_factory):
-    assert CXX, "a host C++ compiler is needed"
     d = tmp_path_factory.mktemp("scene_body")
-    exe = str(d / "scene_body_host")
-    subprocess.check_call([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(HERE, "scene_body_host.cpp")])
+    exe = _host_program.build("scene_body_host", d)
 
     def run(field, x):
         x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)

@@ -4,27 +4,21 @@ under the bounds and conditions of the GPU test: the count and the order exactly
 angle within 4 x the oracle's own float32-to-float64 angle (at least 1e-5 rad) on the non-ambiguous edges.  The volume, the
 weight, the tile and the outputs are allocations of exactly their size, so a node or slot touched outside one ends the program
 with a non-zero status.  No GPU involved."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import _host_program
 import _surfel_oracle as so
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
 SENTINEL = np.float32(-7777.0)
 
 
 @pytest.fixture(scope="module")
 def body(tmp_path_factory):
-    assert CXX, "a host C++ compiler is needed"
     d = tmp_path_factory.mktemp("surfel_body")
-    exe = str(d / "surfel_body_host")
-    subprocess.check_call([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(HERE, "surfel_body_host.cpp")])
+    exe = _host_program.build("surfel_body_host", d)
 
     def run(D, W, origin, voxel, trunc, min_weight=1.0, region=None, capacity=0):
         """-> (points (G,capacity,3), normals (G,capacity,3), count (G,2)); capacity 0 is the counting call.  A sanitizer report

@@ -3,27 +3,21 @@ compiled for the HOST with AddressSanitizer and UBSan, run as a program of its o
 (tests/_tsdf_oracle.py) under the bounds and conditions of the GPU test: the weight exactly and D at rtol 1e-5 / atol 1e-6 on the
 non-ambiguous nodes.  Every image, label and grid buffer is an allocation of exactly its size, so a pixel or node read outside
 it, or a float -> int conversion of an out-of-range value, ends the program with a non-zero status.  No GPU involved."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import _host_program
 import _tsdf_oracle as to
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
 EYE = np.concatenate([np.eye(3), np.zeros((3, 1))], 1).astype(np.float32)  # a camera at the origin looking along +z of the world
 
 
 @pytest.fixture(scope="module")
 def body(tmp_path_factory):
-    assert CXX, "a host C++ compiler is needed"
     d = tmp_path_factory.mktemp("tsdf_body")
-    exe = str(d / "tsdf_body_host")
-    subprocess.check_call([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(HERE, "tsdf_body_host.cpp")])
+    exe = _host_program.build("tsdf_body_host", d)
 
     def run(vol, depth, labels, cam_T, intrinsics, depth_range, trunc, max_weight=64.0, target_T=None, skip=None):
         """The arguments of to.integrate; ``vol`` is the state BEFORE the call and is left alone.  -> (D, W) float32.  A sanitizer

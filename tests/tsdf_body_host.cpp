@@ -1,6 +1,7 @@
 // The device body of the TSDF integration (graspqp_amd/csrc/tsdf_dev.h: one node through every view) compiled for the HOST:
 // tests/test_tsdf_body_host.py builds this program with the host compiler and sanitizers and compares its float32 results with
-// the fp64 oracle.  Every image, label and grid buffer lives in an allocation of exactly its size, so a pixel or node read
+// the fp64 oracle.  The program walks the launch of tsdf.hip one block and one thread at a time, by the kernel's own decode
+// (grid_stack.h).  Every image, label and grid buffer lives in an allocation of exactly its size, so a pixel or node read
 // outside it, or a float -> int conversion of an out-of-range value, ends the program.  No GPU involved.
 // usage: tsdf_body_host in.bin out.bin
 //   in.bin : int32 G nx ny nz, float32 origin[3] voxel, int32 has_target has_skip has_labels, int32 V H W,
@@ -8,23 +9,7 @@
 //            has_skip, float32 cam_T[V][12], float32 depth[V][H][W], int32 labels[V][H][W] if has_labels,
 //            float32 D[G][nx][ny][nz], float32 W[G][nx][ny][nz]
 //   out.bin: float32 D[G][nx][ny][nz], float32 W[G][nx][ny][nz]
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-using std::min;
-#define GQ_SCENE_HOST_BUILD
-#define __device__
-#define __forceinline__ inline
-#define GQ_INF_F __builtin_inff()
-#include "../include/graspqp_hip.h"
-struct gq3 {
-  float x, y, z;
-};
-static inline gq3 gq_mk(float x, float y, float z) { return gq3{x, y, z}; }
+#include "host_shim.h"
 #include "../graspqp_amd/csrc/tsdf_dev.h"
 
 template <class T>
@@ -57,13 +42,17 @@ int main(int argc, char** argv) {
   views.n_views = V, views.width = Wd, views.height = H;
   views.fx = cam[0], views.fy = cam[1], views.cx = cam[2], views.cy = cam[3], views.depth_min = cam[4], views.depth_max = cam[5];
   const float trunc = cam[6], max_weight = cam[7];
-  for (int g = 0; g < G; ++g)
-    for (int i = 0; i < out.nx; ++i)
-      for (int j = 0; j < out.ny; ++j)
-        for (int k = 0; k < out.nz; ++k) {
-          const size_t node = (((size_t)g * out.nx + i) * out.ny + j) * out.nz + k;
-          gq_tsdf_node(out, has[0] ? tT.data() + 12 * g : nullptr, i, j, k, views, has[1] ? skip[g] : -1, trunc, max_weight, D[node], W[node]);
-        }
+  const GqTiling tiling = gq_tiling(out.nx, out.ny, out.nz);
+  for (long long block = 0; block < gq_tiling_blocks(tiling, G); ++block) {
+    const GqTile t = gq_tile_of((unsigned)block, tiling);
+    const size_t g = t.g;
+    for (int tid = 0; tid < GQ_CL_THREADS; ++tid) {
+      int i, j, k;
+      if (!gq_tile_node(t, tid, out.nx, out.ny, out.nz, i, j, k)) continue;
+      const size_t node = ((g * out.nx + i) * out.ny + j) * out.nz + k;
+      gq_tsdf_node(out, has[0] ? tT.data() + 12 * g : nullptr, i, j, k, views, has[1] ? skip[g] : -1, trunc, max_weight, D[node], W[node]);
+    }
+  }
   FILE* o = fopen(argv[2], "wb");
   if (!o) return 6;
   fwrite(D.data(), 4, D.size(), o);
