@@ -23,7 +23,7 @@ deps() {  # headers each translation unit includes
     fc) echo "common.h fc_dev.h qp_core.h wave.h" ;;
     loop) echo "common.h fc_dev.h loop_dev.h wave.h" ;;
     metric) echo "common.h wave.h metric_dev.h" ;;
-    init) echo "common.h wave.h" ;;
+    init) echo "common.h wave.h init_select_dev.h" ;;
     export) echo "common.h kin_dev.h wave.h" ;;
     exact) echo "common.h wave.h exact_dev.h fc_dev.h" ;;
     kin) echo "common.h setup.h cluster_bound.h loop_dev.h sdf_dev.h tri.h kin_dev.h wave.h" ;;

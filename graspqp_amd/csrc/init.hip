@@ -15,8 +15,16 @@
 // The random numbers are inputs (uniform draws made by the host's device generator), exactly like the draws of the MALA*
 // step.  The hull itself (scipy / qhull at object set-up, like the reference's trimesh call) and its area CDF are set-up
 // data.  trimesh's "even" rejection of close sample pairs is not applied: the farthest-point sampling makes it moot.
+//
+// Scene-aware initialisation (graspqp_hip.h, "screened hull candidates"): every sample becomes a candidate pose, the caller scores
+// the candidates with the stepper's own obstacle terms, and the selection runs among the collision-free ones.
+//   gq_init_candidate_kernel  the row body of gq_init_pose_kernel for every sample (row = obj M + m, sample m)
+//   gq_init_penalty_kernel    penalty = fmaf(w_approach, e_approach, w_scene e_scene)
+//   gq_init_select_kernel     farthest-point sampling among {penalty <= tol}, the remaining slots by ascending (penalty, index):
+//                             one 1024-thread block per object, the per-candidate bodies in init_select_dev.h
 #include "common.h"
 #include "wave.h"
+#include "init_select_dev.h"
 
 struct GqInitArgs {
   const float* hull_fv;    // (sumF,3,3)
@@ -83,10 +91,9 @@ __global__ __launch_bounds__(1024) void gq_init_fps_kernel(GqInitArgs g) {
     // key = (distance bits, ~index): the maximum picks the largest distance and, among equals, the smallest index
     unsigned long long best = 0ull;
     for (int i = tid; i < g.M; i += 1024) {
-      const float dx = P[i * 3] - cx, dy = P[i * 3 + 1] - cy, dz = P[i * 3 + 2] - cz;
-      const float d = fminf(dist[i], dx * dx + dy * dy + dz * dz);
+      const float d = fminf(dist[i], gq_fps_dist2(P[i * 3], P[i * 3 + 1], P[i * 3 + 2], cx, cy, cz));
       dist[i] = d;
-      const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
+      const unsigned long long key = gq_fps_key(d, i);
       best = key > best ? key : best;
     }
 #pragma unroll
@@ -99,7 +106,7 @@ __global__ __launch_bounds__(1024) void gq_init_fps_kernel(GqInitArgs g) {
     if (tid == 0) {
       unsigned long long b = s_key[0];
       for (int w = 1; w < 16; ++w) b = s_key[w] > b ? s_key[w] : b;
-      s_pick = (int)(0xffffffffu - (unsigned)(b & 0xffffffffull));
+      s_pick = gq_fps_key_index(b);
     }
     __syncthreads();
     cur = s_pick;
@@ -126,12 +133,8 @@ __device__ __forceinline__ void gq_mat3_mul(const float* A, const float* Bm, flo
     for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i * 3] * Bm[j] + A[i * 3 + 1] * Bm[3 + j] + A[i * 3 + 2] * Bm[6 + j];
 }
 
-__global__ __launch_bounds__(256) void gq_init_pose_kernel(GqInitPoseArgs g) {
-  const int row = blockIdx.x * blockDim.x + threadIdx.x;
-  const int B = g.n_obj * g.K;
-  if (row >= B) return;
-  const int obj = row / g.K, j = row % g.K;
-  const int s = g.sel[(size_t)obj * g.K + j];
+// the pose of one row from sample s of object obj and the row's draws: the body of both kernels below
+__device__ __forceinline__ void gq_init_pose_row(const GqInitPoseArgs& g, int row, int obj, int s) {
   const float* pp = g.pts + ((size_t)obj * g.M + s) * 3;
   const float* nn = g.nrm + ((size_t)obj * g.M + s) * 3;
   const gq3 p = gq_mk(pp[0], pp[1], pp[2]);
@@ -185,6 +188,110 @@ __global__ __launch_bounds__(256) void gq_init_pose_kernel(GqInitPoseArgs g) {
   if (g.n_out) { g.n_out[row * 3] = n.x; g.n_out[row * 3 + 1] = n.y; g.n_out[row * 3 + 2] = n.z; }
 }
 
+__global__ __launch_bounds__(256) void gq_init_pose_kernel(GqInitPoseArgs g) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  const int B = g.n_obj * g.K;
+  if (row >= B) return;
+  const int obj = row / g.K, j = row % g.K;
+  gq_init_pose_row(g, row, obj, g.sel[(size_t)obj * g.K + j]);
+}
+
+// every sample a row: row = obj M + m looks at sample m (K == M, no selection)
+__global__ __launch_bounds__(256) void gq_init_candidate_kernel(GqInitPoseArgs g) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= g.n_obj * g.M) return;
+  gq_init_pose_row(g, row, row / g.M, row % g.M);
+}
+
+__global__ __launch_bounds__(256) void gq_init_penalty_kernel(const float* __restrict__ e_scene, float w_scene,
+                                                              const float* __restrict__ e_approach, float w_approach, int64_t n,
+                                                              float* __restrict__ penalty) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float es = e_scene ? e_scene[i] : 0.0f, ea = e_approach ? e_approach[i] : 0.0f;
+  penalty[i] = fmaf(e_approach ? w_approach : 0.0f, ea, (e_scene ? w_scene : 0.0f) * es);
+}
+
+// One block of 1024 threads per object, like gq_init_fps_kernel.  Phase 1: farthest-point sampling inside A = {penalty <= tol},
+// started at min A; a picked candidate leaves A, so the picks are distinct also among duplicate points.  Phase 2 (|A| < K): the
+// candidates outside A in ascending (penalty, index), one block-wide minimum per slot of the keys above the last one.  Both loops
+// run min(K, |A|) and K - min(K, |A|) times: K in all.  No atomics, nothing waits for another block.
+__global__ __launch_bounds__(1024) void gq_init_select_kernel(const float* __restrict__ points, const float* __restrict__ penalty,
+                                                              int M, int K, float tol, int32_t* __restrict__ sel,
+                                                              int32_t* __restrict__ n_feasible, float* __restrict__ mind) {
+  __shared__ unsigned long long s_key[16];
+  __shared__ int s_cnt[16], s_first[16];
+  __shared__ float s_cur[3];
+  __shared__ unsigned long long s_best;
+  __shared__ int s_na, s_pick;
+  const int obj = blockIdx.x, tid = threadIdx.x, lane = gq_lane(), wv = tid / GQ_WAVE;
+  const float* P = points + (size_t)obj * M * 3;
+  const float* pen = penalty + (size_t)obj * M;
+  float* dist = mind + (size_t)obj * M;
+  int32_t* out = sel + (size_t)obj * K;
+  int cnt, first;
+  gq_sel_init_thread(pen, dist, M, tol, tid, 1024, &cnt, &first);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += __shfl_xor(cnt, o, GQ_WAVE);
+    const int f = __shfl_xor(first, o, GQ_WAVE);
+    first = f < first ? f : first;
+  }
+  if (lane == 0) { s_cnt[wv] = cnt; s_first[wv] = first; }
+  __syncthreads();
+  if (tid == 0) {
+    int c = 0, f = M;
+    for (int w = 0; w < 16; ++w) { c += s_cnt[w]; f = s_first[w] < f ? s_first[w] : f; }
+    s_na = c;
+    s_pick = f;
+    n_feasible[obj] = c;
+  }
+  __syncthreads();
+  const int nA = s_na, n1 = nA < K ? nA : K;
+  int cur = s_pick;
+  for (int it = 0; it < n1; ++it) {
+    if (tid == 0) {
+      out[it] = cur;
+      s_cur[0] = P[(size_t)cur * 3]; s_cur[1] = P[(size_t)cur * 3 + 1]; s_cur[2] = P[(size_t)cur * 3 + 2];
+    }
+    __syncthreads();
+    unsigned long long best = gq_sel_fps_thread(P, dist, M, tid, 1024, cur, s_cur[0], s_cur[1], s_cur[2]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(best, o, GQ_WAVE);
+      best = other > best ? other : best;
+    }
+    if (lane == 0) s_key[wv] = best;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long b = s_key[0];
+      for (int w = 1; w < 16; ++w) b = s_key[w] > b ? s_key[w] : b;
+      s_pick = gq_fps_key_index(b);  // b == GQ_SEL_NO_FPS_KEY only after the last member of A: the loop ends then
+    }
+    __syncthreads();
+    cur = s_pick;
+  }
+  unsigned long long last = 0ull;
+  for (int it = n1; it < K; ++it) {
+    unsigned long long best = gq_sel_fill_thread(pen, M, tol, tid, 1024, it > n1, last);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(best, o, GQ_WAVE);
+      best = other < best ? other : best;
+    }
+    if (lane == 0) s_key[wv] = best;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long b = s_key[0];
+      for (int w = 1; w < 16; ++w) b = s_key[w] < b ? s_key[w] : b;
+      s_best = b;
+      out[it] = gq_sel_fill_key_index(b);  // M >= K: there is a candidate left for every slot
+    }
+    __syncthreads();
+    last = s_best;  // rewritten only behind the next round's first barrier
+  }
+}
+
 extern "C" {
 
 int gq_init_workspace_bytes(int64_t n_obj, int64_t samples_per_object, int64_t batch_each, size_t* bytes) {
@@ -193,18 +300,9 @@ int gq_init_workspace_bytes(int64_t n_obj, int64_t samples_per_object, int64_t b
   return GQ_OK;
 }
 
-int gq_init_convex_hull(const gqInitDesc* d, void* stream) {
-  GQ_REQUIRE(d, "init_convex_hull: null descriptor");
-  GQ_REQUIRE(d->hull_face_verts && d->hull_cdf && d->hull_offsets && d->u_face && d->u_len && d->u_pose && d->u_joint &&
-                 d->default_state && d->joints_lower && d->joints_upper && d->hand_pose && d->workspace,
-             "init_convex_hull: null pointer in the descriptor");
-  GQ_REQUIRE(d->n_obj > 0 && d->batch_each > 0 && d->n_dofs > 0 && d->samples_per_object >= d->batch_each,
-             "init_convex_hull: bad sizes (n_obj=%lld, batch_each=%lld, samples=%lld)", (long long)d->n_obj,
-             (long long)d->batch_each, (long long)d->samples_per_object);
-  GQ_REQUIRE(d->samples_per_object < (1ll << 30), "init_convex_hull: too many samples per object");
-  size_t need = 0;
-  gq_init_workspace_bytes(d->n_obj, d->samples_per_object, d->batch_each, &need);
-  GQ_REQUIRE(d->workspace_bytes >= need, "init_convex_hull: workspace too small (%zu < %zu)", d->workspace_bytes, need);
+// the launches behind a checked descriptor: samples, then farthest-point sampling + one pose per pick, or (candidates) one pose
+// per sample
+static int gq_init_launch(const gqInitDesc* d, void* stream, bool candidates) {
   hipStream_t st = (hipStream_t)stream;
   GqInitArgs a{};
   a.hull_fv = d->hull_face_verts;
@@ -223,8 +321,10 @@ int gq_init_convex_hull(const gqInitDesc* d, void* stream) {
   a.sel = (int32_t*)(a.mind + (size_t)a.n_obj * a.M);
   hipLaunchKernelGGL(gq_init_sample_kernel, dim3((unsigned)((a.M + 255) / 256), (unsigned)a.n_obj), dim3(256), 0, st, a);
   GQ_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gq_init_fps_kernel, dim3((unsigned)a.n_obj), dim3(1024), 0, st, a);
-  GQ_LAUNCH_CHECK();
+  if (!candidates) {
+    hipLaunchKernelGGL(gq_init_fps_kernel, dim3((unsigned)a.n_obj), dim3(1024), 0, st, a);
+    GQ_LAUNCH_CHECK();
+  }
   GqInitPoseArgs p{};
   p.pts = a.pts;
   p.nrm = a.nrm;
@@ -252,7 +352,85 @@ int gq_init_convex_hull(const gqInitDesc* d, void* stream) {
   p.p_out = d->shell_points;
   p.n_out = d->shell_dirs;
   const int B = a.n_obj * a.K;
-  hipLaunchKernelGGL(gq_init_pose_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, p);
+  if (candidates)
+    hipLaunchKernelGGL(gq_init_candidate_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL(gq_init_pose_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, p);
+  GQ_LAUNCH_CHECK();
+  return GQ_OK;
+}
+
+int gq_init_convex_hull(const gqInitDesc* d, void* stream) {
+  GQ_REQUIRE(d, "init_convex_hull: null descriptor");
+  GQ_REQUIRE(d->hull_face_verts && d->hull_cdf && d->hull_offsets && d->u_face && d->u_len && d->u_pose && d->u_joint &&
+                 d->default_state && d->joints_lower && d->joints_upper && d->hand_pose && d->workspace,
+             "init_convex_hull: null pointer in the descriptor");
+  GQ_REQUIRE(d->n_obj > 0 && d->batch_each > 0 && d->n_dofs > 0 && d->samples_per_object >= d->batch_each,
+             "init_convex_hull: bad sizes (n_obj=%lld, batch_each=%lld, samples=%lld)", (long long)d->n_obj,
+             (long long)d->batch_each, (long long)d->samples_per_object);
+  GQ_REQUIRE(d->samples_per_object < (1ll << 30), "init_convex_hull: too many samples per object");
+  size_t need = 0;
+  gq_init_workspace_bytes(d->n_obj, d->samples_per_object, d->batch_each, &need);
+  GQ_REQUIRE(d->workspace_bytes >= need, "init_convex_hull: workspace too small (%zu < %zu)", d->workspace_bytes, need);
+  return gq_init_launch(d, stream, false);
+}
+
+int gq_init_candidates(const gqInitDesc* d, void* stream) {
+  GQ_REQUIRE(d, "init_candidates: null descriptor");
+  GQ_REQUIRE(d->hull_face_verts && d->hull_cdf && d->hull_offsets && d->u_face && d->u_len && d->u_pose && d->u_joint &&
+                 d->default_state && d->joints_lower && d->joints_upper && d->hand_pose && d->workspace,
+             "init_candidates: null pointer in the descriptor");
+  GQ_REQUIRE(d->shell_points && d->shell_dirs, "init_candidates: shell_points and shell_dirs are required");
+  GQ_REQUIRE(d->n_obj > 0 && d->batch_each > 0 && d->n_dofs > 0 && d->samples_per_object == d->batch_each,
+             "init_candidates: batch_each must equal samples_per_object (n_obj=%lld, batch_each=%lld, samples=%lld)",
+             (long long)d->n_obj, (long long)d->batch_each, (long long)d->samples_per_object);
+  GQ_REQUIRE(d->samples_per_object < (1ll << 30) && d->n_obj * d->samples_per_object < (1ll << 28),
+             "init_candidates: n_obj x samples_per_object must be < 2^28");
+  size_t need = 0;
+  gq_init_workspace_bytes(d->n_obj, d->samples_per_object, d->batch_each, &need);
+  GQ_REQUIRE(d->workspace_bytes >= need, "init_candidates: workspace too small (%zu < %zu)", d->workspace_bytes, need);
+  return gq_init_launch(d, stream, true);
+}
+
+int gq_init_penalty(const float* e_scene, float w_scene, const float* e_approach, float w_approach, int64_t n, float* penalty,
+                    void* stream) {
+  GQ_REQUIRE(penalty && n > 0 && n <= 0x7fffffffll, "init_penalty: bad arguments");
+  hipLaunchKernelGGL(gq_init_penalty_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e_scene, w_scene,
+                     e_approach, w_approach, n, penalty);
+  GQ_LAUNCH_CHECK();
+  return GQ_OK;
+}
+
+int gq_init_select_check(const float* points, const float* penalty, int64_t n_obj, int64_t M, int64_t K, float tol,
+                         const int32_t* sel, const int32_t* n_feasible, const void* workspace) {
+  GQ_REQUIRE(points, "init_select: points is NULL");
+  GQ_REQUIRE(penalty, "init_select: penalty is NULL");
+  GQ_REQUIRE(sel, "init_select: sel is NULL");
+  GQ_REQUIRE(n_feasible, "init_select: n_feasible is NULL");
+  GQ_REQUIRE(workspace, "init_select: workspace is NULL");
+  GQ_REQUIRE(n_obj > 0 && n_obj <= 0x7fffffffll, "init_select: n_obj must be in 1..2^31-1, got %lld", (long long)n_obj);
+  GQ_REQUIRE(K > 0, "init_select: K must be > 0, got %lld", (long long)K);
+  GQ_REQUIRE(M >= K, "init_select: M must be >= K, got M = %lld, K = %lld", (long long)M, (long long)K);
+  GQ_REQUIRE(M < (1ll << 30), "init_select: M must be < 2^30, got %lld", (long long)M);
+  GQ_REQUIRE(tol >= 0.0f, "init_select: tol must be >= 0 and not NaN, got %g", (double)tol);
+  return GQ_OK;
+}
+
+int gq_init_select_workspace_bytes(int64_t n_obj, int64_t M, size_t* bytes) {
+  GQ_REQUIRE(bytes && n_obj > 0 && M > 0, "init_select_workspace_bytes: bad arguments");
+  *bytes = (size_t)n_obj * (size_t)M * sizeof(float);
+  return GQ_OK;
+}
+
+int gq_init_select(const float* points, const float* penalty, int64_t n_obj, int64_t M, int64_t K, float tol, int32_t* sel,
+                   int32_t* n_feasible, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = gq_init_select_check(points, penalty, n_obj, M, K, tol, sel, n_feasible, workspace);
+  if (rc != GQ_OK) return rc;
+  size_t need = 0;
+  gq_init_select_workspace_bytes(n_obj, M, &need);
+  GQ_REQUIRE(workspace_bytes >= need, "init_select: workspace too small (%zu < %zu)", workspace_bytes, need);
+  hipLaunchKernelGGL(gq_init_select_kernel, dim3((unsigned)n_obj), dim3(1024), 0, (hipStream_t)stream, points, penalty, (int)M,
+                     (int)K, tol, sel, n_feasible, (float*)workspace);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

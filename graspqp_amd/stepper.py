@@ -71,7 +71,8 @@ class GraspStepper:
                  penetration_only: bool = True, energy_type: str = "graspqp", optimizer: str = "mala_star",
                  tdg_directions=None, point_grid: int = 0, split_self_pen: bool = True, n_surface_points: int = 512,
                  surface_samples=None, table_z: float = 0.0, scene=None, scene_margin: float = 0.0,
-                 approach_distance: float = 0.10, approach_stations: int = 4, approach_margin=None):
+                 approach_distance: float = 0.10, approach_stations: int = 4, approach_margin=None,
+                 init_avoid_scene: bool = False):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -126,6 +127,9 @@ class GraspStepper:
                 raise ValueError(f"GraspStepper: approach_distance = {approach_distance!r} must be finite and > 0")
             if int(approach_stations) != approach_stations or not 1 <= int(approach_stations) <= 32:
                 raise ValueError(f"GraspStepper: approach_stations = {approach_stations!r} must be an integer in 1..32")
+        self.init_avoid_scene = bool(init_avoid_scene)
+        if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
+            raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
         self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
                            + (APPROACH_TERMS if self.approach_mode else ()))
         nT = len(self.term_names)
@@ -279,6 +283,7 @@ class GraspStepper:
             # d (w_prior E_prior) / d R = w_prior * grasp_axis in row 2 does not depend on the pose: set here, once; the launch
             # of every evaluation adds to wrench / gRt and is given no g_R
             self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._grasp_axis), device=self.dev)
+        self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
         pr.hand_pose, pr.grad, pr.contact_idx = self.hand_pose.data_ptr(), self.grad.data_ptr(), self.contact_idx.data_ptr()
@@ -670,12 +675,23 @@ class GraspStepper:
 
     def fresh_state(self):
         """hand_pose (B,D) and contact indices (B,n) of initialize_convex_hull for ALL rows, drawn with the stepper's
-        generator -- device tensors, nothing touches the host."""
-        from .core.initializations import convex_hull_poses
+        generator -- device tensors, nothing touches the host.  With ``init_avoid_scene`` the poses are screened against the
+        scene (constructor docstring) and ``init_feasible`` is refreshed."""
+        from .core.initializations import convex_hull_poses, convex_hull_poses_screened
 
         if getattr(self, "_hulls", None) is None:
             raise RuntimeError("GraspStepper.set_hulls(object_model.convex_hulls()) must be called first")
-        pose = convex_hull_poses(self.hand.spec, self._hulls, self.n_obj, self.be, self._init_args, self.gen, self.dev)
+        if self.init_avoid_scene:
+            approach = None
+            if self.approach_mode:
+                approach = dict(distance=self.approach_distance, stations=self.approach_stations, margin=self.approach_margin,
+                                axis=self.hand.spec.grasp_axis, weight=self.w["E_approach"])
+            pose, info = convex_hull_poses_screened(self.hand, self._hulls, self.n_obj, self.be, self.samples, self.scene,
+                                                    self.scene_margin, self.w["E_scene"], approach, self._init_args, self.gen,
+                                                    return_info=True)
+            self.init_feasible.copy_(info["n_feasible"])
+        else:
+            pose = convex_hull_poses(self.hand.spec, self._hulls, self.n_obj, self.be, self._init_args, self.gen, self.dev)
         idx = torch.randint(self.hand.spec.n_contact_candidates, (self.B, self.n), device=self.dev, generator=self.gen)
         return pose, idx
 

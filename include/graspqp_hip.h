@@ -802,6 +802,44 @@ typedef struct gqInitDesc {
 } gqInitDesc;
 int gq_init_workspace_bytes(int64_t n_obj, int64_t samples_per_object, int64_t batch_each, size_t* bytes);
 int gq_init_convex_hull(const gqInitDesc* desc, void* stream);
+
+/* ---- scene-aware initialisation: screened hull candidates -------------------------------------------------------------
+ * An opt-in route for hands that start next to obstacles: every hull sample becomes a complete candidate pose, the caller
+ * scores every candidate with the obstacle terms the stepper evaluates (gq_fk_forward, gq_scene_terms, gq_approach_terms on
+ * the candidate rows, unweighted, link_wrench = gRt = NULL), and batch_each candidates per object are picked by farthest-point
+ * sampling among the collision-free ones only.
+ *
+ * gq_init_candidates is gq_init_convex_hull with every sample a row: it requires batch_each == samples_per_object = M, runs
+ * no farthest-point pass (the selection is the identity), reads u_pose (n_obj M, 4) and u_joint (n_obj M, n_dofs) and writes
+ * hand_pose (n_obj M, 9 + n_dofs); shell_points and shell_dirs (n_obj M, 3) are required: they are the candidate points and
+ * directions.  n_obj M < 2^28.  Workspace: gq_init_workspace_bytes(n_obj, M, M).  Contract: candidate m's pose is, bit for
+ * bit, what gq_init_convex_hull gives a row that picked sample m with the draws u_pose[m], u_joint[m] (one row body).
+ *
+ * gq_init_penalty: penalty[i] = fmaf(w_approach, e_approach[i], w_scene * e_scene[i]) for i < n; a NULL term is off and
+ * contributes exactly 0.
+ *
+ * gq_init_select: points (n_obj,M,3) and penalty (n_obj,M) -> sel (n_obj,K) int32 candidate indices and n_feasible (n_obj)
+ * int32.  Per object, with A = {m : penalty[m] <= tol} (a NaN penalty is never in A, -0.0 is at tol = 0) and
+ * n_feasible = |A|, not capped by K:
+ *   phase 1, slots t = 0 .. min(K, |A|) - 1: d[m] = +inf, c = min A; repeat: sel[t] = c, remove c from A, for m in A
+ *     d[m] = min(d[m], |P[m] - P[c]|^2), c = argmax over A of d, the smallest index among equals.  The squared distance is the
+ *     expression of gq_init_convex_hull's farthest-point pass: with every candidate feasible and distinct points sel is that
+ *     pass's, bit for bit.  The picks are distinct also among duplicate points.
+ *   phase 2, the remaining slots: the candidates outside the original A in ascending order of (penalty, index); NaN sorts
+ *     after +inf.
+ * One block of 1024 threads per object; no atomics, no block waits for another, every loop is bounded by K; no allocation,
+ * synchronisation or upload: graph-capturable and bitwise reproducible.  workspace: gq_init_select_workspace_bytes(n_obj, M)
+ * bytes on the device, contents irrelevant.
+ * gq_init_select_check (host only, no GPU) refuses: a NULL points, penalty, sel, n_feasible or workspace; n_obj <= 0; K <= 0;
+ * M < K; M >= 2^30; a tol that is NaN or negative.  The message contains "init_select" and names the argument.           */
+int gq_init_candidates(const gqInitDesc* desc, void* stream);
+int gq_init_penalty(const float* e_scene /* (n) or NULL */, float w_scene, const float* e_approach /* (n) or NULL */,
+                    float w_approach, int64_t n, float* penalty, void* stream);
+int gq_init_select_check(const float* points, const float* penalty, int64_t n_obj, int64_t M, int64_t K, float tol,
+                         const int32_t* sel, const int32_t* n_feasible, const void* workspace /* only tested against NULL */);
+int gq_init_select_workspace_bytes(int64_t n_obj, int64_t M, size_t* bytes);
+int gq_init_select(const float* points, const float* penalty, int64_t n_obj, int64_t M, int64_t K, float tol, int32_t* sel,
+                   int32_t* n_feasible, void* workspace, size_t workspace_bytes, void* stream);
 /* Surface samples of object meshes on the device (reference core/object_model.py:163-178: pytorch3d
  * sample_points_from_meshes with 100 x num_samples points, then sample_farthest_points(K = num_samples) starting at sample
  * 0): face_verts (sumF,3,3) of n_obj meshes, area_cdf (sumF) normalised cumulative face area per mesh, face_offsets

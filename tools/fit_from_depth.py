@@ -5,10 +5,13 @@
 turns the target volume into an oriented point cloud on the device (SceneTSDF.extract_clouds -> ObjectModel.initialize_from_tsdf),
 and runs GraspStepper with E_scene on the scene volume and the extracted cloud as the object.  With --esdf MAX_DISTANCE the stepper reads
 the Euclidean distance field of the scene volume instead (SceneTSDF.esdf), which allows a --scene_margin above trunc.  It reports the number of surfels,
+With --init_avoid_scene the initial poses and those of every reset are screened against that field; --reset_epochs N
+turns the z-score resets of the reference's schedule on (default: none).  It reports the number of surfels,
 how far they lie from the true sphere, the mean energy and the mean E_scene before and after --n_iter iterations, and the wall
 times of the stages (each closed by a synchronisation).  Evidence run, not a test: one JSON line is printed and appended to --out.
 
-usage: python tools/fit_from_depth.py [--views 8] [--batch_size 64] [--n_iter 400] [--esdf 0.06 --scene_margin 0.03] [--out file.jsonl]
+usage: python tools/fit_from_depth.py [--views 8] [--batch_size 64] [--n_iter 400] [--esdf 0.06 --scene_margin 0.03]
+       [--init_avoid_scene] [--reset_epochs 600] [--out file.jsonl]
 """
 import argparse
 import json
@@ -33,6 +36,8 @@ ap.add_argument("--min_weight", type=float, default=2.0)
 ap.add_argument("--hand", default="allegro")
 ap.add_argument("--esdf", type=float, default=None, metavar="MAX_DISTANCE", help="run the stepper on scene.esdf(MAX_DISTANCE)")
 ap.add_argument("--scene_margin", type=float, default=0.005)
+ap.add_argument("--init_avoid_scene", action="store_true", help="screen the initial and the re-initialised poses against the scene")
+ap.add_argument("--reset_epochs", type=int, default=None, help="z-score resets every N iterations (default: no resets)")
 ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "fit_from_depth.jsonl"))
 args = ap.parse_args()
 
@@ -115,20 +120,24 @@ if args.esdf is not None:
     scene.esdf(args.esdf)  # warm-up: the output, the workspace and the kernels' code objects
     field, ms_esdf = timed(lambda: scene.esdf(args.esdf))
 st = GraspStepper(ops.HandHandle(get_hand_spec(args.hand)), om._cloudset, om.surface_points_each, be, n, seed=1, weights=weights,
-                  scene=field, scene_margin=args.scene_margin)
+                  scene=field, scene_margin=args.scene_margin, init_avoid_scene=args.init_avoid_scene)
 st.set_hulls(om.convex_hulls())
 st.initialize()
 names = list(st.term_names)
 e0, s0 = st.energy.clone(), st.terms[names.index("E_scene")].clone()
+feasible0 = st.init_feasible.tolist() if args.init_avoid_scene else None
 st.capture(iters=8)
-_, ms_run = timed(lambda: st.run(args.n_iter, reset_epochs=None))
+_, ms_run = timed(lambda: st.run(args.n_iter, reset_epochs=args.reset_epochs))
 e1, s1 = st.energy, st.terms[names.index("E_scene")]
 assert torch.isfinite(e1).all() and torch.isfinite(st.hand_pose).all()
 dis, _ = om.cal_distance(st.cpts)
 
 rec = {"fit_from_depth": True, "hand": args.hand, "views": args.views, "image": [W, H], "batch": be, "n_contact": n, "n_iter": args.n_iter,
        "scene_grid": list(S_SHAPE), "scene_voxel": S_H, "target_grid": list(T_SHAPE), "target_voxel": T_H, "min_weight": args.min_weight,
-       "esdf_max_distance": args.esdf, "scene_margin": args.scene_margin, "surfels": int(len(p)), "radius_used": float(om._cloudset.radius[0]),
+       "esdf_max_distance": args.esdf, "scene_margin": args.scene_margin, "init_avoid_scene": args.init_avoid_scene,
+       "reset_epochs": args.reset_epochs, "init_feasible": feasible0,
+       "rows_in_scene": {"before": float((s0 > 0).float().mean()), "after": float((s1 > 0).float().mean())},
+       "surfels": int(len(p)), "radius_used": float(om._cloudset.radius[0]),
        "radial_error_mm": {"median": 1e3 * float(np.median(radial)), "max": 1e3 * float(radial.max())},
        "normal_angle_deg": {"median": float(np.median(angle)), "p99": float(np.percentile(angle, 99)), "max": float(angle.max())},
        "energy_mean": {"before": float(e0.mean()), "after": float(e1.mean())},
