@@ -151,6 +151,25 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal):
             e = e + torch.relu(margin - ops.scene_distance(x - (D * k / K) * back.unsqueeze(1), scene)).sum(-1)
         losses["E_approach"] = e * (1.0 / K)
 
+    if "E_pregrasp" in energy_names:  # the hinge of the OPENED hand along the corridor, d = 0 included (HandModel.set_pregrasp):
+        pregrasp = getattr(hand_model, "pregrasp", None)  # the surface points of a second FK at the opened pose, then one
+        if pregrasp is None:  # scene_distance per station
+            raise ValueError('calculate_energy: "E_pregrasp" needs HandModel.set_pregrasp(...)')
+        D, K, opening, q_open, margin, scene = pregrasp
+        scene = getattr(hand_model, "scene", None) if scene is None else scene
+        if scene is None:
+            raise ValueError('calculate_energy: "E_pregrasp" needs a scene: HandModel.set_pregrasp(..., scene=) or set_scene(...)')
+        margin = getattr(hand_model, "scene_margin", 0.0) if margin is None else margin
+        hp = hand_model.hand_pose
+        opened = torch.cat([hp[:, :9], (1.0 - opening) * hp[:, 9:] + opening * q_open.unsqueeze(0)], dim=1)
+        x = hand_model.get_surface_points(opened)
+        back = (hand_model.global_rotation @ hand_model.grasp_axis.view(1, -1, 1)).view(-1, 3)  # R a: the root pose is shared
+        e = 0
+        for k in range(K + 1):
+            xk = x if k == 0 else x - (D * k / K) * back.unsqueeze(1)
+            e = e + torch.relu(margin - ops.scene_distance(xk, scene)).sum(-1)
+        losses["E_pregrasp"] = e * (1.0 / (K + 1))
+
     if "E_manipulativity" in energy_names:
         # energy.py:80-87: mean squared contact velocity the joints cannot produce when the contacts move along
         # normal * max(|distance|, 5 mm); differentiable (ops.joint_velocity_residuals: analytic kinematic Hessian)

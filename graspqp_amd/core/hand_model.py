@@ -237,12 +237,42 @@ class HandModel:
             raise ValueError(f"HandModel.set_approach: stations = {stations!r} must be an integer in 1..32")
         self.approach = (float(distance), int(stations), margin)
 
-    def get_surface_points(self):
-        """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose."""
+    def set_pregrasp(self, distance, stations, opening=0.5, open_joints=None, margin=None, scene=None):
+        """The pre-grasp corridor of calculate_energy(..., energy_names=[..., "E_pregrasp"]): the mean over the stations
+        d_k = distance k / stations, k = 0..stations <= 32, of the scene hinge with the joints opened to
+        (1 - opening) theta + opening open_joints and the whole hand moved back by d_k along the spec's grasp_axis.
+        ``open_joints`` (n_dofs) = None takes the default state clamped to the joint limits; ``margin`` = None follows the scene's
+        margin; ``scene`` = None takes the grid of ``set_scene`` -- this term's grid usually contains the target, which the grid
+        of E_scene must not, so it can be given on its own."""
+        if scene is None and getattr(self, "scene", None) is None:
+            raise ValueError("HandModel.set_pregrasp: pass scene=ops.SceneSDF(...) or call set_scene(...) first")
+        if scene is not None and not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
+            raise ValueError("HandModel.set_pregrasp: scene must be an ops.SceneSDF, an ops.SceneSDFSet or None")
+        margin = None if margin is None else float(margin)
+        if margin is not None and not margin >= 0.0:
+            raise ValueError(f"HandModel.set_pregrasp: margin = {margin!r} must be >= 0")
+        if not 0.0 < float(distance) < float("inf"):
+            raise ValueError(f"HandModel.set_pregrasp: distance = {distance!r} must be finite and > 0")
+        if int(stations) != stations or not 0 <= int(stations) <= 32:
+            raise ValueError(f"HandModel.set_pregrasp: stations = {stations!r} must be an integer in 0..32")
+        if not 0.0 <= float(opening) <= 1.0:
+            raise ValueError(f"HandModel.set_pregrasp: opening = {opening!r} must be in [0, 1]")
+        if open_joints is None:
+            q = ops.default_open_joints(self.spec, self.device)
+        else:
+            q = torch.as_tensor(open_joints, dtype=torch.float32).detach().to(self.device)
+        if q.shape != (self.n_dofs,):
+            raise ValueError(f"HandModel.set_pregrasp: open_joints must be ({self.n_dofs},), got {tuple(q.shape)}")
+        self.pregrasp = (float(distance), int(stations), float(opening), q, margin, scene)
+
+    def get_surface_points(self, hand_pose=None):
+        """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose; ``hand_pose`` =
+        None takes the model's own (another pose, e.g. the opened one of E_pregrasp, is a second FK at that pose)."""
         h, pts, _ = self._surface_handle()
-        B = self.hand_pose.shape[0]
+        hp = self.hand_pose if hand_pose is None else hand_pose
+        B = hp.shape[0]
         idx = torch.arange(len(pts), dtype=torch.long, device=self.device).unsqueeze(0).expand(B, -1).contiguous()
-        return ops.fk_contacts(self.hand_pose, idx, h)[2]
+        return ops.fk_contacts(hp, idx, h)[2]
 
     # reference hand_model.py:1073-1077
     def get_manipulability(self, moving_directions, contact_point_indices=None, coupled=True):

@@ -1994,6 +1994,150 @@ def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axi
     return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
 
 
+# ----------------------------------------------------------------------------------------------------------
+# pre-grasp clearance: E_pregrasp, the OPENED hand along the approach corridor (csrc/pregrasp.hip).  One launch does the opened
+# kinematics, the stations and the joint gradient; a single grid crosses as the stack of one
+# ----------------------------------------------------------------------------------------------------------
+def _pregrasp_grids(values, origin, voxel) -> "_C.ClutterGrids":
+    """gqClutterGrids of a (G,nx,ny,nz) stack, or of a single (nx,ny,nz) grid as the stack of one (a view: no copy)."""
+    return _clutter_grids(values if values.dim() == 4 else values.unsqueeze(0), origin, voxel)
+
+
+def pregrasp_check(scene, batch, n_links, n_samples, distance, stations, grasp_axis, opening):
+    """gq_pregrasp_check (host only) of the grid or stack, a launch's shapes, the corridor and the opening; raises ValueError
+    with the library's message."""
+    if not isinstance(scene, (SceneSDF, SceneSDFSet)):
+        raise ValueError("pregrasp: scene must be an ops.SceneSDF or an ops.SceneSDFSet")
+    ax = (ctypes.c_float * 3)(*(float(a) for a in grasp_axis))
+    G = scene.n_grids if isinstance(scene, SceneSDFSet) else 1
+    if int(batch) % G:
+        raise ValueError(f"pregrasp: batch = {batch} is not divisible by n_grids = {G}")
+    try:
+        _C.call("gq_pregrasp_check", ctypes.byref(_pregrasp_grids(scene.values, scene.origin, scene.voxel)),
+                ctypes.c_int64(int(batch)), ctypes.c_int64(int(batch) // G), int(n_links), ctypes.c_int64(int(n_samples)),
+                float(distance), int(stations), ctypes.cast(ax, ctypes.c_void_p), float(opening))
+    except RuntimeError as e:
+        raise ValueError(f"pregrasp: {e}") from None
+
+
+def default_open_joints(spec, device="cuda") -> Tensor:
+    """The joints the term opens the hand towards unless told otherwise: ``spec.default_state`` clamped to the joint limits,
+    the mean ``initialize_convex_hull`` opens the hand to; (JA) float32 on ``device``."""
+    q = np.clip(np.asarray(spec.default_state, dtype=np.float32), np.asarray(spec.joints_lower, dtype=np.float32),
+                np.asarray(spec.joints_upper, dtype=np.float32))
+    return torch.from_numpy(np.ascontiguousarray(q)).to(device)
+
+
+def _pregrasp_call(hand, grids, margin, distance, stations, opening, open_joints, hp, points, link, Rg, axis, up_pregrasp,
+                   w_pregrasp, e_pregrasp, accumulate, g_theta, gRt, st=None):
+    ax = (ctypes.c_float * 3)(*(float(a) for a in axis))
+    B = hp.shape[0]
+    _C.call("gq_pregrasp_terms", hand.handle, ctypes.byref(grids), ctypes.c_int64(B // max(grids.n_grids, 1)), float(margin),
+            float(distance), int(stations), float(opening), _C.f32(open_joints), _C.f32(points), _C.i32(link),
+            ctypes.c_int64(points.shape[0]), _C.f32(hp), hp.shape[1], _C.f32(Rg), ctypes.c_int64(B),
+            ctypes.cast(ax, ctypes.c_void_p), _C.f32(up_pregrasp), float(w_pregrasp), _C.f32(e_pregrasp), int(accumulate),
+            _C.f32(g_theta), _C.f32(gRt), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::pregrasp_terms", mutates_args=(), device_types="cuda")
+def _pregrasp_op(hand_pose: Tensor, points: Tensor, link: Tensor, hand: int, Rg: Tensor, values: Tensor, origin: List[float],
+                 voxel: float, grasp_axis: List[float], distance: float, stations: int, opening: float, open_joints: Tensor,
+                 margin: float) -> Tensor:
+    """-> E_pregrasp (B), unweighted: the mean over the stations d_k = distance k / stations, k = 0..stations, of the hinge sum of
+    the hand's surface samples with the joints opened by ``opening`` towards ``open_joints`` and the hand moved back by d_k along
+    grasp_axis.  ``values`` is one grid (nx,ny,nz) or a stack (G,nx,ny,nz); Rg is the rotation of ``hand_pose``."""
+    h = _handle(hand)
+    hp, v = _c(hand_pose), _c(values)
+    e = torch.empty(hp.shape[0], device=hp.device)
+    _pregrasp_call(h, _pregrasp_grids(v, origin, voxel), margin, distance, stations, opening, _c(open_joints), hp, _c(points),
+                   _c(link, torch.int32), _c(Rg), grasp_axis, None, 0.0, e, 0, None, None)
+    return e
+
+
+@_pregrasp_op.register_fake
+def _(hand_pose, points, link, hand, Rg, values, origin, voxel, grasp_axis, distance, stations, opening, open_joints, margin):
+    return hand_pose.new_empty(hand_pose.shape[0])
+
+
+@_custom_op("graspqp_amd::pregrasp_terms_backward", mutates_args=(), device_types="cuda")
+def _pregrasp_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, hand: int, Rg: Tensor, values: Tensor, origin: List[float],
+                     voxel: float, grasp_axis: List[float], distance: float, stations: int, opening: float, open_joints: Tensor,
+                     margin: float, g_pregrasp: Tensor) -> Tuple[Tensor, Tensor]:
+    """Upstream row gradients (B) on E_pregrasp -> (g_theta (B,JA), gRt (B,12)): the direct joint gradient, and the global-pose
+    part in the form fk_backward takes."""
+    h = _handle(hand)
+    hp, v = _c(hand_pose), _c(values)
+    B, dev = hp.shape[0], hp.device
+    g_theta, gRt = torch.empty(B, hp.shape[1] - 9, device=dev), torch.empty(B, 12, device=dev)
+    _pregrasp_call(h, _pregrasp_grids(v, origin, voxel), margin, distance, stations, opening, _c(open_joints), hp, _c(points),
+                   _c(link, torch.int32), _c(Rg), grasp_axis, _c(g_pregrasp), 0.0, None, 0, g_theta, gRt)
+    return g_theta, gRt
+
+
+@_pregrasp_bwd_op.register_fake
+def _(hand_pose, points, link, hand, Rg, values, origin, voxel, grasp_axis, distance, stations, opening, open_joints, margin,
+      g_pregrasp):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B, hand_pose.shape[1] - 9), hand_pose.new_empty(B, 12)
+
+
+class _PregraspTerms(torch.autograd.Function):
+    """Glue between registered ops (pregrasp_terms + fk_backward), as _ApproachTerms: the backward launch overwrites gRt and
+    g_theta with the per-row upstream; the FK backward of the CLOSED hand turns gRt into the root-pose gradient (the opened hand
+    shares the root pose), and g_theta is the joint part as it stands."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, samples, idx, Rg, LT, ws, scene, axis, distance, stations, opening, open_joints, margin):
+        hp = _c(hand_pose.detach())
+        e = _Eager.pregrasp_terms(hp, samples.points, samples.link, hand.hid, Rg, scene.values, list(scene.origin), scene.voxel,
+                                  axis, distance, stations, opening, open_joints, margin)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, samples.points, samples.link, scene.values, open_joints)
+        ctx.hand, ctx.origin, ctx.voxel = hand, list(scene.origin), scene.voxel
+        ctx.corridor = (axis, distance, stations, opening)
+        ctx.margin = margin
+        return e
+
+    @staticmethod
+    def backward(ctx, g_pregrasp):
+        hp, idx, Rg, LT, ws, points, link, values, open_joints = ctx.saved_tensors
+        hand = ctx.hand
+        g_theta, gRt = _Eager.pregrasp_terms_backward(hp, points, link, hand.hid, Rg, values, ctx.origin, ctx.voxel, *ctx.corridor,
+                                                      open_joints, ctx.margin, g_pregrasp)
+        gp = _fk_backward(hand, hp, idx, Rg, LT, ws, None, None, None, None, gRt, None)
+        gp[:, 9:] += g_theta
+        return (gp,) + (None,) * 13
+
+
+def pregrasp_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, LT, ws, scene, grasp_axis, distance, stations,
+                   opening, open_joints=None, margin=0.0):
+    """-> E_pregrasp (B) = 1/(K+1) sum over the stations k = 0..K and over ``samples`` of max(margin - phi(x_w^k), 0) on the
+    scene's grid, with the joints opened to (1 - opening) theta + opening ``open_joints`` and the whole hand moved back by
+    ``distance`` k / K along ``grasp_axis`` (hand frame); unweighted, differentiable w.r.t. ``hand_pose``.  ``scene`` is an
+    ``ops.SceneSDF`` or an ``ops.SceneSDFSet`` (row b reads grid b // (B / G)); it may contain the target, since station 0 is the
+    opened hand at the grasp pose.  ``idx``, ``Rg``, ``LT``, ``ws`` are the kinematic state of ``hand_pose`` (fk_contacts);
+    K = ``stations`` in 0..32, ``distance`` > 0, ``opening`` in [0,1], ``margin`` >= 0.  ``open_joints`` (JA) = None takes
+    ``default_open_joints(spec)``: the default state clamped to the joint limits."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if samples.n_links != hand.L:
+        raise ValueError(f"pregrasp_terms: the samples refer to {samples.n_links} links, the hand has {hand.L}")
+    if not float(margin) >= 0.0:
+        raise ValueError(f"pregrasp_terms: margin = {margin!r} must be >= 0")
+    if hand_pose.shape[1] != 9 + hand.J:
+        raise ValueError(f"pregrasp_terms: hand_pose must be (B, {9 + hand.J}), got {tuple(hand_pose.shape)}")
+    axis = [float(a) for a in _axis3(grasp_axis)]
+    pregrasp_check(scene, hand_pose.shape[0], hand.L, samples.Ns, distance, stations, axis, opening)
+    dev = hand_pose.device
+    if open_joints is None:
+        open_joints = default_open_joints(hand.spec, dev)
+    else:
+        open_joints = _c(torch.as_tensor(open_joints, dtype=torch.float32).detach().to(dev))
+    if open_joints.shape != (hand.J,):
+        raise ValueError(f"pregrasp_terms: open_joints must be ({hand.J},), got {tuple(open_joints.shape)}")
+    return _PregraspTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws, scene, axis,
+                                float(distance), int(stations), float(opening), open_joints, float(margin))
+
+
 @_custom_op("graspqp_amd::scene_compose", mutates_args=("out_values",), device_types="cuda")
 def _scene_compose_op(out_values: Tensor, origin: List[float], voxel: float, target_T: Tensor, part_values: List[Tensor],
                       part_origins: List[float], part_voxels: List[float], part_T: Tensor, exclude: Optional[Tensor],
@@ -2296,6 +2440,8 @@ _eager("scene_terms_set", _scene_set_op)
 _eager("scene_terms_set_backward", _scene_set_bwd_op)
 _eager("approach_terms_set", _approach_set_op)
 _eager("approach_terms_set_backward", _approach_set_bwd_op)
+_eager("pregrasp_terms", _pregrasp_op)
+_eager("pregrasp_terms_backward", _pregrasp_bwd_op)
 _eager("scene_compose", _scene_compose_op)
 _eager("tsdf_integrate", _tsdf_integrate_op)
 _eager("tsdf_surfels", _tsdf_surfels_op)

@@ -26,6 +26,13 @@ travels along its approach axis must be free of the same grid.  One more launch 
 its link wrenches and gRt the same way; ``terms`` gets [E_approach] appended last, after E_scene; its share of the row total is
 one more gq_scene_total launch, and the proposal and the accept step are the stand-alone launches.
 
+Pre-grasp mode (a weight on "E_pregrasp" and a grid, ``pregrasp_scene`` or else ``scene``): the hand travels the corridor OPEN, so the
+hand with its joints opened by ``pregrasp_opening`` must be free of the grid at every station d_k = D k / K, k = 0..K, the grasp
+pose included -- which is why this term's grid may contain the target and E_scene's must not.  One more launch (gq_pregrasp_terms:
+opened kinematics, stations and joint gradient of the row) after gq_approach_terms adds its gRt to the shared buffer and overwrites
+``g_theta``, the direct joint gradient the FK backward takes in this mode only; ``terms`` gets [E_pregrasp] appended last, its share
+of the row total is one more gq_scene_total launch, and the proposal and the accept step are the stand-alone launches.
+
 Clutter (``scene`` is an ``ops.SceneSDFSet`` with one grid per object): the same two launches read a stack of grids and pick the
 grid from the row, row // batch_each (gq_clutter_terms / gq_clutter_corridor_terms, the same row bodies: bit for bit the single-grid
 launch's numbers on that grid).  ``ops.scene_compose`` refills the stack in place, also between replays of a captured graph.
@@ -46,14 +53,15 @@ TERM_NAMES = ("E_dis", "E_fc", "E_pen", "E_spen", "E_joints")
 TABLETOP_TERMS = ("E_prior", "E_wall")
 SCENE_TERMS = ("E_scene",)
 APPROACH_TERMS = ("E_approach",)
+PREGRASP_TERMS = ("E_pregrasp",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
 def merge_weights(weights=None):
-    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term and of the approach term) updated with
-    ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and so does a
-    negative weight of a tabletop term, of the scene term or of the approach term."""
-    switched = TABLETOP_TERMS + SCENE_TERMS + APPROACH_TERMS
+    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term and of the pre-grasp term)
+    updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and
+    so does a negative weight of a tabletop term, of the scene term, of the approach term or of the pre-grasp term."""
+    switched = TABLETOP_TERMS + SCENE_TERMS + APPROACH_TERMS + PREGRASP_TERMS
     w = dict(DEFAULT_WEIGHTS)
     w.update({k: 0.0 for k in switched})
     for k, v in (weights or {}).items():
@@ -72,7 +80,8 @@ class GraspStepper:
                  tdg_directions=None, point_grid: int = 0, split_self_pen: bool = True, n_surface_points: int = 512,
                  surface_samples=None, table_z: float = 0.0, scene=None, scene_margin: float = 0.0,
                  approach_distance: float = 0.10, approach_stations: int = 4, approach_margin=None,
-                 init_avoid_scene: bool = False):
+                 pregrasp_opening: float = 0.5, pregrasp_joints=None, pregrasp_scene=None, pregrasp_distance=None,
+                 pregrasp_stations=None, pregrasp_margin=None, init_avoid_scene: bool = False):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -90,7 +99,14 @@ class GraspStepper:
         of the same hinge sum with the whole hand moved back by d_k along the spec's grasp_axis; ``approach_margin`` = None
         takes ``scene_margin``.  With weight 0 the three arguments change nothing.
         ``scene`` may be an ``ops.SceneSDFSet`` with one grid per object (``n_grids`` == n_obj, rows object-major): row b of both
-        terms then reads grid b // batch_each (module docstring, "Clutter")."""
+        terms then reads grid b // batch_each (module docstring, "Clutter").
+        weights["E_pregrasp"] > 0 selects the pre-grasp mode (module docstring): the mean over the stations k = 0..pregrasp_stations
+        of the hinge sum of the hand OPENED to (1 - pregrasp_opening) theta + pregrasp_opening pregrasp_joints and moved back by
+        pregrasp_distance k / pregrasp_stations.  ``pregrasp_joints`` (J) = None takes the spec's default state clamped to the joint
+        limits; ``pregrasp_scene`` / ``pregrasp_distance`` / ``pregrasp_stations`` / ``pregrasp_margin`` = None take ``scene``,
+        ``approach_distance``, ``approach_stations`` and ``scene_margin``.  ``pregrasp_scene`` (an ``ops.SceneSDF``, or an
+        ``ops.SceneSDFSet`` with ``n_grids`` == n_obj) exists because this term's grid usually contains the target and the grid of
+        E_scene must not.  With weight 0 the six arguments change nothing."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -127,11 +143,31 @@ class GraspStepper:
                 raise ValueError(f"GraspStepper: approach_distance = {approach_distance!r} must be finite and > 0")
             if int(approach_stations) != approach_stations or not 1 <= int(approach_stations) <= 32:
                 raise ValueError(f"GraspStepper: approach_stations = {approach_stations!r} must be an integer in 1..32")
+        self.pregrasp_mode = self.w["E_pregrasp"] > 0
+        if self.pregrasp_mode:
+            pregrasp_scene = scene if pregrasp_scene is None else pregrasp_scene
+            if not isinstance(pregrasp_scene, (ops.SceneSDF, ops.SceneSDFSet)):
+                raise ValueError('GraspStepper: weights["E_pregrasp"] > 0 needs pregrasp_scene= or scene=ops.SceneSDF(...) or '
+                                 'ops.SceneSDFSet(...)')
+            if isinstance(pregrasp_scene, ops.SceneSDFSet) and pregrasp_scene.n_grids != self.n_obj:
+                raise ValueError(f"GraspStepper: pregrasp_scene has n_grids = {pregrasp_scene.n_grids}, the stepper has n_obj = "
+                                 f"{self.n_obj} objects")
+            pregrasp_margin = scene_margin if pregrasp_margin is None else pregrasp_margin
+            pregrasp_distance = approach_distance if pregrasp_distance is None else pregrasp_distance
+            pregrasp_stations = approach_stations if pregrasp_stations is None else pregrasp_stations
+            if not float(pregrasp_margin) >= 0.0:
+                raise ValueError(f"GraspStepper: pregrasp_margin = {pregrasp_margin!r} must be >= 0")
+            if not 0.0 < float(pregrasp_distance) < float("inf"):
+                raise ValueError(f"GraspStepper: pregrasp_distance = {pregrasp_distance!r} must be finite and > 0")
+            if int(pregrasp_stations) != pregrasp_stations or not 0 <= int(pregrasp_stations) <= 32:
+                raise ValueError(f"GraspStepper: pregrasp_stations = {pregrasp_stations!r} must be an integer in 0..32")
+            if not 0.0 <= float(pregrasp_opening) <= 1.0:
+                raise ValueError(f"GraspStepper: pregrasp_opening = {pregrasp_opening!r} must be in [0, 1]")
         self.init_avoid_scene = bool(init_avoid_scene)
         if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
             raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
         self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
-                           + (APPROACH_TERMS if self.approach_mode else ()))
+                           + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -257,25 +293,40 @@ class GraspStepper:
             ad.e_fc = self.terms_new[1].data_ptr()
             self._alt_desc = ad
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
-        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode)
+        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode)
         self.samples, self.g_R = None, None
         self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode or self.approach_mode else (None, 0.0)
-        if self.tabletop or self.scene_mode or self.approach_mode:  # one set of surface samples for all modes
+        if self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode:  # one set of surface samples for all modes
             if surface_samples is None:
                 from .utils import meshes as mesh_utils
 
                 surface_samples = mesh_utils.hand_surface_samples(hand.spec, int(n_surface_points))
             self.samples = ops.SurfaceSamples(hand, surface_samples[0], surface_samples[1], device=self.dev)
         if self.scene_mode:
-            self._i_scene = nT - 2 if self.approach_mode else nT - 1
+            self._i_scene = self.term_names.index("E_scene")
             scene.check(B, self.be, L, self.samples.Ns) if self.clutter else scene.check(B, L, self.samples.Ns)
         if self.approach_mode:
-            self._i_approach = nT - 1
+            self._i_approach = self.term_names.index("E_approach")
             self.approach_distance, self.approach_stations = float(approach_distance), int(approach_stations)
             self.approach_margin = float(approach_margin)
             self._approach_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
             ops.approach_check(scene, B, L, self.samples.Ns, self.approach_distance, self.approach_stations,
                                hand.spec.grasp_axis)
+        if self.pregrasp_mode:
+            self._i_pregrasp = nT - 1
+            self.pregrasp_scene = pregrasp_scene
+            self.pregrasp_distance, self.pregrasp_stations = float(pregrasp_distance), int(pregrasp_stations)
+            self.pregrasp_margin, self.pregrasp_opening = float(pregrasp_margin), float(pregrasp_opening)
+            if pregrasp_joints is None:
+                self.pregrasp_joints = ops.default_open_joints(hand.spec, self.dev)
+            else:
+                self.pregrasp_joints = torch.as_tensor(pregrasp_joints, dtype=torch.float32).detach().to(self.dev).contiguous()
+            if self.pregrasp_joints.shape != (self.J,):
+                raise ValueError(f"GraspStepper: pregrasp_joints must be ({self.J},), got {tuple(self.pregrasp_joints.shape)}")
+            ops.pregrasp_check(pregrasp_scene, B, L, self.samples.Ns, self.pregrasp_distance, self.pregrasp_stations,
+                               hand.spec.grasp_axis, self.pregrasp_opening)
+            # the stack view of the grid (a single grid is the stack of one): row b reads grid b // (B / n_grids)
+            self._pregrasp_grids = ops._pregrasp_grids(pregrasp_scene.values, pregrasp_scene.origin, pregrasp_scene.voxel)
         if self.tabletop:
             self.g_R = f(B, 9)
             self.table_z = float(table_z)
@@ -301,8 +352,8 @@ class GraspStepper:
                                                                   int(m["annealing_period"]))
         ac.energy, ac.pose, ac.idx, ac.grad = (t.data_ptr() for t in (self.energy, self.hand_pose, self.contact_idx, self.grad))
         ac.accept, ac.temperature = self.accept.data_ptr(), self.temperature.data_ptr()
-        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene and approach mode (six to nine
-        # terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
+        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach and pre-grasp mode
+        # (six to ten terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
         assert self._fuse_loop == (nT == len(TERM_NAMES))
         ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
@@ -420,12 +471,22 @@ class GraspStepper:
                 f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), ctypes.cast(self._approach_axis, ctypes.c_void_p), None,
                 float(self.w["E_approach"]), f32(self.terms_new[self._i_approach]), 1, f32(self.wrench), f32(self.gRt), st)
 
+    def _eval_pregrasp(self, pose, st):
+        """E_pregrasp -> terms_new[-1]; the root-pose part of the gradient of w_pregrasp E_pregrasp is added to the gRt that the
+        FK backward reads (the opened hand shares the closed hand's root pose), the joint part overwrites ``g_theta``."""
+        sm = self.samples
+        ops._pregrasp_call(self.hand, self._pregrasp_grids, self.pregrasp_margin, self.pregrasp_distance, self.pregrasp_stations,
+                           self.pregrasp_opening, self.pregrasp_joints, pose, sm.points, sm.link, self.Rg,
+                           self.hand.spec.grasp_axis, None, float(self.w["E_pregrasp"]), self.terms_new[self._i_pregrasp], 1,
+                           self.g_theta, self.gRt, st)
+
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
         f32 = _C.f32
         _C.call("gq_fk_backward", self.hand.handle, f32(pose), _C.i64(idx), B, n, f32(self.Rg), f32(self.link_T),
                 f32(self.g_cpts), f32(self.g_cnrm), f32(self.g_sph_w) if self.S > 0 else None, f32(self.wrench),
-                f32(self.gRt), None, f32(self.g_R), f32(self.grad_new), ctypes.byref(self._row_energy),
+                f32(self.gRt), f32(self.g_theta) if self.pregrasp_mode else None, f32(self.g_R), f32(self.grad_new),
+                ctypes.byref(self._row_energy),
                 ctypes.byref(self._accept_desc) if loop else None, _C.ptr(self.fk_ws), self.fk_nb, st)
 
     def _evaluate(self, pose, idx, st, fork=False, timer=None, fused=False, loop=False):
@@ -469,6 +530,8 @@ class GraspStepper:
             self._eval_scene(pose, st)
         if self.approach_mode:
             self._eval_approach(pose, st)
+        if self.pregrasp_mode:
+            self._eval_pregrasp(pose, st)
         self._eval_tail(pose, idx, st, loop)
         if self.tabletop:  # the FK backward's total holds the five terms
             _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
@@ -479,6 +542,9 @@ class GraspStepper:
         if self.approach_mode:  # the generic total += w e
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_approach]),
                     float(self.w["E_approach"]), ctypes.c_int64(self.B), st)
+        if self.pregrasp_mode:
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_pregrasp]),
+                    float(self.w["E_pregrasp"]), ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):
         """Energy terms, total and d total / d pose at an arbitrary (pose, idx); returns clones."""

@@ -656,6 +656,44 @@ int gq_clutter_compose(const gqClutterGrids* out, float* out_values /* = out->va
                        const gqSceneGrid* base /* static grid in the world frame, or NULL */,
                        float far /* finite: the value where nothing is known */, void* stream);
 
+/* ---- pre-grasp clearance of the stepper: E_pregrasp, the OPENED hand along the approach corridor ---------------------
+ * E_approach moves the hand back with its joints unchanged; a hand travels the corridor open and closes at the end.  This term
+ * asks that the opened hand is free of the grid at every station, the grasp pose (d = 0) included, so the grid may contain the
+ * target itself.  With theta the actuated joints of hand_pose (B, 9 + JA), q_o = open_joints (JA) and alpha = opening in [0,1]:
+ *   theta_o = (1 - alpha) theta + alpha q_o   (coupled hands: the tree angles follow by coupling theta_o + coupling_offset)
+ *   x_h = T_l(theta_o) p      y_k = x_h - d_k a      x_w^k = R y_k + t      d_k = D k / K for k = 0..K (K = 0: d = 0 only)
+ *   E_pregrasp = 1/(K+1) sum_k sum_s max(margin - phi(x_w^k), 0)
+ * Root pose and R are the closed hand's; a = grasp_axis (hand frame, used as given); phi is the trilinear interpolant of
+ * "scene obstacles" by the same device body: outside the volume is free space, a non-finite point makes the row's energy and
+ * gradient NaN and loads nothing.  ONE launch per call does the opened kinematics of the row, the stations and the joint
+ * gradient: no link_T goes in and no link wrench comes out.  e_pregrasp is written UNWEIGHTED and always overwritten.  The
+ * gradient carries the upstream factor of the row: up_pregrasp[row] if given, else w_pregrasp.  With g_w = -up/(K+1) grad phi
+ * and g_h = R' g_w for every active (s, k):
+ *   gRt (B,12) = [gsum(3), K9(9)]: gsum = -sum g_h, K9 = sum g_h (x) y_k, the layout and signs of gq_approach_terms
+ *   g_theta (B,JA) = (1 - alpha) C' tau: per link f_l = sum g_h, m_l = sum x_h x g_h (x_h unshifted), folded onto the nodes the
+ *     links ride on and children into parents, deepest level first; tau_j = a_j . (m_j - o_j x f_j) (revolute) or a_j . f_j
+ *     (prismatic) with axis a_j and origin o_j of node j in the hand frame at theta_o; C' for a coupled hand.  It is the direct
+ *     joint gradient gq_fk_backward takes as g_theta, next to gRt.
+ * accumulate is two bits: bit 0 (1) adds to gRt, bit 1 (2) adds to g_theta (a plain rounded add of the finished value: the
+ * bits of buffer + the overwriting launch's value); a cleared bit overwrites that buffer.  The stepper passes 1: gRt is shared
+ * with the other terms, g_theta is this term's own.  1/(K+1) is one 1.0f / (K+1), multiplied into the finished row energy and into `up`.
+ * Fixed-order sums, no atomics: bitwise reproducible run to run.  The grids are a gqClutterGrids stack, row b reads grid
+ * b / rows_per_grid; a single grid is the stack of one with rows_per_grid = batch.  The hand has at most 64 joints and 64
+ * links (gq_hand_create).  The row total takes gq_scene_total(total, e_pregrasp, w_pregrasp, B).
+ * gq_pregrasp_check is the argument check of the launch on its own (host only, no GPU): everything gq_clutter_check and
+ * gq_approach_check refuse (but n_stations = 0 is allowed), an opening outside [0,1] or not finite, n_stations outside 0..32;
+ * its message contains "pregrasp" and names the argument.                                                              */
+int gq_pregrasp_check(const gqClutterGrids* grids, int64_t batch, int64_t rows_per_grid, int n_links, int64_t n_samples,
+                      float distance, int n_stations, const float* grasp_axis /* 3 floats, host */, float opening);
+int gq_pregrasp_terms(const gqHand* h, const gqClutterGrids* grids, int64_t rows_per_grid, float margin, float distance,
+                      int n_stations /* 0..32 */, float opening /* 0..1 */, const float* open_joints /* (JA) device */,
+                      const float* samples /* (Ns,3) link frame, device */, const int32_t* sample_link /* (Ns) */,
+                      int64_t n_samples, const float* hand_pose, int pose_dim, const float* Rg /* (B,9) */, int64_t batch,
+                      const float* grasp_axis /* 3 floats, host */, const float* up_pregrasp /* (B) or NULL */,
+                      float w_pregrasp, float* e_pregrasp /* (B) or NULL, unweighted */,
+                      int accumulate /* bit 0: add to gRt, bit 1: add to g_theta; a cleared bit overwrites */,
+                      float* g_theta /* (B,JA) or NULL */, float* gRt /* (B,12) or NULL */, void* stream);
+
 /* ---- scenes from depth images: TSDF fusion on the device into scene grids ---------------------------------------------
  * What a robot has is depth images, not a signed-distance volume.  gq_tsdf_integrate fuses a batch of depth frames into a
  * gqClutterGrids stack IN PLACE, one launch per batch (n_grids = 1 is the single world grid).  State: `values` of the stack IS

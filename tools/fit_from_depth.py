@@ -6,12 +6,15 @@ turns the target volume into an oriented point cloud on the device (SceneTSDF.ex
 and runs GraspStepper with E_scene on the scene volume and the extracted cloud as the object.  With --esdf MAX_DISTANCE the stepper reads
 the Euclidean distance field of the scene volume instead (SceneTSDF.esdf), which allows a --scene_margin above trunc.  It reports the number of surfels,
 With --init_avoid_scene the initial poses and those of every reset are screened against that field; --reset_epochs N
-turns the z-score resets of the reference's schedule on (default: none).  It reports the number of surfels,
+turns the z-score resets of the reference's schedule on (default: none).  The tool also fuses a second scene volume of the same
+frames WITHOUT skip, so the target stays in it: the grid of the pre-grasp term, whose station 0 is the opened hand at the
+grasp pose (with --esdf that volume's ESDF).  --w_pregrasp W > 0 puts the term into the energy; either way the final grasp set is
+evaluated with ops.pregrasp_terms and the mean E_pregrasp and the share of rows with E_pregrasp > 0 are reported.  It reports the number of surfels,
 how far they lie from the true sphere, the mean energy and the mean E_scene before and after --n_iter iterations, and the wall
 times of the stages (each closed by a synchronisation).  Evidence run, not a test: one JSON line is printed and appended to --out.
 
 usage: python tools/fit_from_depth.py [--views 8] [--batch_size 64] [--n_iter 400] [--esdf 0.06 --scene_margin 0.03]
-       [--init_avoid_scene] [--reset_epochs 600] [--out file.jsonl]
+       [--init_avoid_scene] [--reset_epochs 600] [--w_pregrasp 30 --pregrasp_opening 0.5 --pregrasp_stations 4] [--out file.jsonl]
 """
 import argparse
 import json
@@ -38,6 +41,9 @@ ap.add_argument("--esdf", type=float, default=None, metavar="MAX_DISTANCE", help
 ap.add_argument("--scene_margin", type=float, default=0.005)
 ap.add_argument("--init_avoid_scene", action="store_true", help="screen the initial and the re-initialised poses against the scene")
 ap.add_argument("--reset_epochs", type=int, default=None, help="z-score resets every N iterations (default: no resets)")
+ap.add_argument("--w_pregrasp", type=float, default=0.0, help="weight of E_pregrasp (0: evaluated at the end only)")
+ap.add_argument("--pregrasp_opening", type=float, default=0.5)
+ap.add_argument("--pregrasp_stations", type=int, default=4)
 ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "fit_from_depth.jsonl"))
 args = ap.parse_args()
 
@@ -96,12 +102,15 @@ cam_T = torch.as_tensor(cams).cuda().reshape(args.views, 12).contiguous()
 S_SHAPE, S_H, S_TRUNC = (80, 80, 80), 0.005, 0.02
 scene = ops.SceneTSDF([-0.5 * S_H * 79, -0.5 * S_H * 79, -0.1], S_SHAPE, S_H, S_TRUNC)
 skip = torch.tensor([1], dtype=torch.int32, device="cuda")
+# the surroundings AND the target, for the pre-grasp term: the same grid, nothing skipped
+whole = ops.SceneTSDF([-0.5 * S_H * 79, -0.5 * S_H * 79, -0.1], S_SHAPE, S_H, S_TRUNC)
 # the target: 2.5 mm voxels about the sphere, only its own pixels
 T_SHAPE, T_H = (56, 56, 56), 0.0025
 target = ops.SceneTSDF([float(c) - 0.5 * T_H * 55 for c in SPHERE[0]], T_SHAPE, T_H, 3 * T_H, n_grids=1)
 for t in (scene, target):  # warm-up: the first launch of a kernel loads its code object
     t.integrate(ops.keep_label(depth[:1], labels[:1], 1), K, cam_T[:1], depth_range=RANGE).reset()
 _, ms_scene = timed(lambda: scene.integrate(depth, K, cam_T, labels=labels, skip=skip, depth_range=RANGE))
+_, ms_whole = timed(lambda: whole.integrate(depth, K, cam_T, labels=labels, depth_range=RANGE))
 _, ms_target = timed(lambda: target.integrate(ops.keep_label(depth, labels, 1), K, cam_T, depth_range=RANGE))
 target.extract_clouds(args.min_weight)  # warm-up of the three kernels
 clouds, ms_extract = timed(lambda: target.extract_clouds(args.min_weight))
@@ -119,8 +128,13 @@ field, ms_esdf = scene.scene, None
 if args.esdf is not None:
     scene.esdf(args.esdf)  # warm-up: the output, the workspace and the kernels' code objects
     field, ms_esdf = timed(lambda: scene.esdf(args.esdf))
+pre_field = whole.scene if args.esdf is None else whole.esdf(args.esdf)
+if args.w_pregrasp > 0:
+    weights["E_pregrasp"] = args.w_pregrasp
+PG = dict(distance=0.10, stations=args.pregrasp_stations, opening=args.pregrasp_opening)
 st = GraspStepper(ops.HandHandle(get_hand_spec(args.hand)), om._cloudset, om.surface_points_each, be, n, seed=1, weights=weights,
-                  scene=field, scene_margin=args.scene_margin, init_avoid_scene=args.init_avoid_scene)
+                  scene=field, scene_margin=args.scene_margin, init_avoid_scene=args.init_avoid_scene, pregrasp_scene=pre_field,
+                  pregrasp_distance=PG["distance"], pregrasp_stations=PG["stations"], pregrasp_opening=PG["opening"])
 st.set_hulls(om.convex_hulls())
 st.initialize()
 names = list(st.term_names)
@@ -132,6 +146,16 @@ e1, s1 = st.energy, st.terms[names.index("E_scene")]
 assert torch.isfinite(e1).all() and torch.isfinite(st.hand_pose).all()
 dis, _ = om.cal_distance(st.cpts)
 
+
+def pregrasp_of(pose, idx):
+    """E_pregrasp (B) of a grasp set through the op, whatever the weight the run had."""
+    Rg, LT, _, _, _, ws = ops.fk_contacts(pose, idx, st.hand)
+    return ops.pregrasp_terms(pose, st.hand, st.samples, idx, Rg, LT, ws, pre_field, st.hand.spec.grasp_axis, PG["distance"], PG["stations"],
+                              PG["opening"], None, args.scene_margin)
+
+
+p1 = pregrasp_of(st.hand_pose, st.contact_idx)
+
 rec = {"fit_from_depth": True, "hand": args.hand, "views": args.views, "image": [W, H], "batch": be, "n_contact": n, "n_iter": args.n_iter,
        "scene_grid": list(S_SHAPE), "scene_voxel": S_H, "target_grid": list(T_SHAPE), "target_voxel": T_H, "min_weight": args.min_weight,
        "esdf_max_distance": args.esdf, "scene_margin": args.scene_margin, "init_avoid_scene": args.init_avoid_scene,
@@ -142,8 +166,10 @@ rec = {"fit_from_depth": True, "hand": args.hand, "views": args.views, "image": 
        "normal_angle_deg": {"median": float(np.median(angle)), "p99": float(np.percentile(angle, 99)), "max": float(angle.max())},
        "energy_mean": {"before": float(e0.mean()), "after": float(e1.mean())},
        "E_scene_mean": {"before": float(s0.mean()), "after": float(s1.mean())},
+       "w_pregrasp": args.w_pregrasp, "pregrasp": dict(PG, margin=args.scene_margin, grid="esdf" if args.esdf is not None else "tsdf"),
+       "E_pregrasp_mean_after": float(p1.mean()), "rows_with_E_pregrasp_after": float((p1 > 0).float().mean()),
        "contact_distance_mm_mean_abs_after": 1e3 * float(dis.abs().mean()),
-       "ms": {"integrate_scene": ms_scene, "integrate_target_with_keep_label": ms_target, "extract_clouds": ms_extract,
+       "ms": {"integrate_scene": ms_scene, "integrate_whole_scene": ms_whole, "integrate_target_with_keep_label": ms_target, "extract_clouds": ms_extract,
               "initialize_from_tsdf": ms_object, "esdf": ms_esdf, "run": ms_run, "per_iteration": ms_run / args.n_iter}}
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "a") as f:

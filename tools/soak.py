@@ -3,13 +3,17 @@ every `reset_epochs`) on the bench scene, at one or several batch sizes: energie
 counters must not show inline-ranked overflow growing, the stop iteration is histogrammed.  Development aid, not a test.
 
 usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--w_scene W] [--scene_margin M]
-       [--scene box] [--w_approach W] [--approach_distance D] [--approach_stations K] [--out file.json]
+       [--scene box] [--w_approach W] [--approach_distance D] [--approach_stations K]
+       [--w_pregrasp W] [--pregrasp_opening A] [--pregrasp_stations K] [--out file.json]
        (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
        schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
        hand surface samples left below the plane; --w_scene > 0 runs it in scene mode against the ``box`` preset (an open-topped
        bin of five slabs around the first object, 80^3 grid of 5 mm, ops.SceneSDF.from_meshes) and reports the mean E_scene at
        the start and at the end; --w_approach > 0 adds the approach corridor against the same preset (K stations over D metres
-       along the hand's grasp axis) and reports the mean E_approach the same way; --out writes the records as JSON.
+       along the hand's grasp axis) and reports the mean E_approach the same way; --w_pregrasp > 0 adds the pre-grasp term
+       against the same preset (the hand opened by --pregrasp_opening towards its default state, stations 0..K over the
+       approach distance; K defaults to --approach_stations) and reports the mean E_pregrasp the same way; --out writes the
+       records as JSON.
 """
 import argparse
 import json
@@ -39,6 +43,9 @@ ap.add_argument("--scene", choices=("box",), default="box")
 ap.add_argument("--w_approach", type=float, default=0.0)
 ap.add_argument("--approach_distance", type=float, default=0.10)
 ap.add_argument("--approach_stations", type=int, default=4)
+ap.add_argument("--w_pregrasp", type=float, default=0.0)
+ap.add_argument("--pregrasp_opening", type=float, default=0.5)
+ap.add_argument("--pregrasp_stations", type=int, default=None)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
@@ -50,6 +57,9 @@ if SCENE:
 APPROACH = args.w_approach > 0
 if APPROACH:
     weights["E_approach"] = args.w_approach
+PREGRASP = args.w_pregrasp > 0
+if PREGRASP:
+    weights["E_pregrasp"] = args.w_pregrasp
 records = []
 
 
@@ -71,19 +81,23 @@ for n_obj in args.n_objects:
     om = ObjectModel(batch_size_each=256, num_samples=2500)
     om.initialize_from_meshes(fvs, surface_points_list=sps)
     scene = None
-    if SCENE or APPROACH:
+    if SCENE or APPROACH or PREGRASP:
         center = 0.5 * (fvs[0].reshape(-1, 3).min(0) + fvs[0].reshape(-1, 3).max(0))
         scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), [float(c) - 0.5 * 0.005 * 79 for c in center], (80, 80, 80), 0.005)
     st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3, weights=weights or None,
                       table_z=args.table_z, scene=scene, scene_margin=args.scene_margin,
-                      approach_distance=args.approach_distance, approach_stations=args.approach_stations)
+                      approach_distance=args.approach_distance, approach_stations=args.approach_stations,
+                      pregrasp_opening=args.pregrasp_opening, pregrasp_stations=args.pregrasp_stations)
     st.set_hulls(om.convex_hulls())
     st.initialize()
     e0 = st.energy.clone()
     wall0 = float(st.terms[6].mean()) if TABLETOP else None
     i_scene = st.term_names.index("E_scene") if SCENE else None
     scene0 = float(st.terms[i_scene].mean()) if SCENE else None
-    approach0 = float(st.terms[-1].mean()) if APPROACH else None
+    i_approach = st.term_names.index("E_approach") if APPROACH else None
+    approach0 = float(st.terms[i_approach].mean()) if APPROACH else None
+    i_pregrasp = st.term_names.index("E_pregrasp") if PREGRASP else None
+    pregrasp0 = float(st.terms[i_pregrasp].mean()) if PREGRASP else None
     st.capture(iters=8)
     hist = {}
     acc = []
@@ -129,9 +143,16 @@ for n_obj in args.n_objects:
     if APPROACH:
         rec.update({"w_approach": args.w_approach, "approach_distance": args.approach_distance,
                     "approach_stations": args.approach_stations, "E_approach_mean_initial": approach0,
-                    "E_approach_mean_final": float(st.terms[-1].mean()), "rows_with_E_approach_final": int((st.terms[-1] > 0).sum())})
+                    "E_approach_mean_final": float(st.terms[i_approach].mean()),
+                    "rows_with_E_approach_final": int((st.terms[i_approach] > 0).sum())})
         print(f"  approach: mean E_approach {approach0:.4f} -> {rec['E_approach_mean_final']:.6f}, {rec['rows_with_E_approach_final']} "
               f"of {st.B} rows still meet an obstacle on the way in", flush=True)
+    if PREGRASP:
+        rec.update({"w_pregrasp": args.w_pregrasp, "pregrasp_opening": args.pregrasp_opening, "pregrasp_stations": st.pregrasp_stations,
+                    "E_pregrasp_mean_initial": pregrasp0, "E_pregrasp_mean_final": float(st.terms[i_pregrasp].mean()),
+                    "rows_with_E_pregrasp_final": int((st.terms[i_pregrasp] > 0).sum())})
+        print(f"  pregrasp: mean E_pregrasp {pregrasp0:.4f} -> {rec['E_pregrasp_mean_final']:.6f}, {rec['rows_with_E_pregrasp_final']} "
+              f"of {st.B} rows still meet an obstacle with the hand opened", flush=True)
     records.append(rec)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
