@@ -50,30 +50,40 @@ def grasp_snapshot(hand_model, energy, object_model):
             "values": energy.detach(), "contact_idx": hand_model.contact_point_indices.detach()}
 
 
-def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None):
-    """One dict per object in the reference's on-disk layout (CPU tensors)."""
+def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None, selection=None):
+    """One dict per object in the reference's on-disk layout (CPU tensors).  ``selection`` (an ``ops.GraspSelection``, e.g. of
+    ``GraspStepper.select``): each object's dict holds only its selected rows, in pick order, and two more keys,
+    ``selected_rows`` (int64, the rows' indices within the object) and ``n_feasible`` (int); an object with nothing selected
+    gets zero-length tensors.  The consumer reads by key, so the extra keys are harmless."""
+    if selection is not None:
+        sel, n_sel, n_feas = selection.sel.cpu().long(), selection.n_selected.cpu(), selection.n_feasible.cpu()
+        if sel.shape[0] != n_objects:
+            raise ValueError(f"snapshot_dicts: the selection has {sel.shape[0]} objects, the snapshot {n_objects}")
     snap = {k: v.cpu() for k, v in grasp_snapshot(hand_model, energy, object_model).items()}
     names = list(hand_model._actuated_joints_names)
     out = []
     for a in range(n_objects):
-        s, e = a * batch_size, (a + 1) * batch_size
-        params = {names[i]: snap["joint_positions"][s:e, i].clone() for i in range(len(names))}
-        params["root_pose"] = snap["root_pose"][s:e].clone()
-        data = {"values": snap["values"][s:e].clone(), "parameters": params}
+        rows = slice(a * batch_size, (a + 1) * batch_size) if selection is None else sel[a, :int(n_sel[a])]
+        params = {names[i]: snap["joint_positions"][rows, i].clone() for i in range(len(names))}
+        params["root_pose"] = snap["root_pose"][rows].clone()
+        data = {"values": snap["values"][rows].clone(), "parameters": params}
         for key in ("grasp_velocities", "full_grasp_velocities", "grasp_velocities_off"):
-            data[key] = {names[i]: snap[key][s:e, i].clone() for i in range(len(names))}
-        data["contact_idx"] = snap["contact_idx"][s:e].clone()
+            data[key] = {names[i]: snap[key][rows, i].clone() for i in range(len(names))}
+        data["contact_idx"] = snap["contact_idx"][rows].clone()
         data["grasp_type"] = grasp_type
         data["contact_links"] = hand_model._contact_links
+        if selection is not None:
+            data["selected_rows"] = rows - a * batch_size
+            data["n_feasible"] = int(n_feas[a])
         out.append(data)
     return out
 
 
 def export_poses(hand_model, energy, object_model, object_code_list, batch_size, data_root_path, hand_name, n_contact,
-                 energy_name, suffix="None", grasp_type=None):
-    """fit.py:224-300 -> list of the files written."""
+                 energy_name, suffix="None", grasp_type=None, selection=None):
+    """fit.py:224-300 -> list of the files written.  ``selection``: see ``snapshot_dicts``; None writes every row."""
     files = []
-    dicts = snapshot_dicts(hand_model, energy, object_model, len(object_code_list), batch_size, grasp_type)
+    dicts = snapshot_dicts(hand_model, energy, object_model, len(object_code_list), batch_size, grasp_type, selection)
     for code, data in zip(object_code_list, dicts):
         path = os.path.join(get_result_path(data_root_path, code, hand_name, n_contact, energy_name, grasp_type),
                             code + f"{suffix}.dexgrasp.pt")

@@ -18,7 +18,7 @@ asks for the registered route (tests compare the two bit for bit).
 import ctypes
 import os
 import weakref
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -1142,6 +1142,25 @@ class SurfaceSamples:
         order = np.argsort(lnk, kind="stable")
         self.points = torch.from_numpy(pts[order]).to(device).contiguous()
         self.link = torch.from_numpy(lnk[order]).to(device).contiguous()
+        self._host = (pts[order], lnk[order])
+        self._moments = None
+
+    @property
+    def link_moments(self) -> Tensor:
+        """(n_links,10) float32 on the device, built at the first use from the host copy of the samples: per link the number of
+        samples n, their centroid c (3) and the centred second moment sum (p - c)(p - c)' as Cxx Cxy Cxz Cyy Cyz Czz, summed in
+        fp64.  A link without samples has a row of zeros.  ``grasp_distances`` / ``grasp_select`` read the hand surface through
+        these 10 numbers per link."""
+        if self._moments is None:
+            pts, lnk = self._host
+            m = np.zeros((self.n_links, 10), np.float64)
+            for l in np.unique(lnk):
+                p = pts[lnk == l].astype(np.float64)
+                c = p.mean(0)
+                C = (p - c).T @ (p - c)
+                m[l] = [len(p), *c, C[0, 0], C[0, 1], C[0, 2], C[1, 1], C[1, 2], C[2, 2]]
+            self._moments = torch.from_numpy(m.astype(np.float32)).to(self.points.device)
+        return self._moments
 
 
 def _axis3(grasp_axis) -> List[float]:
@@ -2408,6 +2427,105 @@ def energy_pen(distances):
     return _Eager.energy_pen(distances)
 
 
+
+# ----------------------------------------------------------------------------------------------------------
+# grasp-set selection: feasible, ranked, distinct grasps (csrc/select.hip, include/graspqp_hip.h)
+# ----------------------------------------------------------------------------------------------------------
+class GraspSelection(NamedTuple):
+    """Result of ``grasp_select`` (device tensors): ``sel`` (n_obj,K) int32 global row indices in pick order (ascending score),
+    unused slots -1; ``n_selected`` (n_obj) int32; ``n_feasible`` (n_obj) int32, not capped by K; ``feasible`` (B) int32 0/1."""
+    sel: Tensor
+    n_selected: Tensor
+    n_feasible: Tensor
+    feasible: Tensor
+
+
+def _grasp_common(hand_pose, Rg, LT, moments):
+    hp, Rg, LT, mom = _c(hand_pose), _c(Rg), _c(LT), _c(moments)
+    B, L = hp.shape[0], mom.shape[0]
+    # fk_contacts gives (B,3,3) and (B,L,3,4), the stepper keeps (B,9) and (B,L,12): the same memory
+    if hp.dim() != 2 or Rg.shape[0] != B or Rg.numel() != B * 9 or LT.shape[0] != B or LT.numel() != B * L * 12 or mom.shape != (L, 10):
+        raise ValueError(f"grasp_select: hand_pose must be (B,D), Rg ({B},9), LT ({B},{L},12) and the link moments ({L},10), got "
+                         f"{tuple(hp.shape)}, {tuple(Rg.shape)}, {tuple(LT.shape)}, {tuple(mom.shape)}")
+    nb = _size_call("gq_grasp_select_workspace_bytes", ctypes.c_int64(B), L)
+    return hp, Rg, LT, mom, B, L, nb
+
+
+@_custom_op("graspqp_amd::grasp_distances", mutates_args=(), device_types="cuda")
+def _grasp_distances_op(hand_pose: Tensor, Rg: Tensor, LT: Tensor, moments: Tensor, n_samples: int, batch_each: int) -> Tensor:
+    """-> (n_obj, batch_each, batch_each): RMS displacement of the hand surface (metres) between every two rows of an object."""
+    hp, Rg, LT, mom, B, L, nb = _grasp_common(hand_pose, Rg, LT, moments)
+    be = int(batch_each)
+    dist = torch.empty(B // max(be, 1), be, be, device=hp.device)
+    _C.call("gq_grasp_distances", _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT), _C.f32(mom), L, ctypes.c_int64(n_samples),
+            ctypes.c_int64(B), ctypes.c_int64(be), _C.f32(dist), _C.ptr(_ws(nb, hp.device)), nb, _C.stream_ptr())
+    return dist
+
+
+@_grasp_distances_op.register_fake
+def _(hand_pose, Rg, LT, moments, n_samples, batch_each):
+    return hand_pose.new_empty(hand_pose.shape[0] // batch_each, batch_each, batch_each)
+
+
+@_custom_op("graspqp_amd::grasp_select", mutates_args=(), device_types="cuda")
+def _grasp_select_op(hand_pose: Tensor, Rg: Tensor, LT: Tensor, moments: Tensor, n_samples: int, batch_each: int, score: Tensor,
+                     terms: Tensor, tol: List[float], k: int, radius: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (sel (n_obj,k) int32, n_selected (n_obj) int32, n_feasible (n_obj) int32, feasible (B) int32); the rule is stated in
+    include/graspqp_hip.h ("grasp-set selection")."""
+    hp, Rg, LT, mom, B, L, nb = _grasp_common(hand_pose, Rg, LT, moments)
+    be, k, nT = int(batch_each), int(k), len(tol)
+    score, terms = _c(score), _c(terms)
+    if score.shape != (B,) or terms.shape != (nT, B):
+        raise ValueError(f"grasp_select: score must be ({B}) and terms ({nT},{B}), got {tuple(score.shape)}, {tuple(terms.shape)}")
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=hp.device)
+    n_obj = B // max(be, 1)
+    sel, n_sel, n_feas, feas = i32(n_obj, max(k, 0)), i32(n_obj), i32(n_obj), i32(B)
+    tol_c = (ctypes.c_float * max(nT, 1))(*[float(t) for t in tol])
+    _C.call("gq_grasp_select", _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT), _C.f32(mom), L, ctypes.c_int64(n_samples),
+            ctypes.c_int64(B), ctypes.c_int64(be), _C.f32(score), _C.f32(terms) if nT else None,
+            ctypes.cast(tol_c, ctypes.c_void_p), nT, ctypes.c_int64(k), float(radius), _C.i32(sel), _C.i32(n_sel), _C.i32(n_feas),
+            _C.i32(feas), _C.ptr(_ws(nb, hp.device)), nb, _C.stream_ptr())
+    return sel, n_sel, n_feas, feas
+
+
+@_grasp_select_op.register_fake
+def _(hand_pose, Rg, LT, moments, n_samples, batch_each, score, terms, tol, k, radius):
+    B = hand_pose.shape[0]
+    i32 = lambda *s: hand_pose.new_empty(*s, dtype=torch.int32)
+    return i32(B // batch_each, k), i32(B // batch_each), i32(B // batch_each), i32(B)
+
+
+def _grasp_check(name, hand_pose, samples):
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if not isinstance(samples, SurfaceSamples):
+        raise TypeError(f"{name}: samples must be an ops.SurfaceSamples")
+
+
+def grasp_distances(hand_pose, Rg, LT, samples: SurfaceSamples, batch_each: int) -> Tensor:
+    """-> (n_obj, batch_each, batch_each) float32: d(i,j) = sqrt of the mean over ``samples`` of |x_w,i(s) - x_w,j(s)|^2 for the
+    rows i, j of each object (rows object-major), in metres, in closed form from the link moments of ``samples``.  ``Rg`` (B,9)
+    and ``LT`` (B,L,12) are the kinematic state of ``hand_pose`` (fk_contacts).  The diagonal is exactly 0 and the matrix exactly
+    symmetric.  batch_each <= 4096.  No autograd."""
+    _grasp_check("grasp_distances", hand_pose, samples)
+    return _Eager.grasp_distances(hand_pose.detach(), Rg.detach(), LT.detach(), samples.link_moments, samples.Ns, int(batch_each))
+
+
+def grasp_select(hand_pose, Rg, LT, samples: SurfaceSamples, batch_each: int, score, terms, tol, k: int,
+                 radius: float) -> GraspSelection:
+    """Per object the ``k`` best rows that are feasible and pairwise at least ``radius`` (metres, ``grasp_distances``) apart.
+    ``score`` (B): lower is better.  ``terms`` (nT,B) with ``tol`` (nT floats, nT <= 16): row b is feasible iff score[b] is
+    finite and terms[t,b] <= tol[t] for every t with tol[t] < inf.  Greedy: pick the best remaining feasible row (ties: the
+    smaller row), suppress the remaining rows closer than ``radius`` (strictly; 0 suppresses nothing), at most ``k`` times.
+    Fewer than ``k`` is an answer: there is no fill.  Device tensors come back, the host does not wait.  No autograd."""
+    _grasp_check("grasp_select", hand_pose, samples)
+    tol = [float(t) for t in (tol.tolist() if torch.is_tensor(tol) else tol)]
+    if terms is None:
+        terms = hand_pose.new_empty(0, hand_pose.shape[0])
+    return GraspSelection(*_Eager.grasp_select(hand_pose.detach(), Rg.detach(), LT.detach(), samples.link_moments, samples.Ns,
+                                               int(batch_each), score.detach(), terms.detach(), tol, int(k), float(radius)))
+
+
 # eager routes of the registered ops (see the module docstring)
 _eager("sdf_backward", _sdf_backward)
 _eager("compute_sdf", _compute_sdf_op, _sdf_bwd, _sdf_setup)
@@ -2451,3 +2569,5 @@ _eager("signed_distance", _signed_distance_op, _signed_distance_bwd, _signed_dis
 _eager("energy_dis", _energy_dis_op, _energy_dis_bwd, _energy_dis_setup)
 _eager("energy_joints", _energy_joints_op, _energy_joints_bwd, _energy_joints_setup)
 _eager("energy_pen", _energy_pen_op, _energy_pen_bwd, _energy_pen_setup)
+_eager("grasp_distances", _grasp_distances_op)
+_eager("grasp_select", _grasp_select_op)

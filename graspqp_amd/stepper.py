@@ -57,6 +57,26 @@ PREGRASP_TERMS = ("E_pregrasp",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
+OBSTACLE_TERMS = SCENE_TERMS + APPROACH_TERMS + PREGRASP_TERMS
+
+
+def select_tolerances(term_names, gates=None):
+    """The gates of ``GraspStepper.select`` as one tolerance per term of ``term_names`` (+inf: not gated).  ``gates`` = {term name:
+    tol}; None gates every obstacle term that is switched on (E_scene, E_approach, E_pregrasp) at 0.0 and nothing else -- the
+    "collision-free" of ``init_avoid_scene``.  A name that is no term of the stepper, or that names a switched-off term, raises,
+    and so does a NaN tolerance."""
+    if gates is None:
+        gates = {k: 0.0 for k in OBSTACLE_TERMS if k in term_names}
+    tol = [float("inf")] * len(term_names)
+    for k, v in gates.items():
+        if k not in term_names:
+            raise ValueError(f"GraspStepper.select: unknown or switched-off energy term {k!r} in gates (on: {', '.join(term_names)})")
+        if float(v) != float(v):
+            raise ValueError(f"GraspStepper.select: gates[{k!r}] is NaN")
+        tol[term_names.index(k)] = float(v)
+    return tol
+
+
 def merge_weights(weights=None):
     """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term and of the pre-grasp term)
     updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and
@@ -295,6 +315,7 @@ class GraspStepper:
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
         self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode)
         self.samples, self.g_R = None, None
+        self._n_surface_points, self._select_fk = int(n_surface_points), None
         self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode or self.approach_mode else (None, 0.0)
         if self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode:  # one set of surface samples for all modes
             if surface_samples is None:
@@ -782,6 +803,36 @@ class GraspStepper:
                 self.flush()
                 callback(step)
         self.flush()
+
+    def select(self, k, radius=0.01, gates=None, score=None):
+        """The ``k`` best grasps of every object that are feasible and different grasps -> ``ops.GraspSelection`` (device tensors;
+        the host does not wait).  The state read is the ACCEPTED one: ``hand_pose`` / ``contact_idx``, ``terms`` and ``energy`` are
+        what gq_mala_accept (or the accept tail of the FK backward launch) merged, and ``run`` ends with ``flush``.  One FK forward
+        launch gives Rg / link_T of ``hand_pose`` into buffers of the selection's own, then ``ops.grasp_select``.
+        ``gates`` = {term name: tol}: a row is feasible iff its (unweighted) term is <= tol for every gated term; None gates the
+        obstacle terms that are on at 0.0 (``select_tolerances``).  ``score`` (B), lower is better: None takes ``energy``.
+        ``radius`` (metres): picks of one object are at least this far apart in ``ops.grasp_distances``; 0 keeps duplicates.
+        The hand surface is the stepper's ``samples`` (built with ``n_surface_points`` if no mode needed them so far).  Nothing of
+        the chain's state is written: stepping on afterwards gives the bits of a stepper that never selected."""
+        tol = select_tolerances(self.term_names, gates)
+        self.flush()
+        if self.samples is None:
+            from .utils import meshes as mesh_utils
+
+            pts, link = mesh_utils.hand_surface_samples(self.hand.spec, self._n_surface_points)
+            self.samples = ops.SurfaceSamples(self.hand, pts, link, device=self.dev)
+        if self._select_fk is None:
+            self._select_fk = (torch.zeros(self.B, 9, device=self.dev), torch.zeros(self.B, self.L, 12, device=self.dev))
+        Rg, LT = self._select_fk
+        score = self.energy if score is None else score
+        if tuple(score.shape) != (self.B,) or not score.is_floating_point():
+            raise ValueError(f"GraspStepper.select: score must be a float tensor of shape ({self.B},), got {tuple(score.shape)}")
+        # contact points / normals go to the proposal's scratch, which every evaluation rewrites before it reads it
+        _C.call("gq_fk_forward", self.hand.handle, _C.f32(self.hand_pose), _C.i64(self.contact_idx), self.B, self.n, _C.f32(Rg),
+                _C.f32(LT), _C.f32(self.cpts), _C.f32(self.cnrm), None, float(self.w["E_spen"]), None, None, None, None,
+                _C.ptr(self.fk_ws), self.fk_nb, _C.stream_ptr())
+        return ops.grasp_select(self.hand_pose, Rg, LT, self.samples, self.be, score.to(self.dev, torch.float32), self.terms, tol,
+                                k, radius)
 
     def flush(self):
         """Run the iterations that ``step`` has queued for a multi-iteration graph but not yet replayed."""

@@ -878,6 +878,59 @@ int gq_init_select_check(const float* points, const float* penalty, int64_t n_ob
 int gq_init_select_workspace_bytes(int64_t n_obj, int64_t M, size_t* bytes);
 int gq_init_select(const float* points, const float* penalty, int64_t n_obj, int64_t M, int64_t K, float tol, int32_t* sel,
                    int32_t* n_feasible, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- grasp-set selection: feasible, ranked, distinct grasps ---------------------------------------------------------------
+ * The last stage after the optimiser: of the batch_each rows of every object, the K best that are feasible and pairwise
+ * different grasps.  The reference has no counterpart; this replaces the consumer's rule of
+ * graspqp_isaaclab/utils/data.py:97-102,105-150 (get_saved_poses: sort by `values`, take the first num_grasps), which returns
+ * one basin K times and does not look at the obstacle terms.
+ *
+ * Distance of two rows i, j of one object: d(i,j)^2 = (1/Ns) sum_s |x_w,i(s) - x_w,j(s)|^2 over the Ns hand-surface samples
+ * (x_w = Rg (A_l p_s + b_l) + t, link_T = [A_l | b_l] row-major 3x4, t = hand_pose[0:3]), in metres, evaluated in closed form:
+ * with W_l = [Rg A_l | Rg b_l + t], dA, db the difference of two rows' W_l, and per link n_l, the centroid c_l and the centred
+ * second moment C_l = sum (p - c_l)(p - c_l)',
+ *   sum_{s in l} |dA p_s + db|^2 = n_l |dA c_l + db|^2 + tr(dA C_l dA').
+ * link_moments (n_links,10) = n_l, c_l (3), Cxx Cxy Cxz Cyy Cyz Czz, built once at set-up (fp64 sums, stored as float).  Both
+ * summands are >= 0 (the quadratic form is clamped at 0 against rounding), the links are summed serially in ascending order,
+ * a link with n_l = 0 is skipped: d(i,i) = 0 exactly, d(i,j) = d(j,i) exactly.
+ *
+ * gq_grasp_select.  hand_pose (batch,pose_dim), Rg (batch,9), link_T (batch,n_links,12), rows object-major with batch_each per
+ * object; score (batch), lower is better; terms (n_terms,batch); tol: n_terms HOST floats (copied at the call).
+ *   Row b is feasible iff score[b] is finite and terms[t,b] <= tol[t] for every t with tol[t] < +inf (a NaN term under a gate
+ *   makes the row infeasible; a term with tol = +inf is not read).
+ *   Per object, at most K times: pick the feasible row, neither picked nor suppressed, with the smallest key
+ *   (order-preserving bits of score, row) -- ties go to the smallest row; write its global row index to the next slot;
+ *   suppress every remaining row r with d^2(r, pick) < radius^2 (strict: radius = 0 suppresses nothing); stop when no row is left.
+ * Out: sel (n_obj,K) int32 in pick order, unused slots -1; n_selected (n_obj); n_feasible (n_obj), not capped by K; feasible
+ * (batch) 0/1.  There is no fill with infeasible rows.
+ * Two launches: one thread per (row, link) writes W, feasible and the keys into the workspace; one block of 256 threads per
+ * object selects.  No atomics, no block waits for another, every loop is bounded by K or batch_each; no allocation,
+ * synchronisation, upload or host read: graph-capturable on one stream and bitwise reproducible.
+ * Limits: n_links <= 64, 1 <= K <= batch_each < 2^30, batch < 2^31, n_terms <= 16.  Workspace:
+ * gq_grasp_select_workspace_bytes(batch, n_links) bytes on the device, contents irrelevant.
+ *
+ * gq_grasp_distances: dist (n_obj,batch_each,batch_each) = d (not d^2) of every pair of rows of an object, through the same
+ * device function; batch_each <= 4096.  Same workspace.
+ *
+ * gq_grasp_select_check / gq_grasp_distances_check (host only, no GPU) refuse: a NULL pointer (terms and tol may be NULL at
+ * n_terms = 0); pose_dim < 3; n_links outside 1..64; n_samples <= 0; batch_each out of range; a batch that is not a positive
+ * multiple of batch_each; n_terms outside 0..16; a NaN tol; K outside 1..batch_each; a radius that is NaN, negative or
+ * infinite; a workspace that is too small.  The message contains "grasp_select" and names the argument.                  */
+int gq_grasp_select_workspace_bytes(int64_t batch, int n_links, size_t* bytes);
+int gq_grasp_select_check(const float* hand_pose, int pose_dim, const float* Rg, const float* link_T, const float* link_moments,
+                          int n_links, int64_t n_samples, int64_t batch, int64_t batch_each, const float* score,
+                          const float* terms, const float* tol /* host */, int n_terms, int64_t K, float radius,
+                          const int32_t* sel, const int32_t* n_selected, const int32_t* n_feasible, const int32_t* feasible,
+                          const void* workspace /* only tested against NULL */, size_t workspace_bytes);
+int gq_grasp_select(const float* hand_pose, int pose_dim, const float* Rg, const float* link_T, const float* link_moments,
+                    int n_links, int64_t n_samples, int64_t batch, int64_t batch_each, const float* score, const float* terms,
+                    const float* tol /* host */, int n_terms, int64_t K, float radius, int32_t* sel, int32_t* n_selected,
+                    int32_t* n_feasible, int32_t* feasible, void* workspace, size_t workspace_bytes, void* stream);
+int gq_grasp_distances_check(const float* hand_pose, int pose_dim, const float* Rg, const float* link_T,
+                             const float* link_moments, int n_links, int64_t n_samples, int64_t batch, int64_t batch_each,
+                             const float* dist, const void* workspace /* only tested against NULL */, size_t workspace_bytes);
+int gq_grasp_distances(const float* hand_pose, int pose_dim, const float* Rg, const float* link_T, const float* link_moments,
+                       int n_links, int64_t n_samples, int64_t batch, int64_t batch_each, float* dist, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* Surface samples of object meshes on the device (reference core/object_model.py:163-178: pytorch3d
  * sample_points_from_meshes with 100 x num_samples points, then sample_farthest_points(K = num_samples) starting at sample
  * 0): face_verts (sumF,3,3) of n_obj meshes, area_cdf (sumF) normalised cumulative face area per mesh, face_offsets

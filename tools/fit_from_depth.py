@@ -9,12 +9,16 @@ With --init_avoid_scene the initial poses and those of every reset are screened 
 turns the z-score resets of the reference's schedule on (default: none).  The tool also fuses a second scene volume of the same
 frames WITHOUT skip, so the target stays in it: the grid of the pre-grasp term, whose station 0 is the opened hand at the
 grasp pose (with --esdf that volume's ESDF).  --w_pregrasp W > 0 puts the term into the energy; either way the final grasp set is
-evaluated with ops.pregrasp_terms and the mean E_pregrasp and the share of rows with E_pregrasp > 0 are reported.  It reports the number of surfels,
+evaluated with ops.pregrasp_terms and the mean E_pregrasp and the share of rows with E_pregrasp > 0 are reported.  --select K
+--select_radius R ends with GraspStepper.select and appends n_feasible, n_selected, the smallest pairwise distance among the
+selected and, for the consumer's rule (the K lowest energies), how many of those rows are infeasible or lie within R of a better one.
+It reports the number of surfels,
 how far they lie from the true sphere, the mean energy and the mean E_scene before and after --n_iter iterations, and the wall
 times of the stages (each closed by a synchronisation).  Evidence run, not a test: one JSON line is printed and appended to --out.
 
 usage: python tools/fit_from_depth.py [--views 8] [--batch_size 64] [--n_iter 400] [--esdf 0.06 --scene_margin 0.03]
-       [--init_avoid_scene] [--reset_epochs 600] [--w_pregrasp 30 --pregrasp_opening 0.5 --pregrasp_stations 4] [--out file.jsonl]
+       [--init_avoid_scene] [--reset_epochs 600] [--w_pregrasp 30 --pregrasp_opening 0.5 --pregrasp_stations 4]
+       [--select 8 --select_radius 0.01] [--out file.jsonl]
 """
 import argparse
 import json
@@ -44,6 +48,8 @@ ap.add_argument("--reset_epochs", type=int, default=None, help="z-score resets e
 ap.add_argument("--w_pregrasp", type=float, default=0.0, help="weight of E_pregrasp (0: evaluated at the end only)")
 ap.add_argument("--pregrasp_opening", type=float, default=0.5)
 ap.add_argument("--pregrasp_stations", type=int, default=4)
+ap.add_argument("--select", type=int, default=0, metavar="K", help="select the K best feasible, distinct grasps at the end (DESIGN 22)")
+ap.add_argument("--select_radius", type=float, default=0.01, metavar="R", help="grasps closer than R metres (RMS hand surface) are one grasp")
 ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "fit_from_depth.jsonl"))
 args = ap.parse_args()
 
@@ -156,6 +162,25 @@ def pregrasp_of(pose, idx):
 
 p1 = pregrasp_of(st.hand_pose, st.contact_idx)
 
+
+def selection_record(K, R):
+    """GraspStepper.select beside the consumer's rule (the K lowest energies) on the same rows; the objects are looked at one by one"""
+    sel = st.select(K, radius=R)
+    Rg, LT = st._select_fk
+    d = ops.grasp_distances(st.hand_pose, Rg, LT, st.samples, be).cpu()
+    feasible, energy, picks = sel.feasible.bool().cpu(), st.energy.cpu(), sel.sel.cpu().long()
+    min_d, bad = [], []
+    for o in range(d.shape[0]):
+        rows = picks[o][picks[o] >= 0] - o * be
+        min_d.append(float(d[o][rows][:, rows].clone().fill_diagonal_(float("inf")).min()) if len(rows) > 1 else None)
+        low = torch.argsort(energy[o * be:(o + 1) * be], stable=True)[:K]
+        bad.append(sum(1 for i, r in enumerate(low.tolist()) if not feasible[o * be + r] or (i > 0 and bool((d[o][r][low[:i]] < R).any()))))
+    return {"k": K, "radius": R, "n_feasible": sel.n_feasible.tolist(), "n_selected": sel.n_selected.tolist(),
+            "min_pairwise_d_selected": min_d, "lowest_energy_rule_infeasible_or_duplicate": bad}
+
+
+selected = selection_record(args.select, args.select_radius) if args.select > 0 else None
+
 rec = {"fit_from_depth": True, "hand": args.hand, "views": args.views, "image": [W, H], "batch": be, "n_contact": n, "n_iter": args.n_iter,
        "scene_grid": list(S_SHAPE), "scene_voxel": S_H, "target_grid": list(T_SHAPE), "target_voxel": T_H, "min_weight": args.min_weight,
        "esdf_max_distance": args.esdf, "scene_margin": args.scene_margin, "init_avoid_scene": args.init_avoid_scene,
@@ -168,7 +193,7 @@ rec = {"fit_from_depth": True, "hand": args.hand, "views": args.views, "image": 
        "E_scene_mean": {"before": float(s0.mean()), "after": float(s1.mean())},
        "w_pregrasp": args.w_pregrasp, "pregrasp": dict(PG, margin=args.scene_margin, grid="esdf" if args.esdf is not None else "tsdf"),
        "E_pregrasp_mean_after": float(p1.mean()), "rows_with_E_pregrasp_after": float((p1 > 0).float().mean()),
-       "contact_distance_mm_mean_abs_after": 1e3 * float(dis.abs().mean()),
+       "contact_distance_mm_mean_abs_after": 1e3 * float(dis.abs().mean()), "select": selected,
        "ms": {"integrate_scene": ms_scene, "integrate_whole_scene": ms_whole, "integrate_target_with_keep_label": ms_target, "extract_clouds": ms_extract,
               "initialize_from_tsdf": ms_object, "esdf": ms_esdf, "run": ms_run, "per_iteration": ms_run / args.n_iter}}
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
