@@ -774,7 +774,7 @@ int gq_fk_forward(const gqHand* h, const float* hand_pose, const int64_t* contac
   if (propose) {
     const gqProposeDesc& p = *propose;
     GQ_REQUIRE(p.slot_ctr && contact_idx, "fk_forward: incomplete gqProposeDesc");
-    GQ_REQUIRE(!p.energy || p.batch_each > 1, "fk_forward: z-score needs z_out and batch_each > 1");
+    // batch_each = 1 is served like gq_mala_propose serves it: std = 0 / 0, z = NaN, and the accept step rejects the row
     const int rc = gq_propose_fill(p, "fk_forward", batch, a.D, n_contact, const_cast<float*>(hand_pose),
                                    const_cast<int64_t*>(contact_idx), &a.pr);
     if (rc) return rc;

@@ -64,9 +64,11 @@ def forward_state(C, hand, inp):
     return dict(Rg=Rg.cpu().numpy(), link_T=LT.cpu().numpy(), node_W=W.cpu().numpy().copy())
 
 
-def run_backward(C, hand, inp, present=GRAD_INPUTS, tail=True):
+def run_backward(C, hand, inp, present=GRAD_INPUTS, tail=True, reset_mask=None, slots=1, slot_ctr=(0, 1)):
     """One gq_fk_backward launch on `inp` (make_inputs + forward_state).  present: the gradient inputs that are handed over;
-    tail: with the fused energy and accept tail.  -> dict of numpy outputs."""
+    tail: with the fused energy and accept tail.  reset_mask (B,) uint8: rows accepted unconditionally.  slots / slot_ctr: the
+    ring of accept draws -- inp["u_accept"] is then (slots, B) and slot_ctr the device counter pair before the launch (the
+    proposal has advanced [1]); the pair after the launch comes back as "slot_ctr".  -> dict of numpy outputs."""
     cu = {k: torch.tensor(np.ascontiguousarray(v)).cuda() for k, v in inp.items()}
     B, n = inp["idx"].shape
     D = inp["hand_pose"].shape[1]
@@ -95,14 +97,17 @@ def run_backward(C, hand, inp, present=GRAD_INPUTS, tail=True):
         temperature = torch.zeros(B, device="cuda")
         energy, pose, grad, idx, terms = (cu[k].clone() for k in ("energy_old", "pose_old", "grad_old", "idx_old", "terms_old"))
         ac = C.AcceptDesc()
-        ac.u_accept, ac.z, ac.reset_mask, ac.step = cu["u_accept"].data_ptr(), cu["z"].data_ptr(), None, cu["step"].data_ptr()
+        rm = None if reset_mask is None else torch.tensor(np.ascontiguousarray(reset_mask, dtype=np.uint8)).cuda()
+        assert cu["u_accept"].numel() == slots * B
+        ac.u_accept, ac.z, ac.step = cu["u_accept"].data_ptr(), cu["z"].data_ptr(), cu["step"].data_ptr()
+        ac.reset_mask = None if rm is None else rm.data_ptr()
         ac.starting_temperature, ac.decay, ac.annealing_period = 18.0, 0.95, 30
         ac.energy, ac.pose, ac.idx, ac.grad = energy.data_ptr(), pose.data_ptr(), idx.data_ptr(), grad.data_ptr()
         ac.accept, ac.temperature = accept.data_ptr(), temperature.data_ptr()
         ac.n_terms, ac.terms_new, ac.terms = N_TERMS, terms_new.data_ptr(), terms.data_ptr()
-        slot_ctr = torch.tensor([0, 1], dtype=torch.int32, device="cuda")  # one slot of draws, the proposal has advanced [1]
-        ac.slot_ctr, ac.slots = slot_ctr.data_ptr(), 1
-        keep = [jlo, jhi, slot_ctr]
+        slot_ctr = torch.tensor(list(slot_ctr), dtype=torch.int32, device="cuda")  # default: one slot of draws, the proposal has advanced [1]
+        ac.slot_ctr, ac.slots = slot_ctr.data_ptr(), slots
+        keep = [jlo, jhi, rm]
     C.call("gq_fk_backward", hand.handle, C.f32(cu["hand_pose"]), C.i64(cu["idx"]), B, n, C.f32(cu["Rg"]), C.f32(cu["link_T"]),
            opt("g_cpts"), opt("g_cnrm"), opt("g_spheres"), opt("g_wrench"), opt("g_Rt"), opt("g_theta"), opt("g_R"), C.f32(gp),
            ctypes.byref(en) if tail else None, ctypes.byref(ac) if tail else None, C.ptr(ws), nb, C.stream_ptr())
@@ -112,7 +117,8 @@ def run_backward(C, hand, inp, present=GRAD_INPUTS, tail=True):
     if tail:
         out.update(e_dis=terms_new[0].cpu().numpy(), e_joints=terms_new[4].cpu().numpy(), total=total.cpu().numpy(),
                    accept=accept.cpu().numpy(), pose=pose.cpu().numpy(), grad=grad.cpu().numpy(), idx=idx.cpu().numpy(),
-                   terms=terms.cpu().numpy(), energy=energy.cpu().numpy(), temperature=temperature.cpu().numpy())
+                   terms=terms.cpu().numpy(), energy=energy.cpu().numpy(), temperature=temperature.cpu().numpy(),
+                   terms_new=terms_new.cpu().numpy(), slot_ctr=slot_ctr.cpu().numpy())
     return out
 
 
