@@ -25,7 +25,7 @@
 // No atomics: stations ascending inside the lane, then the orders of gq_scene_kernel; bitwise reproducible run to run.
 #include "approach_row_dev.h"  // the row body, shared with gq_clutter_corridor_kernel (clutter.hip)
 
-__global__ __launch_bounds__(GQ_AP_WAVES * GQ_WAVE) void gq_approach_kernel(const GqApproachArgs g) { gq_approach_row(g, g.grid); }
+__global__ __launch_bounds__(GQ_ROW_WAVES * GQ_WAVE) void gq_approach_kernel(const GqApproachArgs g) { gq_approach_row(g, g.grid); }
 
 int gq_approach_check(const gqSceneGrid* grid, int64_t batch, int n_links, int64_t n_samples, float distance, int n_stations,
                       const float* grasp_axis) {
@@ -53,16 +53,10 @@ int gq_approach_terms(const gqSceneGrid* grid, float margin, float distance, int
   if (rc != GQ_OK) return rc;
   GQ_REQUIRE(samples && sample_link && hand_pose && Rg && link_T && pose_dim >= 9, "approach: bad arguments");
   GQ_REQUIRE(margin >= 0.0f && margin < GQ_INF_F, "approach: margin must be finite and >= 0, got %g", (double)margin);
-  GqApproachArgs a{};
-  a.grid = *grid;
-  a.samples = samples, a.sample_link = sample_link, a.hand_pose = hand_pose, a.Rg = Rg, a.link_T = link_T;
-  a.up_approach = up_approach;
-  a.Ns = (int)n_samples, a.L = n_links, a.D = pose_dim, a.K = n_stations;
-  a.margin = margin, a.w_approach = w_approach, a.distance = distance;
-  a.ax = grasp_axis[0], a.ay = grasp_axis[1], a.az = grasp_axis[2];
-  a.accumulate = accumulate != 0;
-  a.e_approach = e_approach, a.wrench = link_wrench, a.gRt = gRt;
-  hipLaunchKernelGGL(gq_approach_kernel, dim3((unsigned)batch), dim3(GQ_AP_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
+  const GqApproachArgs a = gq_approach_args(*grid, margin, distance, n_stations, samples, sample_link, n_samples, n_links, hand_pose,
+                                            pose_dim, Rg, link_T, grasp_axis, up_approach, w_approach, e_approach, accumulate,
+                                            link_wrench, gRt);
+  hipLaunchKernelGGL(gq_approach_kernel, dim3((unsigned)batch), dim3(GQ_ROW_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

@@ -4,9 +4,8 @@
 // object.  Nothing else differs between the two launches, so row b's numbers are bit for bit the same at the same grid.
 #pragma once
 #include "approach_dev.h"
+#include "sample_row_dev.h"  // the row frame the four hand-surface terms share
 
-#define GQ_AP_MAX_LINKS 64     // lane l of a wavefront owns link l
-#define GQ_AP_WAVES 8          // 512 default samples: one 64-sample chunk per wavefront
 #define GQ_AP_MAX_STATIONS 32
 
 struct GqApproachArgs {
@@ -26,24 +25,35 @@ struct GqApproachArgs {
   float* gRt;         // (B,12) or null
 };
 
-// accumulate: a plain rounded add of the finished value (no contraction with the product that made it), so that adding to
-// a buffer gives the bits of buffer + (the overwriting launch's value)
-__device__ __forceinline__ void gq_ap_store(float* p, float v, int accumulate) {
-#pragma clang fp contract(off)
-  *p = accumulate ? *p + v : v;
+// the arguments of a launch, checked by the caller, as the kernels take them; `grid` is the launch's grid or grid 0 of its stack
+static inline GqApproachArgs gq_approach_args(const gqSceneGrid& grid, float margin, float distance, int n_stations,
+                                              const float* samples, const int32_t* sample_link, int64_t n_samples, int n_links,
+                                              const float* hand_pose, int pose_dim, const float* Rg, const float* link_T,
+                                              const float* grasp_axis, const float* up_approach, float w_approach,
+                                              float* e_approach, int accumulate, float* link_wrench, float* gRt) {
+  GqApproachArgs a{};
+  a.grid = grid;
+  a.samples = samples, a.sample_link = sample_link, a.hand_pose = hand_pose, a.Rg = Rg, a.link_T = link_T;
+  a.up_approach = up_approach;
+  a.Ns = (int)n_samples, a.L = n_links, a.D = pose_dim, a.K = n_stations;
+  a.margin = margin, a.w_approach = w_approach, a.distance = distance;
+  a.ax = grasp_axis[0], a.ay = grasp_axis[1], a.az = grasp_axis[2];
+  a.accumulate = accumulate != 0;
+  a.e_approach = e_approach, a.wrench = link_wrench, a.gRt = gRt;
+  return a;
 }
 
 // row = blockIdx.x; `grid` is the grid this row reads (g.grid itself in the single-grid launch)
 __device__ __forceinline__ void gq_approach_row(const GqApproachArgs& g, const gqSceneGrid& grid) {
-  __shared__ float s_T[GQ_AP_MAX_LINKS * 12];
-  __shared__ float s_part[GQ_AP_WAVES][GQ_AP_MAX_LINKS][6];  // per wavefront and link: sum g_h (3), sum x_h x g_h (3), up = 1
-  __shared__ int s_seen[GQ_AP_WAVES][GQ_AP_MAX_LINKS];       // the wavefront met a sample of the link (active or not)
-  __shared__ float s_K[GQ_AP_WAVES][9];
-  __shared__ float s_e[GQ_AP_WAVES];
+  __shared__ float s_T[GQ_ROW_MAX_LINKS * 12];
+  __shared__ float s_part[GQ_ROW_WAVES][GQ_ROW_MAX_LINKS][6];  // per wavefront and link: sum g_h (3), sum x_h x g_h (3), up = 1
+  __shared__ int s_seen[GQ_ROW_WAVES][GQ_ROW_MAX_LINKS];       // the wavefront met a sample of the link (active or not)
+  __shared__ float s_K[GQ_ROW_WAVES][9];
+  __shared__ float s_e[GQ_ROW_WAVES];
   const int tid = threadIdx.x, lane = gq_lane(), wv = tid / GQ_WAVE;
   const size_t row = blockIdx.x;
   const int L = g.L, nK = g.K;
-  for (int i = tid; i < L * 12; i += GQ_AP_WAVES * GQ_WAVE) s_T[i] = g.link_T[row * L * 12 + i];
+  for (int i = tid; i < L * 12; i += GQ_ROW_WAVES * GQ_WAVE) s_T[i] = g.link_T[row * L * 12 + i];
   const float* R = g.Rg + row * 9;
   const gq3 r1 = gq_mk(R[0], R[1], R[2]), r2 = gq_mk(R[3], R[4], R[5]), r3 = gq_mk(R[6], R[7], R[8]);
   const float* tp = g.hand_pose + row * g.D;
@@ -63,13 +73,10 @@ __device__ __forceinline__ void gq_approach_row(const GqApproachArgs& g, const g
   float K[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   float e = 0.0f;
   int seen = 0;
-  for (int c = wv; c < chunks; c += GQ_AP_WAVES) {
+  for (int c = wv; c < chunks; c += GQ_ROW_WAVES) {
     float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if ((unsigned)l < (unsigned)L) {
-      const float* T = s_T + l * 12;
-      const gq3 xh = gq_mk(fmaf(T[0], p.x, fmaf(T[1], p.y, fmaf(T[2], p.z, T[3]))),
-                           fmaf(T[4], p.x, fmaf(T[5], p.y, fmaf(T[6], p.z, T[7]))),
-                           fmaf(T[8], p.x, fmaf(T[9], p.y, fmaf(T[10], p.z, T[11]))));
+      const gq3 xh = gq_row_point(s_T + l * 12, p);
       gq3 G = gq_mk(0, 0, 0);  // sum of g_h over the stations of this sample
       gq_approach_stations(grid, xh, a, r1, r2, r3, t, g.distance, nK, g.margin, e, G, K);
       const gq3 m = gq_cross(xh, G);
@@ -77,34 +84,15 @@ __device__ __forceinline__ void gq_approach_row(const GqApproachArgs& g, const g
     } else {
       l = -1;  // a link id outside the hand (refused by ops.SurfaceSamples): the sample is ignored
     }
-    for (int k = 0; k < L; ++k) {
-      const bool mine = l == k;
-      if (__ballot(mine) == 0ull) continue;  // wave-uniform
-      float r[6];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) r[q] = gq_dpp_sum(mine ? v[q] : 0.0f);
-      if (lane == k) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) acc[q] += r[q];
-        seen = 1;
-      }
-    }
-    s += GQ_AP_WAVES * GQ_WAVE;
+    GQ_ROW_LINK_SUMS(6, l, L, lane, v, acc, seen = 1)
+    s += GQ_ROW_WAVES * GQ_WAVE;
     l = -1;
-    if (c + GQ_AP_WAVES < chunks && s < g.Ns) {
+    if (c + GQ_ROW_WAVES < chunks && s < g.Ns) {
       l = g.sample_link[s];
       p = gq_mk(g.samples[(size_t)s * 3], g.samples[(size_t)s * 3 + 1], g.samples[(size_t)s * 3 + 2]);
     }
   }
-  e = gq_dpp_sum(e);
-  float Kw = 0.0f;  // lane q < 9 of the wavefront keeps the wavefront's K[q]
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    const float kq = gq_dpp_sum(K[q]);
-    if (lane == q) Kw = kq;
-  }
-  if (lane == 0) s_e[wv] = e;
-  if (lane < 9) s_K[wv][lane] = Kw;
+  GQ_ROW_WAVE_PARTIALS(e, K, lane, wv, s_e, s_K)
   if (lane < L) {
 #pragma unroll
     for (int q = 0; q < 6; ++q) s_part[wv][lane][q] = acc[q];
@@ -118,28 +106,13 @@ __device__ __forceinline__ void gq_approach_row(const GqApproachArgs& g, const g
   float tot[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   if (lane < L) {
     int present = 0;
-    for (int w = 0; w < GQ_AP_WAVES; ++w) {
-#pragma unroll
-      for (int q = 0; q < 6; ++q) tot[q] += s_part[w][lane][q];
-      present |= s_seen[w][lane];
-    }
+    GQ_ROW_FOLD(6, s_part, s_seen, lane, tot, present)
     if (g.wrench && (present || !g.accumulate)) {  // links without samples: zero (overwrite) or left alone (accumulate)
       float* w6 = g.wrench + (row * L + lane) * 6;
 #pragma unroll
-      for (int q = 0; q < 6; ++q) gq_ap_store(w6 + q, up * tot[q], g.accumulate);
+      for (int q = 0; q < 6; ++q) gq_row_store(w6 + q, up * tot[q], g.accumulate);
     }
   }
-  // row sums over the links (lanes >= L hold zeros)
-  const float Fx = gq_dpp_sum(tot[0]), Fy = gq_dpp_sum(tot[1]), Fz = gq_dpp_sum(tot[2]);
-  if (g.gRt && lane < 12) {
-    // lanes 0..2: gsum = -sum g_h; lanes 3..11: K9, row-major, folded over the wavefronts in wavefront order
-    float val = lane == 0 ? -Fx : (lane == 1 ? -Fy : -Fz);
-    if (lane >= 3) {
-      val = 0.0f;
-      for (int w = 0; w < GQ_AP_WAVES; ++w) val += s_K[w][lane - 3];
-    }
-    gq_ap_store(g.gRt + row * 12 + lane, up * val, g.accumulate);
-  }
-  if (lane == 0 && g.e_approach)
-    g.e_approach[row] = (((s_e[0] + s_e[1]) + (s_e[2] + s_e[3])) + ((s_e[4] + s_e[5]) + (s_e[6] + s_e[7]))) * invK;
+  GQ_ROW_GRT(g.gRt, row, tot, s_K, lane, up, g.accumulate)  // K is K9 here: g_h (x) the shifted point
+  if (lane == 0 && g.e_approach) g.e_approach[row] = gq_row_energy(s_e) * invK;
 }

@@ -27,16 +27,16 @@ deps() {  # headers each translation unit includes
     export) echo "common.h kin_dev.h wave.h" ;;
     exact) echo "common.h wave.h exact_dev.h fc_dev.h" ;;
     kin) echo "common.h setup.h cluster_bound.h loop_dev.h sdf_dev.h tri.h kin_dev.h wave.h" ;;
-    tabletop) echo "common.h" ;;
+    tabletop) echo "common.h sample_row_dev.h" ;;
     cloud) echo "common.h setup.h cluster_bound.h" ;;
-    scene) echo "common.h grid_stack.h scene_dev.h scene_row_dev.h" ;;
-    approach) echo "common.h grid_stack.h scene_dev.h approach_dev.h approach_row_dev.h" ;;
-    clutter) echo "common.h grid_stack.h scene_dev.h approach_dev.h scene_row_dev.h approach_row_dev.h clutter_dev.h" ;;
-    pregrasp) echo "common.h wave.h kin_dev.h grid_stack.h scene_dev.h approach_dev.h approach_row_dev.h pregrasp_dev.h" ;;
+    scene) echo "common.h grid_stack.h scene_dev.h sample_row_dev.h scene_row_dev.h" ;;
+    approach) echo "common.h grid_stack.h scene_dev.h approach_dev.h sample_row_dev.h approach_row_dev.h" ;;
+    clutter) echo "common.h grid_stack.h scene_dev.h approach_dev.h sample_row_dev.h scene_row_dev.h approach_row_dev.h clutter_dev.h" ;;
+    pregrasp) echo "common.h wave.h kin_dev.h grid_stack.h scene_dev.h approach_dev.h sample_row_dev.h approach_row_dev.h pregrasp_dev.h" ;;
     tsdf) echo "common.h grid_stack.h scene_dev.h clutter_dev.h tsdf_dev.h" ;;
     surfel) echo "common.h grid_stack.h scene_dev.h clutter_dev.h surfel_dev.h" ;;
     edt) echo "common.h grid_stack.h edt_dev.h" ;;
-    select) echo "common.h scene_dev.h scene_row_dev.h init_select_dev.h select_dev.h" ;;
+    select) echo "common.h sample_row_dev.h init_select_dev.h select_dev.h" ;;
     *) echo "common.h" ;;
   esac
 }

@@ -26,7 +26,7 @@ struct GqClutterArgs {
   int rows_per_grid;
 };
 
-__global__ __launch_bounds__(GQ_SC_WAVES * GQ_WAVE) void gq_clutter_kernel(const GqClutterArgs c) {
+__global__ __launch_bounds__(GQ_ROW_WAVES * GQ_WAVE) void gq_clutter_kernel(const GqClutterArgs c) {
   const gqSceneGrid grid = gq_stack_grid(c.a.grid, blockIdx.x / (unsigned)c.rows_per_grid);
   gq_scene_row(c.a, grid);
 }
@@ -36,7 +36,7 @@ struct GqCorridorArgs {
   int rows_per_grid;
 };
 
-__global__ __launch_bounds__(GQ_AP_WAVES * GQ_WAVE) void gq_clutter_corridor_kernel(const GqCorridorArgs c) {
+__global__ __launch_bounds__(GQ_ROW_WAVES * GQ_WAVE) void gq_clutter_corridor_kernel(const GqCorridorArgs c) {
   const gqSceneGrid grid = gq_stack_grid(c.a.grid, blockIdx.x / (unsigned)c.rows_per_grid);
   gq_approach_row(c.a, grid);
 }
@@ -125,16 +125,10 @@ int gq_clutter_terms(const gqClutterGrids* grids, int rows_per_grid, float margi
   GQ_REQUIRE(samples && sample_link && hand_pose && Rg && link_T && pose_dim >= 9, "clutter: bad arguments");
   GQ_REQUIRE(margin >= 0.0f && margin < GQ_INF_F, "clutter: margin must be finite and >= 0, got %g", (double)margin);
   GqClutterArgs c{};
-  GqSceneArgs& a = c.a;
-  a.grid = gq_stack_grid(grids);
-  a.samples = samples, a.sample_link = sample_link, a.hand_pose = hand_pose, a.Rg = Rg, a.link_T = link_T;
-  a.up_scene = up_scene;
-  a.Ns = (int)n_samples, a.L = n_links, a.D = pose_dim;
-  a.margin = margin, a.w_scene = w_scene;
-  a.accumulate = accumulate != 0;
-  a.e_scene = e_scene, a.wrench = link_wrench, a.gRt = gRt;
+  c.a = gq_scene_args(gq_stack_grid(grids), margin, samples, sample_link, n_samples, n_links, hand_pose, pose_dim, Rg, link_T,
+                      up_scene, w_scene, e_scene, accumulate, link_wrench, gRt);
   c.rows_per_grid = rows_per_grid;
-  hipLaunchKernelGGL(gq_clutter_kernel, dim3((unsigned)batch), dim3(GQ_SC_WAVES * GQ_WAVE), 0, (hipStream_t)stream, c);
+  hipLaunchKernelGGL(gq_clutter_kernel, dim3((unsigned)batch), dim3(GQ_ROW_WAVES * GQ_WAVE), 0, (hipStream_t)stream, c);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }
@@ -152,17 +146,10 @@ int gq_clutter_corridor_terms(const gqClutterGrids* grids, int rows_per_grid, fl
   GQ_REQUIRE(samples && sample_link && hand_pose && Rg && link_T && pose_dim >= 9, "clutter: bad arguments");
   GQ_REQUIRE(margin >= 0.0f && margin < GQ_INF_F, "clutter: margin must be finite and >= 0, got %g", (double)margin);
   GqCorridorArgs c{};
-  GqApproachArgs& a = c.a;
-  a.grid = first;
-  a.samples = samples, a.sample_link = sample_link, a.hand_pose = hand_pose, a.Rg = Rg, a.link_T = link_T;
-  a.up_approach = up_approach;
-  a.Ns = (int)n_samples, a.L = n_links, a.D = pose_dim, a.K = n_stations;
-  a.margin = margin, a.w_approach = w_approach, a.distance = distance;
-  a.ax = grasp_axis[0], a.ay = grasp_axis[1], a.az = grasp_axis[2];
-  a.accumulate = accumulate != 0;
-  a.e_approach = e_approach, a.wrench = link_wrench, a.gRt = gRt;
+  c.a = gq_approach_args(first, margin, distance, n_stations, samples, sample_link, n_samples, n_links, hand_pose, pose_dim, Rg,
+                         link_T, grasp_axis, up_approach, w_approach, e_approach, accumulate, link_wrench, gRt);
   c.rows_per_grid = rows_per_grid;
-  hipLaunchKernelGGL(gq_clutter_corridor_kernel, dim3((unsigned)batch), dim3(GQ_AP_WAVES * GQ_WAVE), 0, (hipStream_t)stream, c);
+  hipLaunchKernelGGL(gq_clutter_corridor_kernel, dim3((unsigned)batch), dim3(GQ_ROW_WAVES * GQ_WAVE), 0, (hipStream_t)stream, c);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

@@ -19,11 +19,9 @@
 //
 // One kernel for a single grid and a stack: the row picks its grid by gq_stack_grid, a single grid is the stack of one.
 // No atomics, every sum in a fixed order: bitwise reproducible run to run.
-#include "approach_row_dev.h"  // gq_ap_store, the wavefront / station limits of the corridor launches
+#include "approach_row_dev.h"  // gq_approach_check's station limit; the row frame (sample_row_dev.h)
 #include "kin_dev.h"
 #include "pregrasp_dev.h"
-
-#define GQ_PG_WAVES GQ_AP_WAVES
 
 struct GqPregraspArgs {
   gqHand h;
@@ -52,9 +50,9 @@ __device__ __forceinline__ void gq_pregrasp_row(const GqPregraspArgs& g, const g
   __shared__ float sTh[64];       // coupled hands: the opened actuated joints (head), the tree torques (tail)
   __shared__ int sLN[64];         // link -> node
   __shared__ int sCh[64];         // child lists
-  __shared__ float s_part[GQ_PG_WAVES][64][6];  // per wavefront and link: sum g_h (3), sum x_h x g_h (3), up = 1
-  __shared__ float s_K[GQ_PG_WAVES][9];
-  __shared__ float s_e[GQ_PG_WAVES];
+  __shared__ float s_part[GQ_ROW_WAVES][64][6];  // per wavefront and link: sum g_h (3), sum x_h x g_h (3), up = 1
+  __shared__ float s_K[GQ_ROW_WAVES][9];
+  __shared__ float s_e[GQ_ROW_WAVES];
   __shared__ float sWr[64 * 6];   // link wrenches of the row
   __shared__ float sNF[64 * 6];   // node wrenches of the row
   const int tid = threadIdx.x, lane = gq_lane(), wv = tid / GQ_WAVE;
@@ -141,7 +139,7 @@ __device__ __forceinline__ void gq_pregrasp_row(const GqPregraspArgs& g, const g
   float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   float K[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   float e = 0.0f;
-  for (int c = wv; c < chunks; c += GQ_PG_WAVES) {
+  for (int c = wv; c < chunks; c += GQ_ROW_WAVES) {
     float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if ((unsigned)l < (unsigned)L) {
       const gq3 xh = gq_pregrasp_point(sT + l * 12, p);
@@ -152,33 +150,15 @@ __device__ __forceinline__ void gq_pregrasp_row(const GqPregraspArgs& g, const g
     } else {
       l = -1;  // a link id outside the hand (refused by ops.SurfaceSamples): the sample is ignored
     }
-    for (int k = 0; k < L; ++k) {
-      const bool mine = l == k;
-      if (__ballot(mine) == 0ull) continue;  // wave-uniform
-      float r[6];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) r[q] = gq_dpp_sum(mine ? v[q] : 0.0f);
-      if (lane == k) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) acc[q] += r[q];
-      }
-    }
-    s += GQ_PG_WAVES * GQ_WAVE;
+    GQ_ROW_LINK_SUMS(6, l, L, lane, v, acc, )
+    s += GQ_ROW_WAVES * GQ_WAVE;
     l = -1;
-    if (c + GQ_PG_WAVES < chunks && s < g.Ns) {
+    if (c + GQ_ROW_WAVES < chunks && s < g.Ns) {
       l = g.sample_link[s];
       p = gq_mk(g.samples[(size_t)s * 3], g.samples[(size_t)s * 3 + 1], g.samples[(size_t)s * 3 + 2]);
     }
   }
-  e = gq_dpp_sum(e);
-  float Kw = 0.0f;  // lane q < 9 of the wavefront keeps the wavefront's K[q]
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    const float kq = gq_dpp_sum(K[q]);
-    if (lane == q) Kw = kq;
-  }
-  if (lane == 0) s_e[wv] = e;
-  if (lane < 9) s_K[wv][lane] = Kw;
+  GQ_ROW_WAVE_PARTIALS(e, K, lane, wv, s_e, s_K)
   if (lane < L) {
 #pragma unroll
     for (int q = 0; q < 6; ++q) s_part[wv][lane][q] = acc[q];
@@ -191,26 +171,13 @@ __device__ __forceinline__ void gq_pregrasp_row(const GqPregraspArgs& g, const g
   const float up = (g.up_pregrasp ? g.up_pregrasp[row] : g.w_pregrasp) * invK;
   float tot[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   if (lane < L) {
-    for (int w = 0; w < GQ_PG_WAVES; ++w) {
-#pragma unroll
-      for (int q = 0; q < 6; ++q) tot[q] += s_part[w][lane][q];
-    }
+    GQ_ROW_FOLD_SUMS(6, s_part, lane, tot)
 #pragma unroll
     for (int q = 0; q < 6; ++q) sWr[lane * 6 + q] = tot[q];
   }
-  // row sums over the links (lanes >= L hold zeros)
-  const float Fx = gq_dpp_sum(tot[0]), Fy = gq_dpp_sum(tot[1]), Fz = gq_dpp_sum(tot[2]);
-  if (g.gRt && lane < 12) {
-    // lanes 0..2: gsum = -sum g_h; lanes 3..11: K9, row-major, folded over the wavefronts in wavefront order
-    float val = lane == 0 ? -Fx : (lane == 1 ? -Fy : -Fz);
-    if (lane >= 3) {
-      val = 0.0f;
-      for (int w = 0; w < GQ_PG_WAVES; ++w) val += s_K[w][lane - 3];
-    }
-    gq_ap_store(g.gRt + row * 12 + lane, up * val, g.accumulate & 1);
-  }
+  GQ_ROW_GRT(g.gRt, row, tot, s_K, lane, up, g.accumulate & 1)
   if (lane == 0 && g.e_pregrasp)  // the energy is a value, not a gradient: always overwritten
-    g.e_pregrasp[row] = (((s_e[0] + s_e[1]) + (s_e[2] + s_e[3])) + ((s_e[4] + s_e[5]) + (s_e[6] + s_e[7]))) * invK;
+    g.e_pregrasp[row] = gq_row_energy(s_e) * invK;
   if (!g.g_theta) return;
   // 2. links -> nodes, then children into parents, deepest level first: lane j holds the six components of node j
   gq_wave_sync();
@@ -247,10 +214,10 @@ __device__ __forceinline__ void gq_pregrasp_row(const GqPregraspArgs& g, const g
       for (int j = 0; j < J; ++j) tau = fmaf(h.coup[j * JA + lane], sTh[j], tau);
   }
   // 4. d theta_o / d theta = 1 - alpha
-  if (lane < JA) gq_ap_store(g.g_theta + row * JA + lane, (1.0f - g.opening) * (up * tau), g.accumulate & 2);
+  if (lane < JA) gq_row_store(g.g_theta + row * JA + lane, (1.0f - g.opening) * (up * tau), g.accumulate & 2);
 }
 
-__global__ __launch_bounds__(GQ_PG_WAVES * GQ_WAVE) void gq_pregrasp_kernel(const GqPregraspArgs g) {
+__global__ __launch_bounds__(GQ_ROW_WAVES * GQ_WAVE) void gq_pregrasp_kernel(const GqPregraspArgs g) {
   const gqSceneGrid grid = gq_stack_grid(g.grid, blockIdx.x / (unsigned)g.rows_per_grid);
   gq_pregrasp_row(g, grid);
 }
@@ -294,7 +261,7 @@ int gq_pregrasp_terms(const gqHand* h, const gqClutterGrids* grids, int64_t rows
   a.ax = grasp_axis[0], a.ay = grasp_axis[1], a.az = grasp_axis[2];
   a.accumulate = accumulate & 3;  // bit 0: gRt, bit 1: g_theta
   a.e_pregrasp = e_pregrasp, a.g_theta = g_theta, a.gRt = gRt;
-  hipLaunchKernelGGL(gq_pregrasp_kernel, dim3((unsigned)batch), dim3(GQ_PG_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(gq_pregrasp_kernel, dim3((unsigned)batch), dim3(GQ_ROW_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

@@ -21,7 +21,7 @@
 // reproducible run to run.
 #include "scene_row_dev.h"  // the row body, shared with gq_clutter_kernel (clutter.hip)
 
-__global__ __launch_bounds__(GQ_SC_WAVES * GQ_WAVE) void gq_scene_kernel(const GqSceneArgs g) { gq_scene_row(g, g.grid); }
+__global__ __launch_bounds__(GQ_ROW_WAVES * GQ_WAVE) void gq_scene_kernel(const GqSceneArgs g) { gq_scene_row(g, g.grid); }
 
 // one query per lane: the differentiable building block for arbitrary world points
 __global__ __launch_bounds__(256) void gq_scene_query_kernel(const gqSceneGrid grid, const float* __restrict__ points, int64_t N,
@@ -65,7 +65,7 @@ int gq_scene_check(const gqSceneGrid* grid, int64_t batch, int n_links, int64_t 
   const int rc = gq_scene_check_grid(grid);
   if (rc != GQ_OK) return rc;
   GQ_REQUIRE(batch > 0 && batch <= 0x7fffffffll, "scene: batch must be in 1..2^31-1, got %lld", (long long)batch);
-  GQ_REQUIRE(n_links > 0 && n_links <= GQ_SC_MAX_LINKS, "scene: n_links must be in 1..%d, got %d", GQ_SC_MAX_LINKS, n_links);
+  GQ_REQUIRE(n_links > 0 && n_links <= GQ_ROW_MAX_LINKS, "scene: n_links must be in 1..%d, got %d", GQ_ROW_MAX_LINKS, n_links);
   GQ_REQUIRE(n_samples > 0 && n_samples <= (1ll << 24), "scene: n_samples must be in 1..2^24, got %lld", (long long)n_samples);
   return GQ_OK;
 }
@@ -78,15 +78,9 @@ int gq_scene_terms(const gqSceneGrid* grid, float margin, const float* samples, 
   if (rc != GQ_OK) return rc;
   GQ_REQUIRE(samples && sample_link && hand_pose && Rg && link_T && pose_dim >= 9, "scene: bad arguments");
   GQ_REQUIRE(margin >= 0.0f && margin < GQ_INF_F, "scene: margin must be finite and >= 0, got %g", (double)margin);
-  GqSceneArgs a{};
-  a.grid = *grid;
-  a.samples = samples, a.sample_link = sample_link, a.hand_pose = hand_pose, a.Rg = Rg, a.link_T = link_T;
-  a.up_scene = up_scene;
-  a.Ns = (int)n_samples, a.L = n_links, a.D = pose_dim;
-  a.margin = margin, a.w_scene = w_scene;
-  a.accumulate = accumulate != 0;
-  a.e_scene = e_scene, a.wrench = link_wrench, a.gRt = gRt;
-  hipLaunchKernelGGL(gq_scene_kernel, dim3((unsigned)batch), dim3(GQ_SC_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
+  const GqSceneArgs a = gq_scene_args(*grid, margin, samples, sample_link, n_samples, n_links, hand_pose, pose_dim, Rg, link_T,
+                                      up_scene, w_scene, e_scene, accumulate, link_wrench, gRt);
+  hipLaunchKernelGGL(gq_scene_kernel, dim3((unsigned)batch), dim3(GQ_ROW_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

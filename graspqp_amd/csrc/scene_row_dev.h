@@ -3,10 +3,8 @@
 // with the launch's one grid; gq_clutter_kernel (clutter.hip) with the grid of the row's object.  Nothing else differs between
 // the two launches, so row b's numbers are bit for bit the same at the same grid.
 #pragma once
+#include "sample_row_dev.h"  // the row frame the four hand-surface terms share
 #include "scene_dev.h"
-
-#define GQ_SC_MAX_LINKS 64  // lane l of a wavefront owns link l
-#define GQ_SC_WAVES 8       // 512 default samples: one 64-sample chunk per wavefront
 
 struct GqSceneArgs {
   gqSceneGrid grid;
@@ -24,24 +22,33 @@ struct GqSceneArgs {
   float* gRt;      // (B,12) or null
 };
 
-// accumulate: a plain rounded add of the finished value (no contraction with the product that made it), so that adding to
-// a buffer gives the bits of buffer + (the overwriting launch's value)
-__device__ __forceinline__ void gq_sc_store(float* p, float v, int accumulate) {
-#pragma clang fp contract(off)
-  *p = accumulate ? *p + v : v;
+// the arguments of a launch, checked by the caller, as the kernels take them; `grid` is the launch's grid or grid 0 of its stack
+static inline GqSceneArgs gq_scene_args(const gqSceneGrid& grid, float margin, const float* samples, const int32_t* sample_link,
+                                        int64_t n_samples, int n_links, const float* hand_pose, int pose_dim, const float* Rg,
+                                        const float* link_T, const float* up_scene, float w_scene, float* e_scene, int accumulate,
+                                        float* link_wrench, float* gRt) {
+  GqSceneArgs a{};
+  a.grid = grid;
+  a.samples = samples, a.sample_link = sample_link, a.hand_pose = hand_pose, a.Rg = Rg, a.link_T = link_T;
+  a.up_scene = up_scene;
+  a.Ns = (int)n_samples, a.L = n_links, a.D = pose_dim;
+  a.margin = margin, a.w_scene = w_scene;
+  a.accumulate = accumulate != 0;
+  a.e_scene = e_scene, a.wrench = link_wrench, a.gRt = gRt;
+  return a;
 }
 
 // row = blockIdx.x; `grid` is the grid this row reads (g.grid itself in the single-grid launch)
 __device__ __forceinline__ void gq_scene_row(const GqSceneArgs& g, const gqSceneGrid& grid) {
-  __shared__ float s_T[GQ_SC_MAX_LINKS * 12];
-  __shared__ float s_part[GQ_SC_WAVES][GQ_SC_MAX_LINKS][6];  // per wavefront and link: sum g_h (3), sum x_h x g_h (3), up = 1
-  __shared__ int s_seen[GQ_SC_WAVES][GQ_SC_MAX_LINKS];       // the wavefront met a sample of the link (active or not)
-  __shared__ float s_K[GQ_SC_WAVES][9];
-  __shared__ float s_e[GQ_SC_WAVES];
+  __shared__ float s_T[GQ_ROW_MAX_LINKS * 12];
+  __shared__ float s_part[GQ_ROW_WAVES][GQ_ROW_MAX_LINKS][6];  // per wavefront and link: sum g_h (3), sum x_h x g_h (3), up = 1
+  __shared__ int s_seen[GQ_ROW_WAVES][GQ_ROW_MAX_LINKS];       // the wavefront met a sample of the link (active or not)
+  __shared__ float s_K[GQ_ROW_WAVES][9];
+  __shared__ float s_e[GQ_ROW_WAVES];
   const int tid = threadIdx.x, lane = gq_lane(), wv = tid / GQ_WAVE;
   const size_t row = blockIdx.x;
   const int L = g.L;
-  for (int i = tid; i < L * 12; i += GQ_SC_WAVES * GQ_WAVE) s_T[i] = g.link_T[row * L * 12 + i];
+  for (int i = tid; i < L * 12; i += GQ_ROW_WAVES * GQ_WAVE) s_T[i] = g.link_T[row * L * 12 + i];
   const float* R = g.Rg + row * 9;
   const gq3 r1 = gq_mk(R[0], R[1], R[2]), r2 = gq_mk(R[3], R[4], R[5]), r3 = gq_mk(R[6], R[7], R[8]);
   const float* tp = g.hand_pose + row * g.D;
@@ -60,13 +67,10 @@ __device__ __forceinline__ void gq_scene_row(const GqSceneArgs& g, const gqScene
   float K[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   float e = 0.0f;
   int seen = 0;
-  for (int c = wv; c < chunks; c += GQ_SC_WAVES) {
+  for (int c = wv; c < chunks; c += GQ_ROW_WAVES) {
     float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     if ((unsigned)l < (unsigned)L) {
-      const float* T = s_T + l * 12;
-      const gq3 xh = gq_mk(fmaf(T[0], p.x, fmaf(T[1], p.y, fmaf(T[2], p.z, T[3]))),
-                           fmaf(T[4], p.x, fmaf(T[5], p.y, fmaf(T[6], p.z, T[7]))),
-                           fmaf(T[8], p.x, fmaf(T[9], p.y, fmaf(T[10], p.z, T[11]))));
+      const gq3 xh = gq_row_point(s_T + l * 12, p);
       const gq3 xw = gq_mk(gq_dot(r1, xh) + t.x, gq_dot(r2, xh) + t.y, gq_dot(r3, xh) + t.z);
       float phi = GQ_INF_F;
       gq3 gp = gq_mk(0, 0, 0);
@@ -86,34 +90,15 @@ __device__ __forceinline__ void gq_scene_row(const GqSceneArgs& g, const gqScene
     } else {
       l = -1;  // a link id outside the hand (refused by ops.SurfaceSamples): the sample is ignored
     }
-    for (int k = 0; k < L; ++k) {
-      const bool mine = l == k;
-      if (__ballot(mine) == 0ull) continue;  // wave-uniform
-      float r[6];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) r[q] = gq_dpp_sum(mine ? v[q] : 0.0f);
-      if (lane == k) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) acc[q] += r[q];
-        seen = 1;
-      }
-    }
-    s += GQ_SC_WAVES * GQ_WAVE;
+    GQ_ROW_LINK_SUMS(6, l, L, lane, v, acc, seen = 1)
+    s += GQ_ROW_WAVES * GQ_WAVE;
     l = -1;
-    if (c + GQ_SC_WAVES < chunks && s < g.Ns) {
+    if (c + GQ_ROW_WAVES < chunks && s < g.Ns) {
       l = g.sample_link[s];
       p = gq_mk(g.samples[(size_t)s * 3], g.samples[(size_t)s * 3 + 1], g.samples[(size_t)s * 3 + 2]);
     }
   }
-  e = gq_dpp_sum(e);
-  float Kw = 0.0f;  // lane q < 9 of the wavefront keeps the wavefront's K[q]
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    const float kq = gq_dpp_sum(K[q]);
-    if (lane == q) Kw = kq;
-  }
-  if (lane == 0) s_e[wv] = e;
-  if (lane < 9) s_K[wv][lane] = Kw;
+  GQ_ROW_WAVE_PARTIALS(e, K, lane, wv, s_e, s_K)
   if (lane < L) {
 #pragma unroll
     for (int q = 0; q < 6; ++q) s_part[wv][lane][q] = acc[q];
@@ -126,28 +111,13 @@ __device__ __forceinline__ void gq_scene_row(const GqSceneArgs& g, const gqScene
   float tot[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   if (lane < L) {
     int present = 0;
-    for (int w = 0; w < GQ_SC_WAVES; ++w) {
-#pragma unroll
-      for (int q = 0; q < 6; ++q) tot[q] += s_part[w][lane][q];
-      present |= s_seen[w][lane];
-    }
+    GQ_ROW_FOLD(6, s_part, s_seen, lane, tot, present)
     if (g.wrench && (present || !g.accumulate)) {  // links without samples: zero (overwrite) or left alone (accumulate)
       float* w6 = g.wrench + (row * L + lane) * 6;
 #pragma unroll
-      for (int q = 0; q < 6; ++q) gq_sc_store(w6 + q, up * tot[q], g.accumulate);
+      for (int q = 0; q < 6; ++q) gq_row_store(w6 + q, up * tot[q], g.accumulate);
     }
   }
-  // row sums over the links (lanes >= L hold zeros)
-  const float Fx = gq_dpp_sum(tot[0]), Fy = gq_dpp_sum(tot[1]), Fz = gq_dpp_sum(tot[2]);
-  if (g.gRt && lane < 12) {
-    // lanes 0..2: gsum = -sum g_h; lanes 3..11: K, row-major, folded over the wavefronts in wavefront order
-    float val = lane == 0 ? -Fx : (lane == 1 ? -Fy : -Fz);
-    if (lane >= 3) {
-      val = 0.0f;
-      for (int w = 0; w < GQ_SC_WAVES; ++w) val += s_K[w][lane - 3];
-    }
-    gq_sc_store(g.gRt + row * 12 + lane, up * val, g.accumulate);
-  }
-  if (lane == 0 && g.e_scene)
-    g.e_scene[row] = ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3])) + ((s_e[4] + s_e[5]) + (s_e[6] + s_e[7]));
+  GQ_ROW_GRT(g.gRt, row, tot, s_K, lane, up, g.accumulate)
+  if (lane == 0 && g.e_scene) g.e_scene[row] = gq_row_energy(s_e);
 }

@@ -8,7 +8,7 @@
 // No atomics, no block waits for another, the loops are bounded by K and batch_each, nothing is allocated, uploaded or read
 // back: graph-capturable and bitwise reproducible.  gq_grasp_distance_kernel gives the whole matrix through the same function.
 #include "common.h"
-#include "scene_row_dev.h"  // GQ_SC_MAX_LINKS: the link limit of the surface samples
+#include "sample_row_dev.h"  // GQ_ROW_MAX_LINKS: the link limit of the surface samples
 #include "select_dev.h"
 
 #define GQ_GS_THREADS 256
@@ -62,8 +62,8 @@ __device__ __forceinline__ void gq_gs_block_min(unsigned long long best, unsigne
 }
 
 __global__ __launch_bounds__(GQ_GS_THREADS) void gq_grasp_select_kernel(GqSelectArgs g) {
-  __shared__ float s_W[GQ_SC_MAX_LINKS * 12];
-  __shared__ float s_mom[GQ_SC_MAX_LINKS * GQ_GS_MOM];
+  __shared__ float s_W[GQ_ROW_MAX_LINKS * 12];
+  __shared__ float s_mom[GQ_ROW_MAX_LINKS * GQ_GS_MOM];
   __shared__ unsigned long long s_key[GQ_GS_WAVES];
   __shared__ unsigned long long s_best;
   __shared__ int s_cnt[GQ_GS_WAVES];
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(GQ_GS_THREADS) void gq_grasp_select_kernel(GqSelect
 
 // blockIdx.x: the global row i, staged in LDS; blockIdx.y, thread: the row j of the same object
 __global__ __launch_bounds__(GQ_GS_THREADS) void gq_grasp_distance_kernel(GqSelectArgs g) {
-  __shared__ float s_W[GQ_SC_MAX_LINKS * 12];
-  __shared__ float s_mom[GQ_SC_MAX_LINKS * GQ_GS_MOM];
+  __shared__ float s_W[GQ_ROW_MAX_LINKS * 12];
+  __shared__ float s_mom[GQ_ROW_MAX_LINKS * GQ_GS_MOM];
   const int tid = threadIdx.x, L = g.L, be = g.be;
   const size_t i = blockIdx.x;
   for (int k = tid; k < L * 12; k += GQ_GS_THREADS) s_W[k] = g.W[i * L * 12 + k];
@@ -124,7 +124,7 @@ static int gq_grasp_common_check(const char* who, const float* hand_pose, int po
   GQ_REQUIRE(link_moments, "%s: link_moments is NULL", who);
   GQ_REQUIRE(workspace, "%s: workspace is NULL", who);
   GQ_REQUIRE(pose_dim >= 3, "%s: pose_dim must be >= 3, got %d", who, pose_dim);
-  GQ_REQUIRE(n_links > 0 && n_links <= GQ_SC_MAX_LINKS, "%s: n_links must be in 1..%d, got %d", who, GQ_SC_MAX_LINKS, n_links);
+  GQ_REQUIRE(n_links > 0 && n_links <= GQ_ROW_MAX_LINKS, "%s: n_links must be in 1..%d, got %d", who, GQ_ROW_MAX_LINKS, n_links);
   GQ_REQUIRE(n_samples > 0, "%s: n_samples must be > 0, got %lld", who, (long long)n_samples);
   GQ_REQUIRE(batch_each > 0 && batch_each <= max_each, "%s: batch_each must be in 1..%lld, got %lld", who, (long long)max_each,
              (long long)batch_each);

@@ -19,10 +19,7 @@
 // eight wavefronts' partial sums are then folded in wavefront order.  No atomics: the order of every sum depends only on
 // the order of the samples, so results are bitwise reproducible run to run.  The samples may come in any order (the sums,
 // and so the last bits, follow it); sorted by link a chunk meets two or three links instead of all of them.
-#include "common.h"
-
-#define GQ_TT_MAX_LINKS 64  // lane l of a wavefront owns link l
-#define GQ_TT_WAVES 8  // 512 default samples: one 64-sample chunk per wavefront
+#include "sample_row_dev.h"  // the row frame the four hand-surface terms share
 
 struct GqTabletopArgs {
   const float* samples;        // (Ns,3) link frame
@@ -43,22 +40,15 @@ struct GqTabletopArgs {
   float* g_R;      // (B,9) or null
 };
 
-// accumulate: a plain rounded add of the finished value (no contraction with the product that made it), so that adding to
-// a buffer gives the bits of buffer + (the overwriting launch's value)
-__device__ __forceinline__ void gq_tt_store(float* p, float v, int accumulate) {
-#pragma clang fp contract(off)
-  *p = accumulate ? *p + v : v;
-}
-
-__global__ __launch_bounds__(GQ_TT_WAVES * GQ_WAVE) void gq_tabletop_kernel(const GqTabletopArgs g) {
-  __shared__ float s_T[GQ_TT_MAX_LINKS * 12];
-  __shared__ float s_part[GQ_TT_WAVES][GQ_TT_MAX_LINKS][4];  // per wavefront and link: S_l (3), n_l
-  __shared__ int s_seen[GQ_TT_WAVES][GQ_TT_MAX_LINKS];       // the wavefront met a sample of the link (on either side)
-  __shared__ float s_e[GQ_TT_WAVES];
+__global__ __launch_bounds__(GQ_ROW_WAVES * GQ_WAVE) void gq_tabletop_kernel(const GqTabletopArgs g) {
+  __shared__ float s_T[GQ_ROW_MAX_LINKS * 12];
+  __shared__ float s_part[GQ_ROW_WAVES][GQ_ROW_MAX_LINKS][4];  // per wavefront and link: S_l (3), n_l
+  __shared__ int s_seen[GQ_ROW_WAVES][GQ_ROW_MAX_LINKS];       // the wavefront met a sample of the link (on either side)
+  __shared__ float s_e[GQ_ROW_WAVES];
   const int tid = threadIdx.x, lane = gq_lane(), wv = tid / GQ_WAVE;
   const size_t row = blockIdx.x;
   const int L = g.L;
-  for (int i = tid; i < L * 12; i += GQ_TT_WAVES * GQ_WAVE) s_T[i] = g.link_T[row * L * 12 + i];
+  for (int i = tid; i < L * 12; i += GQ_ROW_WAVES * GQ_WAVE) s_T[i] = g.link_T[row * L * 12 + i];
   const float* R = g.Rg + row * 9;
   const gq3 r3 = gq_mk(R[6], R[7], R[8]);  // x_w.z = r3 . x_h + t.z
   const float tz = g.hand_pose[row * g.D + 2];
@@ -75,13 +65,10 @@ __global__ __launch_bounds__(GQ_TT_WAVES * GQ_WAVE) void gq_tabletop_kernel(cons
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   float e = 0.0f;
   int seen = 0;
-  for (int c = wv; c < chunks; c += GQ_TT_WAVES) {
+  for (int c = wv; c < chunks; c += GQ_ROW_WAVES) {
     float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if ((unsigned)l < (unsigned)L) {
-      const float* T = s_T + l * 12;
-      const gq3 xh = gq_mk(fmaf(T[0], p.x, fmaf(T[1], p.y, fmaf(T[2], p.z, T[3]))),
-                           fmaf(T[4], p.x, fmaf(T[5], p.y, fmaf(T[6], p.z, T[7]))),
-                           fmaf(T[8], p.x, fmaf(T[9], p.y, fmaf(T[10], p.z, T[11]))));
+      const gq3 xh = gq_row_point(s_T + l * 12, p);
       const float z = gq_dot(r3, xh) + tz;
       if (!(z >= g.table_z)) {  // a NaN height counts as below: E_wall of the row is NaN, as in the reference
         v[0] = xh.x, v[1] = xh.y, v[2] = xh.z, v[3] = 1.0f;
@@ -90,21 +77,10 @@ __global__ __launch_bounds__(GQ_TT_WAVES * GQ_WAVE) void gq_tabletop_kernel(cons
     } else {
       l = -1;  // a link id outside the hand (refused by ops.SurfaceSamples): the sample is ignored
     }
-    for (int k = 0; k < L; ++k) {
-      const bool mine = l == k;
-      if (__ballot(mine) == 0ull) continue;  // wave-uniform
-      float t[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) t[q] = gq_dpp_sum(mine ? v[q] : 0.0f);
-      if (lane == k) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] += t[q];
-        seen = 1;
-      }
-    }
-    s += GQ_TT_WAVES * GQ_WAVE;
+    GQ_ROW_LINK_SUMS(4, l, L, lane, v, acc, seen = 1)
+    s += GQ_ROW_WAVES * GQ_WAVE;
     l = -1;
-    if (c + GQ_TT_WAVES < chunks && s < g.Ns) {
+    if (c + GQ_ROW_WAVES < chunks && s < g.Ns) {
       l = g.sample_link[s];
       p = gq_mk(g.samples[(size_t)s * 3], g.samples[(size_t)s * 3 + 1], g.samples[(size_t)s * 3 + 2]);
     }
@@ -124,21 +100,17 @@ __global__ __launch_bounds__(GQ_TT_WAVES * GQ_WAVE) void gq_tabletop_kernel(cons
   float tot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (lane < L) {
     int present = 0;
-    for (int w = 0; w < GQ_TT_WAVES; ++w) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) tot[q] += s_part[w][lane][q];
-      present |= s_seen[w][lane];
-    }
+    GQ_ROW_FOLD(4, s_part, s_seen, lane, tot, present)
     if (g.wrench && (present || !g.accumulate)) {  // links without samples: zero (overwrite) or left alone (accumulate)
       const gq3 f = tot[3] * gh;
       const gq3 m = gq_cross(gq_mk(tot[0], tot[1], tot[2]), gh);
       float* w6 = g.wrench + (row * L + lane) * 6;
-      gq_tt_store(w6 + 0, f.x, g.accumulate);
-      gq_tt_store(w6 + 1, f.y, g.accumulate);
-      gq_tt_store(w6 + 2, f.z, g.accumulate);
-      gq_tt_store(w6 + 3, m.x, g.accumulate);
-      gq_tt_store(w6 + 4, m.y, g.accumulate);
-      gq_tt_store(w6 + 5, m.z, g.accumulate);
+      gq_row_store(w6 + 0, f.x, g.accumulate);
+      gq_row_store(w6 + 1, f.y, g.accumulate);
+      gq_row_store(w6 + 2, f.z, g.accumulate);
+      gq_row_store(w6 + 3, m.x, g.accumulate);
+      gq_row_store(w6 + 4, m.y, g.accumulate);
+      gq_row_store(w6 + 5, m.z, g.accumulate);
     }
   }
   // row sums over the links (lanes >= L hold zeros)
@@ -149,14 +121,14 @@ __global__ __launch_bounds__(GQ_TT_WAVES * GQ_WAVE) void gq_tabletop_kernel(cons
     const int a = lane < 3 ? lane : (lane - 3) / 3, j = (lane - 3) % 3;
     const float gha = a == 0 ? gh.x : (a == 1 ? gh.y : gh.z);
     const float Sj = j == 0 ? Sx : (j == 1 ? Sy : Sz);
-    gq_tt_store(g.gRt + row * 12 + lane, lane < 3 ? -N * gha : gha * Sj, g.accumulate);
+    gq_row_store(g.gRt + row * 12 + lane, lane < 3 ? -N * gha : gha * Sj, g.accumulate);
   }
   if (g.g_R && lane < 9) {  // E_prior = 1 + sum_j R[2][j] a_j
     const float aj = lane == 6 ? g.ax : (lane == 7 ? g.ay : g.az);
-    gq_tt_store(g.g_R + row * 9 + lane, lane >= 6 ? up_p * aj : 0.0f, g.accumulate);
+    gq_row_store(g.g_R + row * 9 + lane, lane >= 6 ? up_p * aj : 0.0f, g.accumulate);
   }
   if (lane == 0) {
-    if (g.e_wall) g.e_wall[row] = ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3])) + ((s_e[4] + s_e[5]) + (s_e[6] + s_e[7]));
+    if (g.e_wall) g.e_wall[row] = gq_row_energy(s_e);
     if (g.e_prior) g.e_prior[row] = 1.0f + fmaf(r3.x, g.ax, fmaf(r3.y, g.ay, r3.z * g.az));
   }
 }
@@ -171,7 +143,7 @@ __global__ __launch_bounds__(256) void gq_tabletop_total_kernel(float* __restric
 
 int gq_tabletop_check(int64_t batch, int n_links, int64_t n_samples) {
   GQ_REQUIRE(batch > 0 && batch <= 0x7fffffffll, "tabletop: batch must be in 1..2^31-1, got %lld", (long long)batch);
-  GQ_REQUIRE(n_links > 0 && n_links <= GQ_TT_MAX_LINKS, "tabletop: n_links must be in 1..%d, got %d", GQ_TT_MAX_LINKS, n_links);
+  GQ_REQUIRE(n_links > 0 && n_links <= GQ_ROW_MAX_LINKS, "tabletop: n_links must be in 1..%d, got %d", GQ_ROW_MAX_LINKS, n_links);
   GQ_REQUIRE(n_samples > 0 && n_samples <= (1ll << 24), "tabletop: n_samples must be in 1..2^24, got %lld", (long long)n_samples);
   return GQ_OK;
 }
@@ -191,7 +163,7 @@ int gq_tabletop_terms(const float* samples, const int32_t* sample_link, int64_t 
   a.table_z = table_z, a.w_wall = w_wall, a.w_prior = w_prior;
   a.accumulate = accumulate != 0;
   a.e_wall = e_wall, a.e_prior = e_prior, a.wrench = link_wrench, a.gRt = gRt, a.g_R = g_R;
-  hipLaunchKernelGGL(gq_tabletop_kernel, dim3((unsigned)batch), dim3(GQ_TT_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(gq_tabletop_kernel, dim3((unsigned)batch), dim3(GQ_ROW_WAVES * GQ_WAVE), 0, (hipStream_t)stream, a);
   GQ_LAUNCH_CHECK();
   return GQ_OK;
 }

@@ -1170,13 +1170,24 @@ def _axis3(grasp_axis) -> List[float]:
     return [float(x) for x in a]
 
 
+def _axis_c(axis):
+    """The float[3] a launch reads its axis from: a ready ctypes array as it is (the stepper builds its own once), else one
+    made of the sequence."""
+    return axis if isinstance(axis, ctypes.Array) else (ctypes.c_float * 3)(*(float(a) for a in axis))
+
+
+def _dev(t, dtype=torch.float32):
+    """A launch's device pointer: of a tensor, checked at every call (``_C.ptr``); or the pointer a caller made with ``_C.f32`` /
+    ``_C.i32`` of a buffer that stays where it is (the stepper converts its own buffers once), passed on as it is; None is NULL."""
+    return t if t is None or type(t) is ctypes.c_void_p else _C.ptr(t, dtype)
+
+
 def _tabletop_call(hp, points, link, n_links, Rg, LT, axis, table_z, up_wall, w_wall, up_prior, w_prior, e_wall, e_prior,
                    accumulate, wrench, gRt, gR, st=None):
-    ax = (ctypes.c_float * 3)(*axis)
-    _C.call("gq_tabletop_terms", _C.f32(points), _C.i32(link), ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp),
-            hp.shape[1], _C.f32(Rg), _C.f32(LT), ctypes.c_int64(hp.shape[0]), ctypes.cast(ax, ctypes.c_void_p), float(table_z),
-            _C.f32(up_wall), float(w_wall), _C.f32(up_prior), float(w_prior), _C.f32(e_wall), _C.f32(e_prior),
-            int(accumulate), _C.f32(wrench), _C.f32(gRt), _C.f32(gR), _C.stream_ptr() if st is None else st)
+    p, (B, D) = _dev, hp.shape  # sizes as plain ints, the axis as its array: the prototypes convert them
+    _C.call("gq_tabletop_terms", _C.f32(points), p(link, torch.int32), points.shape[0], int(n_links), _C.f32(hp), D, p(Rg), p(LT),
+            B, _axis_c(axis), float(table_z), p(up_wall), float(w_wall), p(up_prior), float(w_prior), p(e_wall), p(e_prior),
+            int(accumulate), p(wrench), p(gRt), p(gR), _C.stream_ptr() if st is None else st)
 
 
 @_custom_op("graspqp_amd::tabletop_terms", mutates_args=(), device_types="cuda")
@@ -1670,36 +1681,23 @@ def keep_label(depth, labels, label):
 
 
 def _scene_call(grid, margin, hp, points, link, n_links, Rg, LT, up_scene, w_scene, e_scene, accumulate, wrench, gRt, st=None):
-    if isinstance(grid, _C.ClutterGrids):  # a stack: row b reads grid b // (B / G)
-        B = hp.shape[0]
-        _C.call("gq_clutter_terms", ctypes.byref(grid), B // max(grid.n_grids, 1), float(margin), _C.f32(points), _C.i32(link),
-                ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT), ctypes.c_int64(B),
-                _C.f32(up_scene), float(w_scene), _C.f32(e_scene), int(accumulate), _C.f32(wrench), _C.f32(gRt),
-                _C.stream_ptr() if st is None else st)
+    p, (B, D) = _dev, hp.shape
+    entry, rows = "gq_scene_terms", ()
+    if isinstance(grid, _C.ClutterGrids):  # a stack: rows_per_grid follows the struct, row b reads grid b // (B / G)
+        entry, rows = "gq_clutter_terms", (B // max(grid.n_grids, 1),)
+    _C.call(entry, ctypes.byref(grid), *rows, float(margin), _C.f32(points), p(link, torch.int32), points.shape[0], int(n_links),
+            _C.f32(hp), D, p(Rg), p(LT), B, p(up_scene), float(w_scene), p(e_scene), int(accumulate), p(wrench), p(gRt),
+            _C.stream_ptr() if st is None else st)
+
+
+def _scene_query_call(grid, flat, phi, grad, inside):
+    N = flat.shape[0]
+    if isinstance(grid, _C.ClutterGrids):  # a stack: point i reads grid i // (N / G)
+        _C.call("gq_clutter_query", ctypes.byref(grid), _C.f32(flat), ctypes.c_int64(N), ctypes.c_int64(N // max(grid.n_grids, 1)),
+                _C.f32(phi), _C.f32(grad), _C.u8(inside), _C.stream_ptr())
         return
-    _C.call("gq_scene_terms", ctypes.byref(grid), float(margin), _C.f32(points), _C.i32(link), ctypes.c_int64(points.shape[0]),
-            int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT), ctypes.c_int64(hp.shape[0]), _C.f32(up_scene),
-            float(w_scene), _C.f32(e_scene), int(accumulate), _C.f32(wrench), _C.f32(gRt), _C.stream_ptr() if st is None else st)
-
-
-@_custom_op("graspqp_amd::scene_distance", mutates_args=(), device_types="cuda")
-def _scene_distance_op(points: Tensor, values: Tensor, origin: List[float], voxel: float) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (phi (...), grad phi (...,3), inside (...) uint8) of the grid at world points (...,3); outside the volume
-    phi = +inf, grad = 0, inside = 0."""
-    pts, v = _c(points), _c(values)
-    flat = pts.reshape(-1, 3)
-    N, dev = flat.shape[0], pts.device
-    phi, grad, inside = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
-    grid = _scene_grid(v, origin, voxel)
     _C.call("gq_scene_query", ctypes.byref(grid), _C.f32(flat), ctypes.c_int64(N), _C.f32(phi), _C.f32(grad), _C.u8(inside),
             _C.stream_ptr())
-    return phi.reshape(pts.shape[:-1]), grad.reshape(pts.shape), inside.reshape(pts.shape[:-1])
-
-
-@_scene_distance_op.register_fake
-def _(points, values, origin, voxel):
-    return (points.new_empty(points.shape[:-1]), points.new_empty(points.shape),
-            points.new_empty(points.shape[:-1], dtype=torch.uint8))
 
 
 def _scene_distance_setup(ctx, inputs, output):
@@ -1710,9 +1708,6 @@ def _scene_distance_setup(ctx, inputs, output):
 def _scene_distance_bwd(ctx, g_phi, g_grad, g_inside):
     (grad,) = ctx.saved_tensors
     return grad * g_phi.unsqueeze(-1), None, None, None
-
-
-torch.library.register_autograd("graspqp_amd::scene_distance", _scene_distance_bwd, setup_context=_scene_distance_setup)
 
 
 def scene_distance(points, scene: SceneSDF):
@@ -1728,41 +1723,6 @@ def scene_distance(points, scene: SceneSDF):
         scene.rows_per_grid(points.shape[0], "the points' leading dimension")
         return _Eager.scene_distance_set(points, scene.values, list(scene.origin), scene.voxel)[0]
     return _Eager.scene_distance(points, scene.values, list(scene.origin), scene.voxel)[0]
-
-
-@_custom_op("graspqp_amd::scene_terms", mutates_args=(), device_types="cuda")
-def _scene_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-              origin: List[float], voxel: float, margin: float) -> Tensor:
-    """-> E_scene (B), unweighted: sum over the hand's surface samples of max(margin - phi, 0).  The kinematic state (Rg,
-    link_T) is the one of ``hand_pose``, passed in detached, as for hand_pen."""
-    hp, v = _c(hand_pose), _c(values)
-    e = torch.empty(hp.shape[0], device=hp.device)
-    _scene_call(_scene_grid(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT), None, 0.0,
-                e, 0, None, None)
-    return e
-
-
-@_scene_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin):
-    return hand_pose.new_empty(hand_pose.shape[0])
-
-
-@_custom_op("graspqp_amd::scene_terms_backward", mutates_args=(), device_types="cuda")
-def _scene_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-                  origin: List[float], voxel: float, margin: float, g_scene: Tensor) -> Tuple[Tensor, Tensor]:
-    """Upstream row gradients (B) on E_scene -> (link wrench (B,L,6), gRt (B,12)) for fk_backward."""
-    hp, v = _c(hand_pose), _c(values)
-    B, dev = hp.shape[0], hp.device
-    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
-    _scene_call(_scene_grid(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT),
-                _c(g_scene), 0.0, None, 0, wrench, gRt)
-    return wrench, gRt
-
-
-@_scene_bwd_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin, g_scene):
-    B = hand_pose.shape[0]
-    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
 
 
 class _SceneTerms(torch.autograd.Function):
@@ -1809,7 +1769,7 @@ def scene_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, L
 def approach_check(scene: SceneSDF, batch, n_links, n_samples, distance, stations, grasp_axis):
     """gq_approach_check (host only) of the grid, a launch's shapes and the corridor; raises ValueError with the library's
     message."""
-    ax = (ctypes.c_float * 3)(*(float(a) for a in grasp_axis))
+    ax = _axis_c(grasp_axis)
     if isinstance(scene, SceneSDFSet):  # the stack's own check, then the corridor's on one of its grids
         scene.check(batch, scene.rows_per_grid(int(batch)), n_links, n_samples)
         scene = scene.scene(0)
@@ -1822,56 +1782,109 @@ def approach_check(scene: SceneSDF, batch, n_links, n_samples, distance, station
 
 def _approach_call(grid, margin, distance, stations, hp, points, link, n_links, Rg, LT, axis, up_approach, w_approach, e_approach,
                    accumulate, wrench, gRt, st=None):
-    ax = (ctypes.c_float * 3)(*(float(a) for a in axis))
-    if isinstance(grid, _C.ClutterGrids):  # a stack: row b reads grid b // (B / G)
-        B = hp.shape[0]
-        _C.call("gq_clutter_corridor_terms", ctypes.byref(grid), B // max(grid.n_grids, 1), float(margin), float(distance),
-                int(stations), _C.f32(points), _C.i32(link), ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp), hp.shape[1],
-                _C.f32(Rg), _C.f32(LT), ctypes.c_int64(B), ctypes.cast(ax, ctypes.c_void_p), _C.f32(up_approach),
-                float(w_approach), _C.f32(e_approach), int(accumulate), _C.f32(wrench), _C.f32(gRt),
-                _C.stream_ptr() if st is None else st)
-        return
-    _C.call("gq_approach_terms", ctypes.byref(grid), float(margin), float(distance), int(stations), _C.f32(points), _C.i32(link),
-            ctypes.c_int64(points.shape[0]), int(n_links), _C.f32(hp), hp.shape[1], _C.f32(Rg), _C.f32(LT),
-            ctypes.c_int64(hp.shape[0]), ctypes.cast(ax, ctypes.c_void_p), _C.f32(up_approach), float(w_approach),
-            _C.f32(e_approach), int(accumulate), _C.f32(wrench), _C.f32(gRt), _C.stream_ptr() if st is None else st)
+    p, (B, D) = _dev, hp.shape
+    entry, rows = "gq_approach_terms", ()
+    if isinstance(grid, _C.ClutterGrids):  # a stack: rows_per_grid follows the struct, row b reads grid b // (B / G)
+        entry, rows = "gq_clutter_corridor_terms", (B // max(grid.n_grids, 1),)
+    _C.call(entry, ctypes.byref(grid), *rows, float(margin), float(distance), int(stations), _C.f32(points), p(link, torch.int32),
+            points.shape[0], int(n_links), _C.f32(hp), D, p(Rg), p(LT), B, _axis_c(axis), p(up_approach), float(w_approach),
+            p(e_approach), int(accumulate), p(wrench), p(gRt), _C.stream_ptr() if st is None else st)
 
 
-@_custom_op("graspqp_amd::approach_terms", mutates_args=(), device_types="cuda")
-def _approach_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-                 origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int,
-                 margin: float) -> Tensor:
-    """-> E_approach (B), unweighted: the mean over the stations d_k = distance k / stations of the hinge sum of the hand's
-    surface samples moved back by d_k along grasp_axis.  The kinematic state (Rg, link_T) is the one of ``hand_pose``."""
-    hp, v = _c(hand_pose), _c(values)
-    e = torch.empty(hp.shape[0], device=hp.device)
-    _approach_call(_scene_grid(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
-                   _c(Rg), _c(LT), grasp_axis, None, 0.0, e, 0, None, None)
-    return e
+def _grid_ops(sfx, mk_grid):
+    """The registered ops that read a signed-distance grid, for one kind of grid: ``mk_grid`` = _scene_grid and ``sfx`` = "" for a
+    single grid, ``values`` (nx,ny,nz); _clutter_grids and "_set" for a stack of G grids, one per object (csrc/clutter.hip): the
+    stack crosses the dispatcher as ``values`` (G,nx,ny,nz), and row b of B reads grid b // (B / G).  The two kinds share the
+    schemas, the bodies and the fakes; the launches are picked by the grid struct (_scene_query_call, _scene_call,
+    _approach_call).  -> the five op definitions."""
+
+    @_custom_op(f"graspqp_amd::scene_distance{sfx}", mutates_args=(), device_types="cuda")
+    def distance_op(points: Tensor, values: Tensor, origin: List[float], voxel: float) -> Tuple[Tensor, Tensor, Tensor]:
+        """-> (phi (...), grad phi (...,3), inside (...) uint8) of the grid at world points (...,3); outside the volume
+        phi = +inf, grad = 0, inside = 0.  A stack takes points (B,...,3), B divisible by G."""
+        pts, v = _c(points), _c(values)
+        flat = pts.reshape(-1, 3)
+        N, dev = flat.shape[0], pts.device
+        phi, grad, inside = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
+        _scene_query_call(mk_grid(v, origin, voxel), flat, phi, grad, inside)
+        return phi.reshape(pts.shape[:-1]), grad.reshape(pts.shape), inside.reshape(pts.shape[:-1])
+
+    @distance_op.register_fake
+    def _(points, values, origin, voxel):
+        return (points.new_empty(points.shape[:-1]), points.new_empty(points.shape),
+                points.new_empty(points.shape[:-1], dtype=torch.uint8))
+
+    torch.library.register_autograd(f"graspqp_amd::scene_distance{sfx}", _scene_distance_bwd, setup_context=_scene_distance_setup)
+
+    @_custom_op(f"graspqp_amd::scene_terms{sfx}", mutates_args=(), device_types="cuda")
+    def scene_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                 origin: List[float], voxel: float, margin: float) -> Tensor:
+        """-> E_scene (B), unweighted: sum over the hand's surface samples of max(margin - phi, 0).  The kinematic state (Rg,
+        link_T) is the one of ``hand_pose``, passed in detached, as for hand_pen."""
+        hp, v = _c(hand_pose), _c(values)
+        e = torch.empty(hp.shape[0], device=hp.device)
+        _scene_call(mk_grid(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT), None, 0.0,
+                    e, 0, None, None)
+        return e
+
+    @scene_op.register_fake
+    def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin):
+        return hand_pose.new_empty(hand_pose.shape[0])
+
+    @_custom_op(f"graspqp_amd::scene_terms{sfx}_backward", mutates_args=(), device_types="cuda")
+    def scene_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                     origin: List[float], voxel: float, margin: float, g_scene: Tensor) -> Tuple[Tensor, Tensor]:
+        """Upstream row gradients (B) on E_scene -> (link wrench (B,L,6), gRt (B,12)) for fk_backward."""
+        hp, v = _c(hand_pose), _c(values)
+        B, dev = hp.shape[0], hp.device
+        wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
+        _scene_call(mk_grid(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT),
+                    _c(g_scene), 0.0, None, 0, wrench, gRt)
+        return wrench, gRt
+
+    @scene_bwd_op.register_fake
+    def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin, g_scene):
+        B = hand_pose.shape[0]
+        return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+
+    @_custom_op(f"graspqp_amd::approach_terms{sfx}", mutates_args=(), device_types="cuda")
+    def approach_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                    origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int,
+                    margin: float) -> Tensor:
+        """-> E_approach (B), unweighted: the mean over the stations d_k = distance k / stations of the hinge sum of the hand's
+        surface samples moved back by d_k along grasp_axis.  The kinematic state (Rg, link_T) is the one of ``hand_pose``."""
+        hp, v = _c(hand_pose), _c(values)
+        e = torch.empty(hp.shape[0], device=hp.device)
+        _approach_call(mk_grid(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
+                       _c(Rg), _c(LT), grasp_axis, None, 0.0, e, 0, None, None)
+        return e
+
+    @approach_op.register_fake
+    def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin):
+        return hand_pose.new_empty(hand_pose.shape[0])
+
+    @_custom_op(f"graspqp_amd::approach_terms{sfx}_backward", mutates_args=(), device_types="cuda")
+    def approach_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                        origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int, margin: float,
+                        g_approach: Tensor) -> Tuple[Tensor, Tensor]:
+        """Upstream row gradients (B) on E_approach -> (link wrench (B,L,6), gRt (B,12)) for fk_backward."""
+        hp, v = _c(hand_pose), _c(values)
+        B, dev = hp.shape[0], hp.device
+        wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
+        _approach_call(mk_grid(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
+                       _c(Rg), _c(LT), grasp_axis, _c(g_approach), 0.0, None, 0, wrench, gRt)
+        return wrench, gRt
+
+    @approach_bwd_op.register_fake
+    def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin, g_approach):
+        B = hand_pose.shape[0]
+        return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+
+    return distance_op, scene_op, scene_bwd_op, approach_op, approach_bwd_op
 
 
-@_approach_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin):
-    return hand_pose.new_empty(hand_pose.shape[0])
-
-
-@_custom_op("graspqp_amd::approach_terms_backward", mutates_args=(), device_types="cuda")
-def _approach_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-                     origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int, margin: float,
-                     g_approach: Tensor) -> Tuple[Tensor, Tensor]:
-    """Upstream row gradients (B) on E_approach -> (link wrench (B,L,6), gRt (B,12)) for fk_backward."""
-    hp, v = _c(hand_pose), _c(values)
-    B, dev = hp.shape[0], hp.device
-    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
-    _approach_call(_scene_grid(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
-                   _c(Rg), _c(LT), grasp_axis, _c(g_approach), 0.0, None, 0, wrench, gRt)
-    return wrench, gRt
-
-
-@_approach_bwd_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin, g_approach):
-    B = hand_pose.shape[0]
-    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+_scene_distance_op, _scene_op, _scene_bwd_op, _approach_op, _approach_bwd_op = _grid_ops("", _scene_grid)
+_scene_distance_set_op, _scene_set_op, _scene_set_bwd_op, _approach_set_op, _approach_set_bwd_op = _grid_ops("_set", _clutter_grids)
 
 
 class _ApproachTerms(torch.autograd.Function):
@@ -1918,102 +1931,6 @@ def approach_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg
 
 
 # ----------------------------------------------------------------------------------------------------------
-# clutter scenes: the same routes on a stack of grids, one per object (csrc/clutter.hip); the stack crosses the dispatcher as
-# (values (G,nx,ny,nz), origin, voxel), and row b reads grid b // (B / G)
-# ----------------------------------------------------------------------------------------------------------
-@_custom_op("graspqp_amd::scene_distance_set", mutates_args=(), device_types="cuda")
-def _scene_distance_set_op(points: Tensor, values: Tensor, origin: List[float], voxel: float) -> Tuple[Tensor, Tensor, Tensor]:
-    """scene_distance with points (B,...,3) and a stack of G grids, B divisible by G."""
-    pts, v = _c(points), _c(values)
-    flat = pts.reshape(-1, 3)
-    N, dev = flat.shape[0], pts.device
-    phi, grad, inside = torch.empty(N, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, dtype=torch.uint8, device=dev)
-    grids = _clutter_grids(v, origin, voxel)
-    _C.call("gq_clutter_query", ctypes.byref(grids), _C.f32(flat), ctypes.c_int64(N), ctypes.c_int64(N // max(grids.n_grids, 1)),
-            _C.f32(phi), _C.f32(grad), _C.u8(inside), _C.stream_ptr())
-    return phi.reshape(pts.shape[:-1]), grad.reshape(pts.shape), inside.reshape(pts.shape[:-1])
-
-
-@_scene_distance_set_op.register_fake
-def _(points, values, origin, voxel):
-    return (points.new_empty(points.shape[:-1]), points.new_empty(points.shape),
-            points.new_empty(points.shape[:-1], dtype=torch.uint8))
-
-
-torch.library.register_autograd("graspqp_amd::scene_distance_set", _scene_distance_bwd, setup_context=_scene_distance_setup)
-
-
-@_custom_op("graspqp_amd::scene_terms_set", mutates_args=(), device_types="cuda")
-def _scene_set_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-                  origin: List[float], voxel: float, margin: float) -> Tensor:
-    """scene_terms on a stack of grids (G,nx,ny,nz)."""
-    hp, v = _c(hand_pose), _c(values)
-    e = torch.empty(hp.shape[0], device=hp.device)
-    _scene_call(_clutter_grids(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT), None, 0.0,
-                e, 0, None, None)
-    return e
-
-
-@_scene_set_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin):
-    return hand_pose.new_empty(hand_pose.shape[0])
-
-
-@_custom_op("graspqp_amd::scene_terms_set_backward", mutates_args=(), device_types="cuda")
-def _scene_set_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-                      origin: List[float], voxel: float, margin: float, g_scene: Tensor) -> Tuple[Tensor, Tensor]:
-    """scene_terms_backward on a stack of grids."""
-    hp, v = _c(hand_pose), _c(values)
-    B, dev = hp.shape[0], hp.device
-    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
-    _scene_call(_clutter_grids(v, origin, voxel), margin, hp, _c(points), _c(link, torch.int32), n_links, _c(Rg), _c(LT),
-                _c(g_scene), 0.0, None, 0, wrench, gRt)
-    return wrench, gRt
-
-
-@_scene_set_bwd_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, margin, g_scene):
-    B = hand_pose.shape[0]
-    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
-
-
-@_custom_op("graspqp_amd::approach_terms_set", mutates_args=(), device_types="cuda")
-def _approach_set_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-                     origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int,
-                     margin: float) -> Tensor:
-    """approach_terms on a stack of grids (G,nx,ny,nz)."""
-    hp, v = _c(hand_pose), _c(values)
-    e = torch.empty(hp.shape[0], device=hp.device)
-    _approach_call(_clutter_grids(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
-                   _c(Rg), _c(LT), grasp_axis, None, 0.0, e, 0, None, None)
-    return e
-
-
-@_approach_set_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin):
-    return hand_pose.new_empty(hand_pose.shape[0])
-
-
-@_custom_op("graspqp_amd::approach_terms_set_backward", mutates_args=(), device_types="cuda")
-def _approach_set_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
-                         origin: List[float], voxel: float, grasp_axis: List[float], distance: float, stations: int, margin: float,
-                         g_approach: Tensor) -> Tuple[Tensor, Tensor]:
-    """approach_terms_backward on a stack of grids."""
-    hp, v = _c(hand_pose), _c(values)
-    B, dev = hp.shape[0], hp.device
-    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
-    _approach_call(_clutter_grids(v, origin, voxel), margin, distance, stations, hp, _c(points), _c(link, torch.int32), n_links,
-                   _c(Rg), _c(LT), grasp_axis, _c(g_approach), 0.0, None, 0, wrench, gRt)
-    return wrench, gRt
-
-
-@_approach_set_bwd_op.register_fake
-def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, distance, stations, margin, g_approach):
-    B = hand_pose.shape[0]
-    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
-
-
-# ----------------------------------------------------------------------------------------------------------
 # pre-grasp clearance: E_pregrasp, the OPENED hand along the approach corridor (csrc/pregrasp.hip).  One launch does the opened
 # kinematics, the stations and the joint gradient; a single grid crosses as the stack of one
 # ----------------------------------------------------------------------------------------------------------
@@ -2027,7 +1944,7 @@ def pregrasp_check(scene, batch, n_links, n_samples, distance, stations, grasp_a
     with the library's message."""
     if not isinstance(scene, (SceneSDF, SceneSDFSet)):
         raise ValueError("pregrasp: scene must be an ops.SceneSDF or an ops.SceneSDFSet")
-    ax = (ctypes.c_float * 3)(*(float(a) for a in grasp_axis))
+    ax = _axis_c(grasp_axis)
     G = scene.n_grids if isinstance(scene, SceneSDFSet) else 1
     if int(batch) % G:
         raise ValueError(f"pregrasp: batch = {batch} is not divisible by n_grids = {G}")
@@ -2049,13 +1966,11 @@ def default_open_joints(spec, device="cuda") -> Tensor:
 
 def _pregrasp_call(hand, grids, margin, distance, stations, opening, open_joints, hp, points, link, Rg, axis, up_pregrasp,
                    w_pregrasp, e_pregrasp, accumulate, g_theta, gRt, st=None):
-    ax = (ctypes.c_float * 3)(*(float(a) for a in axis))
-    B = hp.shape[0]
-    _C.call("gq_pregrasp_terms", hand.handle, ctypes.byref(grids), ctypes.c_int64(B // max(grids.n_grids, 1)), float(margin),
-            float(distance), int(stations), float(opening), _C.f32(open_joints), _C.f32(points), _C.i32(link),
-            ctypes.c_int64(points.shape[0]), _C.f32(hp), hp.shape[1], _C.f32(Rg), ctypes.c_int64(B),
-            ctypes.cast(ax, ctypes.c_void_p), _C.f32(up_pregrasp), float(w_pregrasp), _C.f32(e_pregrasp), int(accumulate),
-            _C.f32(g_theta), _C.f32(gRt), _C.stream_ptr() if st is None else st)
+    p, (B, D) = _dev, hp.shape
+    _C.call("gq_pregrasp_terms", hand.handle, ctypes.byref(grids), B // max(grids.n_grids, 1), float(margin), float(distance),
+            int(stations), float(opening), p(open_joints), _C.f32(points), p(link, torch.int32), points.shape[0], _C.f32(hp), D,
+            p(Rg), B, _axis_c(axis), p(up_pregrasp), float(w_pregrasp), p(e_pregrasp), int(accumulate), p(g_theta), p(gRt),
+            _C.stream_ptr() if st is None else st)
 
 
 @_custom_op("graspqp_amd::pregrasp_terms", mutates_args=(), device_types="cuda")

@@ -44,6 +44,7 @@ gq_cloud_forward, always a launch of its own; it fills the same four buffers, so
 from __future__ import annotations
 
 import ctypes
+import types
 
 import torch
 
@@ -81,7 +82,7 @@ def merge_weights(weights=None):
     """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term and of the pre-grasp term)
     updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and
     so does a negative weight of a tabletop term, of the scene term, of the approach term or of the pre-grasp term."""
-    switched = TABLETOP_TERMS + SCENE_TERMS + APPROACH_TERMS + PREGRASP_TERMS
+    switched = TABLETOP_TERMS + OBSTACLE_TERMS
     w = dict(DEFAULT_WEIGHTS)
     w.update({k: 0.0 for k in switched})
     for k, v in (weights or {}).items():
@@ -91,6 +92,17 @@ def merge_weights(weights=None):
         if k in switched and not w[k] >= 0.0:  # these terms are switched by their weight: > 0 on, 0 off
             raise ValueError(f"GraspStepper: weights[{k!r}] = {v!r} must be >= 0")
     return w
+
+
+def _check_corridor(name, margin, distance, stations, first):
+    """The corridor of the approach term (``name`` = "approach", stations ``first`` = 1..32) or of the pre-grasp term ("pregrasp",
+    0..32: d = 0 is a station there)."""
+    if not float(margin) >= 0.0:
+        raise ValueError(f"GraspStepper: {name}_margin = {margin!r} must be >= 0")
+    if not 0.0 < float(distance) < float("inf"):
+        raise ValueError(f"GraspStepper: {name}_distance = {distance!r} must be finite and > 0")
+    if int(stations) != stations or not first <= int(stations) <= 32:
+        raise ValueError(f"GraspStepper: {name}_stations = {stations!r} must be an integer in {first}..32")
 
 
 class GraspStepper:
@@ -157,12 +169,7 @@ class GraspStepper:
             if not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
                 raise ValueError('GraspStepper: weights["E_approach"] > 0 needs scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
             approach_margin = scene_margin if approach_margin is None else approach_margin
-            if not float(approach_margin) >= 0.0:
-                raise ValueError(f"GraspStepper: approach_margin = {approach_margin!r} must be >= 0")
-            if not 0.0 < float(approach_distance) < float("inf"):
-                raise ValueError(f"GraspStepper: approach_distance = {approach_distance!r} must be finite and > 0")
-            if int(approach_stations) != approach_stations or not 1 <= int(approach_stations) <= 32:
-                raise ValueError(f"GraspStepper: approach_stations = {approach_stations!r} must be an integer in 1..32")
+            _check_corridor("approach", approach_margin, approach_distance, approach_stations, 1)
         self.pregrasp_mode = self.w["E_pregrasp"] > 0
         if self.pregrasp_mode:
             pregrasp_scene = scene if pregrasp_scene is None else pregrasp_scene
@@ -175,12 +182,7 @@ class GraspStepper:
             pregrasp_margin = scene_margin if pregrasp_margin is None else pregrasp_margin
             pregrasp_distance = approach_distance if pregrasp_distance is None else pregrasp_distance
             pregrasp_stations = approach_stations if pregrasp_stations is None else pregrasp_stations
-            if not float(pregrasp_margin) >= 0.0:
-                raise ValueError(f"GraspStepper: pregrasp_margin = {pregrasp_margin!r} must be >= 0")
-            if not 0.0 < float(pregrasp_distance) < float("inf"):
-                raise ValueError(f"GraspStepper: pregrasp_distance = {pregrasp_distance!r} must be finite and > 0")
-            if int(pregrasp_stations) != pregrasp_stations or not 0 <= int(pregrasp_stations) <= 32:
-                raise ValueError(f"GraspStepper: pregrasp_stations = {pregrasp_stations!r} must be an integer in 0..32")
+            _check_corridor("pregrasp", pregrasp_margin, pregrasp_distance, pregrasp_stations, 0)
             if not 0.0 <= float(pregrasp_opening) <= 1.0:
                 raise ValueError(f"GraspStepper: pregrasp_opening = {pregrasp_opening!r} must be in [0, 1]")
         self.init_avoid_scene = bool(init_avoid_scene)
@@ -323,18 +325,30 @@ class GraspStepper:
 
                 surface_samples = mesh_utils.hand_surface_samples(hand.spec, int(n_surface_points))
             self.samples = ops.SurfaceSamples(hand, surface_samples[0], surface_samples[1], device=self.dev)
+            self._axis = ops._axis_c(hand.spec.grasp_axis)  # the float[3] every launch of these modes reads
+            # ... and the device pointers of the buffers they read and write, which stay where they are (as the descriptors above
+            # hold them): converted and checked here, once, not at every launch
+            self._ptr = types.SimpleNamespace(link=_C.i32(self.samples.link), Rg=_C.f32(self.Rg), LT=_C.f32(self.link_T),
+                                              wrench=_C.f32(self.wrench), gRt=_C.f32(self.gRt), g_theta=_C.f32(self.g_theta),
+                                              e=[_C.f32(self.terms_new[i]) for i in range(nT)])
+        # the switched-on obstacle terms in launch order: (row of terms_new, weight, evaluate)
+        self._obstacle_terms = []
+        if self.scene_mode or self.approach_mode:  # the grid struct of both launches: the stack (clutter) or the one grid
+            self._scene_grid = scene.grid_set if self.clutter else scene.grid
         if self.scene_mode:
             self._i_scene = self.term_names.index("E_scene")
+            self._obstacle_terms.append((self._i_scene, float(self.w["E_scene"]), self._eval_scene))
             scene.check(B, self.be, L, self.samples.Ns) if self.clutter else scene.check(B, L, self.samples.Ns)
         if self.approach_mode:
             self._i_approach = self.term_names.index("E_approach")
+            self._obstacle_terms.append((self._i_approach, float(self.w["E_approach"]), self._eval_approach))
             self.approach_distance, self.approach_stations = float(approach_distance), int(approach_stations)
             self.approach_margin = float(approach_margin)
-            self._approach_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
             ops.approach_check(scene, B, L, self.samples.Ns, self.approach_distance, self.approach_stations,
                                hand.spec.grasp_axis)
         if self.pregrasp_mode:
             self._i_pregrasp = nT - 1
+            self._obstacle_terms.append((self._i_pregrasp, float(self.w["E_pregrasp"]), self._eval_pregrasp))
             self.pregrasp_scene = pregrasp_scene
             self.pregrasp_distance, self.pregrasp_stations = float(pregrasp_distance), int(pregrasp_stations)
             self.pregrasp_margin, self.pregrasp_opening = float(pregrasp_margin), float(pregrasp_opening)
@@ -346,15 +360,15 @@ class GraspStepper:
                 raise ValueError(f"GraspStepper: pregrasp_joints must be ({self.J},), got {tuple(self.pregrasp_joints.shape)}")
             ops.pregrasp_check(pregrasp_scene, B, L, self.samples.Ns, self.pregrasp_distance, self.pregrasp_stations,
                                hand.spec.grasp_axis, self.pregrasp_opening)
+            self._ptr.joints = _C.f32(self.pregrasp_joints)
             # the stack view of the grid (a single grid is the stack of one): row b reads grid b // (B / n_grids)
             self._pregrasp_grids = ops._pregrasp_grids(pregrasp_scene.values, pregrasp_scene.origin, pregrasp_scene.voxel)
         if self.tabletop:
             self.g_R = f(B, 9)
             self.table_z = float(table_z)
-            self._grasp_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
             # d (w_prior E_prior) / d R = w_prior * grasp_axis in row 2 does not depend on the pose: set here, once; the launch
             # of every evaluation adds to wrench / gRt and is given no g_R
-            self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._grasp_axis), device=self.dev)
+            self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._axis), device=self.dev)
         self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
@@ -456,50 +470,32 @@ class GraspStepper:
     def _eval_tabletop(self, pose, st):
         """E_prior / E_wall -> terms_new[5:7]; the gradient of w_wall E_wall is added to the penetration branch's link
         wrenches and gRt (inputs of the FK backward, like the constant g_R of w_prior E_prior)."""
-        f32, sm = _C.f32, self.samples
-        _C.call("gq_tabletop_terms", f32(sm.points), _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D,
-                f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), ctypes.cast(self._grasp_axis, ctypes.c_void_p),
-                self.table_z, None, float(self.w["E_wall"]), None, float(self.w["E_prior"]), f32(self.terms_new[6]),
-                f32(self.terms_new[5]), 1, f32(self.wrench), f32(self.gRt), None, st)
+        p = self._ptr
+        ops._tabletop_call(pose, self.samples.points, p.link, self.L, p.Rg, p.LT, self._axis, self.table_z, None, self.w["E_wall"],
+                           None, self.w["E_prior"], p.e[6], p.e[5], 1, p.wrench, p.gRt, None, st)
 
     def _eval_scene(self, pose, st):
         """E_scene -> terms_new[-1]; the gradient of w_scene E_scene is added to the link wrenches and gRt that the FK
         backward reads."""
-        f32, sm = _C.f32, self.samples
-        if self.clutter:
-            _C.call("gq_clutter_terms", ctypes.byref(self.scene.grid_set), self.be, self.scene_margin, f32(sm.points),
-                    _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D, f32(self.Rg), f32(self.link_T),
-                    ctypes.c_int64(self.B), None, float(self.w["E_scene"]), f32(self.terms_new[self._i_scene]), 1,
-                    f32(self.wrench), f32(self.gRt), st)
-            return
-        _C.call("gq_scene_terms", ctypes.byref(self.scene.grid), self.scene_margin, f32(sm.points), _C.i32(sm.link),
-                ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D, f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), None,
-                float(self.w["E_scene"]), f32(self.terms_new[self._i_scene]), 1, f32(self.wrench), f32(self.gRt), st)
+        p = self._ptr
+        ops._scene_call(self._scene_grid, self.scene_margin, pose, self.samples.points, p.link, self.L, p.Rg, p.LT, None,
+                        self.w["E_scene"], p.e[self._i_scene], 1, p.wrench, p.gRt, st)
 
     def _eval_approach(self, pose, st):
         """E_approach -> terms_new[-1]; the gradient of w_approach E_approach is added to the link wrenches and gRt that the
         FK backward reads."""
-        f32, sm = _C.f32, self.samples
-        if self.clutter:
-            _C.call("gq_clutter_corridor_terms", ctypes.byref(self.scene.grid_set), self.be, self.approach_margin,
-                    self.approach_distance, self.approach_stations, f32(sm.points), _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L,
-                    f32(pose), self.D, f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B),
-                    ctypes.cast(self._approach_axis, ctypes.c_void_p), None, float(self.w["E_approach"]),
-                    f32(self.terms_new[self._i_approach]), 1, f32(self.wrench), f32(self.gRt), st)
-            return
-        _C.call("gq_approach_terms", ctypes.byref(self.scene.grid), self.approach_margin, self.approach_distance,
-                self.approach_stations, f32(sm.points), _C.i32(sm.link), ctypes.c_int64(sm.Ns), self.L, f32(pose), self.D,
-                f32(self.Rg), f32(self.link_T), ctypes.c_int64(self.B), ctypes.cast(self._approach_axis, ctypes.c_void_p), None,
-                float(self.w["E_approach"]), f32(self.terms_new[self._i_approach]), 1, f32(self.wrench), f32(self.gRt), st)
+        p = self._ptr
+        ops._approach_call(self._scene_grid, self.approach_margin, self.approach_distance, self.approach_stations, pose,
+                           self.samples.points, p.link, self.L, p.Rg, p.LT, self._axis, None, self.w["E_approach"],
+                           p.e[self._i_approach], 1, p.wrench, p.gRt, st)
 
     def _eval_pregrasp(self, pose, st):
         """E_pregrasp -> terms_new[-1]; the root-pose part of the gradient of w_pregrasp E_pregrasp is added to the gRt that the
         FK backward reads (the opened hand shares the closed hand's root pose), the joint part overwrites ``g_theta``."""
-        sm = self.samples
+        p = self._ptr
         ops._pregrasp_call(self.hand, self._pregrasp_grids, self.pregrasp_margin, self.pregrasp_distance, self.pregrasp_stations,
-                           self.pregrasp_opening, self.pregrasp_joints, pose, sm.points, sm.link, self.Rg,
-                           self.hand.spec.grasp_axis, None, float(self.w["E_pregrasp"]), self.terms_new[self._i_pregrasp], 1,
-                           self.g_theta, self.gRt, st)
+                           self.pregrasp_opening, p.joints, pose, self.samples.points, p.link, p.Rg, self._axis, None,
+                           self.w["E_pregrasp"], p.e[self._i_pregrasp], 1, p.g_theta, p.gRt, st)
 
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
@@ -547,25 +543,14 @@ class GraspStepper:
             main.wait_stream(sb)
         if self.tabletop:
             self._eval_tabletop(pose, st)
-        if self.scene_mode:
-            self._eval_scene(pose, st)
-        if self.approach_mode:
-            self._eval_approach(pose, st)
-        if self.pregrasp_mode:
-            self._eval_pregrasp(pose, st)
+        for _, _, evaluate in self._obstacle_terms:  # scene, approach, pre-grasp
+            evaluate(pose, st)
         self._eval_tail(pose, idx, st, loop)
         if self.tabletop:  # the FK backward's total holds the five terms
             _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
                     _C.f32(self.terms_new[6]), float(self.w["E_wall"]), ctypes.c_int64(self.B), st)
-        if self.scene_mode:
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_scene]), float(self.w["E_scene"]),
-                    ctypes.c_int64(self.B), st)
-        if self.approach_mode:  # the generic total += w e
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_approach]),
-                    float(self.w["E_approach"]), ctypes.c_int64(self.B), st)
-        if self.pregrasp_mode:
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_pregrasp]),
-                    float(self.w["E_pregrasp"]), ctypes.c_int64(self.B), st)
+        for i, w, _ in self._obstacle_terms:  # the generic total += w e
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[i]), w, ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):
         """Energy terms, total and d total / d pose at an arbitrary (pose, idx); returns clones."""

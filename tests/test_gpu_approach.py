@@ -165,6 +165,93 @@ def test_op_matches_the_oracle(gq, hand_name, Ns, B, K, D, kind, margin):
     _assert_matches(_op(gq, hand, samples, hp, _field(kind).scene(gq), spec.grasp_axis, D, K, margin), (ref["E"], ref["grad"]), tag)
 
 
+BIG_B, BIG_K, BIG_D, BIG_MARGIN = 3, 3, 0.08, 0.01  # more than 512 samples: 577 = 10 chunks, 1100 = 18
+
+
+def _tail_active(ref):
+    """Samples at indices >= 512 (a wavefront's later chunks) with an active station."""
+    return int(ref["active"][:, :, 512:].any(axis=1).sum())
+
+
+@functools.lru_cache(maxsize=None)
+def _big_samples(Ns):
+    pts, lnk = meshes.hand_surface_samples(get_hand_spec("allegro"), Ns)
+    assert len(pts) == Ns and (np.diff(lnk) >= 0).all()  # they come by link: the order of the launch
+    return pts, lnk
+
+
+def _big_guarded(pts, lnk):
+    """The seeded guard loop on the multilinear field for samples of one's own, with 5 active samples beyond index 511."""
+    spec = get_hand_spec("allegro")
+    for seed in range(100 * BIG_B + len(pts), 100 * BIG_B + len(pts) + 200):
+        hp = _pose(spec, BIG_B, seed)
+        ref = ao.e_approach(spec, pts, lnk, hp.double(), _field("multilinear"), BIG_MARGIN, BIG_D, BIG_K)
+        if _conditions(ref, BIG_MARGIN, len(pts), BIG_B, False) and _tail_active(ref) >= 5:
+            return hp, ref
+    raise AssertionError("no seeded pose passes the guards")
+
+
+@pytest.mark.parametrize("Ns", [577, 1100])
+def test_more_than_512_samples_match_the_oracle(gq, Ns):
+    """A wavefront's second and third trip through the chunk loop, K = 3.  The oracle has 195 samples at indices >= 512 with an
+    active station at Ns = 577 (every one of the 3 x 65) and 1183 at Ns = 1100; all station points lie inside the volume."""
+    spec, hand = get_hand_spec("allegro"), _hand("allegro")
+    pts, lnk = _big_samples(Ns)
+    samples = gq.ops.SurfaceSamples(hand, pts, lnk)
+    assert samples.Ns == Ns and np.array_equal(samples.link.cpu().numpy(), lnk)
+    hp, ref = _big_guarded(pts, lnk)
+    tag = f"allegro Ns={Ns} B={BIG_B} K={BIG_K} D={BIG_D} multilinear margin={BIG_MARGIN}"
+    _assert_guards(ref, BIG_MARGIN, tag, Ns, BIG_B, BIG_K, False)
+    print(f"[{tag}] samples at indices >= 512 with an active station: {_tail_active(ref)}")
+    assert _tail_active(ref) >= 5 and ref["inside"].all()
+    got = _op(gq, hand, samples, hp, _field("multilinear").scene(gq), spec.grasp_axis, BIG_D, BIG_K, BIG_MARGIN)
+    _assert_matches(got, (ref["E"], ref["grad"]), tag)
+
+
+def test_second_chunk_run_to_run_sample_order_and_a_link_without_samples(gq):
+    """Ns = 577 through the C entry: bitwise run to run; the samples by link against the same samples shuffled, within the
+    bounds of ``_assert_matches`` (the order of the samples moves the last bits only); a link without samples."""
+    spec, hand = get_hand_spec("allegro"), _hand("allegro")
+    (p1, l1), (p2, l2) = _big_samples(577), _big_samples(1100)
+    pts = np.concatenate([p1[l1 != 3], p2[l2 != 3]])[:577]  # 577 samples, none on link 3
+    lnk = np.concatenate([l1[l1 != 3], l2[l2 != 3]])[:577]
+    assert len(pts) == 577
+    scene = _field("multilinear").scene(gq)
+    hp, ref = _big_guarded(pts, lnk)
+    B, L = BIG_B, hand.L
+    hp = hp.cuda()
+    idx = torch.zeros(B, 1, dtype=torch.long, device="cuda")
+    Rg, LT, _, _, _, _ = gq.ops.fk_contacts(hp, idx, hand)
+
+    def run(p, l, accumulate=0, bufs=None):
+        p, l = torch.tensor(p).cuda(), torch.tensor(l.astype(np.int32)).cuda()
+        wrench, gRt = bufs or (torch.empty(B, L, 6, device="cuda"), torch.empty(B, 12, device="cuda"))
+        e = torch.empty(B, device="cuda")
+        gq.ops._approach_call(scene.grid, BIG_MARGIN, BIG_D, BIG_K, hp, p, l, L, Rg.contiguous(), LT.contiguous(), spec.grasp_axis,
+                              None, 1.5, e, accumulate, wrench, gRt)
+        torch.cuda.synchronize()
+        return wrench, gRt, e
+
+    order = np.argsort(lnk, kind="stable")
+    by_link, again = run(pts[order], lnk[order]), run(pts[order], lnk[order])
+    for a, b in zip(by_link, again):
+        assert torch.equal(a, b)
+    np.testing.assert_allclose(by_link[2].cpu().numpy(), ref["E"], rtol=1e-5, atol=1e-6)
+    perm = np.random.default_rng(577).permutation(577)
+    assert not (np.diff(lnk[perm]) >= 0).all()
+    shuffled = run(pts[perm], lnk[perm])
+    grad = lambda r: np.concatenate([r[0].cpu().numpy().reshape(B, -1), r[1].cpu().numpy()], 1)
+    _assert_matches((shuffled[2].cpu().numpy(), grad(shuffled)), (by_link[2].cpu().numpy(), grad(by_link)), "Ns=577 shuffled vs by link")
+    for r in (by_link, shuffled):
+        assert (r[0][:, 3] == 0).all() and r[0].abs().max() > 0  # the link without samples: zero wrench
+    gen = torch.Generator().manual_seed(1)
+    pre = [torch.randn(*s, generator=gen).cuda() for s in ((B, L, 6), (B, 12))]
+    acc = run(pts[order], lnk[order], 1, [p.clone() for p in pre])
+    for a, p, v in zip(acc[:2], pre, by_link[:2]):
+        assert torch.equal(a, p + v)
+    assert torch.equal(acc[0][:, 3], pre[0][:, 3])  # left alone
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 2. affine field: the closed form phi(x_w) - d_k n . (R a)
 # ---------------------------------------------------------------------------------------------------------------

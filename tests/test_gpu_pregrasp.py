@@ -140,6 +140,85 @@ def test_op_matches_the_oracle(gq, row):
         _assert_matches(got, (e.detach().cpu().numpy(), hpg.grad.cpu().numpy()), tag + " vs scene_terms + approach_terms", factor=2.0)
 
 
+BIG_B, BIG_K, BIG_OPENING, BIG_MARGIN = 3, 2, 0.5, 0.01  # more than 512 samples: 577 = 10 chunks, 1100 = 18
+
+
+def _tail_active(ref):
+    """Samples at indices >= 512 (a wavefront's later chunks) with an active station."""
+    return int(ref["active"][:, :, 512:].any(axis=1).sum())
+
+
+@functools.lru_cache(maxsize=None)
+def _big_samples(Ns):
+    pts, lnk = meshes.hand_surface_samples(get_hand_spec("allegro"), Ns)
+    assert len(pts) == Ns and (np.diff(lnk) >= 0).all()  # they come by link: the order of the launch
+    return pts, lnk
+
+
+def _big_guarded(pts, lnk):
+    """The seeded guard loop of ``pc.guarded`` on the multilinear field for samples of one's own, with 5 active samples beyond
+    index 511."""
+    spec = pc.spec_of("allegro")
+    for seed in range(100 * BIG_B + len(pts), 100 * BIG_B + len(pts) + 200):
+        hp = pc.pose(spec, BIG_B, seed)
+        ref = po.e_pregrasp(spec, pts, lnk, hp.double(), pc.open_joints(spec), BIG_OPENING, pc.field("multilinear"), BIG_MARGIN,
+                            pc.corridor(BIG_K), BIG_K)
+        if pc.conditions(ref, BIG_MARGIN, len(pts), BIG_B, False, BIG_OPENING) and _tail_active(ref) >= 5:
+            return hp, ref
+    raise AssertionError("no seeded pose passes the guards")
+
+
+@pytest.mark.parametrize("Ns", [577, 1100])
+def test_more_than_512_samples_match_the_oracle(gq, Ns):
+    """A wavefront's second and third trip through the chunk loop, K = 2 (three stations), opening 0.5.  The oracle has 195
+    samples at indices >= 512 with an active station at Ns = 577 (every one of the 3 x 65) and 1204 at Ns = 1100; all station points
+    lie inside the volume."""
+    spec, hand = pc.spec_of("allegro"), _hand("allegro")
+    pts, lnk = _big_samples(Ns)
+    samples = gq.ops.SurfaceSamples(hand, pts, lnk)
+    assert samples.Ns == Ns and np.array_equal(samples.link.cpu().numpy(), lnk)
+    hp, ref = _big_guarded(pts, lnk)
+    D = pc.corridor(BIG_K)
+    tag = f"allegro Ns={Ns} B={BIG_B} K={BIG_K} D={D} multilinear opening={BIG_OPENING} margin={BIG_MARGIN}"
+    pc.assert_guards(ref, BIG_MARGIN, tag, Ns, BIG_B, BIG_K, False, BIG_OPENING)
+    print(f"[{tag}] samples at indices >= 512 with an active station: {_tail_active(ref)}")
+    assert _tail_active(ref) >= 5 and ref["inside"].all()
+    got = _op(gq, hand, samples, hp, pc.field("multilinear").scene(gq), spec.grasp_axis, D, BIG_K, BIG_OPENING, BIG_MARGIN)
+    _assert_matches(got, (ref["E"], ref["grad"]), tag)
+
+
+def test_second_chunk_run_to_run_and_sample_order(gq):
+    """Ns = 577 through the C entry: bitwise run to run; the samples by link against the same samples shuffled, within the
+    bounds of ``_assert_matches`` (the order of the samples moves the last bits only)."""
+    spec, hand = pc.spec_of("allegro"), _hand("allegro")
+    pts, lnk = _big_samples(577)
+    hp, ref = _big_guarded(pts, lnk)
+    scene = pc.field("multilinear").scene(gq)
+    grids = gq.ops._pregrasp_grids(scene.values, scene.origin, scene.voxel)
+    B, D, q = BIG_B, pc.corridor(BIG_K), _q("allegro")
+    hp = hp.cuda()
+    Rg = gq.ops.fk_contacts(hp, torch.zeros(B, 1, dtype=torch.long, device="cuda"), hand)[0].contiguous()
+
+    def run(p, l):
+        p, l = torch.tensor(p).cuda(), torch.tensor(l.astype(np.int32)).cuda()
+        g_theta, gRt, e = torch.empty(B, spec.n_dofs, device="cuda"), torch.empty(B, 12, device="cuda"), torch.empty(B, device="cuda")
+        gq.ops._pregrasp_call(hand, grids, BIG_MARGIN, D, BIG_K, BIG_OPENING, q, hp, p, l, Rg, spec.grasp_axis, None, 1.5, e, 0,
+                              g_theta, gRt)
+        torch.cuda.synchronize()
+        return g_theta, gRt, e
+
+    by_link, again = run(pts, lnk), run(pts, lnk)
+    for a, b in zip(by_link, again):
+        assert torch.equal(a, b)
+    np.testing.assert_allclose(by_link[2].cpu().numpy(), ref["E"], rtol=1e-5, atol=1e-6)
+    assert by_link[0].abs().max() > 0 and by_link[1].abs().max() > 0
+    perm = np.random.default_rng(577).permutation(577)
+    assert not (np.diff(lnk[perm]) >= 0).all()
+    shuffled = run(pts[perm], lnk[perm])
+    grad = lambda r: np.concatenate([r[0].cpu().numpy(), r[1].cpu().numpy()], 1)
+    _assert_matches((shuffled[2].cpu().numpy(), grad(shuffled)), (by_link[2].cpu().numpy(), grad(by_link)), "Ns=577 shuffled vs by link")
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 2. the joint columns alone: the fused launch against the composed route of existing launches
 # ---------------------------------------------------------------------------------------------------------------

@@ -266,6 +266,88 @@ def test_op_shapes_match_the_oracle(gq, hand_name, Ns):
         _assert_matches(_op(gq, hand, samples, hp, scene, margin), (ref["E"], ref["grad"]), tag)
 
 
+BIG_B, BIG_MARGIN = 3, 0.01  # more than 512 samples: 577 = 10 chunks (wavefront 1's second chunk holds one sample), 1100 = 18
+
+
+@functools.lru_cache(maxsize=None)
+def _big_case(Ns):
+    """allegro, ``hand_surface_samples(spec, Ns)`` (they come by link, the order of the launch), B = 3 on the multilinear field; the
+    first pose of the seeded guard loop, and the oracle's results at it."""
+    spec = get_hand_spec("allegro")
+    pts, lnk = meshes.hand_surface_samples(spec, Ns)
+    assert len(pts) == Ns and (np.diff(lnk) >= 0).all()
+    F = _field("multilinear", (100, 96, 104), (-0.5, -0.48, -0.52), 0.01)
+    hp, ref = _guarded_pose(spec, BIG_B, pts, lnk, F, BIG_MARGIN, 100 * BIG_B + Ns, 5, cells=False)
+    return spec, pts, lnk, F, hp, ref
+
+
+@pytest.mark.parametrize("Ns", [577, 1100])
+def test_more_than_512_samples_match_the_oracle(gq, Ns):
+    """A wavefront's second and third trip through the chunk loop.  The oracle has 195 active samples at indices >= 512 at
+    Ns = 577 (every one of the 3 x 65) and 1189 at Ns = 1100; all samples lie inside the volume."""
+    spec, pts, lnk, F, hp, ref = _big_case(Ns)
+    hand = _hand("allegro")
+    samples = gq.ops.SurfaceSamples(hand, pts, lnk)
+    assert samples.Ns == Ns and np.array_equal(samples.link.cpu().numpy(), lnk)
+    tag = f"allegro Ns={Ns} B={BIG_B} multilinear"
+    tail = int(ref["active"][:, 512:].sum())
+    print(f"[{tag}] active samples at indices >= 512: {tail}")
+    assert tail >= 5 and ref["inside"].all()
+    assert so.guards(ref, BIG_MARGIN)[1] >= so.NEAR
+    _assert_matches(_op(gq, hand, samples, hp, F.scene(gq), BIG_MARGIN), (ref["E"], ref["grad"]), tag)
+
+
+def _big_without_link_3():
+    """577 samples of which none rides on link 3: the 577 of ``_big_case`` without that link's, topped up from the 1100."""
+    (_, p1, l1, _, _, _), (_, p2, l2, _, _, _) = _big_case(577), _big_case(1100)
+    k1, k2 = l1 != 3, l2 != 3
+    pts, lnk = np.concatenate([p1[k1], p2[k2]])[:577], np.concatenate([l1[k1], l2[k2]])[:577]
+    assert len(pts) == 577 and (lnk != 3).all()
+    return pts, lnk
+
+
+def test_second_chunk_run_to_run_sample_order_and_a_link_without_samples(gq):
+    """Ns = 577 through the C entry: bitwise run to run; the samples by link against the same samples shuffled, within the
+    bounds of ``_assert_matches`` (the order of the samples moves the last bits only); a link without samples."""
+    spec, hand = get_hand_spec("allegro"), _hand("allegro")
+    pts, lnk = _big_without_link_3()
+    F = _big_case(577)[3]
+    scene = F.scene(gq)
+    hp, ref = _guarded_pose(spec, BIG_B, pts, lnk, F, BIG_MARGIN, 100 * BIG_B + 577, 5, cells=False)
+    assert ref["active"][:, 512:].sum() >= 5
+    B, L = BIG_B, hand.L
+    hp = hp.cuda()
+    idx = torch.zeros(B, 1, dtype=torch.long, device="cuda")
+    Rg, LT, _, _, _, _ = gq.ops.fk_contacts(hp, idx, hand)
+
+    def run(p, l, accumulate=0, bufs=None):
+        p, l = torch.tensor(p).cuda(), torch.tensor(l.astype(np.int32)).cuda()
+        wrench, gRt = bufs or (torch.empty(B, L, 6, device="cuda"), torch.empty(B, 12, device="cuda"))
+        e = torch.empty(B, device="cuda")
+        gq.ops._scene_call(scene.grid, BIG_MARGIN, hp, p, l, L, Rg.contiguous(), LT.contiguous(), None, 1.5, e, accumulate, wrench, gRt)
+        torch.cuda.synchronize()
+        return wrench, gRt, e
+
+    order = np.argsort(lnk, kind="stable")
+    by_link, again = run(pts[order], lnk[order]), run(pts[order], lnk[order])
+    for a, b in zip(by_link, again):
+        assert torch.equal(a, b)
+    np.testing.assert_allclose(by_link[2].cpu().numpy(), ref["E"], rtol=1e-5, atol=1e-6)
+    perm = np.random.default_rng(577).permutation(577)
+    assert not (np.diff(lnk[perm]) >= 0).all()
+    shuffled = run(pts[perm], lnk[perm])
+    grad = lambda r: np.concatenate([r[0].cpu().numpy().reshape(B, -1), r[1].cpu().numpy()], 1)
+    _assert_matches((shuffled[2].cpu().numpy(), grad(shuffled)), (by_link[2].cpu().numpy(), grad(by_link)), "Ns=577 shuffled vs by link")
+    for r in (by_link, shuffled):
+        assert (r[0][:, 3] == 0).all() and r[0].abs().max() > 0  # the link without samples: zero wrench
+    gen = torch.Generator().manual_seed(1)
+    pre = [torch.randn(*s, generator=gen).cuda() for s in ((B, L, 6), (B, 12))]
+    acc = run(pts[order], lnk[order], 1, [p.clone() for p in pre])
+    for a, p, v in zip(acc[:2], pre, by_link[:2]):
+        assert torch.equal(a, p + v)
+    assert torch.equal(acc[0][:, 3], pre[0][:, 3])  # left alone
+
+
 @pytest.mark.parametrize("case", ["one cell", "30^3", "entirely outside"])
 def test_hand_partly_or_entirely_outside_the_volume(gq, golden_dir, case):
     g = _load(golden_dir, "energy_allegro_sphere_b4_n4.npz")

@@ -166,6 +166,89 @@ def test_op_shapes_match_the_oracle(gq, hand_name, Ns):
         _assert_matches(_op(gq, hand, samples, hp), ref, f"{hand_name} Ns={Ns} B={B}")
 
 
+BIG_B, BIG_TABLE_Z = 3, 0.05  # more than 512 samples: 577 = 10 chunks (wavefront 1's second chunk holds one sample), 1100 = 18
+
+
+def _big_pose(spec, pts, lnk):
+    """The seeded loop of ``_straddling_pose`` with the plane at BIG_TABLE_Z, and at least 5 samples beyond index 511 below it.
+    -> (pose float32, oracle results, heights over the plane)."""
+    for seed in range(100 * BIG_B + len(pts), 100 * BIG_B + len(pts) + 50):
+        gen = torch.Generator().manual_seed(seed)
+        t = torch.cat([0.1 * torch.randn(BIG_B, 2, generator=gen), 0.02 * torch.randn(BIG_B, 1, generator=gen)], 1)
+        th = torch.tensor(spec.default_state)[None] + 0.3 * torch.randn(BIG_B, spec.n_dofs, generator=gen)
+        hp = torch.cat([t, torch.randn(BIG_B, 6, generator=gen), th], 1).float()
+        rp, rw, rg, h = _oracle(spec, pts, lnk, hp.double(), table_z=BIG_TABLE_Z)
+        below = (h < 0).sum(-1)
+        if np.abs(h).min() >= NEAR and below.min() > 0 and below.max() < len(pts) and (h[:, 512:] < 0).sum() >= 5:
+            return hp, (rp, rw, rg), h
+    raise AssertionError("no seeded pose leaves samples on both sides of the plane")
+
+
+def _without_link_3(n):
+    """``n`` samples of the allegro hand of which none rides on link 3: those of ``_default_samples(n)`` topped up from 2 n."""
+    (p1, l1), (p2, l2) = _default_samples("allegro", n), _default_samples("allegro", 2 * n)
+    pts, lnk = np.concatenate([p1[l1 != 3], p2[l2 != 3]])[:n], np.concatenate([l1[l1 != 3], l2[l2 != 3]])[:n]
+    assert len(pts) == n
+    return pts, lnk
+
+
+@pytest.mark.parametrize("Ns", [577, 1100])
+def test_more_than_512_samples_match_the_oracle(gq, Ns):
+    """A wavefront's second and third trip through the chunk loop: allegro, B = 3, the plane at z = 0.05 so that samples beyond
+    index 511 lie below it (asserted: at least 5; the oracle has 191 of them at Ns = 577 and 1069 at Ns = 1100)."""
+    spec, hand = get_hand_spec("allegro"), _hand("allegro")
+    pts, lnk = _default_samples("allegro", Ns)
+    samples = gq.ops.SurfaceSamples(hand, pts, lnk)
+    assert samples.Ns == Ns and np.array_equal(samples.link.cpu().numpy(), lnk)  # they come by link: the order of the launch
+    hp, ref, h = _big_pose(spec, pts, lnk)
+    tail = int((h[:, 512:] < 0).sum())
+    print(f"[allegro Ns={Ns} B={BIG_B}] samples below the plane {int((h < 0).sum())}, of them at indices >= 512: {tail}")
+    assert tail >= 5 and np.abs(h).min() >= NEAR
+    _assert_matches(_op(gq, hand, samples, hp, table_z=BIG_TABLE_Z), ref, f"allegro Ns={Ns} B={BIG_B} table_z={BIG_TABLE_Z}")
+
+
+def test_second_chunk_run_to_run_sample_order_and_a_link_without_samples(gq):
+    """Ns = 577 through the C entry: bitwise run to run; the samples by link against the same samples shuffled, within the
+    bounds of ``_assert_matches`` (the order of the samples moves the last bits only); a link without samples."""
+    spec, hand = get_hand_spec("allegro"), _hand("allegro")
+    pts, lnk = _without_link_3(577)
+    hp, ref, h = _big_pose(spec, pts, lnk)
+    B, L = BIG_B, hand.L
+    hp = hp.cuda()
+    idx = torch.zeros(B, 1, dtype=torch.long, device="cuda")
+    Rg, LT, _, _, _, _ = gq.ops.fk_contacts(hp, idx, hand)
+    axis = [float(a) for a in spec.grasp_axis]
+
+    def run(p, l, accumulate=0, bufs=None):
+        p, l = torch.tensor(p).cuda(), torch.tensor(l.astype(np.int32)).cuda()
+        wrench, gRt, gR = bufs or (torch.empty(B, L, 6, device="cuda"), torch.empty(B, 12, device="cuda"), torch.empty(B, 9, device="cuda"))
+        ew, ep = torch.empty(B, device="cuda"), torch.empty(B, device="cuda")
+        gq.ops._tabletop_call(hp, p, l, L, Rg.contiguous(), LT.contiguous(), axis, BIG_TABLE_Z, None, 1.5, None, 0.5, ew, ep,
+                              accumulate, wrench, gRt, gR)
+        torch.cuda.synchronize()
+        return wrench, gRt, gR, ew, ep
+
+    order = np.argsort(lnk, kind="stable")
+    by_link, again = run(pts[order], lnk[order]), run(pts[order], lnk[order])
+    for a, b in zip(by_link, again):
+        assert torch.equal(a, b)
+    np.testing.assert_allclose(by_link[3].cpu().numpy(), ref[1], rtol=1e-5, atol=1e-6)
+    perm = np.random.default_rng(577).permutation(577)
+    assert not (np.diff(lnk[perm]) >= 0).all()
+    shuffled = run(pts[perm], lnk[perm])
+    grad = lambda r: np.concatenate([r[0].cpu().numpy().reshape(B, -1), r[1].cpu().numpy(), r[2].cpu().numpy()], 1)
+    _assert_matches((shuffled[4].cpu().numpy(), shuffled[3].cpu().numpy(), grad(shuffled)),
+                    (by_link[4].cpu().numpy(), by_link[3].cpu().numpy(), grad(by_link)), "Ns=577 shuffled vs by link")
+    for r in (by_link, shuffled):
+        assert (r[0][:, 3] == 0).all() and r[0].abs().max() > 0  # the link without samples: zero wrench
+    gen = torch.Generator().manual_seed(1)
+    pre = [torch.randn(*s, generator=gen).cuda() for s in ((B, L, 6), (B, 12), (B, 9))]
+    acc = run(pts[order], lnk[order], 1, [p.clone() for p in pre])
+    for a, p, v in zip(acc[:3], pre, by_link[:3]):
+        assert torch.equal(a, p + v)
+    assert torch.equal(acc[0][:, 3], pre[0][:, 3])  # left alone
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 3. table_z
 # ---------------------------------------------------------------------------------------------------------------
