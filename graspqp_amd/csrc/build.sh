@@ -26,7 +26,7 @@ deps() {  # headers each translation unit includes
     init) echo "common.h wave.h init_select_dev.h" ;;
     export) echo "common.h kin_dev.h wave.h" ;;
     exact) echo "common.h wave.h exact_dev.h fc_dev.h" ;;
-    kin) echo "common.h setup.h cluster_bound.h loop_dev.h sdf_dev.h tri.h kin_dev.h wave.h" ;;
+    kin) echo "common.h fk_slots.h setup.h cluster_bound.h loop_dev.h sdf_dev.h tri.h kin_dev.h wave.h" ;;
     tabletop) echo "common.h sample_row_dev.h" ;;
     cloud) echo "common.h setup.h cluster_bound.h" ;;
     scene) echo "common.h grid_stack.h scene_dev.h sample_row_dev.h scene_row_dev.h" ;;

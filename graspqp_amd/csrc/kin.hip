@@ -6,6 +6,7 @@
 // sequential 3x3 products down a 16-24 joint tree, i.e. latency- not throughput-bound.  The node frames of the forward
 // pass live in a caller-provided workspace (the backward pass and the export-time Jacobians read them); the node
 // wrenches of the backward pass are folded in LDS.
+#include "fk_slots.h"
 #include "kin_dev.h"
 #include "loop_dev.h"
 #include "sdf_dev.h"
@@ -19,6 +20,10 @@
 // flight take the kernel from 168 VGPRs + 144 B of scratch to 156 VGPRs without scratch, same answers (the search is exact),
 // +0.1 .. +0.6 % on configs[1] (profiles/r03_ab_fk_topk2.txt); the stand-alone query kernel keeps 4
 #define GQ_FK_QUERY_TOPK 2
+#endif
+#ifndef GQ_FK_SLOTS_TOPK
+// ... and of the kernels with at most three box slots per lane: the registers of the fourth slot hold a third record
+#define GQ_FK_SLOTS_TOPK 3
 #endif
 
 struct GqFkArgs {
@@ -191,7 +196,13 @@ __global__ __launch_bounds__(GQ_WAVE) void gq_fk_forward_row_kernel(GqFkArgs g) 
   gq_fk_forward_row(g, (int)blockIdx.x, gq_lane(), sW, sT, sC, sKey, sRad, nullptr, sPose);
 }
 
-__global__ __launch_bounds__(768) void gq_fk_forward_kernel(GqFkArgs g) {
+// KC box slots per lane and TOPK clusters per round of the contact queries (sdf_dev.h).  <4, GQ_FK_QUERY_TOPK> is
+// gq_fk_forward_kernel, the form for any mesh set; gq_fk_forward_slots_kernel<KC> serves sets whose largest mesh has at most
+// 64 * KC clusters (fk_slots.h).  A slot that no cluster occupies is 64 B of loads per lane, a bound, a ballot and a popcount
+// per round, and 16 registers alive across barrier B: without it a third face record per round fits the block's budget
+// (KC = 3: 156 VGPRs, nothing spilled; with four slots three records take 168 VGPRs + 32 B of scratch).
+template <int KC, int TOPK>
+__device__ __forceinline__ void gq_fk_forward_block(const GqFkArgs& g) {
   __shared__ float sW[64 * 12];
   __shared__ float sT[64 * 12];
   __shared__ float sC[256 * 3];             // world sphere centres (self penetration)
@@ -215,26 +226,31 @@ __global__ __launch_bounds__(768) void gq_fk_forward_kernel(GqFkArgs g) {
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();
     for (int c = 0; c < g.n; c += nw) {
-      const GqSdfPre pre = gq_sdf_wave_prefetch(g.sdf, (int64_t)row * g.n + c, lane);
-      gq_sdf_wave_query<GQ_FK_QUERY_TOPK>(g.sdf, (int64_t)row * g.n + c, gq_fk_contact_point(g, sCP, row, c), lane, pre);
+      const GqSdfPre<KC> pre = gq_sdf_wave_prefetch<KC>(g.sdf, (int64_t)row * g.n + c, lane);
+      gq_sdf_wave_query<TOPK>(g.sdf, (int64_t)row * g.n + c, gq_fk_contact_point(g, sCP, row, c), lane, pre);
     }
   } else {
     if (g2_here) {
       gq_colsq_partial(g.pr, wv, nw, lane, sPart);
       __syncthreads();  // barrier A (wavefront 0 waits in gq_fk_forward_row)
     }
-    GqSdfPre pre;
-    if (wv < g.n) pre = gq_sdf_wave_prefetch(g.sdf, (int64_t)row * g.n + wv, lane);
+    GqSdfPre<KC> pre;
+    if (wv < g.n) pre = gq_sdf_wave_prefetch<KC>(g.sdf, (int64_t)row * g.n + wv, lane);
     // the z-score of the old energies (only the accept step needs it) is computed by wavefront 1 while it waits
     if (wv == 1 && g.has_propose) gq_zscore_row(g.pr, row, lane);
     __syncthreads();
-    if (wv < g.n) gq_sdf_wave_query<GQ_FK_QUERY_TOPK>(g.sdf, (int64_t)row * g.n + wv, gq_fk_contact_point(g, sCP, row, wv), lane, pre);
+    if (wv < g.n) gq_sdf_wave_query<TOPK>(g.sdf, (int64_t)row * g.n + wv, gq_fk_contact_point(g, sCP, row, wv), lane, pre);
     for (int c = wv + nw; c < g.n; c += nw) {
-      const GqSdfPre p2 = gq_sdf_wave_prefetch(g.sdf, (int64_t)row * g.n + c, lane);
-      gq_sdf_wave_query<GQ_FK_QUERY_TOPK>(g.sdf, (int64_t)row * g.n + c, gq_fk_contact_point(g, sCP, row, c), lane, p2);
+      const GqSdfPre<KC> p2 = gq_sdf_wave_prefetch<KC>(g.sdf, (int64_t)row * g.n + c, lane);
+      gq_sdf_wave_query<TOPK>(g.sdf, (int64_t)row * g.n + c, gq_fk_contact_point(g, sCP, row, c), lane, p2);
     }
   }
 }
+
+__global__ __launch_bounds__(768) void gq_fk_forward_kernel(GqFkArgs g) { gq_fk_forward_block<4, GQ_FK_QUERY_TOPK>(g); }
+
+template <int KC>
+__global__ __launch_bounds__(768) void gq_fk_forward_slots_kernel(GqFkArgs g) { gq_fk_forward_block<KC, GQ_FK_SLOTS_TOPK>(g); }
 
 struct GqFkBwdArgs {
   gqHand h;
@@ -647,7 +663,7 @@ struct GqHandObject : gqHand {
 
 int gq_colsq_launch_(const float* grad, int B, int D, int clip, float* g2, void* stream);  // loop.hip
 int gq_sdf_wave_args_(const gqMeshSet* ms, int64_t n_points, int64_t queries_per_mesh, float* dist_sq, int32_t* sign,
-                      float* normal, float* closest, GqWaveArgs* out);  // sdf.hip
+                      float* normal, float* closest, GqWaveArgs* out, int* max_clusters);  // sdf.hip
 
 extern "C" {
 
@@ -780,13 +796,15 @@ int gq_fk_forward(const gqHand* h, const float* hand_pose, const int64_t* contac
     if (rc) return rc;
     a.has_propose = 1;
   }
-  int nw = 1;
+  int nw = 1, slots = 0;
   if (sdf) {  // the contact queries of a row are answered by the row's block: up to 12 query wavefronts
     GQ_REQUIRE(n_contact > 0 && contact_points, "fk_forward: gqSdfDesc needs contact points");
+    int max_clusters = 0;
     int rc = gq_sdf_wave_args_(sdf->meshes, batch * n_contact, sdf->queries_per_mesh, sdf->dist_sq, sdf->sign,
-                               sdf->obj_dir, sdf->closest, &a.sdf);
+                               sdf->obj_dir, sdf->closest, &a.sdf, &max_clusters);
     if (rc) return rc;
     a.has_sdf = 1;
+    slots = gq_fk_query_slots(max_clusters);
     const int rounds = (n_contact + 11) / 12;
     nw = (n_contact + rounds - 1) / rounds;
   }
@@ -802,6 +820,12 @@ int gq_fk_forward(const gqHand* h, const float* hand_pose, const int64_t* contac
   }
   if (!a.has_sdf)
     hipLaunchKernelGGL(gq_fk_forward_row_kernel, dim3((unsigned)batch), dim3(GQ_WAVE), 0, (hipStream_t)stream, a);
+  else if (slots == 1)
+    hipLaunchKernelGGL(gq_fk_forward_slots_kernel<1>, dim3((unsigned)batch), dim3(GQ_WAVE * nw), 0, (hipStream_t)stream, a);
+  else if (slots == 2)
+    hipLaunchKernelGGL(gq_fk_forward_slots_kernel<2>, dim3((unsigned)batch), dim3(GQ_WAVE * nw), 0, (hipStream_t)stream, a);
+  else if (slots == 3)
+    hipLaunchKernelGGL(gq_fk_forward_slots_kernel<3>, dim3((unsigned)batch), dim3(GQ_WAVE * nw), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(gq_fk_forward_kernel, dim3((unsigned)batch), dim3(GQ_WAVE * nw), 0, (hipStream_t)stream, a);
   GQ_LAUNCH_CHECK();

@@ -26,6 +26,7 @@ struct gqMeshSet {
   int64_t n_cand;
   int n_mesh;
   int64_t n_faces;
+  int max_clusters;    // the largest per-mesh count of 64-face clusters (gq_fk_forward sizes the box slots of its queries by it)
 };
 
 

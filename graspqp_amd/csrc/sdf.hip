@@ -364,7 +364,7 @@ __global__ __launch_bounds__(256) void gq_occ_centres_kernel(const GqFace* __res
 
 // internal (kin.hip): argument block of the wave-per-query kernel for a mesh set; `points` is left to the caller
 int gq_sdf_wave_args_(const gqMeshSet* ms, int64_t n_points, int64_t queries_per_mesh, float* dist_sq, int32_t* sign,
-                      float* normal, float* closest, GqWaveArgs* out) {
+                      float* normal, float* closest, GqWaveArgs* out, int* max_clusters) {
   GQ_REQUIRE(ms && dist_sq && sign && closest && out, "sdf_forward_meshset: null pointer");
   GQ_REQUIRE(queries_per_mesh > 0 && n_points == queries_per_mesh * ms->n_mesh,
              "sdf_forward_meshset: n_points=%lld != queries_per_mesh=%lld * n_mesh=%d", (long long)n_points,
@@ -382,6 +382,7 @@ int gq_sdf_wave_args_(const gqMeshSet* ms, int64_t n_points, int64_t queries_per
   w.normal = normal;
   w.closest = closest;
   *out = w;
+  if (max_clusters) *max_clusters = ms->max_clusters;
   return GQ_OK;
 }
 
@@ -397,6 +398,7 @@ int gq_meshset_create(const float* face_verts_host, const int32_t* face_offset_h
   std::vector<int32_t> perm(F);
   std::vector<float> mesh_bb((size_t)n_mesh * 8), sub_bb, cl_bb;
   std::vector<int32_t> sub_off(n_mesh + 1, 0), cl_off(n_mesh + 1, 0);
+  int32_t max_clusters = 0;
   for (int m = 0; m < n_mesh; ++m) {
     const int64_t a = face_offset_host[m], b = face_offset_host[m + 1];
     for (int64_t i = a; i < b; ++i) perm[i] = (int32_t)i;
@@ -412,12 +414,14 @@ int gq_meshset_create(const float* face_verts_host, const int32_t* face_offset_h
     }
     sub_off[m + 1] = (int32_t)(sub_bb.size() / 8);
     cl_off[m + 1] = (int32_t)(cl_bb.size() / 16);
+    max_clusters = std::max(max_clusters, cl_off[m + 1] - cl_off[m]);
   }
   auto ms = std::make_unique<gqMeshSet>();
   GqOwner& mem = ms->mem;
   GqOwner scratch;
   ms->n_mesh = n_mesh;
   ms->n_faces = F;
+  ms->max_clusters = max_clusters;
   ms->off_host = mem.host_copy(face_offset_host, (size_t)n_mesh + 1);
   ms->aabb_host = mem.host_copy(mesh_bb.data(), mesh_bb.size());
   ms->rec = mem.alloc<GqFace>(F);
@@ -573,7 +577,7 @@ int gq_sdf_forward_meshset(const gqMeshSet* ms, const float* points, int64_t n_p
   if (n_points == 0) return GQ_OK;
   GQ_REQUIRE(points, "sdf_forward_meshset: null pointer");
   GqWaveArgs w{};
-  int rc = gq_sdf_wave_args_(ms, n_points, queries_per_mesh, dist_sq, sign, normal, closest, &w);
+  int rc = gq_sdf_wave_args_(ms, n_points, queries_per_mesh, dist_sq, sign, normal, closest, &w, nullptr);
   if (rc) return rc;
   w.points = points;
   unsigned blocks = (unsigned)((n_points + 3) / 4);

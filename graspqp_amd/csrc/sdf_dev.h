@@ -46,15 +46,18 @@ __device__ __forceinline__ void gq_wave_eval_cluster(const GqFace* __restrict__ 
   }
 }
 
-// What a query can load before its point is known: mesh offsets and the oriented boxes of the first 256 clusters
-// (lane l: clusters l, l + 64, l + 128, l + 192).  In the FK forward kernel the query wavefronts fetch this while
+// What a query can load before its point is known: mesh offsets and the oriented boxes of the first 64 * KC clusters
+// (lane l: clusters l, l + 64, ..., l + 64 (KC - 1)).  In the FK forward kernel the query wavefronts fetch this while
 // wavefront 0 is still computing the contact points.
+template <int KC = 4>
 struct GqSdfPre {
   int f0, f1, c0, nC;
-  float4 box[4][4];
+  float4 box[KC][4];
 };
-__device__ __forceinline__ GqSdfPre gq_sdf_wave_prefetch(const GqWaveArgs& g, int64_t q, int lane) {
-  GqSdfPre s;
+template <int KC = 4>
+__device__ __forceinline__ GqSdfPre<KC> gq_sdf_wave_prefetch(const GqWaveArgs& g, int64_t q, int lane) {
+  static_assert(KC >= 1 && KC <= 4, "one to four box slots per lane");
+  GqSdfPre<KC> s;
   const int mesh = (int)(q / g.queries_per_mesh);
   s.f0 = g.off ? g.off[mesh] : 0;
   s.f1 = g.off ? g.off[mesh + 1] : g.single_F;
@@ -64,7 +67,7 @@ __device__ __forceinline__ GqSdfPre gq_sdf_wave_prefetch(const GqWaveArgs& g, in
     s.c0 = g.cl_off[mesh];
     s.nC = g.cl_off[mesh + 1] - s.c0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < KC; ++k) {
       const int c = k * GQ_WAVE + lane;
       const float4* r = reinterpret_cast<const float4*>(g.cl_aabb + (size_t)(s.c0 + (c < s.nC ? c : 0)) * 16);
 #pragma unroll
@@ -78,9 +81,10 @@ __device__ __forceinline__ GqSdfPre gq_sdf_wave_prefetch(const GqWaveArgs& g, in
 // record loads in flight make a round one L2 round trip for four clusters (latency: the FK forward block, small
 // launches); two keep 40 registers less alive and tighten the bound after every second cluster (throughput: large
 // launches, where registers x lifetime is what the kernels next to it compete for).  The answer does not depend on it:
-// the search is exact and ties go to the smallest original face index.
-template <int GQ_TOPK = 4>
-__device__ __forceinline__ void gq_sdf_wave_query(const GqWaveArgs& g, int64_t q, gq3 p, int lane, const GqSdfPre& pre) {
+// the search is exact and ties go to the smallest original face index.  Nor does it depend on KC (box slots per lane: a pass
+// of the cb loop covers 64 * KC clusters, meshes with more take further passes).
+template <int GQ_TOPK = 4, int KC = 4>
+__device__ __forceinline__ void gq_sdf_wave_query(const GqWaveArgs& g, int64_t q, gq3 p, int lane, const GqSdfPre<KC>& pre) {
   const int f0 = pre.f0, f1 = pre.f1;
   float best = GQ_INF_F;
   unsigned borig = 0xffffffffu;
@@ -95,7 +99,6 @@ __device__ __forceinline__ void gq_sdf_wave_query(const GqWaveArgs& g, int64_t q
     // are in flight at once, which is what matters: a round is one L2 round trip) and evaluates them.  It stops as
     // soon as the smallest remaining bound exceeds the best distance: for a point at distance d only clusters whose
     // box intersects the ball of radius d are ever touched.
-    constexpr int KC = 4;  // 256 clusters (16384 faces) per pass
     float ub = GQ_INF_F;
     int visits = 0;
     float lb[KC];

@@ -92,7 +92,7 @@ def run(mode):
 
 
 def fold(paths):
-    """Counter values of gq_fk_forward_kernel per launch, grouped by the marker fills (element counts 1000, 1007, 1014)."""
+    """Counter values of the FK forward kernel (gq_fk_forward_kernel or its sized sibling gq_fk_forward_slots_kernel<KC>) per launch, grouped by the marker fills (element counts 1000, 1007, 1014)."""
     res = {}
     for p in paths:
         rows = list(csv.DictReader(open(p)))
@@ -108,7 +108,7 @@ def fold(paths):
                     seen.add(r.get("Dispatch_Id"))
                     group = (g - 2560) // 256
                 continue
-            if "gq_fk_forward_kernel" in k and 0 <= group < 3:
+            if ("gq_fk_forward_kernel" in k or "gq_fk_forward_slots_kernel" in k) and 0 <= group < 3:
                 acc[names[group + 1]][r["Counter_Name"]].append(float(r["Counter_Value"]))
         for gname, cs in acc.items():
             for cname, v in cs.items():
