@@ -96,7 +96,7 @@ def calculate_energy(hand_model, object_model, energy_fnc=None, energy_names=[],
         (losses["E_dis"], losses["E_fc"], losses["E_joints"], losses["E_pen"], losses["E_spen"], distance, contact_normal,
          _lambda) = _FusedTerms.apply(hand_model.hand_pose, hand_model, object_model, energy_fnc.fc_config(svd_gain=svd_gain),
                                       method == "gendexgrasp")
-        return _extra_terms(losses, hand_model, energy_names, distance, contact_normal)
+        return _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model)
     distance, contact_normal = object_model.cal_distance(hand_model.contact_points)
     # (each term below is one launch that also writes its derivative, csrc/terms.hip: the torch expressions of the
     # reference, energy.py:25-28,47-52,58-61, cost a dozen launches each, forward and backward, in a host-bound loop)
@@ -118,10 +118,10 @@ def calculate_energy(hand_model, object_model, energy_fnc=None, energy_names=[],
     losses["E_pen"] = ops.energy_pen(distances)  # sum of where(distances <= 0, 0, distances)
     losses["E_spen"] = hand_model.self_penetration()
 
-    return _extra_terms(losses, hand_model, energy_names, distance, contact_normal)
+    return _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model)
 
 
-def _extra_terms(losses, hand_model, energy_names, distance, contact_normal):
+def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model=None):
     if "E_prior" in energy_names:  # energy.py:68-74: the grasp axis should point down
         forward_axis = (hand_model.global_rotation @ hand_model.grasp_axis.view(1, -1, 1)).view(-1, 3)
         axis_prior = torch.tensor([0, 0, -1], dtype=torch.float, device=forward_axis.device).view(1, 3)
@@ -169,6 +169,23 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal):
             xk = x if k == 0 else x - (D * k / K) * back.unsqueeze(1)
             e = e + torch.relu(margin - ops.scene_distance(xk, scene)).sum(-1)
         losses["E_pregrasp"] = e * (1.0 / (K + 1))
+
+    if "E_squeeze" in energy_names:
+        # contact closing feasibility as ONE launch (ops.squeeze_terms; parameters: HandModel.set_squeeze): at the defaults the value
+        # and gradient of E_manipulativity below, whose composed route stays as it is.  The op takes the squared distance and the
+        # closest points of the contact query, so the query runs once more here, detached.
+        tau, lam = getattr(hand_model, "squeeze", (5e-3, 1e-3))
+        cp = hand_model.contact_points
+        B, n, _ = cp.shape
+        flat = cp.detach().reshape(-1, 3)
+        if getattr(object_model, "_cloudset", None) is not None:
+            d2, sgn, nrm, cls = ops.sdf_cloud(flat, object_model._cloudset, object_model.batch_size_each * n)
+        else:
+            d2, sgn, nrm, cls = ops.sdf_meshset(flat, object_model._meshset, object_model.batch_size_each * n)
+        _, onrm = ops.signed_distance(d2, sgn, nrm)
+        losses["E_squeeze"] = ops.squeeze_terms(hand_model.hand_pose, hand_model._hand, hand_model._fk_idx, hand_model.global_rotation,
+                                                hand_model.current_status, hand_model._fk_ws, d2.reshape(B, n), onrm.reshape(B, n, 3),
+                                                cls.reshape(B, n, 3), cp, tau, lam)
 
     if "E_manipulativity" in energy_names:
         # energy.py:80-87: mean squared contact velocity the joints cannot produce when the contacts move along

@@ -265,6 +265,13 @@ class HandModel:
             raise ValueError(f"HandModel.set_pregrasp: open_joints must be ({self.n_dofs},), got {tuple(q.shape)}")
         self.pregrasp = (float(distance), int(stations), float(opening), q, margin, scene)
 
+    def set_squeeze(self, min_travel=5e-3, damping=1e-3):
+        """The two parameters of calculate_energy(..., energy_names=[..., "E_squeeze"]): every contact moves along the object
+        normal by max(|distance|, min_travel), and the joint velocities come from the pseudo-inverse of the contact Jacobian damped
+        by ``damping``.  Both finite and > 0; the defaults make the term the reference's E_manipulativity (core/energy.py:80-87)."""
+        ops.squeeze_check(None, 1, min_travel, damping, "HandModel.set_squeeze")
+        self.squeeze = (float(min_travel), float(damping))
+
     def get_surface_points(self, hand_pose=None):
         """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose; ``hand_pose`` =
         None takes the model's own (another pose, e.g. the opened one of E_pregrasp, is a second FK at that pose)."""

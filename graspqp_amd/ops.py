@@ -2072,6 +2072,120 @@ def pregrasp_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg
                                 float(distance), int(stations), float(opening), open_joints, float(margin))
 
 
+# ----------------------------------------------------------------------------------------------------------
+# contact closing feasibility: E_squeeze (csrc/squeeze.hip), the reference's E_manipulativity (core/energy.py:80-87) as ONE launch:
+# contact Jacobian, damped normal equations in fp64, both solves, residual, and the three gradient parts
+# ----------------------------------------------------------------------------------------------------------
+def squeeze_check(hand, n_contact, min_travel, damping, who="squeeze_terms"):
+    """The parameters of the squeeze term (no GPU): finite min_travel > 0 and damping > 0 (J'J alone is singular for 3n < JA), at
+    most 64 joints and 64 contacts; raises ValueError."""
+    if not 0.0 < float(min_travel) < float("inf"):
+        raise ValueError(f"{who}: squeeze_min_travel = {min_travel!r} must be finite and > 0")
+    if not 0.0 < float(damping) < float("inf"):
+        raise ValueError(f"{who}: squeeze_damping = {damping!r} must be finite and > 0")
+    if hand is not None and not (1 <= int(n_contact) <= 64 and hand.spec.n_nodes <= 64 and hand.J <= 64):
+        raise ValueError(f"{who}: the squeeze term takes at most 64 joints and 64 contacts, got {hand.spec.n_nodes} joints, "
+                         f"n_contact = {n_contact}")
+
+
+def _squeeze_call(hand, idx, Rg, LT, ws, d2, onrm, closest, cpts, min_travel, damping, up, w, e, theta, accumulate, g_theta, g_R,
+                  g_R_base, g_cpts, st=None):
+    p, (B, n) = _dev, idx.shape
+    _C.call("gq_squeeze_terms", hand.handle, _C.i64(idx), ctypes.c_int64(B), n, p(d2), p(onrm), p(closest), p(cpts), p(Rg), p(LT),
+            _C.ptr(ws), ws.numel(), float(min_travel), float(damping), p(up), float(w), p(e), p(theta), int(accumulate), p(g_theta),
+            p(g_R), p(g_R_base), p(g_cpts), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::squeeze_terms", mutates_args=(), device_types="cuda")
+def _squeeze_op(hand: int, idx: Tensor, Rg: Tensor, LT: Tensor, ws: Tensor, dist_sq: Tensor, obj_normal: Tensor, min_travel: float,
+                damping: float) -> Tuple[Tensor, Tensor]:
+    """-> (E_squeeze (B), unweighted; theta (B,JA), the squeeze joint velocities) of the kinematic state (idx, Rg, LT, ws) and the
+    contact query (dist_sq (B,n), outward obj_normal (B,n,3))."""
+    h = _handle(hand)
+    ix = _c(idx, torch.int64)
+    B, dev = ix.shape[0], ix.device
+    e, theta = torch.empty(B, device=dev), torch.empty(B, h.J, device=dev)
+    _squeeze_call(h, ix, _c(Rg), _c(LT), ws, _c(dist_sq), _c(obj_normal), None, None, min_travel, damping, None, 0.0, e, theta, 0,
+                  None, None, None, None)
+    return e, theta
+
+
+@_squeeze_op.register_fake
+def _(hand, idx, Rg, LT, ws, dist_sq, obj_normal, min_travel, damping):
+    B = idx.shape[0]
+    return dist_sq.new_empty(B), dist_sq.new_empty(B, _handle(hand).J)
+
+
+@_custom_op("graspqp_amd::squeeze_terms_backward", mutates_args=(), device_types="cuda")
+def _squeeze_bwd_op(hand: int, idx: Tensor, Rg: Tensor, LT: Tensor, ws: Tensor, dist_sq: Tensor, obj_normal: Tensor, closest: Tensor,
+                    contact_pts: Tensor, min_travel: float, damping: float, g_squeeze: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """Upstream row gradients (B) on E_squeeze -> (g_theta (B,JA), g_R (B,3,3), g_contact_pts (B,n,3)): the direct joint gradient,
+    dE/dR in the form fk_backward takes, and the gradient to the contact points.  One launch."""
+    h = _handle(hand)
+    ix = _c(idx, torch.int64)
+    (B, n), dev = ix.shape, ix.device
+    g_theta, g_R, g_cp = torch.empty(B, h.J, device=dev), torch.empty(B, 3, 3, device=dev), torch.empty(B, n, 3, device=dev)
+    _squeeze_call(h, ix, _c(Rg), _c(LT), ws, _c(dist_sq), _c(obj_normal), _c(closest), _c(contact_pts), min_travel, damping,
+                  _c(g_squeeze), 1.0, None, None, 0, g_theta, g_R, None, g_cp)
+    return g_theta, g_R, g_cp
+
+
+@_squeeze_bwd_op.register_fake
+def _(hand, idx, Rg, LT, ws, dist_sq, obj_normal, closest, contact_pts, min_travel, damping, g_squeeze):
+    B, n = idx.shape
+    e = dist_sq.new_empty
+    return e(B, _handle(hand).J), e(B, 3, 3), e(B, n, 3)
+
+
+class _SqueezeTerms(torch.autograd.Function):
+    """Glue between registered ops (squeeze_terms + fk_backward), as _PregraspTerms: the backward launch writes g_theta, g_R and
+    the contact-point gradient with the per-row upstream; the FK backward turns g_R into the root-rotation gradient, and g_theta is
+    the joint part as it stands.  The contact-point gradient goes back to ``contact_pts`` (whose own graph carries it on)."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, contact_pts, hand, idx, Rg, LT, ws, dist_sq, obj_normal, closest, min_travel, damping):
+        hp = _c(hand_pose.detach())
+        e, theta = _Eager.squeeze_terms(hand.hid, idx, Rg, LT, ws, dist_sq, obj_normal, min_travel, damping)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, dist_sq, obj_normal, closest, _c(contact_pts.detach()))
+        ctx.hand, ctx.par = hand, (min_travel, damping)
+        ctx.mark_non_differentiable(theta)
+        return e, theta
+
+    @staticmethod
+    def backward(ctx, g_squeeze, _g_theta):
+        hp, idx, Rg, LT, ws, dist_sq, obj_normal, closest, cpts = ctx.saved_tensors
+        hand = ctx.hand
+        g_theta, g_R, g_cp = _Eager.squeeze_terms_backward(hand.hid, idx, Rg, LT, ws, dist_sq, obj_normal, closest, cpts, *ctx.par,
+                                                           _c(g_squeeze))
+        gp = _fk_backward(hand, hp, idx, Rg, LT, ws, None, None, None, None, None, g_R)
+        gp[:, 9:] += g_theta
+        return (gp, g_cp) + (None,) * 10
+
+
+def squeeze_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, dist_sq, obj_normal, closest, contact_pts, min_travel=5e-3,
+                  damping=1e-3, return_theta=False):
+    """-> E_squeeze (B) = 1/(3n) sum r^2, r = J theta - R' d, theta = (J'J + damping I)^-1 J' R' d, d_i = obj_normal_i
+    max(sqrt(dist_sq_i + 1e-8), min_travel): the mean squared part of the contacts' closing motion that the joints cannot produce.
+    At the defaults it is the reference's E_manipulativity (core/energy.py:80-87) in value and gradient.  Unweighted; differentiable
+    w.r.t. ``hand_pose`` (joints through the contact Jacobian, root rotation through R' d) and ``contact_pts`` (through the travel
+    of the contacts above ``min_travel``; the normals are constants, as in the reference).  ``idx``, ``Rg``, ``LT``, ``ws`` are the
+    kinematic state of ``hand_pose`` (fk_contacts); ``dist_sq`` (B,n), ``obj_normal`` (B,n,3, outward), ``closest`` (B,n,3) the object
+    query of ``contact_pts`` (B,n,3).  ``return_theta``: also the squeeze joint velocities theta (B,JA)."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if hand_pose.shape[1] != 9 + hand.J:
+        raise ValueError(f"squeeze_terms: hand_pose must be (B, {9 + hand.J}), got {tuple(hand_pose.shape)}")
+    B, n = idx.shape
+    squeeze_check(hand, n, min_travel, damping)
+    if tuple(dist_sq.shape) != (B, n) or tuple(obj_normal.shape) != (B, n, 3) or tuple(closest.shape) != (B, n, 3) or \
+            tuple(contact_pts.shape) != (B, n, 3):
+        raise ValueError(f"squeeze_terms: dist_sq must be ({B}, {n}) and obj_normal / closest / contact_pts ({B}, {n}, 3)")
+    e, theta = _SqueezeTerms.apply(hand_pose, contact_pts, hand, _c(idx, torch.int64), _c(Rg.detach()), _c(LT.detach()), ws,
+                                   _c(dist_sq.detach()), _c(obj_normal.detach()), _c(closest.detach()), float(min_travel),
+                                   float(damping))
+    return (e, theta) if return_theta else e
+
+
 @_custom_op("graspqp_amd::scene_compose", mutates_args=("out_values",), device_types="cuda")
 def _scene_compose_op(out_values: Tensor, origin: List[float], voxel: float, target_T: Tensor, part_values: List[Tensor],
                       part_origins: List[float], part_voxels: List[float], part_T: Tensor, exclude: Optional[Tensor],
@@ -2475,6 +2589,8 @@ _eager("approach_terms_set", _approach_set_op)
 _eager("approach_terms_set_backward", _approach_set_bwd_op)
 _eager("pregrasp_terms", _pregrasp_op)
 _eager("pregrasp_terms_backward", _pregrasp_bwd_op)
+_eager("squeeze_terms", _squeeze_op)
+_eager("squeeze_terms_backward", _squeeze_bwd_op)
 _eager("scene_compose", _scene_compose_op)
 _eager("tsdf_integrate", _tsdf_integrate_op)
 _eager("tsdf_surfels", _tsdf_surfels_op)

@@ -33,6 +33,17 @@ opened kinematics, stations and joint gradient of the row) after gq_approach_ter
 ``g_theta``, the direct joint gradient the FK backward takes in this mode only; ``terms`` gets [E_pregrasp] appended last, its share
 of the row total is one more gq_scene_total launch, and the proposal and the accept step are the stand-alone launches.
 
+Squeeze mode (a weight on "E_squeeze"): can the fingers close onto the object from this pose?  Every contact moves along the outward
+object normal by max(|distance|, ``squeeze_min_travel``); the damped pseudo-inverse of the stacked contact Jacobian gives the joint
+velocities that produce this motion best (``squeeze_theta``), and the term charges the mean squared part of the motion the joints
+cannot produce.  At the defaults (5 mm, damping 1e-3) it is the reference's E_manipulativity (core/energy.py:80-87) in value and
+gradient -- that name stays refused as a stepper weight; the class surface (``calculate_energy``) keeps it for the composed route.
+One more launch (gq_squeeze_terms: Jacobian, fp64 normal equations, both solves, residual and the three gradient parts of the row)
+after the joined branches and the obstacle terms adds to ``g_cpts``, which the contact branch has written by then, writes ``g_theta``
+(adds to it when E_pregrasp is on too) and writes the per-iteration ``g_R`` buffer the FK backward reads (E_prior's constant plus this
+term's part; the constant itself is never modified); ``terms`` gets [E_squeeze] appended last, its share of the row total is one more
+gq_scene_total launch, and the proposal and the accept step are the stand-alone launches.
+
 Clutter (``scene`` is an ``ops.SceneSDFSet`` with one grid per object): the same two launches read a stack of grids and pick the
 grid from the row, row // batch_each (gq_clutter_terms / gq_clutter_corridor_terms, the same row bodies: bit for bit the single-grid
 launch's numbers on that grid).  ``ops.scene_compose`` refills the stack in place, also between replays of a captured graph.
@@ -55,6 +66,7 @@ TABLETOP_TERMS = ("E_prior", "E_wall")
 SCENE_TERMS = ("E_scene",)
 APPROACH_TERMS = ("E_approach",)
 PREGRASP_TERMS = ("E_pregrasp",)
+SQUEEZE_TERMS = ("E_squeeze",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
@@ -79,12 +91,12 @@ def select_tolerances(term_names, gates=None):
 
 
 def merge_weights(weights=None):
-    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term and of the pre-grasp term)
-    updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and
-    so does a negative weight of a tabletop term, of the scene term, of the approach term or of the pre-grasp term."""
-    switched = TABLETOP_TERMS + OBSTACLE_TERMS
+    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term, of the pre-grasp term and of
+    the squeeze term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
+    never used), and so does a negative weight of one of the terms that are switched by their weight."""
+    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS
     w = dict(DEFAULT_WEIGHTS)
-    w.update({k: 0.0 for k in switched})
+    w.update({k: 0.0 for k in SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
     for k, v in (weights or {}).items():
         if k not in w:
             raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
@@ -113,7 +125,8 @@ class GraspStepper:
                  surface_samples=None, table_z: float = 0.0, scene=None, scene_margin: float = 0.0,
                  approach_distance: float = 0.10, approach_stations: int = 4, approach_margin=None,
                  pregrasp_opening: float = 0.5, pregrasp_joints=None, pregrasp_scene=None, pregrasp_distance=None,
-                 pregrasp_stations=None, pregrasp_margin=None, init_avoid_scene: bool = False):
+                 pregrasp_stations=None, pregrasp_margin=None, squeeze_min_travel: float = 5e-3, squeeze_damping: float = 1e-3,
+                 init_avoid_scene: bool = False):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -138,7 +151,12 @@ class GraspStepper:
         limits; ``pregrasp_scene`` / ``pregrasp_distance`` / ``pregrasp_stations`` / ``pregrasp_margin`` = None take ``scene``,
         ``approach_distance``, ``approach_stations`` and ``scene_margin``.  ``pregrasp_scene`` (an ``ops.SceneSDF``, or an
         ``ops.SceneSDFSet`` with ``n_grids`` == n_obj) exists because this term's grid usually contains the target and the grid of
-        E_scene must not.  With weight 0 the six arguments change nothing."""
+        E_scene must not.  With weight 0 the six arguments change nothing.
+        weights["E_squeeze"] > 0 selects the squeeze mode (module docstring): the mean squared part of the contacts' closing motion
+        n_i max(|distance_i|, squeeze_min_travel) that the joints cannot produce, with the damped pseudo-inverse (squeeze_damping) of
+        the contact Jacobian; at the defaults the reference's E_manipulativity.  Both must be finite and > 0 (J'J alone is singular
+        for 3 n_contact < n_dofs).  ``squeeze_theta`` (B,J) holds the joint velocities of the last evaluation.  With weight 0 the two
+        arguments change nothing."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -185,11 +203,15 @@ class GraspStepper:
             _check_corridor("pregrasp", pregrasp_margin, pregrasp_distance, pregrasp_stations, 0)
             if not 0.0 <= float(pregrasp_opening) <= 1.0:
                 raise ValueError(f"GraspStepper: pregrasp_opening = {pregrasp_opening!r} must be in [0, 1]")
+        self.squeeze_mode = self.w["E_squeeze"] > 0
+        if self.squeeze_mode:
+            ops.squeeze_check(hand, n_contact, squeeze_min_travel, squeeze_damping, "GraspStepper")
         self.init_avoid_scene = bool(init_avoid_scene)
         if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
             raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
         self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
-                           + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ()))
+                           + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ())
+                           + (SQUEEZE_TERMS if self.squeeze_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -315,7 +337,7 @@ class GraspStepper:
             ad.e_fc = self.terms_new[1].data_ptr()
             self._alt_desc = ad
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
-        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode)
+        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode or self.squeeze_mode)
         self.samples, self.g_R = None, None
         self._n_surface_points, self._select_fk = int(n_surface_points), None
         self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode or self.approach_mode else (None, 0.0)
@@ -347,7 +369,7 @@ class GraspStepper:
             ops.approach_check(scene, B, L, self.samples.Ns, self.approach_distance, self.approach_stations,
                                hand.spec.grasp_axis)
         if self.pregrasp_mode:
-            self._i_pregrasp = nT - 1
+            self._i_pregrasp = self.term_names.index("E_pregrasp")
             self._obstacle_terms.append((self._i_pregrasp, float(self.w["E_pregrasp"]), self._eval_pregrasp))
             self.pregrasp_scene = pregrasp_scene
             self.pregrasp_distance, self.pregrasp_stations = float(pregrasp_distance), int(pregrasp_stations)
@@ -369,6 +391,13 @@ class GraspStepper:
             # d (w_prior E_prior) / d R = w_prior * grasp_axis in row 2 does not depend on the pose: set here, once; the launch
             # of every evaluation adds to wrench / gRt and is given no g_R
             self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._axis), device=self.dev)
+        self.squeeze_theta, self._g_R_const = None, self.g_R
+        if self.squeeze_mode:
+            self._i_squeeze = nT - 1
+            self.squeeze_min_travel, self.squeeze_damping = float(squeeze_min_travel), float(squeeze_damping)
+            self.squeeze_theta = f(B, self.J)
+            # the g_R the FK backward reads in this mode: written by every evaluation (E_prior's constant + this term's part)
+            self.g_R = f(B, 9)
         self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
@@ -387,8 +416,8 @@ class GraspStepper:
                                                                   int(m["annealing_period"]))
         ac.energy, ac.pose, ac.idx, ac.grad = (t.data_ptr() for t in (self.energy, self.hand_pose, self.contact_idx, self.grad))
         ac.accept, ac.temperature = self.accept.data_ptr(), self.temperature.data_ptr()
-        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach and pre-grasp mode
-        # (six to ten terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
+        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach, pre-grasp and squeeze
+        # mode (six to eleven terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
         assert self._fuse_loop == (nT == len(TERM_NAMES))
         ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
@@ -497,12 +526,20 @@ class GraspStepper:
                            self.pregrasp_opening, p.joints, pose, self.samples.points, p.link, p.Rg, self._axis, None,
                            self.w["E_pregrasp"], p.e[self._i_pregrasp], 1, p.g_theta, p.gRt, st)
 
+    def _eval_squeeze(self, idx, st):
+        """E_squeeze -> terms_new[-1], the joint velocities -> ``squeeze_theta``; the gradient of w_squeeze E_squeeze is added to
+        ``g_cpts`` (the contact branch has written it), written to ``g_theta`` (added when the pre-grasp launch has written it) and
+        written, on top of E_prior's constant, to the ``g_R`` the FK backward reads."""
+        ops._squeeze_call(self.hand, idx, self.Rg, self.link_T, self.fk_ws, self.d2, self.obj_normal, self.closest, self.cpts,
+                          self.squeeze_min_travel, self.squeeze_damping, None, self.w["E_squeeze"], self.terms_new[self._i_squeeze],
+                          self.squeeze_theta, 3 if self.pregrasp_mode else 1, self.g_theta, self.g_R, self._g_R_const, self.g_cpts, st)
+
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
         f32 = _C.f32
         _C.call("gq_fk_backward", self.hand.handle, f32(pose), _C.i64(idx), B, n, f32(self.Rg), f32(self.link_T),
                 f32(self.g_cpts), f32(self.g_cnrm), f32(self.g_sph_w) if self.S > 0 else None, f32(self.wrench),
-                f32(self.gRt), f32(self.g_theta) if self.pregrasp_mode else None, f32(self.g_R), f32(self.grad_new),
+                f32(self.gRt), f32(self.g_theta) if self.pregrasp_mode or self.squeeze_mode else None, f32(self.g_R), f32(self.grad_new),
                 ctypes.byref(self._row_energy),
                 ctypes.byref(self._accept_desc) if loop else None, _C.ptr(self.fk_ws), self.fk_nb, st)
 
@@ -545,12 +582,17 @@ class GraspStepper:
             self._eval_tabletop(pose, st)
         for _, _, evaluate in self._obstacle_terms:  # scene, approach, pre-grasp
             evaluate(pose, st)
+        if self.squeeze_mode:
+            self._eval_squeeze(idx, st)
         self._eval_tail(pose, idx, st, loop)
         if self.tabletop:  # the FK backward's total holds the five terms
             _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
                     _C.f32(self.terms_new[6]), float(self.w["E_wall"]), ctypes.c_int64(self.B), st)
         for i, w, _ in self._obstacle_terms:  # the generic total += w e
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[i]), w, ctypes.c_int64(self.B), st)
+        if self.squeeze_mode:
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_squeeze]), float(self.w["E_squeeze"]),
+                    ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):
         """Energy terms, total and d total / d pose at an arbitrary (pose, idx); returns clones."""

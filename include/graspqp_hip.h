@@ -694,6 +694,36 @@ int gq_pregrasp_terms(const gqHand* h, const gqClutterGrids* grids, int64_t rows
                       int accumulate /* bit 0: add to gRt, bit 1: add to g_theta; a cleared bit overwrites */,
                       float* g_theta /* (B,JA) or NULL */, float* gRt /* (B,12) or NULL */, void* stream);
 
+/* ---- contact closing feasibility of the stepper: E_squeeze ------------------------------------------------------------
+ * reference: core/energy.py:80-87 (E_manipulativity) -> core/hand_model.py:1155-1218 (get_req_joint_velocities, coupled form)
+ * with the damped pseudo-inverse of hand_model.py:46-54; the same least-squares problem writes the squeeze command of every
+ * exported grasp (scripts/fit.py:224-300).  At min_travel = 5e-3 and damping = 1e-3 the term IS the reference's E_manipulativity
+ * in value and gradient.  Per row, with the n contacts contact_idx, J (3n x JA) the linear contact Jacobian in the hand frame
+ * (gq_contact_jacobian's, the fold with the coupling matrix C included), n_i = obj_normal, tau = min_travel, lambda = damping:
+ *   s_i = max(sqrt(dist_sq_i + 1e-8), tau)    d_i = n_i s_i    d_h = R' d
+ *   M = J'J + lambda I    theta = M^-1 J' d_h    r = J theta - d_h    E = 1/(3n) sum r^2
+ * M, its Cholesky factor and the solves are fp64 (as gq_joint_velocities); J, r and the rest fp32.  Gradient with the row's
+ * upstream c = w (up[row] if given, else 1) / (3n), g = 2 c r, u = M^-1 J' g = -2 c lambda M^-1 theta, v = g - J u:
+ *   g_theta (B,JA)        = sum_ij (theta_j v_i - u_j r_i) . dJ_ij/dtheta_k, the closed-form kinematic Hessian of
+ *                           gq_contact_jacobian_backward (C / C' for coupled hands): the direct joint gradient gq_fk_backward takes
+ *   g_R (B,9)             = dE/dR[a][c] = sum_i d_i[a] (-v_i)[c], plus g_R_base (B,9) if given (a constant of another term: the
+ *                           launch reads it and never writes it); always overwritten; gq_fk_backward takes it as g_R
+ *   g_contact_pts (B,n,3) = (n_i . R(-v_i)) [s_i > tau] (p_i - closest_i) / sqrt(dist_sq_i + 1e-8); the normals are constants
+ * accumulate is two bits: bit 0 (1) adds to g_contact_pts, bit 1 (2) adds to g_theta; a cleared bit overwrites.  e (B) is written
+ * UNWEIGHTED and always overwritten; theta (B,JA) are the squeeze joint velocities.  Any output may be NULL; without a gradient
+ * output the second solve and the Hessian walk are skipped.  link_T / workspace are gq_fk_forward's of the same poses.
+ * One wavefront per row, fixed-order sums, no atomics: bitwise reproducible run to run.  J, JA, n_contact <= 64, else an error
+ * status.  The row total takes gq_scene_total(total, e, w, B).                                                             */
+int gq_squeeze_terms(const gqHand* h, const int64_t* contact_idx /* (B,n) */, int64_t batch, int n_contact,
+                     const float* dist_sq /* (B,n) */, const float* obj_normal /* (B,n,3) outward */,
+                     const float* closest /* (B,n,3) or NULL without g_contact_pts */,
+                     const float* contact_pts /* (B,n,3) or NULL without g_contact_pts */, const float* Rg /* (B,9) */,
+                     const float* link_T /* (B,L,12) */, const void* workspace, size_t workspace_bytes, float min_travel,
+                     float damping, const float* up /* (B) or NULL */, float w, float* e /* (B) or NULL */,
+                     float* theta /* (B,JA) or NULL */, int accumulate, float* g_theta /* (B,JA) or NULL */,
+                     float* g_R /* (B,9) or NULL */, const float* g_R_base /* (B,9) or NULL */,
+                     float* g_contact_pts /* (B,n,3) or NULL */, void* stream);
+
 /* ---- scenes from depth images: TSDF fusion on the device into scene grids ---------------------------------------------
  * What a robot has is depth images, not a signed-distance volume.  gq_tsdf_integrate fuses a batch of depth frames into a
  * gqClutterGrids stack IN PLACE, one launch per batch (n_grids = 1 is the single world grid).  State: `values` of the stack IS

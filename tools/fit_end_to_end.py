@@ -11,6 +11,7 @@ then three independent checks of what came out:
 Evidence run, not a test: writes one JSON record (default gpurun_out/fit_end_to_end.json).
 
 usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_iter 7000] [--out file.json]
+       [--w_squeeze 0] [--squeeze_min_travel 5e-3] [--squeeze_damping 1e-3]   (contact closing feasibility, E_squeeze)
        [--w_wall 0] [--w_prior 0]   (scripts/fit.py:77-78: tabletop synthesis; the class surface and the oracle then carry
        E_wall / E_prior on the stepper's surface samples, st.samples)
        [--w_scene 0] [--scene_margin 0] [--scene box]   (scene obstacles: the ``box`` preset is an open-topped bin of five slabs
@@ -47,6 +48,9 @@ ap.add_argument("--scene", choices=("box",), default="box")
 ap.add_argument("--w_approach", type=float, default=0.0)
 ap.add_argument("--approach_distance", type=float, default=0.10)
 ap.add_argument("--approach_stations", type=int, default=4)
+ap.add_argument("--w_squeeze", type=float, default=0.0)
+ap.add_argument("--squeeze_min_travel", type=float, default=5e-3)
+ap.add_argument("--squeeze_damping", type=float, default=1e-3)
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "fit_end_to_end.json"))
 args = ap.parse_args()
 
@@ -70,6 +74,9 @@ if SCENE:
 APPROACH = args.w_approach > 0
 if APPROACH:
     W["E_approach"] = args.w_approach
+SQUEEZE = args.w_squeeze > 0  # contact closing feasibility (E_squeeze: the reference's E_manipulativity as one launch)
+if SQUEEZE:
+    W["E_squeeze"] = args.w_squeeze
 spec = get_hand_spec(args.hand)
 n_obj, be, n = args.n_objects, args.batch_size, args.n_contact
 B = n_obj * be
@@ -88,8 +95,11 @@ if SCENE or APPROACH:  # the ``box`` preset: an open-topped bin around the first
         weights["E_scene"] = args.w_scene
     if APPROACH:
         weights["E_approach"] = args.w_approach
+if SQUEEZE:
+    weights["E_squeeze"] = args.w_squeeze
 st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1, weights=weights or None, scene=scene,
-                  scene_margin=args.scene_margin, approach_distance=args.approach_distance, approach_stations=args.approach_stations)
+                  scene_margin=args.scene_margin, approach_distance=args.approach_distance, approach_stations=args.approach_stations,
+                  squeeze_min_travel=args.squeeze_min_travel, squeeze_damping=args.squeeze_damping)
 st.set_hulls(om.convex_hulls())
 st.initialize()  # on-device initialize_convex_hull + the first evaluation
 e0, t0_terms = st.energy.clone(), st.terms.clone()
@@ -121,10 +131,12 @@ if SCENE or APPROACH:
     hm.set_scene(scene, args.scene_margin)
 if APPROACH:
     hm.set_approach(args.approach_distance, args.approach_stations)
+if SQUEEZE:
+    hm.set_squeeze(args.squeeze_min_travel, args.squeeze_damping)
 metric = GraspSpanMetricFactory.create(GraspSpanMetricFactory.MetricType.GRASPQP, {"friction": 0.2, "max_limit": 20.0, "n_cone_vecs": 4})
 losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1,
                           energy_names=(["E_prior", "E_wall"] if TABLETOP else []) + (["E_scene"] if SCENE else []) +
-                          (["E_approach"] if APPROACH else []))
+                          (["E_approach"] if APPROACH else []) + (["E_squeeze"] if SQUEEZE else []))
 total_cls = sum(W[k] * losses[k] for k in W)
 rel_cls = ((total_cls.detach() - st.energy).abs() / st.energy.abs().clamp_min(1e-6))
 

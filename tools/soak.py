@@ -4,7 +4,7 @@ counters must not show inline-ranked overflow growing, the stop iteration is his
 
 usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--w_scene W] [--scene_margin M]
        [--scene box] [--w_approach W] [--approach_distance D] [--approach_stations K]
-       [--w_pregrasp W] [--pregrasp_opening A] [--pregrasp_stations K] [--out file.json]
+       [--w_pregrasp W] [--pregrasp_opening A] [--pregrasp_stations K] [--w_squeeze W] [--out file.json]
        (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
        schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
        hand surface samples left below the plane; --w_scene > 0 runs it in scene mode against the ``box`` preset (an open-topped
@@ -12,8 +12,9 @@ usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_
        the start and at the end; --w_approach > 0 adds the approach corridor against the same preset (K stations over D metres
        along the hand's grasp axis) and reports the mean E_approach the same way; --w_pregrasp > 0 adds the pre-grasp term
        against the same preset (the hand opened by --pregrasp_opening towards its default state, stations 0..K over the
-       approach distance; K defaults to --approach_stations) and reports the mean E_pregrasp the same way; --out writes the
-       records as JSON.
+       approach distance; K defaults to --approach_stations) and reports the mean E_pregrasp the same way; --w_squeeze > 0
+       adds the squeeze term (contact closing feasibility, the reference's E_manipulativity as one launch) and reports the mean
+       E_squeeze at the start and at the end; --out writes the records as JSON.
 """
 import argparse
 import json
@@ -46,6 +47,7 @@ ap.add_argument("--approach_stations", type=int, default=4)
 ap.add_argument("--w_pregrasp", type=float, default=0.0)
 ap.add_argument("--pregrasp_opening", type=float, default=0.5)
 ap.add_argument("--pregrasp_stations", type=int, default=None)
+ap.add_argument("--w_squeeze", type=float, default=0.0)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
@@ -60,6 +62,9 @@ if APPROACH:
 PREGRASP = args.w_pregrasp > 0
 if PREGRASP:
     weights["E_pregrasp"] = args.w_pregrasp
+SQUEEZE = args.w_squeeze > 0
+if SQUEEZE:
+    weights["E_squeeze"] = args.w_squeeze
 records = []
 
 
@@ -98,6 +103,8 @@ for n_obj in args.n_objects:
     approach0 = float(st.terms[i_approach].mean()) if APPROACH else None
     i_pregrasp = st.term_names.index("E_pregrasp") if PREGRASP else None
     pregrasp0 = float(st.terms[i_pregrasp].mean()) if PREGRASP else None
+    i_squeeze = st.term_names.index("E_squeeze") if SQUEEZE else None
+    squeeze0 = float(st.terms[i_squeeze].mean()) if SQUEEZE else None
     st.capture(iters=8)
     hist = {}
     acc = []
@@ -153,6 +160,9 @@ for n_obj in args.n_objects:
                     "rows_with_E_pregrasp_final": int((st.terms[i_pregrasp] > 0).sum())})
         print(f"  pregrasp: mean E_pregrasp {pregrasp0:.4f} -> {rec['E_pregrasp_mean_final']:.6f}, {rec['rows_with_E_pregrasp_final']} "
               f"of {st.B} rows still meet an obstacle with the hand opened", flush=True)
+    if SQUEEZE:
+        rec.update({"w_squeeze": args.w_squeeze, "E_squeeze_mean_initial": squeeze0, "E_squeeze_mean_final": float(st.terms[i_squeeze].mean())})
+        print(f"  squeeze: mean E_squeeze {squeeze0:.3e} -> {rec['E_squeeze_mean_final']:.3e}", flush=True)
     records.append(rec)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
