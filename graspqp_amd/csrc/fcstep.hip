@@ -3,11 +3,12 @@
 //   gq_fc_head_kernel   contact terms of E_dis (energy.py:25-28) -> outward object normals (object_model.py:246) ->
 //                       friction-cone grasp matrix F (span.py:263-295,341-346) -> all PDIPM iterations of the box QP
 //                       (qp_solver.py:60-134 -> qpth), F never leaves the registers in between
-//   gq_fc_tail_kernel   the row's best iterate (two candidates with fixed addresses are requested at once: the slot the
-//                       head keeps current and the last iteration's snapshot) -> E_fc (span.py:402, registry.py:82-87)
-//                       -> KKT-implicit backward of the QP -> d E_fc / d contact points; beside the row's wavefront three
-//                       more share qpth's batch-global stop rule on the (B, max_iter) residual table (no grid-wide
-//                       dependency, no extra launch) and hand k* over through LDS (see gq_fc_tail_body)
+//   gq_fc_tail_kernel   the row's best iterate (two candidates have fixed addresses: the slot the head keeps current and
+//                       the last iteration's snapshot) -> E_fc (span.py:402, registry.py:82-87) -> KKT-implicit backward
+//                       of the QP -> d E_fc / d contact points.  Small batches: two wavefronts evaluate one candidate each
+//                       while two more share qpth's batch-global stop rule on the (B, max_iter) residual table (no
+//                       grid-wide dependency, no extra launch) and hand k* over through LDS; the wavefront that holds the
+//                       best iterate among 0..k* stores (see gq_fc_tail_body)
 //
 // Same arithmetic as the building blocks gq_contact_terms / gq_fc_forward / gq_fc_backward (fc.hip, loop.hip), which
 // remain the C-ABI surface of the autograd route; this file is what GraspStepper runs.
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(GQ_HEAD_ROWS* GQ_WAVE, NC == 1 ? 4 : 2) void gq_fc_
 }
 template <int NC, int RPL>
 __global__ __launch_bounds__(RPL > 0 ? 4 * GQ_WAVE : GQ_WAVE, (NC == 1 && RPL == 0) ? 4 : 1) void gq_fc_tail_kernel(GqFcStepArgs g) {  // NC = 1: 4 wavefronts per SIMD (<= 128 VGPRs)
-  extern __shared__ float gq_sh[];  // RPL > 0: three more wavefronts per row share the stop rule (gq_fc_tail_body)
+  extern __shared__ float gq_sh[];  // RPL > 0: two wavefronts evaluate, two share the stop rule (gq_fc_tail_body)
   gq_fc_tail_body<NC, RPL>(g, (int)blockIdx.x, gq_sh);
 }
 
@@ -60,7 +61,7 @@ int gq_fc_step(const float* dist_sq, const int32_t* sign, const float* obj_dir, 
   int rc = gq_fc_step_fill(d, &a, &runmin, &stop);
   if (rc) return rc;
   const int nz = a.nz;
-  const dim3 grid((unsigned)batch), block(GQ_WAVE), block4(4 * GQ_WAVE);  // block4: the row's wavefront + three that share the stop rule
+  const dim3 grid((unsigned)batch), block(GQ_WAVE), block4(4 * GQ_WAVE);  // block4: two evaluating wavefronts + two that share the stop rule
   const size_t lds_head = (size_t)n_contact * 6 * sizeof(float), lds_tail = gq_fc_tail_lds_bytes(nz);
   const bool two = nz > GQ_WAVE;
   if (stop == GQ_STOP_HEAD) {  // the stop rule rides in the head launch (see gq_fc_head_epilogue)

@@ -335,37 +335,19 @@ __device__ __forceinline__ int gq_qp_stop_apply(const float* red, int max_iter, 
   return stop_at;
 }
 
-// LDS of one tail row (bytes): nz x 3 floats (x for x_sum, then the per-column gradient contributions) | 16 x 3 words of
-// stop-rule records
-__host__ __device__ inline size_t gq_fc_tail_lds_bytes(int nz) { return ((size_t)nz * 3 + 48) * sizeof(float); }
+// LDS of one tail row (bytes): 2 x nz x 3 floats (per evaluating wavefront: x for x_sum, then the per-column gradient
+// contributions) | 16 x 3 words of stop-rule records
+__host__ __device__ inline size_t gq_fc_tail_lds_bytes(int nz) { return ((size_t)nz * 6 + 48) * sizeof(float); }
 
-// One block = one row, called by every thread of the block; wavefront 0 does the row's work.
-// RPL > 0: the stop rule is replayed here (B <= 64*RPL, max_iter <= 16) by the block's OTHER wavefronts (at least one),
-// which divide its iterations among themselves (gq_qp_stop_reduce) and hand their records over through LDS and one block
-// barrier; wavefront 0 applies the rule to them (gq_qp_stop_apply).  RPL == 0: k* was written by the head epilogue or a
-// stop launch and the block's other wavefronts leave.
-// The row does not wait for k* to ask for its iterate.  Two candidates have fixed addresses and are requested with the
-// first loads: the slot in which the head keeps the row's best iterate among iterations 0 .. max_iter - 2
-// (GqQpArgs.slot), and the snapshot of the last iteration.  In the regime of the MALA* loop the rule stops at the last
-// iteration or the one before in all but a few per cent of the launches, and then one of the two IS the best iterate
-// among 0..k*; only when the rule stops before the slot's iteration does the row go back to memory for the snapshot of
-// the true best.  What does not depend on the iterate (F F', its factor, the svd term) is computed while the stop
-// rule runs.  Nothing of the row is stored before k* is known.
-// sh: gq_fc_tail_lds_bytes(nz) of LDS; rec: -DGQ_BLOCK_TIMES record of the block or null.
-template <int NC, int RPL>
-__device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, float* sh, uint64_t* rec = nullptr) {
+// The tail of a row whose k* is in memory already (RPL == 0 of gq_fc_tail_body: large batches, the head epilogue or a stop
+// launch wrote it): wavefront 0 does the row's work in one pass, storing as it goes, and the block's other wavefronts
+// leave.  Both candidates are requested with the first loads all the same, so that k* costs no dependent round trip.
+// The arithmetic is that of the evaluation in gq_fc_tail_body, statement by statement.
+template <int NC>
+__device__ __forceinline__ void gq_fc_tail_known_body(const GqFcStepArgs& g, int row, float* sh) {
   const int lane = gq_lane(), wv = (int)threadIdx.x / GQ_WAVE;
   const int nz = g.nz;
-  float* s_red = sh + (size_t)nz * 3;
-  if (wv > 0) {
-    if (RPL == 0) return;
-    gq_qp_stop_reduce<(RPL > 0 ? RPL : 1)>(g.resid, g.mu_tab, g.B, g.max_iter, lane, wv - 1, (int)blockDim.x / GQ_WAVE - 1, s_red);
-#ifdef GQ_BLOCK_TIMES
-    if (rec && wv == 1 && lane == 0) rec[2] = __builtin_amdgcn_s_memrealtime();
-#endif
-    __syncthreads();
-    return;
-  }
+  if (wv > 0) return;
   // loads that depend on nothing computed here go first: the row's columns of F, the E_dis part of the contact gradient
   // that the E_fc part is added to at the very end, the row's residuals (lane it holds iteration it), both candidates
   GqLr<6, NC> S;
@@ -392,8 +374,7 @@ __device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, 
     const float* o = g.g_cpts + ((size_t)row * g.n + lane) * 3;
     gc0 = gq_mk(o[0], o[1], o[2]);
   }
-  int ks = 0;
-  if (RPL == 0) ks = g.kstar[0];
+  int ks = g.kstar[0];
   const float mine = (lane < g.max_iter) ? g.resid[(size_t)row * g.max_iter + lane] : 0.0f;  // max_iter <= 64
   // ---- what does not depend on the iterate: F F' and its Cholesky factor -------------------------------------------
   double part[21];
@@ -424,29 +405,10 @@ __device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, 
     }
   }
   const float r_last = gq_readlane(mine, last);
-#ifdef GQ_BLOCK_TIMES
-  if (rec && lane == 0) rec[3] = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (RPL > 0) {  // the only wait for the stop wavefronts
-    __syncthreads();
-    ks = gq_qp_stop_apply(s_red, g.max_iter, g.eps, g.not_improved_lim);
-    if (row == 0 && lane == 0) {
-      g.kstar[0] = ks;
-      g.kstar[1] = ks + 1;
-      if (g.n_iter) *g.n_iter = ks + 1;
-    }
-  }
   ks = __builtin_amdgcn_readfirstlane(ks);
   // best iterate of this row among iterations 0..k* (qpth returns the per-row best, not the last)
   const bool use_last = ks == last && (last == 0 || r_last < bst_a);  // false for NaN: a NaN iterate never becomes best
   const bool redo = !use_last && bi_a > ks;  // the rule stopped before the slot's iteration
-#ifdef GQ_BLOCK_TIMES
-  if (rec && lane == 0) {  // k* known | running counts over the launches: rows that went back to memory, launches
-    rec[7] = __builtin_amdgcn_s_memrealtime();
-    rec[4] += redo ? 1u : 0u;
-    rec[5] += 1u;
-  }
-#endif
   float it5[NC][5];
 #pragma unroll
   for (int c = 0; c < NC; ++c)
@@ -581,6 +543,310 @@ __device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, 
       o[0] += sx;
       o[1] += sy;
       o[2] += sz;
+    }
+  }
+}
+
+// One block = one row, called by every thread of the block.
+// RPL == 0: k* was written by the head epilogue or a stop launch: gq_fc_tail_known_body.
+// RPL > 0: the stop rule is replayed here (B <= 64*RPL, max_iter <= 16) by the block's wavefronts 2.. (at least one),
+// which divide its iterations among themselves (gq_qp_stop_reduce) and hand their records over through LDS and one block
+// barrier.  The row does not wait for k* to do its arithmetic.  Two candidates have fixed addresses: the slot in which
+// the head keeps the row's best iterate among iterations 0 .. max_iter - 2 (GqQpArgs.slot), and the snapshot of the last
+// iteration.  In the regime of the MALA* loop the rule stops at the last iteration or the one before in all but a few
+// per cent of the launches, and then one of the two IS the best iterate among 0..k*.  So wavefront 0 EVALUATES the slot
+// and wavefront 1 the last snapshot (when the row's own residuals make it eligible at all) while the rule runs: E_fc,
+// the QP backward and the contact gradient, all kept in registers.  After the barrier both apply the rule
+// (gq_qp_stop_apply) and the wavefront that holds the row's best iterate COMMITS, i.e. stores.  Only when the rule
+// stops before the slot's iteration does wavefront 0 go back to memory for the snapshot of the true best and evaluate
+// again.  Both wavefronts run the same instruction stream on different data (one evaluation, in a loop that the rare
+// case enters twice), and what does not depend on the iterate (F F', its factor, the svd term) is computed by both.
+// Nothing of the row is stored before k* is known, and nothing twice.
+// sh: gq_fc_tail_lds_bytes(nz) of LDS; rec: -DGQ_BLOCK_TIMES record of the block or null.
+template <int NC, int RPL>
+__device__ __forceinline__ void gq_fc_tail_body(const GqFcStepArgs& g, int row, float* sh, uint64_t* rec = nullptr) {
+  if (RPL == 0) return gq_fc_tail_known_body<NC>(g, row, sh);
+  constexpr int NEV = 2;  // evaluating wavefronts
+  const int lane = gq_lane(), wv = (int)threadIdx.x / GQ_WAVE;
+  const int nz = g.nz;
+  float* s_red = sh + (size_t)nz * 3 * NEV;
+  if (wv >= NEV) {
+    gq_qp_stop_reduce<(RPL > 0 ? RPL : 1)>(g.resid, g.mu_tab, g.B, g.max_iter, lane, wv - NEV, (int)blockDim.x / GQ_WAVE - NEV, s_red);
+#ifdef GQ_BLOCK_TIMES
+    if (rec && wv == NEV && lane == 0) rec[2] = __builtin_amdgcn_s_memrealtime();
+#endif
+    __syncthreads();
+    // k* goes to memory (gq_fc_peek, n_iter) from here and not from an evaluating wavefront, whose scalar registers are
+    // all taken while the candidates are evaluated: two pointers less to hold across the evaluation
+    if (row == 0 && wv == NEV) {
+      const int ks = gq_qp_stop_apply(s_red, g.max_iter, g.eps, g.not_improved_lim);
+      if (lane == 0) {
+        g.kstar[0] = ks;
+        g.kstar[1] = ks + 1;
+        if (g.n_iter) *g.n_iter = ks + 1;
+      }
+    }
+    return;
+  }
+  const int ev = __builtin_amdgcn_readfirstlane(wv);  // 0: the slot candidate, 1: the last snapshot
+  float* shw = sh + (size_t)ev * nz * 3;
+  // ---- prologue -----------------------------------------------------------------------------------------------------
+  // loads that depend on nothing computed here go first: the row's columns of F, the E_dis part of the contact gradient
+  // that the E_fc part is added to at the very end, the row's residuals (lane it holds iteration it), the candidate
+  GqLr<6, NC> S;
+  S.ridge = g.ridge;
+  bool live[NC];
+  const int last = g.max_iter - 1;
+  const float* sl_a = g.slot + ((size_t)row * nz) * 5;
+  const float* sn_l = g.snap + (((size_t)row * g.max_iter + last) * 5) * nz;
+  float it5[NC][5];  // the iterate (x, z_u, z_l, s_u, s_l): this wavefront's candidate
+  const float* cand = ev ? sn_l : sl_a;
+  const size_t cs_i = ev ? 1 : 5, cs_q = ev ? (size_t)nz : 1;  // slot: (nz, 5); snapshot: (5, nz)
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int i = lane + GQ_WAVE * c;
+    live[c] = i < nz;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) S.a[c][q] = live[c] ? g.F[((size_t)row * 6 + q) * nz + i] : 0.0f;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) it5[c][q] = live[c] ? cand[(size_t)i * cs_i + (size_t)q * cs_q] : 0.0f;
+  }
+  gq3 gc0 = gq_mk(0, 0, 0);
+  if (lane < g.n) {
+    const float* o = g.g_cpts + ((size_t)row * g.n + lane) * 3;
+    gc0 = gq_mk(o[0], o[1], o[2]);
+  }
+  int ks = 0;
+  const float mine = (lane < g.max_iter) ? g.resid[(size_t)row * g.max_iter + lane] : 0.0f;  // max_iter <= 64
+  // what does not depend on the iterate: F F' and its Cholesky factor
+  double part[21];
+#pragma unroll
+  for (int i = 0; i < 21; ++i) part[i] = 0.0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = 0; b <= a; ++b) part[a * (a + 1) / 2 + b] += (double)S.a[c][a] * (double)S.a[c][b];
+  gq_wave_sums_d<21>(part);  // F F'
+  double Lm[21], inv[6];
+  const bool ok = gq_chol6(part, Lm, inv);
+  double lp = 1.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) lp *= Lm[i * (i + 1) / 2 + i];
+  const float svd = ok ? powf((float)lp, 1.0f / 6.0f) : 0.0f;  // (prod sigma)^(1/6) = det(F F')^(1/12)
+  const float ex = expf(-g.svd_gain * svd);
+  // the slot's iteration: the last one among 0 .. last - 1 that improved the row's residual (the head's recording rule)
+  int bi_a = 0;
+  float bst_a = 0.0f;
+  for (int it = 0; it < last; ++it) {
+    const float rs = gq_readlane(mine, it);
+    if (it == 0 || rs < bst_a) {
+      bst_a = rs;
+      bi_a = it;
+    }
+  }
+  const float r_last = gq_readlane(mine, last);
+  const bool last_ok = last == 0 || r_last < bst_a;  // false for NaN: a NaN iterate never becomes best
+#ifdef GQ_BLOCK_TIMES
+  if (rec && ev == 0 && lane == 0) rec[3] = __builtin_amdgcn_s_memrealtime();
+#endif
+  // best iterate of this row among iterations 0..k* (qpth returns the per-row best, not the last):
+  //   use_last  k* is the last iteration and that iterate improved the row
+  //   redo      else, and the rule stopped before the slot's iteration: back to the table
+  bool use_last = false, redo = false;
+  bool decided = false;  // k* is known
+  bool have = ev ? last_ok : last > 0;  // this wavefront has a candidate to evaluate (wave-uniform)
+  // results of an evaluation, in registers until the commit
+  float x[NC], xs[NC], val = 0.0f;
+  gq3 gps[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    x[c] = xs[c] = 0.0f;
+    gps[c] = gq_mk(0, 0, 0);
+  }
+#pragma nounroll
+  for (;;) {
+    if (decided && redo) {  // wave-uniform, rare: the snapshot of the best iteration among 0..k*
+      int bi = 0;
+      float bst = 0.0f;
+      for (int it = 0; it <= ks; ++it) {
+        const float rs = gq_readlane(mine, it);
+        if (it == 0 || rs < bst) {
+          bst = rs;
+          bi = it;
+        }
+      }
+      const float* sn = g.snap + (((size_t)row * g.max_iter + bi) * 5) * nz;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int q = 0; q < 5; ++q) it5[c][q] = live[c] ? sn[(size_t)q * nz + lane + GQ_WAVE * c] : 0.0f;
+    }
+    int nk = g.k;  // opaque like max_iter below: no loop-invariant condition on it is formed in front of the loop
+    asm volatile("" : "+s"(nk));
+    if (have) {
+      // ---- evaluate: E_fc, the QP backward and the contact gradient of the iterate in it5; no store ---------------------
+      float du[NC], dl[NC], lam[NC];
+      float r[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        x[c] = 0.0f;
+        du[c] = dl[c] = 1.0f;
+        if (live[c]) {
+          x[c] = it5[c][0];
+          const float zu = it5[c][1], zl = it5[c][2], su = it5[c][3], sl = it5[c][4];
+          du[c] = fmaxf(zu, 1e-8f) / fmaxf(su, 1e-8f);
+          dl[c] = fmaxf(zl, 1e-8f) / fmaxf(sl, 1e-8f);
+        }
+        lam[c] = g.ridge + du[c] + dl[c];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) r[a] = fmaf(S.a[c][a], x[c], r[a]);
+      }
+#pragma unroll
+      for (int a = 0; a < 6; ++a) r[a] = gq_dpp_sum(r[a]);  // F x
+      val = 0.0f;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) val = fmaf(r[a], r[a], val);
+      val *= 0.5f;
+      if (g.x_sum) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (live[c]) shw[lane + GQ_WAVE * c] = x[c];
+        gq_wave_sync();
+#pragma unroll
+        for (int j = 0; j < NC; ++j) {  // n <= nz <= 64 NC
+          const int c = lane + GQ_WAVE * j;
+          if (c < g.n) {
+            float s = 0.0f;
+            for (int e = 0; e < nk; ++e) s += shw[c * nk + e];
+            xs[j] = s;
+          }
+        }
+        gq_wave_sync();
+      }
+      // backward with upstream gradient w_fc on E_fc
+      const float gval = g.w_fc * g.values_gain * ex;
+      const float gsvd = ok ? g.w_fc * g.values_gain * (val + g.eps_add) * ex * (-g.svd_gain) : 0.0f;
+      // QP backward (qpth QPFunction.backward): dx = -(Q + diag(d_u + d_l))^-1 dl/dx with dl/dx = gval * F'(F x)
+      float rhs[NC], dx[NC];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        float ftr = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) ftr = fmaf(S.a[c][q], r[q], ftr);
+        rhs[c] = live[c] ? -gval * ftr : 0.0f;
+      }
+      S.factor(lam, live);
+      S.solve(rhs, dx);
+      float fd[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int a = 0; a < 6; ++a) fd[a] = fmaf(S.a[c][a], live[c] ? dx[c] : 0.0f, fd[a]);
+#pragma unroll
+      for (int a = 0; a < 6; ++a) fd[a] = gq_dpp_sum(fd[a]);  // F dx
+      const float s6 = gsvd * svd / 6.0f;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        if (live[c]) {
+          const int i = lane + GQ_WAVE * c;
+          // d(prod sigma^(1/6))/dF = svd/6 * (F F')^-1 F : solve L L' w = f_i
+          double w[6];
+#pragma unroll
+          for (int a = 0; a < 6; ++a) w[a] = (double)S.a[c][a];
+#pragma unroll
+          for (int a = 0; a < 6; ++a) {
+#pragma unroll
+            for (int t = 0; t < a; ++t) w[a] -= Lm[a * (a + 1) / 2 + t] * w[t];
+            w[a] *= inv[a];
+          }
+#pragma unroll
+          for (int a = 5; a >= 0; --a) {
+#pragma unroll
+            for (int t = a + 1; t < 6; ++t) w[a] -= Lm[t * (t + 1) / 2 + a] * w[t];
+            w[a] *= inv[a];
+          }
+          // gradient wrt the torque rows of column i (rows 3..5); tau = tw (r x f) -> d/dr = tw (f x g_tau)
+          //   g_tau = (gval r + F dx) x + r dx + s6 w, with the roundings spelled out (the sums of two products leave the
+          //   compiler a choice of which product to fuse, and it depends on the code around them)
+          gq3 gt;
+          gt.x = fmaf(s6, (float)w[3], fmaf(fmaf(gval, r[3], fd[3]), x[c], r[3] * dx[c]));
+          gt.y = fmaf(s6, (float)w[4], fmaf(fmaf(gval, r[4], fd[4]), x[c], r[4] * dx[c]));
+          gt.z = fmaf(s6, (float)w[5], fmaf(fmaf(gval, r[5], fd[5]), x[c], r[5] * dx[c]));
+          const gq3 gp = g.tw * gq_cross(gq_mk(S.a[c][0], S.a[c][1], S.a[c][2]), gt);
+          shw[i * 3] = gp.x;
+          shw[i * 3 + 1] = gp.y;
+          shw[i * 3 + 2] = gp.z;
+        }
+      }
+      gq_wave_sync();
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        const int c = lane + GQ_WAVE * j;
+        if (c < g.n) {
+          float sx = 0, sy = 0, sz = 0;
+          for (int e = 0; e < nk; ++e) {
+            sx += shw[(c * nk + e) * 3];
+            sy += shw[(c * nk + e) * 3 + 1];
+            sz += shw[(c * nk + e) * 3 + 2];
+          }
+          gps[j] = gq_mk(sx, sy, sz);
+        }
+      }
+    }
+    if (decided) break;
+    // ---- the only wait for the stop wavefronts ------------------------------------------------------------------------
+#ifdef GQ_BLOCK_TIMES
+    if (rec && ev == 0 && lane == 0) rec[5] = __builtin_amdgcn_s_memrealtime();  // candidate evaluated
+#endif
+    __syncthreads();
+    // the rule's sixteen `it < max_iter` are loop-invariant, and hoisted in front of the loop they would hold 32 scalar
+    // registers across the evaluation: max_iter is made opaque here so that they are formed where they are used
+    int mi = g.max_iter;
+    asm volatile("" : "+s"(mi));
+    ks = __builtin_amdgcn_readfirstlane(gq_qp_stop_apply(s_red, mi, g.eps, g.not_improved_lim));
+    use_last = ks == last && last_ok;
+    redo = !use_last && bi_a > ks;
+    decided = true;
+#ifdef GQ_BLOCK_TIMES
+    if (rec && ev == 0 && lane == 0) {  // k* known | running counts: rows that went back to memory (low word), launches (high word)
+      rec[7] = __builtin_amdgcn_s_memrealtime();
+      rec[4] += (redo ? 1ull : 0ull) + (1ull << 32);
+    }
+#endif
+    if (ev) {  // wavefront 1 commits the last snapshot or leaves
+      have = use_last;
+      break;
+    }
+    have = !use_last;  // wavefront 0 commits the slot, or the table's iterate after a second evaluation
+    if (!redo) break;
+  }
+  if (!have) return;
+  // ---- commit: the stores of the row ---------------------------------------------------------------------------------
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (live[c]) g.x[(size_t)row * nz + lane + GQ_WAVE * c] = x[c];
+  if (lane == 0) {
+    g.val[row] = val;
+    g.svd[row] = svd;
+    g.e_fc[row] = g.values_gain * (val + g.eps_add) * ex;
+  }
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const int c = lane + GQ_WAVE * j;
+    if (c < g.n) {
+      if (g.x_sum) g.x_sum[(size_t)row * g.n + c] = xs[j];
+      float* o = g.g_cpts + ((size_t)row * g.n + c) * 3;
+      if (j == 0) {  // c == lane: the E_dis part was fetched at the top
+        o[0] = gc0.x + gps[j].x;
+        o[1] = gc0.y + gps[j].y;
+        o[2] = gc0.z + gps[j].z;
+      } else {
+        o[0] += gps[j].x;
+        o[1] += gps[j].y;
+        o[2] += gps[j].z;
+      }
     }
   }
 }

@@ -726,9 +726,15 @@ __host__ __device__ inline size_t gq_pen_bwd_lds_bytes() {
 // registers per thread whether it exists or not, so the launcher picks the smallest K that covers the surface points in
 // one round (K = 10 for the 2500 points of the reference: 120 instead of 162 VGPRs for the stand-alone kernel).  The
 // order of all sums is independent of K.
-template <int K = GQ_PENB_K>
-__device__ __forceinline__ void gq_pen_bwd_body(const GqPenBwdArgs& g, int row, char* lds) {
+// ESUM_EARLY (the role of stage B, which is as long as its chain of barriers): the E_pen wave sums are formed before the
+// fold of the last round and published through the barrier behind that round's list, in the counter table behind the K
+// slices, instead of two barriers of their own at the very end; the barrier behind the last fold goes as well, since
+// nothing writes the list again.  Point order, lane order and wave order of the sum stay as they are.
+// rec: -DGQ_BLOCK_TIMES record of the block or null ([2] dis landed, [3] list built, [4] fold done; first round).
+template <int K = GQ_PENB_K, bool ESUM_EARLY = false>
+__device__ __forceinline__ void gq_pen_bwd_body(const GqPenBwdArgs& g, int row, char* lds, uint64_t* rec = nullptr) {
   static_assert(K >= 4 && K <= GQ_PENB_K, "a round must fit the LDS list and the counter table");
+  static_assert(!ESUM_EARLY || K < GQ_PENB_K, "the E_pen wave sums ride in the counter table behind the K slices");
   float* s_rec = reinterpret_cast<float*>(lds);
   int* s_cnt = reinterpret_cast<int*>(s_rec + GQ_PENB_LIST * 6);
   unsigned char* s_lnk = reinterpret_cast<unsigned char*>(s_cnt + GQ_PENB_K * 4);
@@ -753,6 +759,7 @@ __device__ __forceinline__ void gq_pen_bwd_body(const GqPenBwdArgs& g, int row, 
     }
   }
   float e_acc = 0.0f;
+  bool e_done = false;  // ESUM_EARLY: e_pen went out with the last round's list
   for (int base = 0; base < g.P;) {
     float w[K], dpos[K];
 #pragma unroll
@@ -773,6 +780,9 @@ __device__ __forceinline__ void gq_pen_bwd_body(const GqPenBwdArgs& g, int row, 
       m[k] = __ballot(w[k] != 0.0f);
       if (lane == 0) s_cnt[k * 4 + wv] = __popcll(m[k]);
     }
+#ifdef GQ_BLOCK_TIMES
+    if (rec && base == 0 && tid == 0) rec[2] = __builtin_amdgcn_s_memrealtime();
+#endif
     __syncthreads();
     // as many 256-point slices as fit into the LDS list (a slice holds <= 256 entries, so at least four always do);
     // the remaining slices are taken up again by the next round.  The (slice, wave) counts are read once, 16 B each.
@@ -813,7 +823,19 @@ __device__ __forceinline__ void gq_pen_bwd_body(const GqPenBwdArgs& g, int row, 
     }
     const bool first = base == 0;
     base += kfit * 256;
+    if (ESUM_EARLY && g.e_pen && base >= g.P) {  // block-uniform: the last round, e_acc is complete
+      const float ws = gq_dpp_sum(e_acc);
+      if (lane == 0) reinterpret_cast<float*>(s_cnt)[K * 4 + wv] = ws;
+      e_done = true;
+    }
     __syncthreads();
+    if (ESUM_EARLY && e_done && tid == 0) {  // waves 0..3, as below
+      const float* s_e = reinterpret_cast<const float*>(s_cnt) + K * 4;
+      g.e_pen[row] = ((s_e[0] + s_e[1]) + s_e[2]) + s_e[3];
+    }
+#ifdef GQ_BLOCK_TIMES
+    if (rec && first && tid == 0) rec[3] = __builtin_amdgcn_s_memrealtime();
+#endif
     const int n = run;  // block-uniform
     // fold, wave-parallel and in a fixed order: a wavefront takes a group of 4 links (24 accumulators) or the group of
     // the 12 global sums; lane j adds entries j, j+64, ... into registers, then the fixed DPP tree adds the lanes.
@@ -881,9 +903,13 @@ __device__ __forceinline__ void gq_pen_bwd_body(const GqPenBwdArgs& g, int row, 
         }
       }
     }
+#ifdef GQ_BLOCK_TIMES
+    if (rec && first && tid == 0) rec[4] = __builtin_amdgcn_s_memrealtime();
+#endif
+    if (ESUM_EARLY && e_done) break;
     __syncthreads();
   }
-  if (g.e_pen) {  // fixed order: thread-local (k ascending), DPP tree per wave, waves 0..3
+  if (g.e_pen && !e_done) {  // fixed order: thread-local (k ascending), DPP tree per wave, waves 0..3
     const float ws = gq_dpp_sum(e_acc);
     if (lane == 0) s_rec[wv] = ws;
     __syncthreads();

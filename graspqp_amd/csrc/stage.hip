@@ -4,9 +4,11 @@
 //   stage A   blocks [0, B/4)        fc head   contact terms + cone matrix + all QP iterations; 4 rows per block,
 //                                              one wavefront (SIMD) each
 //             blocks [B/4, .. + gx B) pen query penetration-only hand query of 256 surface points of one row
-//   stage B   blocks [0, B)          fc tail   E_fc + QP backward + contact gradient (wave 0) beside the stop rule (waves
-//                                              1..3 share its iterations); the row's iterate is requested before k* is known
-//             blocks [B, 2B)         pen bwd   link wrenches + E_pen of one row
+//   stage B   blocks [0, B)          fc tail   E_fc + QP backward + contact gradient of BOTH candidate iterates (wave 0 the
+//                                              best-iterate slot, wave 1 the last snapshot) beside the stop rule (waves 2..3
+//                                              share its iterations); the wave that holds the iterate k* selects stores
+//             blocks [B, 2B)         pen bwd   link wrenches + E_pen of one row (small batches, <= 2560 surface points: ten
+//                                              slices per round, E_pen published through the barrier behind the list)
 //             blocks [2B, 2B + B/4)  spheres   world sphere centres + self penetration (optional; 4 rows per block)
 //
 // With B = 256 rows neither branch fills 256 CUs on its own (the QP is one wavefront per row), and separate streams
@@ -122,7 +124,7 @@ __global__ __launch_bounds__(256) void gq_stage_b_kernel(GqFcStepArgs f, GqPenBw
   if (b >= 2 * f.B) {
     gq_spen_role_body(sp, b - 2 * f.B, f.B, gq_lds);
   } else if (b < f.B) {  // one row per block here: 2B blocks = two per CU at B = 256, every tail wavefront has a CU's L1 to itself
-    // wavefront 0 = the row, wavefronts 1..3 = the stop rule beside it (RPL > 0)
+    // RPL > 0: wavefronts 0 and 1 = the row's two candidate iterates, wavefronts 2..3 = the stop rule beside them
     __builtin_amdgcn_s_setprio(3);  // the longest role of this launch: dependent instruction streams
 #ifdef GQ_BLOCK_TIMES
     gq_fc_tail_body<NC, RPL>(f, b, reinterpret_cast<float*>(gq_lds), rec);
@@ -130,7 +132,15 @@ __global__ __launch_bounds__(256) void gq_stage_b_kernel(GqFcStepArgs f, GqPenBw
     gq_fc_tail_body<NC, RPL>(f, b, reinterpret_cast<float*>(gq_lds));
 #endif
   } else {
-    gq_pen_bwd_body(p, b - f.B, gq_lds);
+    // small batches (RPL > 0), where the launch is as long as its longest block: ten slices cover the reference's 2500
+    // surface points in one round, and E_pen rides on the barrier behind the list
+#ifdef GQ_BLOCK_TIMES
+    if (RPL > 0 && p.P <= 2560) gq_pen_bwd_body<10, true>(p, b - f.B, gq_lds, rec);
+    else gq_pen_bwd_body(p, b - f.B, gq_lds, rec);
+#else
+    if (RPL > 0 && p.P <= 2560) gq_pen_bwd_body<10, true>(p, b - f.B, gq_lds);
+    else gq_pen_bwd_body(p, b - f.B, gq_lds);
+#endif
   }
 #ifdef GQ_BLOCK_TIMES
   if (rec && threadIdx.x == 0) rec[1] = __builtin_amdgcn_s_memrealtime();

@@ -1,5 +1,6 @@
 """Block timeline of stage B (config 2), role by role: fc tail, penetration backward, self penetration.  How long does every
-role run beside the others, and inside the tail: when is k* known, when does the row wavefront reach the hand-over?
+role run beside the others, and inside the tail: when is k* known, when does the row wavefront reach the hand-over, when
+is its candidate evaluated?  Inside the penetration backward: when has dis landed, when is the list built, the fold done?
 Needs the -DGQ_BLOCK_TIMES build (tools/block_timeline.sh) through GRASPQP_HIP_LIB.  Same record scheme as
 block_timeline_stage_a.py: eight words per block behind the 128 span words, the blocks of stage A first."""
 import os, sys
@@ -53,6 +54,17 @@ tail = roles["fc tail"]
 if (tail[:, 2] != 0).any():  # the one-trip tail stamps its hand-over: [2] k* known (stop wavefront), [3] row done on the slot
     print(f"   fc tail: k* known after {pc((tail[:, 2] - tail[:, 0]) / 100.0)} us of the block, row wavefront ready to commit "
           f"after {pc((tail[:, 3] - tail[:, 0]) / 100.0)} us")
-    n_l = int(tail[:, 5].max())  # [4] / [5]: launches in which the row had to redo from the table / launches, since the start
+    print(f"   fc tail: k* known -> block end (apply + commit) {pc((tail[:, 1] - tail[:, 7]) / 100.0)} us")
+    # [4] / [5]: launches in which the row had to redo from the table / launches, since the start.  The tail that evaluates
+    # both candidates before k* packs the two counts into [4] (low / high word) and stamps "candidate evaluated" in [5]
+    redo, n_l = tail[:, 4], int(tail[:, 5].max())
+    if (tail[:, 4] >> 32).any():
+        redo, n_l = tail[:, 4] & 0xFFFFFFFF, int((tail[:, 4] >> 32).max())
+        print(f"   fc tail: candidate evaluated (wavefront 0) after {pc((tail[:, 5] - tail[:, 0]) / 100.0)} us of the block")
+    tail = np.concatenate([tail[:, :4], redo[:, None], tail[:, 5:]], 1)
     print(f"   fc tail: {n_l} launches; rows that redo from the table per launch: mean {tail[:, 4].sum() / max(n_l, 1):.2f} of {B}, "
           f"per-row redo rate min / max {tail[:, 4].min() / max(n_l, 1):.3f} / {tail[:, 4].max() / max(n_l, 1):.3f}")
+pen = roles["pen backward"]
+if (pen[:, 2] != 0).any():  # phases of the penetration backward's first round: [2] dis landed, [3] list built, [4] fold done
+    for name, a, b in (("dis landed", 0, 2), ("list built", 2, 3), ("fold done", 3, 4), ("end", 4, 1)):
+        print(f"   pen backward: {name:10s} +{pc((pen[:, b] - pen[:, a]) / 100.0)} us   (after the block start {pc((pen[:, b] - pen[:, 0]) / 100.0)})")
