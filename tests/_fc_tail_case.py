@@ -1,7 +1,5 @@
 """One gq_fc_step launch on recorded contacts with every output of the tail kept -- shared by
 tools/make_golden_fc_tail.py (which records the parent's bits) and tests/test_gpu_fc_tail_candidates.py."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -12,42 +10,16 @@ SENTINEL = 12345.0
 OUTPUTS = ("e_fc", "val", "svd", "x", "x_sum", "g_cpts", "n_iter")
 
 
-def _view(ws, ptr, count):
-    off = int(ptr.value) - ws.data_ptr()
-    return ws[off:off + 4 * count].view(torch.float32)
-
-
 def run(gq, pts, nrm, cog, eps, max_iter):
     """gq_fc_step on B rows -> dict of numpy arrays (OUTPUTS) + F.  e_fc, x_sum and the workspace's x, val, svd are
-    pre-filled with SENTINEL; g_cpts is the head's E_dis part plus the tail's E_fc part."""
-    from graspqp_amd import _C
+    pre-filled with SENTINEL; g_cpts is the head's E_dis part plus the tail's E_fc part.  The launch is that of
+    tests/_fc_step_case.py::run at these settings, with its guard rows."""
+    import _fc_step_case as fsc
 
-    B = pts.shape[0]
-    f = lambda t: torch.as_tensor(t).float().cuda().contiguous()
-    p, nr, cg = f(pts), f(nrm), f(cog)
-    d2 = torch.full((B, N), 1e-4, device="cuda")
-    sgn = torch.ones(B, N, dtype=torch.int32, device="cuda")
-    closest = (p - 0.01 * nr).contiguous()
-    hand_n = (-nr).contiguous()
-    obj_normal, g_cpts, g_cnrm = (torch.full_like(p, SENTINEL) for _ in range(3))
-    e = torch.full((B,), SENTINEL, device="cuda")
-    xs = torch.full((B, N), SENTINEL, device="cuda")
-    nit = torch.zeros(1, dtype=torch.int32, device="cuda")
-    nb = gq._size_call("gq_fc_workspace_bytes", ctypes.c_int64(B), N, K, max_iter)
-    ws = gq._ws(nb, p.device).zero_()
-    Fp, xp, vp, sp = gq.fc_peek(ws, B, N, K)
-    x, val, svd = _view(ws, xp, B * N * K), _view(ws, vp, B), _view(ws, sp, B)
-    for t in (x, val, svd):
-        t.fill_(SENTINEL)
-    _C.call("gq_fc_step", _C.f32(d2), _C.i32(sgn), _C.f32(nr), _C.f32(closest), _C.f32(p), _C.f32(hand_n), _C.f32(cg), B, N, K,
-            FC["friction"], FC["torque_weight"], FC["max_limit"], FC["svd_gain"], FC["values_gain"], float(eps), int(max_iter),
-            W_DIS, W_FC, _C.f32(obj_normal), _C.f32(g_cpts), _C.f32(g_cnrm), _C.f32(e), _C.f32(xs), _C.i32(nit), _C.ptr(ws), nb,
-            _C.stream_ptr())
-    torch.cuda.synchronize()
-    out = {"e_fc": e, "val": val, "svd": svd, "x": x.view(B, N * K), "x_sum": xs, "g_cpts": g_cpts, "n_iter": nit}
-    out = {k: v.detach().cpu().numpy().copy() for k, v in out.items()}
-    out["F"] = _view(ws, Fp, B * 6 * N * K).view(B, 6, N * K).clone()
-    return out
+    assert fsc.SENTINEL == SENTINEL
+    d2, sgn, obj_dir, closest, hand_n = fsc.plain_contact_inputs(pts, nrm)
+    out = fsc.run(gq, N, K, FC, eps, max_iter, W_DIS, W_FC, d2, sgn, obj_dir, closest, pts, hand_n, cog)
+    return {k: out[k] for k in OUTPUTS + ("F",)}
 
 
 def best_iterations(gq, F, max_iter):

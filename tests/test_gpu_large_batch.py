@@ -1,7 +1,10 @@
 """GPU parity at the batch sizes of BASELINE configs 3 / 4 / 5 (per rank), which take a different launch sequence than
 config 2: for more than 512 rows the contact queries of the object SDF get their own launch (gq_sdf_forward_meshset
-instead of riding in the FK block), above 256 rows qpth's batch-global stop rule runs as a launch of its own (one
-wavefront up to 1024 rows, the tiled 1024-thread kernel above), and nz = 96 (8-edge cones) puts two QP columns on a lane.
+instead of riding in the FK block), above 256 rows qpth's batch-global stop rule runs as the epilogue of the
+force-closure head block that finishes last (max_iter <= 16: csrc/fcstep_dev.h::gq_fc_head_epilogue; a launch of its own
+-- one wavefront up to 1024 rows, the tiled 1024-thread kernel above -- serves max_iter > 16 and the raw box-QP ops), and
+nz = 96 (8-edge cones) puts two QP columns on a lane.  The routes of the fused step one by one, with the deciding row at
+every position: tests/test_gpu_fc_step_routes.py.
 
 Also here: the stop rule itself on arbitrary residual tables (bit-exact against oracle/ref_cpu/qp.py::stop_rule, with the
 deciding row in the LAST tile), a heterogeneous >= 3000-row QP batch against the oracle's PDIPM, and a scene that
