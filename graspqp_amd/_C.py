@@ -128,6 +128,10 @@ InitDesc = _struct("InitDesc", [
     ("shell_dirs", "p"), ("workspace", "p"), ("workspace_bytes", "z")])
 
 
+ArmDesc = _struct("ArmDesc", [("n_joints", "i"), ("n_seeds", "i"), ("joint_type", "p"), ("joint_T", "p"), ("joint_axis", "p"),
+                              ("lower", "p"), ("upper", "p"), ("tool_T", "p"), ("seeds", "p")])
+
+
 class SceneGrid(ctypes.Structure):
     """gqSceneGrid: a signed-distance grid of the surroundings (positive outside the obstacles), a plain struct."""
     _fields_ = [("values", ctypes.c_void_p), ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nz", ctypes.c_int),

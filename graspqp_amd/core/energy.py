@@ -187,6 +187,20 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, obj
                                                 hand_model.current_status, hand_model._fk_ws, d2.reshape(B, n), onrm.reshape(B, n, 3),
                                                 cls.reshape(B, n, 3), cp, tau, lam)
 
+    if "E_reach" in energy_names:
+        # arm reachability as ONE launch (ops.reach_terms; arm and parameters: HandModel.set_reach)
+        if getattr(hand_model, "reach", None) is None:
+            raise ValueError('calculate_energy: "E_reach" needs HandModel.set_reach(arm, arm_base, ...)')
+        arm, base, dist, stations, iters, damping, rot_scale = hand_model.reach
+        B = hand_model.hand_pose.shape[0]
+        be = object_model.batch_size_each
+        if base.shape[0] not in (1, B // be):
+            raise ValueError(f"calculate_energy: set_reach got {base.shape[0]} arm bases, the batch has {B // be} objects")
+        base_T = base if base.shape[0] == B // be else base.expand(B // be, 3, 4).contiguous()
+        losses["E_reach"] = ops.reach_terms(hand_model.hand_pose, hand_model._hand, hand_model._fk_idx, hand_model.global_rotation,
+                                            hand_model.current_status, hand_model._fk_ws, arm, base_T, be, hand_model.grasp_axis,
+                                            dist, stations, iters, damping, rot_scale)
+
     if "E_manipulativity" in energy_names:
         # energy.py:80-87: mean squared contact velocity the joints cannot produce when the contacts move along
         # normal * max(|distance|, 5 mm); differentiable (ops.joint_velocity_residuals: analytic kinematic Hessian)

@@ -272,6 +272,20 @@ class HandModel:
         ops.squeeze_check(None, 1, min_travel, damping, "HandModel.set_squeeze")
         self.squeeze = (float(min_travel), float(damping))
 
+    def set_reach(self, arm, arm_base, distance=0.10, stations=0, iterations=24, damping=1e-4, rot_scale=0.1):
+        """The arm of calculate_energy(..., energy_names=[..., "E_reach"]): ``arm`` an ``ops.ArmSpec`` or ``ops.ArmHandle``,
+        ``arm_base`` (3,4) or (n_obj,3,4) the arm base in the frame of each object, and the parameters of ``ops.reach_terms``
+        (stations in 0..3 beyond the grasp pose over ``distance`` metres, damped-least-squares updates, damping in m^2, metres per
+        radian).  Checked here, without a launch."""
+        ops.reach_check(arm, distance, stations, iterations, damping, rot_scale, self.grasp_axis, "HandModel.set_reach")
+        if arm is None:
+            raise ValueError("HandModel.set_reach: arm must be an ops.ArmSpec or an ops.ArmHandle")
+        base = torch.as_tensor(arm_base)
+        # (n,3,4) float32 on the device, converted once; n = 1 serves every object
+        base = ops.reach_base(base, base.shape[0] if base.dim() == 3 else 1, "HandModel.set_reach").to(self.device)
+        handle = arm if isinstance(arm, ops.ArmHandle) else ops.ArmHandle(arm, self.device)
+        self.reach = (handle, base, float(distance), int(stations), int(iterations), float(damping), float(rot_scale))
+
     def get_surface_points(self, hand_pose=None):
         """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose; ``hand_pose`` =
         None takes the model's own (another pose, e.g. the opened one of E_pregrasp, is a second FK at that pose)."""

@@ -25,6 +25,7 @@ import torch
 from torch import Tensor
 
 from . import _C
+from .arm import ArmSpec
 
 _custom_op = torch.library.custom_op
 _ROUTE = {"dispatcher": os.environ.get("GRASPQP_DISPATCH", "eager") == "dispatcher"}
@@ -2186,6 +2187,172 @@ def squeeze_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, dist_sq, obj_nor
     return (e, theta) if return_theta else e
 
 
+# ----------------------------------------------------------------------------------------------------------
+# arm reachability: E_reach (csrc/reach.hip), batched damped-least-squares wrist IK as ONE launch: eight lanes per IK problem, the
+# seeds and stations of a row side by side in one block, the gradient in the gRt layout the FK backward takes
+# ----------------------------------------------------------------------------------------------------------
+REACH_DEFAULTS = {"distance": 0.10, "stations": 0, "iterations": 24, "damping": 1e-4, "rot_scale": 0.1}
+
+
+class ArmHandle(_DeviceObject):
+    """Device copy of an ``ArmSpec`` (gq_arm_create: the set-up owner of csrc/setup.h holds the memory)."""
+
+    def __init__(self, spec: ArmSpec, device=None):
+        if not isinstance(spec, ArmSpec):
+            raise ValueError("ArmHandle: spec must be an ops.ArmSpec")
+        self.spec = spec
+        keep = []
+
+        def arr(a, dt):
+            a = np.ascontiguousarray(np.asarray(a, dtype=dt))
+            keep.append(a)
+            return a.ctypes.data_as(ctypes.c_void_p)
+
+        d = _C.ArmDesc()
+        d.n_joints, d.n_seeds = spec.n_joints, spec.n_seeds
+        d.joint_type, d.joint_T, d.joint_axis = arr(spec.joint_type, np.int32), arr(spec.joint_T, np.float32), arr(spec.joint_axis, np.float32)
+        d.lower, d.upper = arr(spec.lower, np.float32), arr(spec.upper, np.float32)
+        d.tool_T = arr(spec.tool_T, np.float32)
+        # float32 of a seed on a limit may round across it: keep every seed inside the float32 limits
+        lo32, hi32 = np.asarray(spec.lower, np.float32), np.asarray(spec.upper, np.float32)
+        d.seeds = arr(np.clip(np.asarray(spec.seeds, np.float32), lo32, hi32), np.float32)
+        super().__init__("gq_arm_create", "gq_arm_destroy", device, ctypes.byref(d))
+        self.N, self.S = spec.n_joints, spec.n_seeds
+        self.hid = _register_handle(self)
+
+
+def reach_check(arm, distance=0.10, stations=0, iterations=24, damping=1e-4, rot_scale=0.1, grasp_axis=(0.0, 0.0, 1.0),
+                who="reach_terms"):
+    """The parameters of the reach term (no GPU): ``arm`` an ArmSpec or ArmHandle (None: not checked), stations in 0..3, a finite
+    distance > 0 when there are stations, iterations in 0..4096, finite damping > 0 and rot_scale > 0, a finite non-zero grasp_axis;
+    raises ValueError."""
+    if arm is not None and not isinstance(arm, (ArmSpec, ArmHandle)):
+        raise ValueError(f"{who}: arm must be an ops.ArmSpec or an ops.ArmHandle, got {type(arm).__name__}")
+    if int(stations) != stations or not 0 <= int(stations) <= 3:
+        raise ValueError(f"{who}: reach_stations = {stations!r} must be an integer in 0..3")
+    if int(stations) > 0 and not 0.0 < float(distance) < float("inf"):
+        raise ValueError(f"{who}: reach_distance = {distance!r} must be finite and > 0")
+    if int(iterations) != iterations or not 0 <= int(iterations) <= 4096:
+        raise ValueError(f"{who}: reach_iterations = {iterations!r} must be an integer in 0..4096")
+    if not 0.0 < float(damping) < float("inf"):
+        raise ValueError(f"{who}: reach_damping = {damping!r} must be finite and > 0")
+    if not 0.0 < float(rot_scale) < float("inf"):
+        raise ValueError(f"{who}: reach_rot_scale = {rot_scale!r} must be finite and > 0")
+    a = _axis3(grasp_axis)
+    if not all(abs(x) < float("inf") for x in a) or not any(x != 0.0 for x in a):
+        raise ValueError(f"{who}: grasp_axis = {a!r} must be finite and not all zero")
+
+
+def reach_base(arm_base, n_obj, who="reach_terms"):
+    """``arm_base`` (3,4) / (4,4) or (n_obj,3,4) / (n_obj,4,4), numpy or tensor -> float32 CPU tensor (n_obj,3,4); raises ValueError."""
+    b = torch.as_tensor(np.asarray(arm_base.detach().cpu()) if torch.is_tensor(arm_base) else np.asarray(arm_base, dtype=np.float64))
+    if b.dim() == 2:
+        b = b.unsqueeze(0).expand(int(n_obj), *b.shape)
+    if b.dim() != 3 or b.shape[0] != int(n_obj) or tuple(b.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"{who}: arm_base must be (3,4) or ({n_obj},3,4), got {tuple(b.shape)}")
+    if not bool(torch.isfinite(b).all()):
+        raise ValueError(f"{who}: arm_base is not finite")
+    return b[:, :3, :].to(torch.float32).contiguous()
+
+
+def _reach_call(arm, hp, Rg, base_T, batch_each, axis, distance, stations, iterations, damping, rot_scale, up, w, e, q, seed,
+                accumulate, gRt, st=None):
+    p, (B, D) = _dev, hp.shape
+    _C.call("gq_reach_terms", arm.handle, _C.f32(hp), D, p(Rg), ctypes.c_int64(B), p(base_T), ctypes.c_int64(B // int(batch_each)),
+            ctypes.c_int64(int(batch_each)), ctypes.cast(_axis_c(axis), ctypes.c_void_p), float(distance), int(stations),
+            int(iterations), float(damping), float(rot_scale), p(up), float(w), p(e), p(q), p(seed, torch.int32), int(accumulate),
+            p(gRt), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::reach_terms", mutates_args=(), device_types="cuda")
+def _reach_op(arm: int, hand_pose: Tensor, Rg: Tensor, base_T: Tensor, batch_each: int, grasp_axis: List[float], distance: float,
+              stations: int, iterations: int, damping: float, rot_scale: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (E_reach (B), unweighted; reach_q (B,K+1,N), the winning arm configuration per station; reach_seed (B,K+1) int32) of
+    the root pose (hand_pose[:, :3], Rg)."""
+    a = _handle(arm)
+    hp = _c(hand_pose)
+    B, dev = hp.shape[0], hp.device
+    e, q = torch.empty(B, device=dev), torch.empty(B, stations + 1, a.N, device=dev)
+    seed = torch.empty(B, stations + 1, dtype=torch.int32, device=dev)
+    _reach_call(a, hp, _c(Rg), _c(base_T), batch_each, grasp_axis, distance, stations, iterations, damping, rot_scale, None, 0.0, e, q,
+                seed, 0, None)
+    return e, q, seed
+
+
+@_reach_op.register_fake
+def _(arm, hand_pose, Rg, base_T, batch_each, grasp_axis, distance, stations, iterations, damping, rot_scale):
+    B = hand_pose.shape[0]
+    return (hand_pose.new_empty(B), hand_pose.new_empty(B, stations + 1, _handle(arm).N),
+            hand_pose.new_empty(B, stations + 1, dtype=torch.int32))
+
+
+@_custom_op("graspqp_amd::reach_terms_backward", mutates_args=(), device_types="cuda")
+def _reach_bwd_op(arm: int, hand_pose: Tensor, Rg: Tensor, base_T: Tensor, batch_each: int, grasp_axis: List[float], distance: float,
+                  stations: int, iterations: int, damping: float, rot_scale: float, g_reach: Tensor) -> Tensor:
+    """Upstream row gradients (B) on E_reach -> gRt (B,12) for fk_backward.  One launch (the iteration runs again: the term keeps
+    no state)."""
+    a = _handle(arm)
+    hp = _c(hand_pose)
+    gRt = torch.empty(hp.shape[0], 12, device=hp.device)
+    _reach_call(a, hp, _c(Rg), _c(base_T), batch_each, grasp_axis, distance, stations, iterations, damping, rot_scale, _c(g_reach), 1.0,
+                None, None, None, 0, gRt)
+    return gRt
+
+
+@_reach_bwd_op.register_fake
+def _(arm, hand_pose, Rg, base_T, batch_each, grasp_axis, distance, stations, iterations, damping, rot_scale, g_reach):
+    return hand_pose.new_empty(hand_pose.shape[0], 12)
+
+
+class _ReachTerms(torch.autograd.Function):
+    """Glue between two registered ops (reach_terms + fk_backward), as _ApproachTerms: the backward launch writes gRt with the
+    per-row upstream, the FK backward turns it into the root translation and rotation gradient.  The joints get none."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, idx, Rg, LT, ws, arm, base_T, batch_each, axis, par):
+        hp = _c(hand_pose.detach())
+        e, q, seed = _Eager.reach_terms(arm.hid, hp, Rg, base_T, batch_each, axis, *par)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, base_T)
+        ctx.hand, ctx.arm, ctx.par = hand, arm, (batch_each, axis) + tuple(par)
+        ctx.mark_non_differentiable(q, seed)
+        return e, q, seed
+
+    @staticmethod
+    def backward(ctx, g_reach, _gq, _gs):
+        hp, idx, Rg, LT, ws, base_T = ctx.saved_tensors
+        gRt = _Eager.reach_terms_backward(ctx.arm.hid, hp, Rg, base_T, *ctx.par, _c(g_reach))
+        gp = _fk_backward(ctx.hand, hp, idx, Rg, LT, ws, None, None, None, None, gRt, None)
+        return (gp,) + (None,) * 10
+
+
+def reach_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, arm: ArmHandle, base_T, batch_each, grasp_axis, distance=0.10,
+                stations=0, iterations=24, damping=1e-4, rot_scale=0.1, return_q=False):
+    """-> E_reach (B) in m^2 = the mean over the stations k = 0..K of min over the arm's seeds of |e|^2, e = [p* - p(q) ;
+    rot_scale log(R* R(q)')] after ``iterations`` damped-least-squares updates of the arm's joints q from the seed (include/
+    graspqp_hip.h, "arm reachability", has the iteration); the target of station k is the root pose of ``hand_pose`` moved back by
+    ``distance`` k / K along ``grasp_axis`` (hand frame), station 0 the grasp pose itself.  ``base_T`` (n_obj,3,4) places the arm
+    base in the frame of each object; row b takes ``base_T[b // batch_each]``.  Unweighted; differentiable w.r.t. the root
+    translation and rotation of ``hand_pose`` -- the partial derivative with respect to the target at the final q, which is the
+    gradient of the converged energy where the iteration has converged and an approximation elsewhere.  ``idx``, ``Rg``, ``LT``,
+    ``ws`` are the kinematic state of ``hand_pose`` (fk_contacts).  ``return_q``: also reach_q (B,K+1,N), the winning configuration
+    per station, and reach_seed (B,K+1) int32."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if not isinstance(arm, ArmHandle):
+        raise ValueError("reach_terms: arm must be an ops.ArmHandle")
+    axis = [float(a) for a in _axis3(grasp_axis)]
+    reach_check(arm, distance, stations, iterations, damping, rot_scale, axis)
+    B = hand_pose.shape[0]
+    if int(batch_each) < 1 or B % int(batch_each):
+        raise ValueError(f"reach_terms: batch = {B} is not divisible by batch_each = {batch_each}")
+    if tuple(base_T.shape) != (B // int(batch_each), 3, 4):
+        raise ValueError(f"reach_terms: base_T must be ({B // int(batch_each)}, 3, 4), got {tuple(base_T.shape)}")
+    e, q, seed = _ReachTerms.apply(hand_pose, hand, _c(idx, torch.int64), _c(Rg.detach()), _c(LT.detach()), ws, arm,
+                                   _c(base_T.detach()), int(batch_each), axis,
+                                   (float(distance), int(stations), int(iterations), float(damping), float(rot_scale)))
+    return (e, q, seed) if return_q else e
+
+
 @_custom_op("graspqp_amd::scene_compose", mutates_args=("out_values",), device_types="cuda")
 def _scene_compose_op(out_values: Tensor, origin: List[float], voxel: float, target_T: Tensor, part_values: List[Tensor],
                       part_origins: List[float], part_voxels: List[float], part_T: Tensor, exclude: Optional[Tensor],
@@ -2591,6 +2758,8 @@ _eager("pregrasp_terms", _pregrasp_op)
 _eager("pregrasp_terms_backward", _pregrasp_bwd_op)
 _eager("squeeze_terms", _squeeze_op)
 _eager("squeeze_terms_backward", _squeeze_bwd_op)
+_eager("reach_terms", _reach_op)
+_eager("reach_terms_backward", _reach_bwd_op)
 _eager("scene_compose", _scene_compose_op)
 _eager("tsdf_integrate", _tsdf_integrate_op)
 _eager("tsdf_surfels", _tsdf_surfels_op)

@@ -44,6 +44,20 @@ after the joined branches and the obstacle terms adds to ``g_cpts``, which the c
 term's part; the constant itself is never modified); ``terms`` gets [E_squeeze] appended last, its share of the row total is one more
 gq_scene_total launch, and the proposal and the accept step are the stand-alone launches.
 
+Reach mode (a weight on "E_reach", with ``arm`` and ``arm_base``): can the arm the hand sits on bring it to this pose, and to the
+stations of its retreat?  Station k = 0..``reach_stations`` is the root pose moved back by ``reach_distance`` k / ``reach_stations``
+along the grasp axis (station 0: the grasp pose); per station and per seed of the arm ``reach_iterations`` damped-least-squares
+updates of the arm's joints (``reach_damping``, rotation weighed by ``reach_rot_scale`` metres per radian, steps capped at 0.5 and
+clamped to the limits) are followed by one more FK, and the term is the mean over the stations of the smallest squared pose error over
+the seeds, in m^2.  ``arm_base`` places the arm base in the frame of each object.  One more launch (gq_reach_terms: eight lanes per
+IK problem, the stations and seeds of a row side by side in one block) after gq_squeeze_terms and before gq_fk_backward ADDS its
+gradient to ``gRt``; ``g_R`` and ``g_theta`` are not touched.  The gradient is the partial derivative with respect to the target with
+the final joints held fixed: the gradient of the converged energy where the iteration has converged, an approximation elsewhere
+(the Metropolis test sees the value, which is a pure function of the pose: no joint state is carried between evaluations).
+``reach_q`` (B,K+1,N) and ``reach_seed`` (B,K+1) hold the winning arm configuration and its seed of the last evaluation; ``terms`` gets
+[E_reach] appended last, its share of the row total is one more gq_scene_total launch, and the proposal and the accept step are the
+stand-alone launches.
+
 Clutter (``scene`` is an ``ops.SceneSDFSet`` with one grid per object): the same two launches read a stack of grids and pick the
 grid from the row, row // batch_each (gq_clutter_terms / gq_clutter_corridor_terms, the same row bodies: bit for bit the single-grid
 launch's numbers on that grid).  ``ops.scene_compose`` refills the stack in place, also between replays of a captured graph.
@@ -67,6 +81,7 @@ SCENE_TERMS = ("E_scene",)
 APPROACH_TERMS = ("E_approach",)
 PREGRASP_TERMS = ("E_pregrasp",)
 SQUEEZE_TERMS = ("E_squeeze",)
+REACH_TERMS = ("E_reach",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
@@ -91,12 +106,12 @@ def select_tolerances(term_names, gates=None):
 
 
 def merge_weights(weights=None):
-    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term, of the pre-grasp term and of
-    the squeeze term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
+    """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term, of the pre-grasp term, of
+    the squeeze term and of the reach term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
     never used), and so does a negative weight of one of the terms that are switched by their weight."""
-    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS
+    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS
     w = dict(DEFAULT_WEIGHTS)
-    w.update({k: 0.0 for k in SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
+    w.update({k: 0.0 for k in REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
     for k, v in (weights or {}).items():
         if k not in w:
             raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
@@ -126,7 +141,8 @@ class GraspStepper:
                  approach_distance: float = 0.10, approach_stations: int = 4, approach_margin=None,
                  pregrasp_opening: float = 0.5, pregrasp_joints=None, pregrasp_scene=None, pregrasp_distance=None,
                  pregrasp_stations=None, pregrasp_margin=None, squeeze_min_travel: float = 5e-3, squeeze_damping: float = 1e-3,
-                 init_avoid_scene: bool = False):
+                 arm=None, arm_base=None, reach_distance: float = 0.10, reach_stations: int = 0, reach_iterations: int = 24,
+                 reach_damping: float = 1e-4, reach_rot_scale: float = 0.1, init_avoid_scene: bool = False):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -156,7 +172,12 @@ class GraspStepper:
         n_i max(|distance_i|, squeeze_min_travel) that the joints cannot produce, with the damped pseudo-inverse (squeeze_damping) of
         the contact Jacobian; at the defaults the reference's E_manipulativity.  Both must be finite and > 0 (J'J alone is singular
         for 3 n_contact < n_dofs).  ``squeeze_theta`` (B,J) holds the joint velocities of the last evaluation.  With weight 0 the two
-        arguments change nothing."""
+        arguments change nothing.
+        weights["E_reach"] > 0 selects the reach mode (module docstring) and needs ``arm``, an ``ops.ArmSpec`` or ``ops.ArmHandle``,
+        and ``arm_base``, (3,4) or (n_obj,3,4): the arm base in the frame of each object.  ``reach_stations`` in 0..3 stations beyond
+        the grasp pose over ``reach_distance`` metres (> 0 when there are stations), ``reach_iterations`` in 0..4096,
+        ``reach_damping`` (m^2) and ``reach_rot_scale`` (metres per radian) finite and > 0.  ``reach_q`` / ``reach_seed`` hold the arm
+        configurations of the last evaluation.  No default weight is set.  With weight 0 the seven arguments change nothing."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -206,12 +227,21 @@ class GraspStepper:
         self.squeeze_mode = self.w["E_squeeze"] > 0
         if self.squeeze_mode:
             ops.squeeze_check(hand, n_contact, squeeze_min_travel, squeeze_damping, "GraspStepper")
+        self.reach_mode = self.w["E_reach"] > 0
+        if self.reach_mode:
+            if not isinstance(arm, (ops.ArmSpec, ops.ArmHandle)):
+                raise ValueError('GraspStepper: weights["E_reach"] > 0 needs arm=ops.ArmSpec(...) or ops.ArmHandle(...)')
+            if arm_base is None:
+                raise ValueError('GraspStepper: weights["E_reach"] > 0 needs arm_base, (3,4) or (n_obj,3,4)')
+            ops.reach_check(arm, reach_distance, reach_stations, reach_iterations, reach_damping, reach_rot_scale, hand.spec.grasp_axis,
+                            "GraspStepper")
+            arm_base = ops.reach_base(arm_base, self.n_obj, "GraspStepper")
         self.init_avoid_scene = bool(init_avoid_scene)
         if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
             raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
         self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
                            + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ())
-                           + (SQUEEZE_TERMS if self.squeeze_mode else ()))
+                           + (SQUEEZE_TERMS if self.squeeze_mode else ()) + (REACH_TERMS if self.reach_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -337,7 +367,8 @@ class GraspStepper:
             ad.e_fc = self.terms_new[1].data_ptr()
             self._alt_desc = ad
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
-        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode or self.squeeze_mode)
+        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode or self.squeeze_mode
+                               or self.reach_mode)
         self.samples, self.g_R = None, None
         self._n_surface_points, self._select_fk = int(n_surface_points), None
         self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode or self.approach_mode else (None, 0.0)
@@ -393,11 +424,21 @@ class GraspStepper:
             self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._axis), device=self.dev)
         self.squeeze_theta, self._g_R_const = None, self.g_R
         if self.squeeze_mode:
-            self._i_squeeze = nT - 1
+            self._i_squeeze = self.term_names.index("E_squeeze")
             self.squeeze_min_travel, self.squeeze_damping = float(squeeze_min_travel), float(squeeze_damping)
             self.squeeze_theta = f(B, self.J)
             # the g_R the FK backward reads in this mode: written by every evaluation (E_prior's constant + this term's part)
             self.g_R = f(B, 9)
+        self.arm, self.arm_base, self.reach_q, self.reach_seed = None, None, None, None
+        if self.reach_mode:
+            self._i_reach = self.term_names.index("E_reach")
+            self.arm = arm if isinstance(arm, ops.ArmHandle) else ops.ArmHandle(arm, self.dev)
+            self.arm_base = arm_base.to(self.dev)
+            self.reach_distance, self.reach_stations, self.reach_iterations = float(reach_distance), int(reach_stations), int(reach_iterations)
+            self.reach_damping, self.reach_rot_scale = float(reach_damping), float(reach_rot_scale)
+            self.reach_q = f(B, self.reach_stations + 1, self.arm.N)
+            self.reach_seed = torch.zeros(B, self.reach_stations + 1, dtype=torch.int32, device=self.dev)
+            self._reach_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
         self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
@@ -416,8 +457,8 @@ class GraspStepper:
                                                                   int(m["annealing_period"]))
         ac.energy, ac.pose, ac.idx, ac.grad = (t.data_ptr() for t in (self.energy, self.hand_pose, self.contact_idx, self.grad))
         ac.accept, ac.temperature = self.accept.data_ptr(), self.temperature.data_ptr()
-        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach, pre-grasp and squeeze
-        # mode (six to eleven terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
+        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach, pre-grasp, squeeze
+        # and reach mode (six to twelve terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
         assert self._fuse_loop == (nT == len(TERM_NAMES))
         ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
@@ -534,6 +575,13 @@ class GraspStepper:
                           self.squeeze_min_travel, self.squeeze_damping, None, self.w["E_squeeze"], self.terms_new[self._i_squeeze],
                           self.squeeze_theta, 3 if self.pregrasp_mode else 1, self.g_theta, self.g_R, self._g_R_const, self.g_cpts, st)
 
+    def _eval_reach(self, pose, st):
+        """E_reach -> its row of terms_new (``_i_reach``), the winning arm configurations -> ``reach_q`` / ``reach_seed``; the gradient of w_reach E_reach
+        is ADDED to ``gRt`` (the penetration branch has written it).  g_R and g_theta are not touched."""
+        ops._reach_call(self.arm, pose, self.Rg, self.arm_base, self.be, self._reach_axis, self.reach_distance, self.reach_stations,
+                        self.reach_iterations, self.reach_damping, self.reach_rot_scale, None, self.w["E_reach"],
+                        self.terms_new[self._i_reach], self.reach_q, self.reach_seed, 1, self.gRt, st)
+
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
         f32 = _C.f32
@@ -584,6 +632,8 @@ class GraspStepper:
             evaluate(pose, st)
         if self.squeeze_mode:
             self._eval_squeeze(idx, st)
+        if self.reach_mode:
+            self._eval_reach(pose, st)
         self._eval_tail(pose, idx, st, loop)
         if self.tabletop:  # the FK backward's total holds the five terms
             _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
@@ -592,6 +642,9 @@ class GraspStepper:
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[i]), w, ctypes.c_int64(self.B), st)
         if self.squeeze_mode:
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_squeeze]), float(self.w["E_squeeze"]),
+                    ctypes.c_int64(self.B), st)
+        if self.reach_mode:
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_reach]), float(self.w["E_reach"]),
                     ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):

@@ -724,6 +724,57 @@ int gq_squeeze_terms(const gqHand* h, const int64_t* contact_idx /* (B,n) */, in
                      float* g_R /* (B,9) or NULL */, const float* g_R_base /* (B,9) or NULL */,
                      float* g_contact_pts /* (B,n,3) or NULL */, void* stream);
 
+/* ---- arm reachability of the stepper: E_reach, batched damped-least-squares wrist IK ----------------------------------------
+ * Every other term treats the hand as a free-flying body; this one knows that it sits on an arm.  The arm is a serial chain of
+ * N <= 8 revolute (1) or prismatic (2) joints with limits: FK(q) = base_T joint_T[0] m_0(q_0) ... joint_T[N-1] m_{N-1}(q_{N-1}) tool_T
+ * is the hand-root pose (p(q), R(q)) in the frame the row lives in (its object's): base_T[b / batch_each] is the arm base in that
+ * frame, joint_T[j] the fixed transform parent -> joint frame, m_j the rotation about / shift along the unit joint_axis[j], tool_T
+ * flange -> hand root.  Transforms are 3x4 row-major [R|t].  gq_arm_create takes HOST arrays, checks them (types, unit axes, finite
+ * limits with lower < upper, seeds (S,N) inside the limits, 1 <= N <= 8, 1 <= S <= 8) and owns the device copy
+ * (counted in gq_setup_live_allocations).
+ * Row b with root translation t and root rotation R (Rg of gq_fk_forward), station k = 0..K (K = n_stations, station 0 = the grasp
+ * pose): R*_k = R, p*_k = t - (D k / K) R a, a = grasp_axis as given (the direction convention of gq_approach_terms).  Per station and
+ * seed q0: q <- q0, then M = n_iterations times
+ *   e = [p* - p(q) ; rho log(R* R(q)')]    J = [J_v ; rho J_w] (6 x N, geometric, same frame)    dq = J' (J J' + lambda I)^-1 e
+ *   if max|dq| > 0.5: dq <- dq 0.5 / max|dq|    q <- clamp(q + dq, lower, upper)
+ * and one more FK for e and E_{k,seed} = |e|^2.  The log map takes its angle from atan2(|vee|, (trace - 1) / 2) and the series
+ * 1 + |vee|^2 / 6 of angle / |vee| for |vee| < 1e-6 (a target exactly half a turn away therefore reads as no rotation error).
+ * E_k = min over the seeds, the lowest seed index on a tie; E_reach = 1/(K+1) sum_k E_k in m^2, all fp32 (csrc/reach_dev.h says why
+ * the 6 x 6 is too).  Gradient: the partial derivative with respect to the target with the winner's final q held fixed,
+ * dE_k/dp*_k = 2 e_p and, for R* <- exp(d^) R*, the torque 2 rho^2 log(R* R(q)') = 2 rho e_w.  Where the iteration has reached a
+ * fixed point with no joint on a limit -- target reachable or not -- this IS the gradient of the converged E (envelope theorem:
+ * dq = 0 means J'e = 0, E is stationary in q); elsewhere it is an approximation: before convergence, with a joint ON its limit (the
+ * clamped fixed point is not the constrained minimiser), and past the outer boundary of a revolute arm, where at the default damping
+ * the iteration ends in a two-cycle about the stretched configuration.  With c = w (up[row] if given, else 1) / (K+1) and d_k = D k / K it goes to
+ *   gRt (B,12) = [gsum(3), K9(9)]: gsum = -R' sum_k 2 c e_p,k;  K9 = sum_k (R' 2 c e_p,k) (x) (-d_k a) + hat(R' sum_k 2 c rho e_w,k) / 2
+ * in the layout and signs of gq_approach_terms (grad_t = -R gsum, grad_R = R K9); accumulate = 1 adds to gRt, 0 overwrites it.
+ * g_R and g_theta of gq_fk_backward are not touched.  e_reach (B) is written UNWEIGHTED and always overwritten; reach_q (B,K+1,N) is
+ * the winner's joint vector per station and reach_seed (B,K+1) its seed.  Any output may be NULL.  One block per row, eight lanes
+ * per IK problem, fixed-order sums, no atomics: bitwise reproducible run to run; no joint state is carried between launches, so the
+ * term is a pure function of the pose.  The row total takes gq_scene_total(total, e_reach, w, B).
+ * gq_reach_check is the parameter check on its own (host only, no GPU); its message contains "reach" and names the argument.   */
+typedef struct gqArmDesc { /* all pointers HOST */
+  int32_t n_joints, n_seeds;
+  const int32_t* joint_type; /* (N) 1 revolute, 2 prismatic */
+  const float* joint_T;      /* (N,12) */
+  const float* joint_axis;   /* (N,3) unit */
+  const float* lower;        /* (N) */
+  const float* upper;        /* (N) */
+  const float* tool_T;       /* (12) */
+  const float* seeds;        /* (S,N) */
+} gqArmDesc;
+typedef struct gqArm gqArm;
+int gq_arm_create(const gqArmDesc* desc, gqArm** out);
+int gq_arm_destroy(gqArm* arm);
+int gq_reach_check(int n_joints, int n_seeds, float distance, int n_stations, int n_iterations, float damping, float rot_scale,
+                   const float* grasp_axis /* (3) host */);
+int gq_reach_terms(const gqArm* arm, const float* hand_pose /* (B,pose_dim) */, int pose_dim, const float* Rg /* (B,9) */,
+                   int64_t batch, const float* base_T /* (n_obj,12) */, int64_t n_obj, int64_t batch_each,
+                   const float* grasp_axis /* (3) host */, float distance, int n_stations, int n_iterations, float damping,
+                   float rot_scale, const float* up /* (B) or NULL */, float w, float* e_reach /* (B) or NULL */,
+                   float* reach_q /* (B,K+1,N) or NULL */, int32_t* reach_seed /* (B,K+1) or NULL */, int accumulate,
+                   float* gRt /* (B,12) or NULL */, void* stream);
+
 /* ---- scenes from depth images: TSDF fusion on the device into scene grids ---------------------------------------------
  * What a robot has is depth images, not a signed-distance volume.  gq_tsdf_integrate fuses a batch of depth frames into a
  * gqClutterGrids stack IN PLACE, one launch per batch (n_grids = 1 is the single world grid).  State: `values` of the stack IS

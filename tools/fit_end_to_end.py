@@ -12,6 +12,7 @@ Evidence run, not a test: writes one JSON record (default gpurun_out/fit_end_to_
 
 usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_iter 7000] [--out file.json]
        [--w_squeeze 0] [--squeeze_min_travel 5e-3] [--squeeze_damping 1e-3]   (contact closing feasibility, E_squeeze)
+       [--w_reach 0] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations 0]   (arm reachability, E_reach)
        [--w_wall 0] [--w_prior 0]   (scripts/fit.py:77-78: tabletop synthesis; the class surface and the oracle then carry
        E_wall / E_prior on the stepper's surface samples, st.samples)
        [--w_scene 0] [--scene_margin 0] [--scene box]   (scene obstacles: the ``box`` preset is an open-topped bin of five slabs
@@ -51,6 +52,13 @@ ap.add_argument("--approach_stations", type=int, default=4)
 ap.add_argument("--w_squeeze", type=float, default=0.0)
 ap.add_argument("--squeeze_min_travel", type=float, default=5e-3)
 ap.add_argument("--squeeze_damping", type=float, default=1e-3)
+ap.add_argument("--w_reach", type=float, default=0.0)
+ap.add_argument("--arm", default="arm7")  # a preset of graspqp_amd.arm, or a URDF file (then --arm_tip, optionally --arm_base_link)
+ap.add_argument("--arm_tip", default=None)
+ap.add_argument("--arm_base_link", default=None)
+ap.add_argument("--arm_base", type=float, nargs=4, default=(-0.45, 0.0, -0.3, 0.0), metavar=("X", "Y", "Z", "YAW"))
+ap.add_argument("--reach_stations", type=int, default=0)
+ap.add_argument("--reach_distance", type=float, default=0.10)
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "fit_end_to_end.json"))
 args = ap.parse_args()
 
@@ -77,6 +85,14 @@ if APPROACH:
 SQUEEZE = args.w_squeeze > 0  # contact closing feasibility (E_squeeze: the reference's E_manipulativity as one launch)
 if SQUEEZE:
     W["E_squeeze"] = args.w_squeeze
+REACH = args.w_reach > 0  # arm reachability (E_reach: batched wrist IK as one launch)
+reach_kw = {}
+if REACH:
+    from graspqp_amd.arm import arm_from_arg, base_from_arg
+
+    W["E_reach"] = args.w_reach
+    reach_kw = dict(arm=arm_from_arg(args.arm, args.arm_tip, args.arm_base_link), arm_base=base_from_arg(args.arm_base),
+                    reach_stations=args.reach_stations, reach_distance=args.reach_distance)
 spec = get_hand_spec(args.hand)
 n_obj, be, n = args.n_objects, args.batch_size, args.n_contact
 B = n_obj * be
@@ -97,9 +113,11 @@ if SCENE or APPROACH:  # the ``box`` preset: an open-topped bin around the first
         weights["E_approach"] = args.w_approach
 if SQUEEZE:
     weights["E_squeeze"] = args.w_squeeze
+if REACH:
+    weights["E_reach"] = args.w_reach
 st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1, weights=weights or None, scene=scene,
                   scene_margin=args.scene_margin, approach_distance=args.approach_distance, approach_stations=args.approach_stations,
-                  squeeze_min_travel=args.squeeze_min_travel, squeeze_damping=args.squeeze_damping)
+                  squeeze_min_travel=args.squeeze_min_travel, squeeze_damping=args.squeeze_damping, **reach_kw)
 st.set_hulls(om.convex_hulls())
 st.initialize()  # on-device initialize_convex_hull + the first evaluation
 e0, t0_terms = st.energy.clone(), st.terms.clone()
@@ -133,10 +151,13 @@ if APPROACH:
     hm.set_approach(args.approach_distance, args.approach_stations)
 if SQUEEZE:
     hm.set_squeeze(args.squeeze_min_travel, args.squeeze_damping)
+if REACH:
+    hm.set_reach(reach_kw["arm"], reach_kw["arm_base"], args.reach_distance, args.reach_stations)
 metric = GraspSpanMetricFactory.create(GraspSpanMetricFactory.MetricType.GRASPQP, {"friction": 0.2, "max_limit": 20.0, "n_cone_vecs": 4})
 losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1,
                           energy_names=(["E_prior", "E_wall"] if TABLETOP else []) + (["E_scene"] if SCENE else []) +
-                          (["E_approach"] if APPROACH else []) + (["E_squeeze"] if SQUEEZE else []))
+                          (["E_approach"] if APPROACH else []) + (["E_squeeze"] if SQUEEZE else []) +
+                          (["E_reach"] if REACH else []))
 total_cls = sum(W[k] * losses[k] for k in W)
 rel_cls = ((total_cls.detach() - st.energy).abs() / st.energy.abs().clamp_min(1e-6))
 

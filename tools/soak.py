@@ -4,7 +4,8 @@ counters must not show inline-ranked overflow growing, the stop iteration is his
 
 usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--w_scene W] [--scene_margin M]
        [--scene box] [--w_approach W] [--approach_distance D] [--approach_stations K]
-       [--w_pregrasp W] [--pregrasp_opening A] [--pregrasp_stations K] [--w_squeeze W] [--out file.json]
+       [--w_pregrasp W] [--pregrasp_opening A] [--pregrasp_stations K] [--w_squeeze W]
+       [--w_reach W] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations K] [--out file.json]
        (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
        schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
        hand surface samples left below the plane; --w_scene > 0 runs it in scene mode against the ``box`` preset (an open-topped
@@ -14,7 +15,9 @@ usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_
        against the same preset (the hand opened by --pregrasp_opening towards its default state, stations 0..K over the
        approach distance; K defaults to --approach_stations) and reports the mean E_pregrasp the same way; --w_squeeze > 0
        adds the squeeze term (contact closing feasibility, the reference's E_manipulativity as one launch) and reports the mean
-       E_squeeze at the start and at the end; --out writes the records as JSON.
+       E_squeeze at the start and at the end; --w_reach > 0 adds the reach term (arm reachability: batched wrist IK of --arm, a
+       preset or a URDF chain ending in --arm_tip, its base placed at --arm_base in every object's frame) and reports the mean
+       E_reach and the share of rows under 1e-6 at the start and at the end; --out writes the records as JSON.
 """
 import argparse
 import json
@@ -48,6 +51,13 @@ ap.add_argument("--w_pregrasp", type=float, default=0.0)
 ap.add_argument("--pregrasp_opening", type=float, default=0.5)
 ap.add_argument("--pregrasp_stations", type=int, default=None)
 ap.add_argument("--w_squeeze", type=float, default=0.0)
+ap.add_argument("--w_reach", type=float, default=0.0)
+ap.add_argument("--arm", default="arm7")  # a preset of graspqp_amd.arm, or a URDF file (then --arm_tip, optionally --arm_base_link)
+ap.add_argument("--arm_tip", default=None)
+ap.add_argument("--arm_base_link", default=None)
+ap.add_argument("--arm_base", type=float, nargs=4, default=(-0.45, 0.0, -0.3, 0.0), metavar=("X", "Y", "Z", "YAW"))
+ap.add_argument("--reach_stations", type=int, default=0)
+ap.add_argument("--reach_distance", type=float, default=0.10)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
@@ -65,6 +75,14 @@ if PREGRASP:
 SQUEEZE = args.w_squeeze > 0
 if SQUEEZE:
     weights["E_squeeze"] = args.w_squeeze
+REACH = args.w_reach > 0
+reach_kw = {}
+if REACH:
+    from graspqp_amd.arm import arm_from_arg, base_from_arg
+
+    weights["E_reach"] = args.w_reach
+    reach_kw = dict(arm=arm_from_arg(args.arm, args.arm_tip, args.arm_base_link), arm_base=base_from_arg(args.arm_base),
+                    reach_stations=args.reach_stations, reach_distance=args.reach_distance)
 records = []
 
 
@@ -92,7 +110,7 @@ for n_obj in args.n_objects:
     st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3, weights=weights or None,
                       table_z=args.table_z, scene=scene, scene_margin=args.scene_margin,
                       approach_distance=args.approach_distance, approach_stations=args.approach_stations,
-                      pregrasp_opening=args.pregrasp_opening, pregrasp_stations=args.pregrasp_stations)
+                      pregrasp_opening=args.pregrasp_opening, pregrasp_stations=args.pregrasp_stations, **reach_kw)
     st.set_hulls(om.convex_hulls())
     st.initialize()
     e0 = st.energy.clone()
@@ -105,6 +123,8 @@ for n_obj in args.n_objects:
     pregrasp0 = float(st.terms[i_pregrasp].mean()) if PREGRASP else None
     i_squeeze = st.term_names.index("E_squeeze") if SQUEEZE else None
     squeeze0 = float(st.terms[i_squeeze].mean()) if SQUEEZE else None
+    i_reach = st.term_names.index("E_reach") if REACH else None
+    reach0 = (float(st.terms[i_reach].mean()), float((st.terms[i_reach] < 1e-6).float().mean())) if REACH else None
     st.capture(iters=8)
     hist = {}
     acc = []
@@ -163,6 +183,11 @@ for n_obj in args.n_objects:
     if SQUEEZE:
         rec.update({"w_squeeze": args.w_squeeze, "E_squeeze_mean_initial": squeeze0, "E_squeeze_mean_final": float(st.terms[i_squeeze].mean())})
         print(f"  squeeze: mean E_squeeze {squeeze0:.3e} -> {rec['E_squeeze_mean_final']:.3e}", flush=True)
+    if REACH:
+        rec.update({"w_reach": args.w_reach, "E_reach_mean_initial": reach0[0], "E_reach_mean_final": float(st.terms[i_reach].mean()),
+                    "reachable_share_initial": reach0[1], "reachable_share_final": float((st.terms[i_reach] < 1e-6).float().mean())})
+        print(f"  reach: mean E_reach {reach0[0]:.3e} -> {rec['E_reach_mean_final']:.3e}, rows under 1e-6: {reach0[1]:.2f} -> "
+              f"{rec['reachable_share_final']:.2f}", flush=True)
     records.append(rec)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
