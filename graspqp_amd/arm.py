@@ -5,7 +5,9 @@ A serial chain of N <= 8 revolute or prismatic joints with limits:
     FK(q) = base_T  joint_T[0] m_0(q_0)  joint_T[1] m_1(q_1) ... joint_T[N-1] m_{N-1}(q_{N-1})  tool_T
 
 ``joint_T[j]`` is the fixed transform parent -> joint frame, ``m_j`` the rotation about (revolute) or the shift along (prismatic)
-the unit ``joint_axis[j]`` given in the joint frame, ``tool_T`` flange -> hand root.  ``base_T`` is not part of the arm: it places
+the unit ``joint_axis[j]`` given in the joint frame, ``tool_T`` flange -> hand root.  Link j is the frame after joint j has moved;
+``spheres`` = (link (Ns), centre (Ns,3) in the link frame, radius (Ns)), at most 64, are the arm's collision spheres for the arm
+clearance term (``ops.arm_terms``); the hand and a fixed base link carry none.  ``base_T`` is not part of the arm: it places
 the arm in the frame of an object and belongs to the call (``ops.reach_terms``, ``GraspStepper(arm_base=...)``).  ``seeds`` (S, N),
 1 <= S <= 8, are the joint vectors the IK iteration starts from; the default is the one mid-range configuration.
 """
@@ -15,7 +17,7 @@ import numpy as np
 
 from .hands.spec import _origin, rpy_to_matrix
 
-MAX_JOINTS, MAX_SEEDS = 8, 8
+MAX_JOINTS, MAX_SEEDS, MAX_SPHERES = 8, 8, 64
 REVOLUTE, PRISMATIC = 1, 2
 _TYPES = {"revolute": REVOLUTE, "prismatic": PRISMATIC, REVOLUTE: REVOLUTE, PRISMATIC: PRISMATIC}
 
@@ -40,9 +42,10 @@ def _T44(T34):
 class ArmSpec:
     """joint_types: N entries "revolute" / "prismatic" (or 1 / 2); joint_T (N,3,4) or (N,4,4); joint_axis (N,3), normalised here;
     lower / upper (N), finite with lower < upper; tool_T (3,4) or (4,4), default identity; seeds (S,N) inside the limits, default
-    the mid-range configuration.  Anything else raises ValueError."""
+    the mid-range configuration; spheres None or (link (Ns) integers in 0..N-1, centre (Ns,3) finite, radius (Ns) finite and > 0)
+    with 1 <= Ns <= 64.  Anything else raises ValueError."""
 
-    def __init__(self, joint_types, joint_T, joint_axis, lower, upper, tool_T=None, seeds=None):
+    def __init__(self, joint_types, joint_T, joint_axis, lower, upper, tool_T=None, seeds=None, spheres=None):
         types = list(joint_types)
         N = len(types)
         if not 1 <= N <= MAX_JOINTS:
@@ -78,10 +81,59 @@ class ArmSpec:
             raise ValueError("ArmSpec: every seed must lie inside the joint limits")
         self.seeds = np.ascontiguousarray(s)
         self.n_seeds = int(s.shape[0])
+        self.sphere_link = self.sphere_centre = self.sphere_radius = None
+        self.n_spheres = 0
+        if spheres is not None:
+            if len(spheres) != 3:
+                raise ValueError("ArmSpec: spheres must be (link, centre, radius)")
+            link, centre, radius = (np.asarray(v, dtype=np.float64) for v in spheres)
+            Ns = link.shape[0] if link.ndim == 1 else -1
+            if not 1 <= Ns <= MAX_SPHERES:
+                raise ValueError(f"ArmSpec: sphere link must be (Ns,) with 1 <= Ns <= {MAX_SPHERES}, got {link.shape}")
+            if centre.shape != (Ns, 3) or radius.shape != (Ns,):
+                raise ValueError(f"ArmSpec: sphere centre must be ({Ns},3) and sphere radius ({Ns},), got {centre.shape} and {radius.shape}")
+            if not np.isfinite(link).all() or (link != np.floor(link)).any() or (link < 0).any() or (link > N - 1).any():
+                raise ValueError(f"ArmSpec: every sphere link must be an integer in 0..{N - 1}")
+            if not np.isfinite(centre).all():
+                raise ValueError("ArmSpec: sphere centre is not finite")
+            if not np.isfinite(radius).all() or not (radius > 0).all():
+                raise ValueError("ArmSpec: every sphere radius must be finite and > 0")
+            self.sphere_link, self.sphere_centre, self.sphere_radius = link.astype(np.int32), np.ascontiguousarray(centre), radius
+            self.n_spheres = int(Ns)
+
+    @property
+    def spheres(self):
+        """(link, centre, radius) or None."""
+        return None if self.n_spheres == 0 else (self.sphere_link, self.sphere_centre, self.sphere_radius)
 
     def with_seeds(self, seeds):
         """The same arm with other seeds."""
-        return ArmSpec(self.joint_type.tolist(), self.joint_T, self.joint_axis, self.lower, self.upper, self.tool_T, seeds)
+        return ArmSpec(self.joint_type.tolist(), self.joint_T, self.joint_axis, self.lower, self.upper, self.tool_T, seeds, self.spheres)
+
+    def with_spheres(self, link, centre, radius):
+        """The same arm with the collision spheres (link (Ns), centre (Ns,3) in the link frame, radius (Ns) or one number)."""
+        link = np.asarray(link)
+        radius = np.full(link.shape, float(radius)) if np.ndim(radius) == 0 else radius
+        return ArmSpec(self.joint_type.tolist(), self.joint_T, self.joint_axis, self.lower, self.upper, self.tool_T, self.seeds,
+                       (link, centre, radius))
+
+    def with_link_spheres(self, radius, spacing):
+        """The same arm with spheres of ``radius`` along the segment of every link: from the link's origin to the fixed offset of
+        the next joint (``joint_T[j+1]``'s translation; ``tool_T``'s for the last link), a sphere at the origin and then one every
+        ``spacing`` metres, the far end included when the segment is longer than half a spacing.  Links are served in order until
+        64 spheres are placed."""
+        if not (np.isfinite(radius) and radius > 0 and np.isfinite(spacing) and spacing > 0):
+            raise ValueError(f"ArmSpec.with_link_spheres: radius = {radius!r} and spacing = {spacing!r} must be finite and > 0")
+        link, centre = [], []
+        for j in range(self.n_joints):
+            end = (self.joint_T[j + 1] if j + 1 < self.n_joints else self.tool_T)[:, 3]
+            length = float(np.linalg.norm(end))
+            n = int(np.floor(length / spacing + 0.5))  # pieces of the segment
+            for i in range(n + 1):
+                link.append(j)
+                centre.append(end * (i / n) if n else np.zeros(3))
+        link, centre = link[:MAX_SPHERES], centre[:MAX_SPHERES]
+        return self.with_spheres(link, np.array(centre), float(radius))
 
     # ---- constructors ---------------------------------------------------------------------------------------------------
     @classmethod

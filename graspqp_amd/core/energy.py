@@ -197,9 +197,35 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, obj
         if base.shape[0] not in (1, B // be):
             raise ValueError(f"calculate_energy: set_reach got {base.shape[0]} arm bases, the batch has {B // be} objects")
         base_T = base if base.shape[0] == B // be else base.expand(B // be, 3, 4).contiguous()
-        losses["E_reach"] = ops.reach_terms(hand_model.hand_pose, hand_model._hand, hand_model._fk_idx, hand_model.global_rotation,
-                                            hand_model.current_status, hand_model._fk_ws, arm, base_T, be, hand_model.grasp_axis,
-                                            dist, stations, iters, damping, rot_scale)
+        # return_q: the arm configurations go on to E_arm below, which then needs no reach launch of its own
+        losses["E_reach"], reach_q, _ = ops.reach_terms(hand_model.hand_pose, hand_model._hand, hand_model._fk_idx,
+                                                        hand_model.global_rotation, hand_model.current_status, hand_model._fk_ws, arm, base_T,
+                                                        be, hand_model.grasp_axis, dist, stations, iters, damping, rot_scale, return_q=True)
+
+    if "E_arm" in energy_names:
+        # arm clearance as ONE launch after the reach launch (ops.arm_terms; HandModel.set_reach + set_arm_scene) on the arm
+        # configurations of E_reach above; without that name the reach launch runs here, detached, for them alone -- the term's
+        # gradient goes through its own formula
+        if getattr(hand_model, "reach", None) is None or getattr(hand_model, "arm_scene", None) is None:
+            raise ValueError('calculate_energy: "E_arm" needs HandModel.set_reach(arm, arm_base, ...) and HandModel.set_arm_scene(...)')
+        arm, base, dist, stations, iters, damping, rot_scale = hand_model.reach
+        scene, margin, lam_a = hand_model.arm_scene
+        scene = getattr(hand_model, "scene", None) if scene is None else scene
+        if scene is None:
+            raise ValueError('calculate_energy: "E_arm" needs a scene: HandModel.set_arm_scene(scene=) or set_scene(...)')
+        margin = getattr(hand_model, "scene_margin", 0.0) if margin is None else margin
+        B = hand_model.hand_pose.shape[0]
+        be = object_model.batch_size_each
+        if base.shape[0] not in (1, B // be):
+            raise ValueError(f"calculate_energy: set_reach got {base.shape[0]} arm bases, the batch has {B // be} objects")
+        base_T = base if base.shape[0] == B // be else base.expand(B // be, 3, 4).contiguous()
+        state = (hand_model._hand, hand_model._fk_idx, hand_model.global_rotation, hand_model.current_status, hand_model._fk_ws)
+        if "E_reach" not in energy_names:
+            with torch.no_grad():
+                _, reach_q, _ = ops.reach_terms(hand_model.hand_pose, *state, arm, base_T, be, hand_model.grasp_axis, dist, stations, iters,
+                                                damping, rot_scale, return_q=True)
+        losses["E_arm"] = ops.arm_terms(hand_model.hand_pose, *state, arm, base_T, be, scene, hand_model.grasp_axis, reach_q, dist,
+                                        stations, margin, lam_a, rot_scale)
 
     if "E_manipulativity" in energy_names:
         # energy.py:80-87: mean squared contact velocity the joints cannot produce when the contacts move along

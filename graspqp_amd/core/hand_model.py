@@ -286,6 +286,23 @@ class HandModel:
         handle = arm if isinstance(arm, ops.ArmHandle) else ops.ArmHandle(arm, self.device)
         self.reach = (handle, base, float(distance), int(stations), int(iterations), float(damping), float(rot_scale))
 
+    def set_arm_scene(self, scene=None, margin=None, damping=1e-6):
+        """The arm clearance of calculate_energy(..., energy_names=[..., "E_arm"]): the collision spheres of the arm of
+        ``set_reach`` (call it first, with an arm that has spheres) on ``scene``, an ``ops.SceneSDF`` or ``ops.SceneSDFSet`` -- None takes
+        the grid of ``set_scene``; ``margin`` = None follows the scene's margin; ``damping`` is the term's own lambda_a.  The stations
+        and the rotation scale are the reach term's."""
+        if getattr(self, "reach", None) is None:
+            raise ValueError("HandModel.set_arm_scene: call set_reach(arm, arm_base, ...) first")
+        if scene is None and getattr(self, "scene", None) is None:
+            raise ValueError("HandModel.set_arm_scene: pass scene=ops.SceneSDF(...) or call set_scene(...) first")
+        if scene is not None and not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
+            raise ValueError("HandModel.set_arm_scene: scene must be an ops.SceneSDF, an ops.SceneSDFSet or None")
+        margin = None if margin is None else float(margin)
+        arm, _, dist, stations, _, _, rot_scale = self.reach
+        ops.arm_check(arm, None, 1, 0.0 if margin is None else margin, damping, rot_scale, dist, stations, self.grasp_axis,
+                      "HandModel.set_arm_scene")
+        self.arm_scene = (scene, margin, float(damping))
+
     def get_surface_points(self, hand_pose=None):
         """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose; ``hand_pose`` =
         None takes the model's own (another pose, e.g. the opened one of E_pregrasp, is a second FK at that pose)."""

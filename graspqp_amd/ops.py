@@ -2218,6 +2218,12 @@ class ArmHandle(_DeviceObject):
         d.seeds = arr(np.clip(np.asarray(spec.seeds, np.float32), lo32, hi32), np.float32)
         super().__init__("gq_arm_create", "gq_arm_destroy", device, ctypes.byref(d))
         self.N, self.S = spec.n_joints, spec.n_seeds
+        # the collision spheres of the arm clearance term (arm_terms), if the spec has any: float32 / int32 on the device
+        self.Ns, self.sphere_link, self.sphere_centre, self.sphere_radius = spec.n_spheres, None, None, None
+        if spec.n_spheres:
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt))).to(self.device)
+            self.sphere_link, self.sphere_centre = up(spec.sphere_link, np.int32), up(spec.sphere_centre, np.float32)
+            self.sphere_radius = up(spec.sphere_radius, np.float32)
         self.hid = _register_handle(self)
 
 
@@ -2351,6 +2357,143 @@ def reach_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, arm: ArmHandle, ba
                                    _c(base_T.detach()), int(batch_each), axis,
                                    (float(distance), int(stations), int(iterations), float(damping), float(rot_scale)))
     return (e, q, seed) if return_q else e
+
+
+# ----------------------------------------------------------------------------------------------------------
+# arm clearance: E_arm (csrc/armscene.hip), the arm's collision spheres on the scene grid at the joints the reach launch has left in
+# reach_q; ONE launch: a block per row, a wavefront per station, lane = sphere; the gradient in the gRt layout the FK backward takes
+# ----------------------------------------------------------------------------------------------------------
+ARM_DEFAULTS = {"margin": 0.0, "damping": 1e-6, "rot_scale": 0.1, "distance": 0.10, "stations": 0}
+
+
+def _arm_scene_grids(scene, who="arm_terms"):
+    if not isinstance(scene, (SceneSDF, SceneSDFSet)):
+        raise ValueError(f"{who}: arm scene must be an ops.SceneSDF or an ops.SceneSDFSet, got {type(scene).__name__}")
+    return _pregrasp_grids(scene.values, scene.origin, scene.voxel)
+
+
+def arm_check(arm, grids=None, batch=1, margin=0.0, damping=1e-6, rot_scale=0.1, distance=0.10, stations=0,
+              grasp_axis=(0.0, 0.0, 1.0), who="arm_terms"):
+    """The parameters of the arm clearance term (no GPU): ``arm`` an ArmSpec or ArmHandle WITH collision spheres; ``grids`` a
+    ``_C.ClutterGrids`` (or None: the parameters alone are checked, before a scene exists), ``batch`` divisible by its n_grids; a finite margin >= 0, finite damping > 0 and rot_scale > 0, stations in 0..3, a finite
+    distance > 0 when there are stations, a finite non-zero grasp_axis.  Raises ValueError; the library's message (gq_arm_check)
+    contains "arm" and names the argument."""
+    if not isinstance(arm, (ArmSpec, ArmHandle)):
+        raise ValueError(f"{who}: arm must be an ops.ArmSpec or an ops.ArmHandle, got {type(arm).__name__}")
+    spec = arm.spec if isinstance(arm, ArmHandle) else arm
+    if not spec.n_spheres:
+        raise ValueError(f"{who}: the arm has no collision spheres (ArmSpec.with_spheres / with_link_spheres)")
+    if int(stations) != stations:
+        raise ValueError(f"{who}: arm stations = {stations!r} must be an integer in 0..3")
+    G = 1 if grids is None else max(int(grids.n_grids), 1)  # None: gq_arm_check takes a NULL stack and checks the parameters alone
+    if int(batch) % G:
+        raise ValueError(f"{who}: arm: batch = {batch} is not divisible by n_grids = {G}")
+    ax = _axis_c(_axis3(grasp_axis))
+    try:
+        _C.call("gq_arm_check", None if grids is None else ctypes.byref(grids), ctypes.c_int64(int(batch)), ctypes.c_int64(int(batch) // G), int(spec.n_joints),
+                int(spec.n_spheres), float(margin), float(damping), float(rot_scale), float(distance), int(stations),
+                ctypes.cast(ax, ctypes.c_void_p))
+    except RuntimeError as e:
+        raise ValueError(f"{who}: {e}") from None
+
+
+def _arm_call(arm, grids, margin, damping, rot_scale, hp, Rg, base_T, batch_each, axis, distance, stations, reach_q, up, w, e,
+              accumulate, gRt, st=None):
+    p, (B, D) = _dev, hp.shape
+    _C.call("gq_arm_terms", arm.handle, ctypes.byref(grids), ctypes.c_int64(B // max(grids.n_grids, 1)), float(margin), float(damping),
+            float(rot_scale), _C.i32(arm.sphere_link), _C.f32(arm.sphere_centre), _C.f32(arm.sphere_radius), int(arm.Ns), _C.f32(hp), D,
+            p(Rg), ctypes.c_int64(B), p(base_T), ctypes.c_int64(B // int(batch_each)), ctypes.c_int64(int(batch_each)),
+            ctypes.cast(_axis_c(axis), ctypes.c_void_p), float(distance), int(stations), p(reach_q), p(up), float(w), p(e),
+            int(accumulate), p(gRt), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::arm_terms", mutates_args=(), device_types="cuda")
+def _arm_op(arm: int, hand_pose: Tensor, Rg: Tensor, base_T: Tensor, batch_each: int, values: Tensor, origin: List[float],
+            voxel: float, grasp_axis: List[float], distance: float, stations: int, reach_q: Tensor, margin: float, damping: float,
+            rot_scale: float) -> Tensor:
+    """-> E_arm (B), unweighted, in metres: the mean over the stations of the hinge sum of the arm's collision spheres at the joints
+    ``reach_q`` (B,K+1,N).  ``values`` is one grid (nx,ny,nz) or a stack (G,nx,ny,nz)."""
+    a = _handle(arm)
+    hp, v = _c(hand_pose), _c(values)
+    e = torch.empty(hp.shape[0], device=hp.device)
+    _arm_call(a, _pregrasp_grids(v, origin, voxel), margin, damping, rot_scale, hp, _c(Rg), _c(base_T), batch_each, grasp_axis,
+              distance, stations, _c(reach_q), None, 0.0, e, 0, None)
+    return e
+
+
+@_arm_op.register_fake
+def _(arm, hand_pose, Rg, base_T, batch_each, values, origin, voxel, grasp_axis, distance, stations, reach_q, margin, damping, rot_scale):
+    return hand_pose.new_empty(hand_pose.shape[0])
+
+
+@_custom_op("graspqp_amd::arm_terms_backward", mutates_args=(), device_types="cuda")
+def _arm_bwd_op(arm: int, hand_pose: Tensor, Rg: Tensor, base_T: Tensor, batch_each: int, values: Tensor, origin: List[float],
+                voxel: float, grasp_axis: List[float], distance: float, stations: int, reach_q: Tensor, margin: float, damping: float,
+                rot_scale: float, g_arm: Tensor) -> Tensor:
+    """Upstream row gradients (B) on E_arm -> gRt (B,12) for fk_backward.  One launch."""
+    a = _handle(arm)
+    hp, v = _c(hand_pose), _c(values)
+    gRt = torch.empty(hp.shape[0], 12, device=hp.device)
+    _arm_call(a, _pregrasp_grids(v, origin, voxel), margin, damping, rot_scale, hp, _c(Rg), _c(base_T), batch_each, grasp_axis,
+              distance, stations, _c(reach_q), _c(g_arm), 1.0, None, 0, gRt)
+    return gRt
+
+
+@_arm_bwd_op.register_fake
+def _(arm, hand_pose, Rg, base_T, batch_each, values, origin, voxel, grasp_axis, distance, stations, reach_q, margin, damping, rot_scale,
+      g_arm):
+    return hand_pose.new_empty(hand_pose.shape[0], 12)
+
+
+class _ArmTerms(torch.autograd.Function):
+    """Glue between two registered ops (arm_terms + fk_backward), as _ReachTerms: the backward launch writes gRt with the per-row
+    upstream, the FK backward turns it into the root translation and rotation gradient.  The hand's joints get none."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, idx, Rg, LT, ws, arm, base_T, batch_each, scene, axis, reach_q, par):
+        hp = _c(hand_pose.detach())
+        distance, stations, margin, damping, rot_scale = par
+        args = (arm.hid, hp, Rg, base_T, batch_each, scene.values, list(scene.origin), scene.voxel, axis, distance, stations, reach_q,
+                margin, damping, rot_scale)
+        e = _Eager.arm_terms(*args)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, base_T, scene.values, reach_q)
+        ctx.hand, ctx.arm, ctx.args = hand, arm, args
+        return e
+
+    @staticmethod
+    def backward(ctx, g_arm):
+        hp, idx, Rg, LT, ws, base_T, values, reach_q = ctx.saved_tensors
+        gRt = _Eager.arm_terms_backward(*ctx.args, _c(g_arm))
+        gp = _fk_backward(ctx.hand, hp, idx, Rg, LT, ws, None, None, None, None, gRt, None)
+        return (gp,) + (None,) * 12
+
+
+def arm_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, arm: ArmHandle, base_T, batch_each, scene, grasp_axis, reach_q,
+              distance=0.10, stations=0, margin=0.0, damping=1e-6, rot_scale=0.1):
+    """-> E_arm (B) in metres = the mean over the stations k = 0..K of sum_s max(margin + r_s - phi(x_s), 0): the arm's collision
+    spheres (``ArmSpec.with_spheres``) at the arm configuration ``reach_q`` (B,K+1,N) -- what ``reach_terms(..., return_q=True)``
+    returned for the same poses and the same ``distance`` / ``stations`` / ``rot_scale`` -- on the grid of ``scene``, an
+    ``ops.SceneSDF`` or an ``ops.SceneSDFSet`` (row b reads grid b // (B / G)).  ``base_T`` (n_obj,3,4) as in ``reach_terms``.
+    Unweighted; differentiable w.r.t. the root translation and rotation of ``hand_pose`` through the minimum-norm joint motion
+    that follows the target, dq = J' (J J' + damping I)^-1 de (include/graspqp_hip.h, "arm clearance": exact along that tracking for
+    a reached target with no joint on a limit, an approximation elsewhere).  ``idx``, ``Rg``, ``LT``, ``ws`` are the kinematic state
+    of ``hand_pose`` (fk_contacts)."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if not isinstance(arm, ArmHandle):
+        raise ValueError("arm_terms: arm must be an ops.ArmHandle")
+    axis = [float(a) for a in _axis3(grasp_axis)]
+    B = hand_pose.shape[0]
+    arm_check(arm, _arm_scene_grids(scene), B, margin, damping, rot_scale, distance, stations, axis)
+    if int(batch_each) < 1 or B % int(batch_each):
+        raise ValueError(f"arm_terms: batch = {B} is not divisible by batch_each = {batch_each}")
+    if tuple(base_T.shape) != (B // int(batch_each), 3, 4):
+        raise ValueError(f"arm_terms: base_T must be ({B // int(batch_each)}, 3, 4), got {tuple(base_T.shape)}")
+    if tuple(reach_q.shape) != (B, int(stations) + 1, arm.N):
+        raise ValueError(f"arm_terms: reach_q must be ({B}, {int(stations) + 1}, {arm.N}), got {tuple(reach_q.shape)}")
+    return _ArmTerms.apply(hand_pose, hand, _c(idx, torch.int64), _c(Rg.detach()), _c(LT.detach()), ws, arm, _c(base_T.detach()),
+                           int(batch_each), scene, axis, _c(reach_q.detach()),
+                           (float(distance), int(stations), float(margin), float(damping), float(rot_scale)))
 
 
 @_custom_op("graspqp_amd::scene_compose", mutates_args=("out_values",), device_types="cuda")
@@ -2760,6 +2903,8 @@ _eager("squeeze_terms", _squeeze_op)
 _eager("squeeze_terms_backward", _squeeze_bwd_op)
 _eager("reach_terms", _reach_op)
 _eager("reach_terms_backward", _reach_bwd_op)
+_eager("arm_terms", _arm_op)
+_eager("arm_terms_backward", _arm_bwd_op)
 _eager("scene_compose", _scene_compose_op)
 _eager("tsdf_integrate", _tsdf_integrate_op)
 _eager("tsdf_surfels", _tsdf_surfels_op)

@@ -58,6 +58,14 @@ the final joints held fixed: the gradient of the converged energy where the iter
 [E_reach] appended last, its share of the row total is one more gq_scene_total launch, and the proposal and the accept step are the
 stand-alone launches.
 
+Arm mode (a weight on "E_arm", in reach mode, with an arm that has collision spheres and ``arm_scene`` or ``scene``): where does the arm
+configuration of the reach term put the arm?  E_arm is the mean over the reach term's stations of sum_s max(``arm_margin`` + r_s -
+phi(x_s), 0) over the arm's collision spheres at ``reach_q``, in metres, on the grid of ``arm_scene`` (one grid, or one per object; it
+may contain the target).  One more launch right after the reach launch (gq_arm_terms: a block per row, a wavefront per station,
+lane = sphere) ADDS its gradient to ``gRt``: the minimum-norm tracking of the target at the term's own damping ``arm_damping``
+(include/graspqp_hip.h, "arm clearance": exact along that tracking for a reached target with no joint on a limit, an approximation
+elsewhere).  ``terms`` gets [E_arm] appended after [E_reach]; ``select`` gates it at 0 by default; with weight 0 nothing changes.
+
 Clutter (``scene`` is an ``ops.SceneSDFSet`` with one grid per object): the same two launches read a stack of grids and pick the
 grid from the row, row // batch_each (gq_clutter_terms / gq_clutter_corridor_terms, the same row bodies: bit for bit the single-grid
 launch's numbers on that grid).  ``ops.scene_compose`` refills the stack in place, also between replays of a captured graph.
@@ -82,6 +90,7 @@ APPROACH_TERMS = ("E_approach",)
 PREGRASP_TERMS = ("E_pregrasp",)
 SQUEEZE_TERMS = ("E_squeeze",)
 REACH_TERMS = ("E_reach",)
+ARM_TERMS = ("E_arm",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
@@ -90,11 +99,11 @@ OBSTACLE_TERMS = SCENE_TERMS + APPROACH_TERMS + PREGRASP_TERMS
 
 def select_tolerances(term_names, gates=None):
     """The gates of ``GraspStepper.select`` as one tolerance per term of ``term_names`` (+inf: not gated).  ``gates`` = {term name:
-    tol}; None gates every obstacle term that is switched on (E_scene, E_approach, E_pregrasp) at 0.0 and nothing else -- the
-    "collision-free" of ``init_avoid_scene``.  A name that is no term of the stepper, or that names a switched-off term, raises,
+    tol}; None gates every obstacle term that is switched on (E_scene, E_approach, E_pregrasp, and E_arm for the arm) at 0.0 and
+    nothing else -- the "collision-free" of ``init_avoid_scene``.  A name that is no term of the stepper, or that names a switched-off term, raises,
     and so does a NaN tolerance."""
     if gates is None:
-        gates = {k: 0.0 for k in OBSTACLE_TERMS if k in term_names}
+        gates = {k: 0.0 for k in OBSTACLE_TERMS + ARM_TERMS if k in term_names}
     tol = [float("inf")] * len(term_names)
     for k, v in gates.items():
         if k not in term_names:
@@ -107,11 +116,11 @@ def select_tolerances(term_names, gates=None):
 
 def merge_weights(weights=None):
     """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term, of the pre-grasp term, of
-    the squeeze term and of the reach term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
+    the squeeze term, of the reach term and of the arm clearance term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
     never used), and so does a negative weight of one of the terms that are switched by their weight."""
-    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS
+    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS + ARM_TERMS
     w = dict(DEFAULT_WEIGHTS)
-    w.update({k: 0.0 for k in REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
+    w.update({k: 0.0 for k in ARM_TERMS + REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
     for k, v in (weights or {}).items():
         if k not in w:
             raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
@@ -142,7 +151,8 @@ class GraspStepper:
                  pregrasp_opening: float = 0.5, pregrasp_joints=None, pregrasp_scene=None, pregrasp_distance=None,
                  pregrasp_stations=None, pregrasp_margin=None, squeeze_min_travel: float = 5e-3, squeeze_damping: float = 1e-3,
                  arm=None, arm_base=None, reach_distance: float = 0.10, reach_stations: int = 0, reach_iterations: int = 24,
-                 reach_damping: float = 1e-4, reach_rot_scale: float = 0.1, init_avoid_scene: bool = False):
+                 reach_damping: float = 1e-4, reach_rot_scale: float = 0.1, arm_scene=None, arm_margin=None, arm_damping: float = 1e-6,
+                 init_avoid_scene: bool = False):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -177,7 +187,10 @@ class GraspStepper:
         and ``arm_base``, (3,4) or (n_obj,3,4): the arm base in the frame of each object.  ``reach_stations`` in 0..3 stations beyond
         the grasp pose over ``reach_distance`` metres (> 0 when there are stations), ``reach_iterations`` in 0..4096,
         ``reach_damping`` (m^2) and ``reach_rot_scale`` (metres per radian) finite and > 0.  ``reach_q`` / ``reach_seed`` hold the arm
-        configurations of the last evaluation.  No default weight is set.  With weight 0 the seven arguments change nothing."""
+        configurations of the last evaluation.  No default weight is set.  With weight 0 the seven arguments change nothing.
+        weights["E_arm"] > 0 selects the arm mode (module docstring): it needs weights["E_reach"] > 0, an ``arm`` with collision spheres
+        and ``arm_scene`` (None: ``scene``), an ``ops.SceneSDF`` or an ``ops.SceneSDFSet`` with one grid per object; ``arm_margin`` >= 0
+        (None: ``scene_margin``), ``arm_damping`` finite and > 0 (the term's own lambda_a, not ``reach_damping``)."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -236,12 +249,27 @@ class GraspStepper:
             ops.reach_check(arm, reach_distance, reach_stations, reach_iterations, reach_damping, reach_rot_scale, hand.spec.grasp_axis,
                             "GraspStepper")
             arm_base = ops.reach_base(arm_base, self.n_obj, "GraspStepper")
+        self.arm_mode = self.w["E_arm"] > 0
+        if self.arm_mode:
+            if not self.reach_mode:
+                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs weights["E_reach"] > 0: the term reads the reach term\'s reach_q')
+            if not (arm.spec if isinstance(arm, ops.ArmHandle) else arm).n_spheres:
+                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs an arm with collision spheres (ArmSpec.with_spheres / '
+                                 'with_link_spheres)')
+            arm_scene = scene if arm_scene is None else arm_scene
+            if not isinstance(arm_scene, (ops.SceneSDF, ops.SceneSDFSet)):
+                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs arm_scene= or scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
+            if isinstance(arm_scene, ops.SceneSDFSet) and arm_scene.n_grids != self.n_obj:
+                raise ValueError(f"GraspStepper: arm_scene has n_grids = {arm_scene.n_grids}, the stepper has n_obj = {self.n_obj} objects")
+            arm_margin = scene_margin if arm_margin is None else arm_margin
+            ops.arm_check(arm, ops._arm_scene_grids(arm_scene, "GraspStepper"), self.B, arm_margin, arm_damping, reach_rot_scale,
+                          reach_distance, reach_stations, hand.spec.grasp_axis, "GraspStepper")
         self.init_avoid_scene = bool(init_avoid_scene)
         if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
             raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
         self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
                            + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ())
-                           + (SQUEEZE_TERMS if self.squeeze_mode else ()) + (REACH_TERMS if self.reach_mode else ()))
+                           + (SQUEEZE_TERMS if self.squeeze_mode else ()) + (REACH_TERMS if self.reach_mode else ()) + (ARM_TERMS if self.arm_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -439,6 +467,11 @@ class GraspStepper:
             self.reach_q = f(B, self.reach_stations + 1, self.arm.N)
             self.reach_seed = torch.zeros(B, self.reach_stations + 1, dtype=torch.int32, device=self.dev)
             self._reach_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
+        self.arm_scene = None
+        if self.arm_mode:
+            self._i_arm = self.term_names.index("E_arm")
+            self.arm_scene, self.arm_margin, self.arm_damping = arm_scene, float(arm_margin), float(arm_damping)
+            self._arm_grids = ops._arm_scene_grids(arm_scene, "GraspStepper")  # the stack view: a single grid is the stack of one
         self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
@@ -582,6 +615,13 @@ class GraspStepper:
                         self.reach_iterations, self.reach_damping, self.reach_rot_scale, None, self.w["E_reach"],
                         self.terms_new[self._i_reach], self.reach_q, self.reach_seed, 1, self.gRt, st)
 
+    def _eval_arm(self, pose, st):
+        """E_arm -> its row of terms_new (``_i_arm``) from the ``reach_q`` the reach launch of this evaluation has just written; the
+        gradient of w_arm E_arm is ADDED to ``gRt``.  g_R and g_theta are not touched."""
+        ops._arm_call(self.arm, self._arm_grids, self.arm_margin, self.arm_damping, self.reach_rot_scale, pose, self.Rg, self.arm_base,
+                      self.be, self._reach_axis, self.reach_distance, self.reach_stations, self.reach_q, None, self.w["E_arm"],
+                      self.terms_new[self._i_arm], 1, self.gRt, st)
+
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
         f32 = _C.f32
@@ -634,6 +674,8 @@ class GraspStepper:
             self._eval_squeeze(idx, st)
         if self.reach_mode:
             self._eval_reach(pose, st)
+        if self.arm_mode:  # after the reach launch (it reads reach_q), before the FK backward (it adds to gRt)
+            self._eval_arm(pose, st)
         self._eval_tail(pose, idx, st, loop)
         if self.tabletop:  # the FK backward's total holds the five terms
             _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
@@ -645,6 +687,9 @@ class GraspStepper:
                     ctypes.c_int64(self.B), st)
         if self.reach_mode:
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_reach]), float(self.w["E_reach"]),
+                    ctypes.c_int64(self.B), st)
+        if self.arm_mode:
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_arm]), float(self.w["E_arm"]),
                     ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):

@@ -775,6 +775,54 @@ int gq_reach_terms(const gqArm* arm, const float* hand_pose /* (B,pose_dim) */, 
                    float* reach_q /* (B,K+1,N) or NULL */, int32_t* reach_seed /* (B,K+1) or NULL */, int accumulate,
                    float* gRt /* (B,12) or NULL */, void* stream);
 
+/* ---- arm clearance of the stepper: E_arm, the arm's collision spheres on the scene grid -----------------------------------------
+ * E_reach says whether the wrist can get to a pose and leaves the arm configuration of every station in reach_q; this term looks at
+ * where that configuration puts the arm.  The arm carries Ns <= 64 collision spheres (link l_s in 0..N-1, centre c_s in the link
+ * frame, radius r_s > 0), all three arrays on the device.  Link j is the frame after joint j has moved,
+ * W_j(q) = base_T joint_T[0] m_0(q_0) ... joint_T[j] m_j(q_j), the chain of gq_reach_terms in the row's object frame (products taken
+ * left to right).  The hand is not part of the term (the hand-surface terms cover it), nor is a fixed base link.  Per row b and
+ * station k = 0..K (K = n_stations, distance and grasp_axis are the reach term's), with q_k = reach_q[b,k] -- an INPUT, the winner's
+ * joints of the reach launch of the same evaluation; nothing is recomputed:
+ *   x_s = W_{l_s}(q_k) c_s      h_s = max((margin + r_s) - phi(x_s), 0)      E_k = sum_s h_s (spheres ascending)
+ *   E_arm = 1/(K+1) sum_k E_k   in metres, written UNWEIGHTED and always overwritten
+ * phi is the trilinear interpolant of "scene obstacles" by the same device body (the bits of gq_clutter_query at the same point):
+ * h_s = 0 outside the volume and at a non-finite point.  The grids are a gqClutterGrids stack, row b reads grid b / rows_per_grid,
+ * batch == n_grids * rows_per_grid; n_grids = 1 is the single scene.  The grid may contain the target object.
+ * Gradient.  E_arm depends on the pose only through q.  The term DEFINES dq = J' (J J' + lambda_a I)^-1 de, the minimum-norm joint
+ * motion that follows a small motion de = [dp* ; rho d omega] of the target; J = [J_v ; rho J_w] (6 x N) is the reach term's matrix at
+ * the hand root, lambda_a = damping is this term's OWN parameter (default 1e-6, not the reach iteration's 1e-4: beside
+ * sigma_min^2(J) of 1e-4..1e-2 at rho = 0.1 the latter is not small).  With f_s = -grad phi(x_s) where h_s > 0:
+ *   g_q[j] = sum_{s : l_s >= j} f_s . col_j(x_s)     col_j(x) = z_j x (x - o_j) (revolute) or z_j (prismatic)
+ *   a joint is free when lower_j < q_j < upper_j on the float32 numbers the device holds; a joint ON a limit gets g_q[j] = 0 and a
+ *   zero column in J
+ *   y = (J J' + lambda_a I)^-1 J g_q      dE_k/dp*_k = y_p      the torque for R* <- exp(d^) R* is rho y_w
+ * and with c = w (up[row] if given, else 1) / (K+1), d_k = D k / K, in the layout and signs of gq_reach_terms (2 e_p -> y_p,
+ * 2 rho e_w -> rho y_w):
+ *   gRt (B,12) = [gsum(3), K9(9)]: gsum = -R' sum_k c y_p,k;  K9 = sum_k (R' c y_p,k) (x) (-d_k a) + hat(R' sum_k c rho y_w,k) / 2
+ * accumulate = 1 adds to gRt, 0 overwrites it; g_R and g_theta of gq_fk_backward are not touched; gRt = NULL skips the gradient.
+ * What this is: for a target the arm reaches with no joint on a limit it is the derivative of E_arm along the arm's minimum-norm
+ * tracking of the target, with an error of at most lambda_a / sigma_min^2(J).  Elsewhere it is an approximation: for an unreachable
+ * target the Jacobian of the log map is dropped; a joint on a limit is frozen; for a redundant arm the from-seed iteration of the
+ * reach term need not follow the minimum-norm branch.  |y| <= |g_q| / (2 sqrt(lambda_a)) bounds it at a singular configuration.
+ * Precision: J g_q, J J' and the 6 x 6 Cholesky solve are fp64 (one solve per station whose result IS the gradient, usable to a
+ * condition number of 8e6); the kinematics, the sphere points, the field samples and the columns are fp32.
+ * One block per row, one wavefront per station, lane = sphere; fixed-order sums, no atomics: bitwise reproducible run to run, and a
+ * pure function of (reach_q, Rg).  hand_pose is the row's pose as every term takes it (the term reads its rotation from Rg).
+ * The row total takes gq_scene_total(total, e_arm, w, B).
+ * gq_arm_check is the argument check on its own (host only, no GPU): the stack and the batch (gq_clutter_check; grids = NULL checks
+ * the parameters alone, before a scene exists -- gq_arm_terms itself refuses a NULL stack), n_joints in 1..8,
+ * n_spheres in 1..64, a finite margin >= 0, finite damping > 0 and rot_scale > 0, n_stations in 0..3, a finite distance > 0 when
+ * there are stations, a finite non-zero grasp_axis; its message contains "arm" and names the argument.                          */
+int gq_arm_check(const gqClutterGrids* grids, int64_t batch, int64_t rows_per_grid, int n_joints, int n_spheres, float margin,
+                 float damping, float rot_scale, float distance, int n_stations, const float* grasp_axis /* (3) host */);
+int gq_arm_terms(const gqArm* arm, const gqClutterGrids* grids, int64_t rows_per_grid, float margin, float damping, float rot_scale,
+                 const int32_t* sphere_link /* (Ns) device */, const float* sphere_centre /* (Ns,3) device */,
+                 const float* sphere_radius /* (Ns) device */, int n_spheres, const float* hand_pose /* (B,pose_dim) */,
+                 int pose_dim, const float* Rg /* (B,9) */, int64_t batch, const float* base_T /* (n_obj,12) */, int64_t n_obj,
+                 int64_t batch_each, const float* grasp_axis /* (3) host */, float distance, int n_stations,
+                 const float* reach_q /* (B,K+1,N) input */, const float* up /* (B) or NULL */, float w,
+                 float* e_arm /* (B) or NULL */, int accumulate, float* gRt /* (B,12) or NULL */, void* stream);
+
 /* ---- scenes from depth images: TSDF fusion on the device into scene grids ---------------------------------------------
  * What a robot has is depth images, not a signed-distance volume.  gq_tsdf_integrate fuses a batch of depth frames into a
  * gqClutterGrids stack IN PLACE, one launch per batch (n_grids = 1 is the single world grid).  State: `values` of the stack IS

@@ -13,6 +13,7 @@ Evidence run, not a test: writes one JSON record (default gpurun_out/fit_end_to_
 usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_iter 7000] [--out file.json]
        [--w_squeeze 0] [--squeeze_min_travel 5e-3] [--squeeze_damping 1e-3]   (contact closing feasibility, E_squeeze)
        [--w_reach 0] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations 0]   (arm reachability, E_reach)
+       [--w_arm 0] [--arm_margin 0] [--arm_sphere_radius 0.05] [--arm_sphere_spacing 0.08]   (arm clearance, E_arm: needs --w_reach > 0)
        [--w_wall 0] [--w_prior 0]   (scripts/fit.py:77-78: tabletop synthesis; the class surface and the oracle then carry
        E_wall / E_prior on the stepper's surface samples, st.samples)
        [--w_scene 0] [--scene_margin 0] [--scene box]   (scene obstacles: the ``box`` preset is an open-topped bin of five slabs
@@ -54,6 +55,10 @@ ap.add_argument("--squeeze_min_travel", type=float, default=5e-3)
 ap.add_argument("--squeeze_damping", type=float, default=1e-3)
 ap.add_argument("--w_reach", type=float, default=0.0)
 ap.add_argument("--arm", default="arm7")  # a preset of graspqp_amd.arm, or a URDF file (then --arm_tip, optionally --arm_base_link)
+ap.add_argument("--w_arm", type=float, default=0.0)  # arm clearance: the arm's link spheres on the ``box`` scene
+ap.add_argument("--arm_margin", type=float, default=0.0)
+ap.add_argument("--arm_sphere_radius", type=float, default=0.05)
+ap.add_argument("--arm_sphere_spacing", type=float, default=0.08)
 ap.add_argument("--arm_tip", default=None)
 ap.add_argument("--arm_base_link", default=None)
 ap.add_argument("--arm_base", type=float, nargs=4, default=(-0.45, 0.0, -0.3, 0.0), metavar=("X", "Y", "Z", "YAW"))
@@ -93,6 +98,12 @@ if REACH:
     W["E_reach"] = args.w_reach
     reach_kw = dict(arm=arm_from_arg(args.arm, args.arm_tip, args.arm_base_link), arm_base=base_from_arg(args.arm_base),
                     reach_stations=args.reach_stations, reach_distance=args.reach_distance)
+ARM = args.w_arm > 0  # arm clearance (E_arm: the arm's collision spheres on the scene grid, one launch after the reach launch)
+if ARM:
+    if not REACH:
+        ap.error("--w_arm needs --w_reach > 0")
+    W["E_arm"] = args.w_arm
+    reach_kw["arm"] = reach_kw["arm"].with_link_spheres(args.arm_sphere_radius, args.arm_sphere_spacing)
 spec = get_hand_spec(args.hand)
 n_obj, be, n = args.n_objects, args.batch_size, args.n_contact
 B = n_obj * be
@@ -104,7 +115,7 @@ om.initialize_from_meshes(fvs, codes, surface_points_list=sps)
 hand = ops.HandHandle(spec)
 weights = {"E_prior": args.w_prior, "E_wall": args.w_wall} if TABLETOP else {}
 scene = None
-if SCENE or APPROACH:  # the ``box`` preset: an open-topped bin around the first object
+if SCENE or APPROACH or ARM:  # the ``box`` preset: an open-topped bin around the first object
     center = 0.5 * (fvs[0].reshape(-1, 3).min(0) + fvs[0].reshape(-1, 3).max(0))
     scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), [float(c) - 0.5 * 0.005 * 79 for c in center], (80, 80, 80), 0.005)
     if SCENE:
@@ -115,6 +126,9 @@ if SQUEEZE:
     weights["E_squeeze"] = args.w_squeeze
 if REACH:
     weights["E_reach"] = args.w_reach
+if ARM:
+    weights["E_arm"] = args.w_arm
+    reach_kw.update(arm_scene=scene, arm_margin=args.arm_margin)
 st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1, weights=weights or None, scene=scene,
                   scene_margin=args.scene_margin, approach_distance=args.approach_distance, approach_stations=args.approach_stations,
                   squeeze_min_travel=args.squeeze_min_travel, squeeze_damping=args.squeeze_damping, **reach_kw)
@@ -153,11 +167,13 @@ if SQUEEZE:
     hm.set_squeeze(args.squeeze_min_travel, args.squeeze_damping)
 if REACH:
     hm.set_reach(reach_kw["arm"], reach_kw["arm_base"], args.reach_distance, args.reach_stations)
+if ARM:
+    hm.set_arm_scene(scene, args.arm_margin)
 metric = GraspSpanMetricFactory.create(GraspSpanMetricFactory.MetricType.GRASPQP, {"friction": 0.2, "max_limit": 20.0, "n_cone_vecs": 4})
 losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1,
                           energy_names=(["E_prior", "E_wall"] if TABLETOP else []) + (["E_scene"] if SCENE else []) +
                           (["E_approach"] if APPROACH else []) + (["E_squeeze"] if SQUEEZE else []) +
-                          (["E_reach"] if REACH else []))
+                          (["E_reach"] if REACH else []) + (["E_arm"] if ARM else []))
 total_cls = sum(W[k] * losses[k] for k in W)
 rel_cls = ((total_cls.detach() - st.energy).abs() / st.energy.abs().clamp_min(1e-6))
 

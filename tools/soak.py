@@ -5,7 +5,8 @@ counters must not show inline-ranked overflow growing, the stop iteration is his
 usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_z Z] [--w_scene W] [--scene_margin M]
        [--scene box] [--w_approach W] [--approach_distance D] [--approach_stations K]
        [--w_pregrasp W] [--pregrasp_opening A] [--pregrasp_stations K] [--w_squeeze W]
-       [--w_reach W] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations K] [--out file.json]
+       [--w_reach W] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations K] [--w_arm W] [--arm_report]
+       [--out file.json]
        (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
        schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
        hand surface samples left below the plane; --w_scene > 0 runs it in scene mode against the ``box`` preset (an open-topped
@@ -58,6 +59,12 @@ ap.add_argument("--arm_base_link", default=None)
 ap.add_argument("--arm_base", type=float, nargs=4, default=(-0.45, 0.0, -0.3, 0.0), metavar=("X", "Y", "Z", "YAW"))
 ap.add_argument("--reach_stations", type=int, default=0)
 ap.add_argument("--reach_distance", type=float, default=0.10)
+# arm clearance (E_arm, needs --w_reach > 0): the arm's link spheres on the bin's grid; --arm_report measures the term with the weight off
+ap.add_argument("--w_arm", type=float, default=0.0)
+ap.add_argument("--arm_report", action="store_true")
+ap.add_argument("--arm_margin", type=float, default=0.0)
+ap.add_argument("--arm_sphere_radius", type=float, default=0.05)
+ap.add_argument("--arm_sphere_spacing", type=float, default=0.08)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
@@ -83,7 +90,25 @@ if REACH:
     weights["E_reach"] = args.w_reach
     reach_kw = dict(arm=arm_from_arg(args.arm, args.arm_tip, args.arm_base_link), arm_base=base_from_arg(args.arm_base),
                     reach_stations=args.reach_stations, reach_distance=args.reach_distance)
+ARM = args.w_arm > 0
+ARM_REPORT = REACH and (ARM or args.arm_report)
+if ARM and not REACH:
+    ap.error("--w_arm needs --w_reach > 0")
+if ARM_REPORT:
+    reach_kw["arm"] = reach_kw["arm"].with_link_spheres(args.arm_sphere_radius, args.arm_sphere_spacing)
+if ARM:
+    weights["E_arm"] = args.w_arm
 records = []
+
+
+def arm_clearance(st, scene):
+    """E_arm (B) of the accepted poses, unweighted, whether the term is on or not: one evaluation at the accepted state (it leaves the
+    arm configurations in ``reach_q``), then the term's launch on them."""
+    st.evaluate(st.hand_pose.clone(), st.contact_idx.clone())
+    e = torch.empty(st.B, device=st.dev)
+    ops._arm_call(st.arm, ops._arm_scene_grids(scene), args.arm_margin, 1e-6, st.reach_rot_scale, st.pose_new, st.Rg, st.arm_base, st.be,
+                  st._reach_axis, st.reach_distance, st.reach_stations, st.reach_q, None, 0.0, e, 0, None)
+    return e
 
 
 def samples_below(st):
@@ -104,13 +129,14 @@ for n_obj in args.n_objects:
     om = ObjectModel(batch_size_each=256, num_samples=2500)
     om.initialize_from_meshes(fvs, surface_points_list=sps)
     scene = None
-    if SCENE or APPROACH or PREGRASP:
+    if SCENE or APPROACH or PREGRASP or ARM_REPORT:
         center = 0.5 * (fvs[0].reshape(-1, 3).min(0) + fvs[0].reshape(-1, 3).max(0))
         scene = ops.SceneSDF.from_meshes(meshes.open_bin(center), [float(c) - 0.5 * 0.005 * 79 for c in center], (80, 80, 80), 0.005)
     st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), 256, 12, seed=3, weights=weights or None,
                       table_z=args.table_z, scene=scene, scene_margin=args.scene_margin,
                       approach_distance=args.approach_distance, approach_stations=args.approach_stations,
-                      pregrasp_opening=args.pregrasp_opening, pregrasp_stations=args.pregrasp_stations, **reach_kw)
+                      pregrasp_opening=args.pregrasp_opening, pregrasp_stations=args.pregrasp_stations, **reach_kw,
+                      **(dict(arm_scene=scene, arm_margin=args.arm_margin) if ARM else {}))
     st.set_hulls(om.convex_hulls())
     st.initialize()
     e0 = st.energy.clone()
@@ -125,6 +151,7 @@ for n_obj in args.n_objects:
     squeeze0 = float(st.terms[i_squeeze].mean()) if SQUEEZE else None
     i_reach = st.term_names.index("E_reach") if REACH else None
     reach0 = (float(st.terms[i_reach].mean()), float((st.terms[i_reach] < 1e-6).float().mean())) if REACH else None
+    arm0 = arm_clearance(st, scene) if ARM_REPORT else None
     st.capture(iters=8)
     hist = {}
     acc = []
@@ -188,6 +215,13 @@ for n_obj in args.n_objects:
                     "reachable_share_initial": reach0[1], "reachable_share_final": float((st.terms[i_reach] < 1e-6).float().mean())})
         print(f"  reach: mean E_reach {reach0[0]:.3e} -> {rec['E_reach_mean_final']:.3e}, rows under 1e-6: {reach0[1]:.2f} -> "
               f"{rec['reachable_share_final']:.2f}", flush=True)
+    if ARM_REPORT:
+        arm1 = arm_clearance(st, scene)
+        rec.update({"w_arm": args.w_arm, "arm_spheres": st.arm.Ns, "E_arm_mean_initial": float(arm0.mean()), "E_arm_mean_final": float(arm1.mean()),
+                    "arm_clear_share_initial": float((arm0 <= 0).float().mean()), "arm_clear_share_final": float((arm1 <= 0).float().mean()),
+                    "terms_mean_final": {k: float(st.terms[i].mean()) for i, k in enumerate(st.term_names)}})
+        print(f"  arm: mean E_arm {rec['E_arm_mean_initial']:.4f} -> {rec['E_arm_mean_final']:.4f} m, rows with E_arm = 0: "
+              f"{rec['arm_clear_share_initial']:.2f} -> {rec['arm_clear_share_final']:.2f}", flush=True)
     records.append(rec)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
