@@ -202,6 +202,25 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, obj
                                                         hand_model.global_rotation, hand_model.current_status, hand_model._fk_ws, arm, base_T,
                                                         be, hand_model.grasp_axis, dist, stations, iters, damping, rot_scale, return_q=True)
 
+    if "E_track" in energy_names:
+        # approach tracking as ONE launch after the reach launch (ops.track_terms; HandModel.set_reach + set_track), from the reach
+        # term's retreated station; without "E_reach" the reach launch runs here, detached, for the start configuration alone
+        if getattr(hand_model, "reach", None) is None or getattr(hand_model, "track", None) is None:
+            raise ValueError('calculate_energy: "E_track" needs HandModel.set_reach(arm, arm_base, ...) and HandModel.set_track(...)')
+        arm, base, dist, stations, iters, damping, rot_scale = hand_model.reach
+        B = hand_model.hand_pose.shape[0]
+        be = object_model.batch_size_each
+        if base.shape[0] not in (1, B // be):
+            raise ValueError(f"calculate_energy: set_reach got {base.shape[0]} arm bases, the batch has {B // be} objects")
+        base_T = base if base.shape[0] == B // be else base.expand(B // be, 3, 4).contiguous()
+        state = (hand_model._hand, hand_model._fk_idx, hand_model.global_rotation, hand_model.current_status, hand_model._fk_ws)
+        if "E_reach" not in energy_names:
+            with torch.no_grad():
+                _, reach_q, _ = ops.reach_terms(hand_model.hand_pose, *state, arm, base_T, be, hand_model.grasp_axis, dist, stations, iters,
+                                                damping, rot_scale, return_q=True)
+        losses["E_track"] = ops.track_terms(hand_model.hand_pose, *state, arm, base_T, be, hand_model.grasp_axis, reach_q[:, stations],
+                                            dist, hand_model.track[0], hand_model.track[1], damping, rot_scale)
+
     if "E_arm" in energy_names:
         # arm clearance as ONE launch after the reach launch (ops.arm_terms; HandModel.set_reach + set_arm_scene) on the arm
         # configurations of E_reach above; without that name the reach launch runs here, detached, for them alone -- the term's

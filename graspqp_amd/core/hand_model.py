@@ -286,6 +286,19 @@ class HandModel:
         handle = arm if isinstance(arm, ops.ArmHandle) else ops.ArmHandle(arm, self.device)
         self.reach = (handle, base, float(distance), int(stations), int(iterations), float(damping), float(rot_scale))
 
+    def set_track(self, waypoints=8, updates=3):
+        """The approach tracking of calculate_energy(..., energy_names=[..., "E_track"]): the arm of ``set_reach`` (call it first, with
+        stations >= 1) follows the straight approach line over ``waypoints`` + 1 waypoints (1..64) from the retreated station to the
+        grasp pose with ``updates`` (1..16) updates per waypoint (``ops.track_terms``); the distance, the damping and the rotation
+        scale are the reach term's.  Checked here, without a launch."""
+        if getattr(self, "reach", None) is None:
+            raise ValueError("HandModel.set_track: call set_reach(arm, arm_base, ...) first")
+        arm, _, dist, stations, _, damping, rot_scale = self.reach
+        if stations < 1:
+            raise ValueError("HandModel.set_track: set_reach needs stations >= 1: the path starts at the retreated station")
+        ops.track_check(arm, dist, waypoints, updates, damping, rot_scale, self.grasp_axis, stations, False, "HandModel.set_track")
+        self.track = (int(waypoints), int(updates))
+
     def set_arm_scene(self, scene=None, margin=None, damping=1e-6):
         """The arm clearance of calculate_energy(..., energy_names=[..., "E_arm"]): the collision spheres of the arm of
         ``set_reach`` (call it first, with an arm that has spheres) on ``scene``, an ``ops.SceneSDF`` or ``ops.SceneSDFSet`` -- None takes

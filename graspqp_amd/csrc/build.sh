@@ -34,7 +34,8 @@ deps() {  # headers each translation unit includes
     clutter) echo "common.h grid_stack.h scene_dev.h approach_dev.h sample_row_dev.h scene_row_dev.h approach_row_dev.h clutter_dev.h" ;;
     pregrasp) echo "common.h wave.h kin_dev.h grid_stack.h scene_dev.h approach_dev.h sample_row_dev.h approach_row_dev.h pregrasp_dev.h" ;;
     squeeze) echo "common.h wave.h kin_dev.h squeeze_dev.h" ;;
-    reach) echo "common.h wave.h setup.h cluster_bound.h reach_dev.h" ;;
+    reach) echo "common.h wave.h setup.h cluster_bound.h reach_dev.h reach_lanes.h" ;;
+    track) echo "common.h wave.h reach_dev.h reach_lanes.h track_dev.h" ;;
     armscene) echo "common.h wave.h grid_stack.h scene_dev.h reach_dev.h armscene_dev.h" ;;
     tsdf) echo "common.h grid_stack.h scene_dev.h clutter_dev.h tsdf_dev.h" ;;
     surfel) echo "common.h grid_stack.h scene_dev.h clutter_dev.h surfel_dev.h" ;;
@@ -43,7 +44,7 @@ deps() {  # headers each translation unit includes
     *) echo "common.h" ;;
   esac
 }
-for f in api qp qp_lr qp_dense qp_nz16 qp_nz32 qp_nz48 qp_nz64 sdf bvh kin fc fcstep stage loop export init metric terms exact tabletop cloud scene approach clutter pregrasp squeeze reach armscene tsdf surfel edt select; do
+for f in api qp qp_lr qp_dense qp_nz16 qp_nz32 qp_nz48 qp_nz64 sdf bvh kin fc fcstep stage loop export init metric terms exact tabletop cloud scene approach clutter pregrasp squeeze reach track armscene tsdf surfel edt select; do
   stale=0
   [ -f "$OUT/$f.o" ] || stale=1
   for d in $f.hip $(deps $f); do [ "$HERE/$d" -nt "$OUT/$f.o" ] && stale=1; done

@@ -16,9 +16,8 @@
 // station (lowest seed on a tie), forms the mean and the gradient in the gRt layout; the winners' joints are written side by side.
 // No atomics, no block waits for another, every sum in a fixed order, no array indexed at run time: bitwise reproducible,
 // graph-capturable, no scratch.  Joint state is never carried from one launch to the next: the term is a pure function of the pose.
-#include "reach_dev.h"
+#include "reach_lanes.h"
 #include "setup.h"
-#include "wave.h"
 
 #include <memory>
 
@@ -33,48 +32,6 @@ struct GqReachArgs {
   float *e, *q, *gRt;
   int32_t* seed;
 };
-
-// value of the lane `d` places below in the row of 16; the first d lanes of a row keep their own (no lane of a group that uses the
-// shifted value -- j >= d -- sits there)
-template <int CTRL>
-__device__ __forceinline__ float gq_reach_shr(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-template <int CTRL>
-__device__ __forceinline__ void gq_reach_scan_step(GqRT& X, bool take) {
-  GqRT Y;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Y.m[i] = gq_reach_shr<CTRL>(X.m[i]);
-  const GqRT Z = gq_reach_mul(Y, X);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) X.m[i] = take ? Z.m[i] : X.m[i];
-}
-__device__ __forceinline__ float gq_reach_group_sum(float t) {
-  t += gq_dpp_all_f<0xb1>(t);   // quad_perm [1,0,3,2]
-  t += gq_dpp_all_f<0x4e>(t);   // quad_perm [2,3,0,1]
-  t += gq_dpp_all_f<0x141>(t);  // row_half_mirror: lane j <-> 7 - j of the group
-  return t;
-}
-__device__ __forceinline__ float gq_reach_group_max(float t) {
-  t = fmaxf(t, gq_dpp_all_f<0xb1>(t));
-  t = fmaxf(t, gq_dpp_all_f<0x4e>(t));
-  t = fmaxf(t, gq_dpp_all_f<0x141>(t));
-  return t;
-}
-
-// base -> hand root for the group's joints q (lane j holds q_j); W is base -> joint j on lane j
-__device__ __forceinline__ GqRT gq_reach_fk(const GqRT& base, const GqRT& pre, const GqRT& tool, int type, gq3 ax, float q, int j,
-                                            GqRT& W) {
-  GqRT X = gq_reach_joint(pre, type, ax, q);
-  gq_reach_scan_step<0x111>(X, j >= 1);  // row_shr:1
-  gq_reach_scan_step<0x112>(X, j >= 2);  // row_shr:2
-  gq_reach_scan_step<0x114>(X, j >= 4);  // row_shr:4
-  W = gq_reach_mul(base, X);
-  GqRT W7;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) W7.m[i] = __shfl(W.m[i], GQ_REACH_MAX_JOINTS - 1, GQ_REACH_MAX_JOINTS);
-  return gq_reach_mul(W7, tool);
-}
 
 __global__ __launch_bounds__(GQ_REACH_MAX_PROBLEMS* GQ_REACH_MAX_JOINTS) void gq_reach_kernel(const GqReachArgs g) {
   __shared__ float s_E[GQ_REACH_MAX_PROBLEMS], s_e[GQ_REACH_MAX_PROBLEMS * 6], s_q[GQ_REACH_MAX_PROBLEMS * GQ_REACH_MAX_JOINTS];

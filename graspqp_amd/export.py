@@ -50,11 +50,18 @@ def grasp_snapshot(hand_model, energy, object_model):
             "values": energy.detach(), "contact_idx": hand_model.contact_point_indices.detach()}
 
 
-def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None, selection=None):
+def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None, arm_path=None, selection=None):
     """One dict per object in the reference's on-disk layout (CPU tensors).  ``selection`` (an ``ops.GraspSelection``, e.g. of
     ``GraspStepper.select``): each object's dict holds only its selected rows, in pick order, and two more keys,
     ``selected_rows`` (int64, the rows' indices within the object) and ``n_feasible`` (int); an object with nothing selected
-    gets zero-length tensors.  The consumer reads by key, so the extra keys are harmless."""
+    gets zero-length tensors.  The consumer reads by key, so the extra keys are harmless.  ``arm_path`` (B,T+1,N), such as
+    ``GraspStepper.track_q``: the arm's joint path along the approach, waypoint 0 the retreated pose and waypoint T the grasp,
+    written under the key ``arm_path`` for the rows each object's dict holds (in pick order under a ``selection``).  Pass both by
+    keyword: ``selection`` stays the last parameter."""
+    if arm_path is not None:
+        arm_path = torch.as_tensor(arm_path).detach().cpu()
+        if arm_path.dim() != 3 or arm_path.shape[0] != n_objects * batch_size:
+            raise ValueError(f"snapshot_dicts: arm_path must be ({n_objects * batch_size}, T+1, N), got {tuple(arm_path.shape)}")
     if selection is not None:
         sel, n_sel, n_feas = selection.sel.cpu().long(), selection.n_selected.cpu(), selection.n_feasible.cpu()
         if sel.shape[0] != n_objects:
@@ -72,6 +79,8 @@ def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, gras
         data["contact_idx"] = snap["contact_idx"][rows].clone()
         data["grasp_type"] = grasp_type
         data["contact_links"] = hand_model._contact_links
+        if arm_path is not None:
+            data["arm_path"] = arm_path[rows].clone()
         if selection is not None:
             data["selected_rows"] = rows - a * batch_size
             data["n_feasible"] = int(n_feas[a])
@@ -80,10 +89,11 @@ def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, gras
 
 
 def export_poses(hand_model, energy, object_model, object_code_list, batch_size, data_root_path, hand_name, n_contact,
-                 energy_name, suffix="None", grasp_type=None, selection=None):
-    """fit.py:224-300 -> list of the files written.  ``selection``: see ``snapshot_dicts``; None writes every row."""
+                 energy_name, suffix="None", grasp_type=None, arm_path=None, selection=None):
+    """fit.py:224-300 -> list of the files written.  ``selection`` and ``arm_path``: see ``snapshot_dicts``; None writes every row / no arm motion."""
     files = []
-    dicts = snapshot_dicts(hand_model, energy, object_model, len(object_code_list), batch_size, grasp_type, selection)
+    dicts = snapshot_dicts(hand_model, energy, object_model, len(object_code_list), batch_size, grasp_type, arm_path=arm_path,
+                           selection=selection)
     for code, data in zip(object_code_list, dicts):
         path = os.path.join(get_result_path(data_root_path, code, hand_name, n_contact, energy_name, grasp_type),
                             code + f"{suffix}.dexgrasp.pt")

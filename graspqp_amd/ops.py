@@ -2360,6 +2360,141 @@ def reach_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, arm: ArmHandle, ba
 
 
 # ----------------------------------------------------------------------------------------------------------
+# approach tracking: E_track (csrc/track.hip), damped-least-squares tracking of the straight approach line from ONE start
+# configuration, each waypoint warm-started from the one before; ONE launch: eight lanes per row, eight rows per wavefront
+# ----------------------------------------------------------------------------------------------------------
+def track_check(arm, distance=0.10, waypoints=8, updates=3, damping=1e-4, rot_scale=0.1, grasp_axis=(0.0, 0.0, 1.0), stations=0,
+                with_station_q=False, who="track_terms"):
+    """The parameters of the tracking term (no GPU): ``arm`` an ArmSpec or ArmHandle (None: not checked), waypoints in 1..64, updates
+    in 1..16, finite distance, damping and rot_scale > 0, stations in 0..3 (>= 1 and a divisor of ``waypoints`` when
+    ``with_station_q``), a finite non-zero grasp_axis.  Raises ValueError; the library's message (gq_track_check) is kept."""
+    if arm is not None and not isinstance(arm, (ArmSpec, ArmHandle)):
+        raise ValueError(f"{who}: arm must be an ops.ArmSpec or an ops.ArmHandle, got {type(arm).__name__}")
+    for name, v in (("track_waypoints", waypoints), ("track_updates", updates), ("reach_stations", stations)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{who}: {name} = {v!r} must be an integer")
+    spec = arm.spec if isinstance(arm, ArmHandle) else arm
+    a = _axis3(grasp_axis)
+    try:
+        _C.call("gq_track_check", 1 if spec is None else int(spec.n_joints), float(distance), int(waypoints), int(updates), float(damping),
+                float(rot_scale), int(stations), int(bool(with_station_q)), ctypes.cast(_axis_c(a), ctypes.c_void_p))
+    except RuntimeError as err:
+        raise ValueError(f"{who}: {err}") from None
+
+
+def _track_call(arm, hp, Rg, base_T, batch_each, axis, distance, waypoints, updates, damping, rot_scale, q_start, stations, up, w, e,
+                q, worst, step, station_q, accumulate, gRt, st=None):
+    """``q_start`` (B,N) may be a view with a row stride (``reach_q[:, K]``): it is passed by pointer and stride, without a copy."""
+    p, (B, D) = _dev, hp.shape
+    if q_start.dim() != 2 or q_start.shape[0] != B or q_start.shape[1] != arm.N or q_start.stride(1) != 1 or q_start.dtype != torch.float32:
+        raise ValueError(f"track_terms: q_start must be float32 ({B}, {arm.N}) with unit stride along the joints, got "
+                         f"{tuple(q_start.shape)} {q_start.dtype} strides {q_start.stride()}")
+    if not q_start.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    stride = q_start.stride(0) if B > 1 else arm.N
+    _C.call("gq_track_terms", arm.handle, _C.f32(hp), D, p(Rg), ctypes.c_int64(B), p(base_T), ctypes.c_int64(B // int(batch_each)),
+            ctypes.c_int64(int(batch_each)), ctypes.cast(_axis_c(axis), ctypes.c_void_p), float(distance), int(waypoints), int(updates),
+            float(damping), float(rot_scale), ctypes.c_void_p(q_start.data_ptr()), ctypes.c_int64(int(stride)), int(stations), p(up),
+            float(w), p(e), p(q), p(worst), p(step), p(station_q), int(accumulate), p(gRt), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::track_terms", mutates_args=(), device_types="cuda")
+def _track_op(arm: int, hand_pose: Tensor, Rg: Tensor, base_T: Tensor, batch_each: int, grasp_axis: List[float], distance: float,
+              waypoints: int, updates: int, damping: float, rot_scale: float, q_start: Tensor,
+              stations: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (E_track (B), unweighted; track_q (B,T+1,N); track_worst (B); track_step (B); track_station_q (B,K+1,N), empty (B,0,N) for
+    stations = 0) of the root pose (hand_pose[:, :3], Rg) from the start configuration q_start (B,N), which may be a strided view."""
+    a = _handle(arm)
+    hp = _c(hand_pose)
+    B, dev = hp.shape[0], hp.device
+    e, q = torch.empty(B, device=dev), torch.empty(B, waypoints + 1, a.N, device=dev)
+    worst, step = torch.empty(B, device=dev), torch.empty(B, device=dev)
+    sq = torch.empty(B, stations + 1 if stations else 0, a.N, device=dev)
+    _track_call(a, hp, _c(Rg), _c(base_T), batch_each, grasp_axis, distance, waypoints, updates, damping, rot_scale, q_start, stations,
+                None, 0.0, e, q, worst, step, sq if stations else None, 0, None)
+    return e, q, worst, step, sq
+
+
+@_track_op.register_fake
+def _(arm, hand_pose, Rg, base_T, batch_each, grasp_axis, distance, waypoints, updates, damping, rot_scale, q_start, stations):
+    B, N = hand_pose.shape[0], _handle(arm).N
+    return (hand_pose.new_empty(B), hand_pose.new_empty(B, waypoints + 1, N), hand_pose.new_empty(B), hand_pose.new_empty(B),
+            hand_pose.new_empty(B, stations + 1 if stations else 0, N))
+
+
+@_custom_op("graspqp_amd::track_terms_backward", mutates_args=(), device_types="cuda")
+def _track_bwd_op(arm: int, hand_pose: Tensor, Rg: Tensor, base_T: Tensor, batch_each: int, grasp_axis: List[float], distance: float,
+                  waypoints: int, updates: int, damping: float, rot_scale: float, q_start: Tensor, g_track: Tensor) -> Tensor:
+    """Upstream row gradients (B) on E_track -> gRt (B,12) for fk_backward.  One launch (the iteration runs again: the term keeps
+    no state)."""
+    a = _handle(arm)
+    hp = _c(hand_pose)
+    gRt = torch.empty(hp.shape[0], 12, device=hp.device)
+    _track_call(a, hp, _c(Rg), _c(base_T), batch_each, grasp_axis, distance, waypoints, updates, damping, rot_scale, q_start, 0,
+                _c(g_track), 1.0, None, None, None, None, None, 0, gRt)
+    return gRt
+
+
+@_track_bwd_op.register_fake
+def _(arm, hand_pose, Rg, base_T, batch_each, grasp_axis, distance, waypoints, updates, damping, rot_scale, q_start, g_track):
+    return hand_pose.new_empty(hand_pose.shape[0], 12)
+
+
+class _TrackTerms(torch.autograd.Function):
+    """Glue between two registered ops (track_terms + fk_backward), as _ReachTerms: the backward launch writes gRt with the per-row
+    upstream, the FK backward turns it into the root translation and rotation gradient.  The joints and q_start get none."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, idx, Rg, LT, ws, arm, base_T, batch_each, axis, q_start, par, stations):
+        hp = _c(hand_pose.detach())
+        e, q, worst, step, sq = _Eager.track_terms(arm.hid, hp, Rg, base_T, batch_each, axis, *par, q_start, stations)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, base_T, q_start)
+        ctx.hand, ctx.arm, ctx.par = hand, arm, (batch_each, axis) + tuple(par)
+        ctx.mark_non_differentiable(q, worst, step, sq)
+        return e, q, worst, step, sq
+
+    @staticmethod
+    def backward(ctx, g_track, *_):
+        hp, idx, Rg, LT, ws, base_T, q_start = ctx.saved_tensors
+        gRt = _Eager.track_terms_backward(ctx.arm.hid, hp, Rg, base_T, *ctx.par, q_start, _c(g_track))
+        gp = _fk_backward(ctx.hand, hp, idx, Rg, LT, ws, None, None, None, None, gRt, None)
+        return (gp,) + (None,) * 12
+
+
+def track_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, arm: ArmHandle, base_T, batch_each, grasp_axis, q_start, distance=0.10,
+                waypoints=8, updates=3, damping=1e-4, rot_scale=0.1, stations=0, return_path=False):
+    """-> E_track (B) in m^2 = the mean over the waypoints i = 0..T of |e_i|^2 along the straight approach line: waypoint i is the
+    root pose of ``hand_pose`` moved back by ``distance`` (T - i) / T along ``grasp_axis`` (waypoint 0 the retreated pose, waypoint T
+    the grasp pose), the arm starts at ``q_start`` (B,N) -- a strided view such as ``reach_q[:, K]`` is taken without a copy -- and
+    every waypoint runs ``updates`` damped-least-squares updates of the reach term from the configuration of the one before
+    (include/graspqp_hip.h, "approach tracking").  ``base_T``, ``batch_each``, ``damping``, ``rot_scale`` as in ``reach_terms``.
+    Unweighted; differentiable w.r.t. the root translation and rotation of ``hand_pose``: the partial derivative with respect to the
+    targets with every q_i held fixed -- the gradient of the converged path energy where every waypoint is at a fixed point with no
+    joint on a limit, an approximation elsewhere (finite ``updates``, a clamped joint, the two-cycle out of range).
+    ``return_path``: also track_q (B,T+1,N), track_worst (B) = max_i E_i, track_step (B) = the largest joint move between
+    neighbouring waypoints, and track_station_q (B,K+1,N) for ``stations`` = K >= 1 dividing T (None for K = 0): the waypoints that
+    are the reach term's stations, in the layout of reach_q, for ``arm_terms``."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if not isinstance(arm, ArmHandle):
+        raise ValueError("track_terms: arm must be an ops.ArmHandle")
+    axis = [float(a) for a in _axis3(grasp_axis)]
+    track_check(arm, distance, waypoints, updates, damping, rot_scale, axis, stations, int(stations) > 0)
+    B = hand_pose.shape[0]
+    if int(batch_each) < 1 or B % int(batch_each):
+        raise ValueError(f"track_terms: batch = {B} is not divisible by batch_each = {batch_each}")
+    if tuple(base_T.shape) != (B // int(batch_each), 3, 4):
+        raise ValueError(f"track_terms: base_T must be ({B // int(batch_each)}, 3, 4), got {tuple(base_T.shape)}")
+    if tuple(q_start.shape) != (B, arm.N):
+        raise ValueError(f"track_terms: q_start must be ({B}, {arm.N}), got {tuple(q_start.shape)}")
+    e, q, worst, step, sq = _TrackTerms.apply(hand_pose, hand, _c(idx, torch.int64), _c(Rg.detach()), _c(LT.detach()), ws, arm,
+                                              _c(base_T.detach()), int(batch_each), axis, q_start.detach(),
+                                              (float(distance), int(waypoints), int(updates), float(damping), float(rot_scale)),
+                                              int(stations))
+    return (e, q, worst, step, sq if int(stations) else None) if return_path else e
+
+
+# ----------------------------------------------------------------------------------------------------------
 # arm clearance: E_arm (csrc/armscene.hip), the arm's collision spheres on the scene grid at the joints the reach launch has left in
 # reach_q; ONE launch: a block per row, a wavefront per station, lane = sphere; the gradient in the gRt layout the FK backward takes
 # ----------------------------------------------------------------------------------------------------------
@@ -2903,6 +3038,8 @@ _eager("squeeze_terms", _squeeze_op)
 _eager("squeeze_terms_backward", _squeeze_bwd_op)
 _eager("reach_terms", _reach_op)
 _eager("reach_terms_backward", _reach_bwd_op)
+_eager("track_terms", _track_op)
+_eager("track_terms_backward", _track_bwd_op)
 _eager("arm_terms", _arm_op)
 _eager("arm_terms_backward", _arm_bwd_op)
 _eager("scene_compose", _scene_compose_op)

@@ -66,6 +66,17 @@ lane = sphere) ADDS its gradient to ``gRt``: the minimum-norm tracking of the ta
 (include/graspqp_hip.h, "arm clearance": exact along that tracking for a reached target with no joint on a limit, an approximation
 elsewhere).  ``terms`` gets [E_arm] appended after [E_reach]; ``select`` gates it at 0 by default; with weight 0 nothing changes.
 
+Track mode (a weight on "E_track", in reach mode with ``reach_stations`` >= 1): can the arm FOLLOW the straight approach line?  The reach
+term's stations are independent IK problems, so ``reach_q`` is not a path; this term tracks ``track_waypoints`` + 1 waypoints from the
+retreated pose to the grasp pose, starting at ``reach_q[:, K]`` and warm-starting every waypoint from the one before with
+``track_updates`` updates of the reach term's update (its distance, damping, rotation scale and axis).  E_track is the mean of |e_i|^2
+over the waypoints, in m^2.  One more launch right after the reach launch (gq_track_terms: eight lanes per row, eight rows per
+wavefront) ADDS its gradient to ``gRt`` (the partial derivative with respect to the targets with the path held fixed: include/
+graspqp_hip.h, "approach tracking").  ``track_q`` (B,T+1,N), ``track_step`` (B) and ``track_worst`` (B) hold the path, its largest
+joint move between waypoints and its worst waypoint; ``terms`` gets [E_track] appended last; ``select`` does not gate it by default.
+``arm_on_track`` = True makes E_arm read the path's configurations at the stations (``track_station_q``) in place of ``reach_q``: the
+launch order is then reach, track, arm.  With weight 0 and the switch off nothing changes.
+
 Clutter (``scene`` is an ``ops.SceneSDFSet`` with one grid per object): the same two launches read a stack of grids and pick the
 grid from the row, row // batch_each (gq_clutter_terms / gq_clutter_corridor_terms, the same row bodies: bit for bit the single-grid
 launch's numbers on that grid).  ``ops.scene_compose`` refills the stack in place, also between replays of a captured graph.
@@ -91,6 +102,7 @@ PREGRASP_TERMS = ("E_pregrasp",)
 SQUEEZE_TERMS = ("E_squeeze",)
 REACH_TERMS = ("E_reach",)
 ARM_TERMS = ("E_arm",)
+TRACK_TERMS = ("E_track",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
@@ -116,11 +128,11 @@ def select_tolerances(term_names, gates=None):
 
 def merge_weights(weights=None):
     """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term, of the pre-grasp term, of
-    the squeeze term, of the reach term and of the arm clearance term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
+    the squeeze term, of the reach term, of the arm clearance term and of the tracking term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
     never used), and so does a negative weight of one of the terms that are switched by their weight."""
-    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS + ARM_TERMS
+    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS + ARM_TERMS + TRACK_TERMS
     w = dict(DEFAULT_WEIGHTS)
-    w.update({k: 0.0 for k in ARM_TERMS + REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
+    w.update({k: 0.0 for k in TRACK_TERMS + ARM_TERMS + REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
     for k, v in (weights or {}).items():
         if k not in w:
             raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
@@ -152,7 +164,7 @@ class GraspStepper:
                  pregrasp_stations=None, pregrasp_margin=None, squeeze_min_travel: float = 5e-3, squeeze_damping: float = 1e-3,
                  arm=None, arm_base=None, reach_distance: float = 0.10, reach_stations: int = 0, reach_iterations: int = 24,
                  reach_damping: float = 1e-4, reach_rot_scale: float = 0.1, arm_scene=None, arm_margin=None, arm_damping: float = 1e-6,
-                 init_avoid_scene: bool = False):
+                 track_waypoints: int = 8, track_updates: int = 3, arm_on_track: bool = False, init_avoid_scene: bool = False):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -190,7 +202,12 @@ class GraspStepper:
         configurations of the last evaluation.  No default weight is set.  With weight 0 the seven arguments change nothing.
         weights["E_arm"] > 0 selects the arm mode (module docstring): it needs weights["E_reach"] > 0, an ``arm`` with collision spheres
         and ``arm_scene`` (None: ``scene``), an ``ops.SceneSDF`` or an ``ops.SceneSDFSet`` with one grid per object; ``arm_margin`` >= 0
-        (None: ``scene_margin``), ``arm_damping`` finite and > 0 (the term's own lambda_a, not ``reach_damping``)."""
+        (None: ``scene_margin``), ``arm_damping`` finite and > 0 (the term's own lambda_a, not ``reach_damping``).
+        weights["E_track"] > 0 selects the track mode (module docstring): it needs weights["E_reach"] > 0 with ``reach_stations`` >= 1;
+        ``track_waypoints`` in 1..64 waypoints beyond the first, ``track_updates`` in 1..16 updates per waypoint.  ``track_q``,
+        ``track_step`` and ``track_worst`` hold the last evaluation.  No default weight is set.  ``arm_on_track`` = True makes E_arm read
+        the tracked path's configurations at the stations (``track_station_q``) in place of ``reach_q``: it needs both terms on and
+        ``reach_stations`` dividing ``track_waypoints``.  With weight 0 and the switch off the three arguments change nothing."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -264,12 +281,29 @@ class GraspStepper:
             arm_margin = scene_margin if arm_margin is None else arm_margin
             ops.arm_check(arm, ops._arm_scene_grids(arm_scene, "GraspStepper"), self.B, arm_margin, arm_damping, reach_rot_scale,
                           reach_distance, reach_stations, hand.spec.grasp_axis, "GraspStepper")
+        self.track_mode = self.w["E_track"] > 0
+        if self.track_mode:
+            if not self.reach_mode:
+                raise ValueError('GraspStepper: weights["E_track"] > 0 needs weights["E_reach"] > 0: the path starts at the reach term\'s '
+                                 'reach_q[:, reach_stations]')
+            if int(reach_stations) < 1:
+                raise ValueError('GraspStepper: weights["E_track"] > 0 needs reach_stations >= 1: the path starts at the retreated station')
+            ops.track_check(arm, reach_distance, track_waypoints, track_updates, reach_damping, reach_rot_scale, hand.spec.grasp_axis,
+                            reach_stations, False, "GraspStepper")
+        self.arm_on_track = bool(arm_on_track)
+        if self.arm_on_track:
+            if not (self.track_mode and self.arm_mode):
+                raise ValueError('GraspStepper: arm_on_track=True needs weights["E_track"] > 0 and weights["E_arm"] > 0')
+            if int(track_waypoints) % int(reach_stations):
+                raise ValueError(f"GraspStepper: arm_on_track=True needs reach_stations = {reach_stations} to divide track_waypoints = "
+                                 f"{track_waypoints}")
         self.init_avoid_scene = bool(init_avoid_scene)
         if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
             raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
         self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
                            + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ())
-                           + (SQUEEZE_TERMS if self.squeeze_mode else ()) + (REACH_TERMS if self.reach_mode else ()) + (ARM_TERMS if self.arm_mode else ()))
+                           + (SQUEEZE_TERMS if self.squeeze_mode else ()) + (REACH_TERMS if self.reach_mode else ()) + (ARM_TERMS if self.arm_mode else ())
+                           + (TRACK_TERMS if self.track_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -472,6 +506,14 @@ class GraspStepper:
             self._i_arm = self.term_names.index("E_arm")
             self.arm_scene, self.arm_margin, self.arm_damping = arm_scene, float(arm_margin), float(arm_damping)
             self._arm_grids = ops._arm_scene_grids(arm_scene, "GraspStepper")  # the stack view: a single grid is the stack of one
+        self.track_q, self.track_step, self.track_worst, self.track_station_q = None, None, None, None
+        if self.track_mode:
+            self._i_track = self.term_names.index("E_track")
+            self.track_waypoints, self.track_updates = int(track_waypoints), int(track_updates)
+            self.track_q = f(B, self.track_waypoints + 1, self.arm.N)
+            self.track_step, self.track_worst = f(B), f(B)
+            if self.arm_on_track:
+                self.track_station_q = f(B, self.reach_stations + 1, self.arm.N)
         self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
@@ -619,8 +661,19 @@ class GraspStepper:
         """E_arm -> its row of terms_new (``_i_arm``) from the ``reach_q`` the reach launch of this evaluation has just written; the
         gradient of w_arm E_arm is ADDED to ``gRt``.  g_R and g_theta are not touched."""
         ops._arm_call(self.arm, self._arm_grids, self.arm_margin, self.arm_damping, self.reach_rot_scale, pose, self.Rg, self.arm_base,
-                      self.be, self._reach_axis, self.reach_distance, self.reach_stations, self.reach_q, None, self.w["E_arm"],
+                      self.be, self._reach_axis, self.reach_distance, self.reach_stations,
+                      self.track_station_q if self.arm_on_track else self.reach_q, None, self.w["E_arm"],
                       self.terms_new[self._i_arm], 1, self.gRt, st)
+
+    def _eval_track(self, pose, st):
+        """E_track -> its row of terms_new (``_i_track``) from the start configuration ``reach_q[:, K]`` the reach launch of this
+        evaluation has just written (a view: pointer and row stride, no copy); the path -> ``track_q``, ``track_step``,
+        ``track_worst`` (and ``track_station_q`` for ``arm_on_track``); the gradient of w_track E_track is ADDED to ``gRt``.  g_R and
+        g_theta are not touched."""
+        ops._track_call(self.arm, pose, self.Rg, self.arm_base, self.be, self._reach_axis, self.reach_distance, self.track_waypoints,
+                        self.track_updates, self.reach_damping, self.reach_rot_scale, self.reach_q[:, self.reach_stations],
+                        self.reach_stations, None, self.w["E_track"], self.terms_new[self._i_track], self.track_q, self.track_worst,
+                        self.track_step, self.track_station_q, 1, self.gRt, st)
 
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
@@ -674,6 +727,8 @@ class GraspStepper:
             self._eval_squeeze(idx, st)
         if self.reach_mode:
             self._eval_reach(pose, st)
+        if self.track_mode:  # right after the reach launch (it starts at reach_q[:, K]); before the arm launch, which may read its stations
+            self._eval_track(pose, st)
         if self.arm_mode:  # after the reach launch (it reads reach_q), before the FK backward (it adds to gRt)
             self._eval_arm(pose, st)
         self._eval_tail(pose, idx, st, loop)
@@ -690,6 +745,9 @@ class GraspStepper:
                     ctypes.c_int64(self.B), st)
         if self.arm_mode:
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_arm]), float(self.w["E_arm"]),
+                    ctypes.c_int64(self.B), st)
+        if self.track_mode:
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_track]), float(self.w["E_track"]),
                     ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):

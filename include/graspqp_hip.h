@@ -823,6 +823,50 @@ int gq_arm_terms(const gqArm* arm, const gqClutterGrids* grids, int64_t rows_per
                  const float* reach_q /* (B,K+1,N) input */, const float* up /* (B) or NULL */, float w,
                  float* e_arm /* (B) or NULL */, int accumulate, float* gRt /* (B,12) or NULL */, void* stream);
 
+/* ---- approach tracking of the stepper: E_track, one continuous arm path along the retreat line -------------------------------
+ * E_reach solves every station of the retreat from scratch, the best of its seeds: nothing puts two neighbouring stations on the
+ * same IK branch, so reach_q is not a path.  This term follows the straight approach line from ONE start configuration, each
+ * waypoint warm-started from the one before.  The arm, base_T, batch_each, grasp_axis a, D = distance > 0, lambda = damping and
+ * rho = rot_scale are those of gq_reach_terms.  Row b with root translation t and rotation R (Rg), T = n_waypoints waypoints beyond
+ * the first, i = 0..T in the order the robot moves:
+ *   d_i = D (T - i) / T      p*_i = t - d_i R a      R*_i = R      (waypoint 0: the retreated pose, the target of the reach term's
+ *                                                                   station K; waypoint T: the grasp pose)
+ * q_{-1} = q_start[b] (q_start_stride floats from row to row, so reach_q[:, K] is passed as a view: pointer reach_q + K N, stride
+ * (K+1) N; it is used as given, not clamped).  For i = 0..T: q <- q_{i-1}, then U = n_updates times exactly the update of
+ * gq_reach_terms, by the same device bodies:
+ *   e = [p*_i - p(q) ; rho log(R* R(q)')]    J = [J_v ; rho J_w]    dq = J' (J J' + lambda I)^-1 e
+ *   if max|dq| > 0.5: dq <- dq 0.5 / max|dq|    q <- clamp(q + dq, lower, upper)
+ * and one more FK for e_i and E_i = |e_i|^2; q_i = q.  Outputs, all fp32, any may be NULL:
+ *   e_track (B)              1/(T+1) sum_i E_i in m^2, i ascending, then x 1/(T+1); UNWEIGHTED, always overwritten
+ *   track_q (B,T+1,N)        the q_i
+ *   track_worst (B)          max_i E_i
+ *   track_step (B)           max over i = 0..T and j < N of |q_i,j - q_{i-1},j| (rad or m), the first move from q_start included
+ *   track_station_q (B,K+1,N) given only with K = n_stations >= 1 that divides T: station k holds q_i at i = T (K - k) / K, in the
+ *                            layout and station order of reach_q and bitwise equal to those track_q entries -- what gq_arm_terms
+ *                            takes in place of reach_q to look at the configurations the arm passes through
+ * Gradient: the partial derivative with respect to the targets with every q_i held fixed, in the form of gq_reach_terms: with
+ * c = w (up[row] if given, else 1) / (T+1), waypoints ascending,
+ *   gRt (B,12) = [gsum(3), K9(9)]: gsum = -R' sum_i 2 c e_p,i;  K9 = sum_i (R' 2 c e_p,i) (x) (-d_i a) + hat(R' sum_i 2 c rho e_w,i) / 2
+ * accumulate = 1 adds to gRt, 0 overwrites it; g_R and g_theta of gq_fk_backward are not touched.  What this is: the gradient of the
+ * converged path energy where every waypoint has reached a fixed point with no joint on a limit (J'e_i = 0: E_i is stationary in
+ * q_i, and the warm start drops out).  It is an approximation elsewhere: at finite U, with a clamped joint, and in the two-cycle
+ * past the outer boundary of a revolute arm.
+ * Limits: T in 1..64, U in 1..16, D, lambda and rho finite and > 0, K in 0..3 (K >= 1 and K | T when track_station_q is given),
+ * batch, base_T, n_obj and batch_each as in gq_reach_terms, q_start_stride >= N.  Eight lanes per row, eight rows per wavefront,
+ * one wavefront per block; no LDS, no atomics, fixed-order sums: bitwise reproducible run to run, a row's bits do not depend on the
+ * batch it sits in, and the term is a pure function of (pose, q_start).  The row total takes gq_scene_total(total, e_track, w, B).
+ * gq_track_check is the parameter check on its own (host only, no GPU; with_station_q != 0 checks K against T as the launch with
+ * a track_station_q does); its message contains "track" and names the argument.                                               */
+int gq_track_check(int n_joints, float distance, int n_waypoints, int n_updates, float damping, float rot_scale, int n_stations,
+                   int with_station_q, const float* grasp_axis /* (3) host */);
+int gq_track_terms(const gqArm* arm, const float* hand_pose /* (B,pose_dim) */, int pose_dim, const float* Rg /* (B,9) */,
+                   int64_t batch, const float* base_T /* (n_obj,12) */, int64_t n_obj, int64_t batch_each,
+                   const float* grasp_axis /* (3) host */, float distance, int n_waypoints, int n_updates, float damping,
+                   float rot_scale, const float* q_start /* row b at q_start + b q_start_stride, (N) */, int64_t q_start_stride,
+                   int n_stations, const float* up /* (B) or NULL */, float w, float* e_track /* (B) or NULL */,
+                   float* track_q /* (B,T+1,N) or NULL */, float* track_worst /* (B) or NULL */, float* track_step /* (B) or NULL */,
+                   float* track_station_q /* (B,K+1,N) or NULL */, int accumulate, float* gRt /* (B,12) or NULL */, void* stream);
+
 /* ---- scenes from depth images: TSDF fusion on the device into scene grids ---------------------------------------------
  * What a robot has is depth images, not a signed-distance volume.  gq_tsdf_integrate fuses a batch of depth frames into a
  * gqClutterGrids stack IN PLACE, one launch per batch (n_grids = 1 is the single world grid).  State: `values` of the stack IS

@@ -13,6 +13,8 @@ Evidence run, not a test: writes one JSON record (default gpurun_out/fit_end_to_
 usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_iter 7000] [--out file.json]
        [--w_squeeze 0] [--squeeze_min_travel 5e-3] [--squeeze_damping 1e-3]   (contact closing feasibility, E_squeeze)
        [--w_reach 0] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations 0]   (arm reachability, E_reach)
+       [--w_track 0] [--track_waypoints 8] [--track_updates 3] [--arm_on_track]   (approach tracking, E_track: needs --w_reach > 0 and
+                                                                                   --reach_stations >= 1; the path is exported as arm_path)
        [--w_arm 0] [--arm_margin 0] [--arm_sphere_radius 0.05] [--arm_sphere_spacing 0.08]   (arm clearance, E_arm: needs --w_reach > 0)
        [--w_wall 0] [--w_prior 0]   (scripts/fit.py:77-78: tabletop synthesis; the class surface and the oracle then carry
        E_wall / E_prior on the stepper's surface samples, st.samples)
@@ -64,6 +66,10 @@ ap.add_argument("--arm_base_link", default=None)
 ap.add_argument("--arm_base", type=float, nargs=4, default=(-0.45, 0.0, -0.3, 0.0), metavar=("X", "Y", "Z", "YAW"))
 ap.add_argument("--reach_stations", type=int, default=0)
 ap.add_argument("--reach_distance", type=float, default=0.10)
+ap.add_argument("--w_track", type=float, default=0.0)  # approach tracking: one continuous arm path along the retreat line
+ap.add_argument("--track_waypoints", type=int, default=8)
+ap.add_argument("--track_updates", type=int, default=3)
+ap.add_argument("--arm_on_track", action="store_true")  # E_arm at the path's configurations (needs --w_arm and --w_track)
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "fit_end_to_end.json"))
 args = ap.parse_args()
 
@@ -104,6 +110,16 @@ if ARM:
         ap.error("--w_arm needs --w_reach > 0")
     W["E_arm"] = args.w_arm
     reach_kw["arm"] = reach_kw["arm"].with_link_spheres(args.arm_sphere_radius, args.arm_sphere_spacing)
+TRACK = args.w_track > 0  # approach tracking (E_track: the straight approach line followed from reach_q[:, K], one launch)
+if TRACK:
+    if not REACH or args.reach_stations < 1:
+        ap.error("--w_track needs --w_reach > 0 and --reach_stations >= 1")
+    W["E_track"] = args.w_track
+    reach_kw.update(track_waypoints=args.track_waypoints, track_updates=args.track_updates)
+if args.arm_on_track:
+    if not (TRACK and ARM):
+        ap.error("--arm_on_track needs --w_track > 0 and --w_arm > 0")
+    reach_kw["arm_on_track"] = True
 spec = get_hand_spec(args.hand)
 n_obj, be, n = args.n_objects, args.batch_size, args.n_contact
 B = n_obj * be
@@ -129,6 +145,8 @@ if REACH:
 if ARM:
     weights["E_arm"] = args.w_arm
     reach_kw.update(arm_scene=scene, arm_margin=args.arm_margin)
+if TRACK:
+    weights["E_track"] = args.w_track
 st = GraspStepper(hand, ops.MeshSet(fvs), torch.tensor(np.stack(sps)), be, n, seed=1, weights=weights or None, scene=scene,
                   scene_margin=args.scene_margin, approach_distance=args.approach_distance, approach_stations=args.approach_stations,
                   squeeze_min_travel=args.squeeze_min_travel, squeeze_damping=args.squeeze_damping, **reach_kw)
@@ -169,12 +187,16 @@ if REACH:
     hm.set_reach(reach_kw["arm"], reach_kw["arm_base"], args.reach_distance, args.reach_stations)
 if ARM:
     hm.set_arm_scene(scene, args.arm_margin)
+if TRACK:
+    hm.set_track(args.track_waypoints, args.track_updates)
 metric = GraspSpanMetricFactory.create(GraspSpanMetricFactory.MetricType.GRASPQP, {"friction": 0.2, "max_limit": 20.0, "n_cone_vecs": 4})
 losses = calculate_energy(hm, om, energy_fnc=metric, method="gendexgrasp", svd_gain=0.1,
                           energy_names=(["E_prior", "E_wall"] if TABLETOP else []) + (["E_scene"] if SCENE else []) +
                           (["E_approach"] if APPROACH else []) + (["E_squeeze"] if SQUEEZE else []) +
-                          (["E_reach"] if REACH else []) + (["E_arm"] if ARM else []))
-total_cls = sum(W[k] * losses[k] for k in W)
+                          (["E_reach"] if REACH else []) + (["E_arm"] if ARM and not args.arm_on_track else []) +
+                          (["E_track"] if TRACK else []))
+# (with --arm_on_track E_arm reads the tracked path: the class surface has no such switch, the term is taken from the stepper)
+total_cls = sum(W[k] * (losses[k] if k in losses else st.terms[list(st.term_names).index(k)]) for k in W)
 rel_cls = ((total_cls.detach() - st.energy).abs() / st.energy.abs().clamp_min(1e-6))
 
 # ---- (2) the CPU oracle (fp64) on a few rows ------------------------------------------------------------------------------
@@ -204,7 +226,8 @@ if TABLETOP:
 # ---- (3) export + reload the way the consumer does ----------------------------------------------------------------------
 with tempfile.TemporaryDirectory() as tmp:
     hm.set_parameters(st.hand_pose.clone(), st.contact_idx.clone())
-    files = export_poses(hm, st.energy.clone(), om, codes, be, tmp, args.hand, n, "graspqp", suffix="")  # fit.py:521
+    files = export_poses(hm, st.energy.clone(), om, codes, be, tmp, args.hand, n, "graspqp", suffix="",  # fit.py:521
+                         arm_path=st.track_q if TRACK else None)
     data = torch.load(files[0], weights_only=True)
     jn = list(spec.joint_names)
     params = torch.cat([data["parameters"]["root_pose"], torch.stack([data["parameters"][k] for k in jn], -1)], -1)

@@ -6,6 +6,7 @@ usage: python tools/soak.py [n_objects ...] [--w_wall W] [--w_prior W] [--table_
        [--scene box] [--w_approach W] [--approach_distance D] [--approach_stations K]
        [--w_pregrasp W] [--pregrasp_opening A] [--pregrasp_stations K] [--w_squeeze W]
        [--w_reach W] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations K] [--w_arm W] [--arm_report]
+       [--w_track W] [--track_waypoints T] [--track_updates U] [--track_report] [--arm_on_track]
        [--out file.json]
        (256 rows each; default 1 8).  --w_wall / --w_prior (scripts/fit.py:77-78, default 0 = the five-term energy) run the
        schedule in the stepper's tabletop mode and report the mean E_wall at the start and at the end and the number of
@@ -65,6 +66,13 @@ ap.add_argument("--arm_report", action="store_true")
 ap.add_argument("--arm_margin", type=float, default=0.0)
 ap.add_argument("--arm_sphere_radius", type=float, default=0.05)
 ap.add_argument("--arm_sphere_spacing", type=float, default=0.08)
+# approach tracking (E_track, needs --w_reach > 0 and --reach_stations >= 1); --track_report measures the path with the weight off;
+# --arm_on_track makes E_arm read the path's configurations (needs --w_arm > 0 and --w_track > 0)
+ap.add_argument("--w_track", type=float, default=0.0)
+ap.add_argument("--track_waypoints", type=int, default=8)
+ap.add_argument("--track_updates", type=int, default=3)
+ap.add_argument("--track_report", action="store_true")
+ap.add_argument("--arm_on_track", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 N_ITER, RESET = int(os.environ.get("SOAK_ITERS", 7000)), 600
@@ -98,7 +106,29 @@ if ARM_REPORT:
     reach_kw["arm"] = reach_kw["arm"].with_link_spheres(args.arm_sphere_radius, args.arm_sphere_spacing)
 if ARM:
     weights["E_arm"] = args.w_arm
+TRACK = args.w_track > 0
+TRACK_REPORT = REACH and args.reach_stations >= 1 and (TRACK or args.track_report)
+if TRACK and not (REACH and args.reach_stations >= 1):
+    ap.error("--w_track needs --w_reach > 0 and --reach_stations >= 1")
+if TRACK:
+    weights["E_track"] = args.w_track
+    reach_kw.update(track_waypoints=args.track_waypoints, track_updates=args.track_updates)
+if args.arm_on_track:
+    if not (TRACK and ARM):
+        ap.error("--arm_on_track needs --w_track > 0 and --w_arm > 0")
+    reach_kw["arm_on_track"] = True
 records = []
+
+
+def track_path(st):
+    """(track_worst (B), track_step (B)) of the accepted poses, whether the term is on or not: one evaluation at the accepted state
+    (it leaves the start configurations in ``reach_q``), then the term's launch from them."""
+    st.evaluate(st.hand_pose.clone(), st.contact_idx.clone())
+    worst, step = torch.empty(st.B, device=st.dev), torch.empty(st.B, device=st.dev)
+    ops._track_call(st.arm, st.pose_new, st.Rg, st.arm_base, st.be, st._reach_axis, st.reach_distance, args.track_waypoints,
+                    args.track_updates, st.reach_damping, st.reach_rot_scale, st.reach_q[:, st.reach_stations], 0, None, 0.0, None, None,
+                    worst, step, None, 0, None)
+    return worst, step
 
 
 def arm_clearance(st, scene):
@@ -222,6 +252,14 @@ for n_obj in args.n_objects:
                     "terms_mean_final": {k: float(st.terms[i].mean()) for i, k in enumerate(st.term_names)}})
         print(f"  arm: mean E_arm {rec['E_arm_mean_initial']:.4f} -> {rec['E_arm_mean_final']:.4f} m, rows with E_arm = 0: "
               f"{rec['arm_clear_share_initial']:.2f} -> {rec['arm_clear_share_final']:.2f}", flush=True)
+    if TRACK_REPORT:
+        worst, step = track_path(st)
+        rec.update({"w_track": args.w_track, "track_waypoints": args.track_waypoints, "track_updates": args.track_updates,
+                    "arm_on_track": bool(args.arm_on_track), "track_followed_share_final": float((worst < 1e-6).float().mean()),
+                    "track_smooth_share_final": float((step < 0.3).float().mean()),
+                    "terms_mean_final": {k: float(st.terms[i].mean()) for i, k in enumerate(st.term_names)}})
+        print(f"  track: rows with track_worst < 1e-6: {rec['track_followed_share_final']:.2f}, with track_step < 0.3: "
+              f"{rec['track_smooth_share_final']:.2f}", flush=True)
     records.append(rec)
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
