@@ -246,6 +246,28 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, obj
         losses["E_arm"] = ops.arm_terms(hand_model.hand_pose, *state, arm, base_T, be, scene, hand_model.grasp_axis, reach_q, dist,
                                         stations, margin, lam_a, rot_scale)
 
+    if "E_lift" in energy_names:  # the scene hinge of hand AND held object on the way out (HandModel.set_lift): both carried by
+        scene, lift = getattr(hand_model, "scene", None), getattr(hand_model, "lift", None)  # (k / K) (H u - D R a), k = 1..K
+        if scene is None or lift is None:
+            raise ValueError('calculate_energy: "E_lift" needs HandModel.set_scene(...) and HandModel.set_lift(...)')
+        H, D, K, u, margin, object_margin, pts = lift
+        margin = hand_model.scene_margin if margin is None else margin
+        x = hand_model.get_surface_points()
+        B = x.shape[0]
+        if pts is None:  # the object model's surface points, one row each already
+            obj = object_model.surface_points_tensor
+        else:
+            if B % pts.shape[0]:
+                raise ValueError(f"calculate_energy: set_lift got points of {pts.shape[0]} objects, the batch has {B} rows")
+            obj = pts.repeat_interleave(B // pts.shape[0], dim=0)
+        back = (hand_model.global_rotation @ hand_model.grasp_axis.view(1, -1, 1)).view(-1, 3)  # R a
+        e = 0
+        for k in range(1, K + 1):
+            c = ((k / K) * (H * u.unsqueeze(0) - D * back)).unsqueeze(1)  # (B,1,3)
+            e = e + torch.relu(margin - ops.scene_distance(x + c, scene)).sum(-1)
+            e = e + torch.relu(object_margin - ops.scene_distance(obj + c, scene)).sum(-1)
+        losses["E_lift"] = e * (1.0 / K)
+
     if "E_manipulativity" in energy_names:
         # energy.py:80-87: mean squared contact velocity the joints cannot produce when the contacts move along
         # normal * max(|distance|, 5 mm); differentiable (ops.joint_velocity_residuals: analytic kinematic Hessian)

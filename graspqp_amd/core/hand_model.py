@@ -316,6 +316,26 @@ class HandModel:
                       "HandModel.set_arm_scene")
         self.arm_scene = (scene, margin, float(damping))
 
+    def set_lift(self, height, retreat, stations, direction=(0.0, 0.0, 1.0), margin=None, object_margin=0.0, object_points=None):
+        """The way out of calculate_energy(..., energy_names=[..., "E_lift"]): the mean over the stations k = 1..stations <= 32 of the
+        scene hinge of the hand's surface samples (``margin``; None follows the scene's margin) and of the held object's points
+        (``object_margin``, finite, may be negative), both carried by (k / stations) (height u - retreat R a): u = ``direction`` in the
+        object's frame (normalised here), a the spec's grasp_axis, ``height`` and ``retreat`` >= 0 in metres and not both zero.
+        ``object_points`` (n_obj,M,3) in the object's frame; None takes the object model's surface points.  Needs ``set_scene``
+        first, with a grid that does not contain the target."""
+        if getattr(self, "scene", None) is None:
+            raise ValueError("HandModel.set_lift: call set_scene(ops.SceneSDF(...)) first")
+        margin = None if margin is None else float(margin)
+        if object_points is not None:
+            object_points = torch.as_tensor(object_points, dtype=torch.float32).detach().to(self.device).contiguous()
+            if object_points.dim() != 3 or object_points.shape[2] != 3:
+                raise ValueError(f"HandModel.set_lift: object_points must be (n_obj, M, 3), got {tuple(object_points.shape)}")
+        u = ops.lift_direction(direction)
+        ops.lift_check(None, 1, 1, 1, 1, 1, 0 if object_points is None else object_points.shape[1], height, retreat, stations,
+                       self.grasp_axis, u, 0.0 if margin is None else margin, object_margin, "HandModel.set_lift")
+        self.lift = (float(height), float(retreat), int(stations), torch.tensor(u, dtype=torch.float32, device=self.device), margin,
+                     float(object_margin), object_points)
+
     def get_surface_points(self, hand_pose=None):
         """(B, n_surface_points, 3) hand surface samples in the world frame, differentiable w.r.t. hand_pose; ``hand_pose`` =
         None takes the model's own (another pose, e.g. the opened one of E_pregrasp, is a second FK at that pose)."""

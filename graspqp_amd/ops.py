@@ -2631,6 +2631,160 @@ def arm_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, arm: ArmHandle, base
                            (float(distance), int(stations), float(margin), float(damping), float(rot_scale)))
 
 
+# ----------------------------------------------------------------------------------------------------------
+# lift clearance: E_lift, the hand and the held object on the way out (csrc/lift.hip).  One launch; a single grid crosses as
+# the stack of one
+# ----------------------------------------------------------------------------------------------------------
+def lift_direction(direction) -> List[float]:
+    """``direction`` normalised once in double: the unit vector the launches use as given.  Raises ValueError for a vector that
+    is not three finite numbers or has no length."""
+    u = np.asarray(direction.detach().cpu().tolist() if torch.is_tensor(direction) else direction, dtype=np.float64).reshape(-1)
+    if u.shape != (3,) or not np.isfinite(u).all() or not np.linalg.norm(u) > 0.0:
+        raise ValueError(f"lift: direction = {direction!r} must be three finite numbers, not all zero")
+    return [float(x) for x in u / np.linalg.norm(u)]
+
+
+def lift_check(scene=None, batch=1, n_links=1, n_samples=1, n_obj=None, batch_each=None, n_object_points=0, height=0.05, retreat=0.0,
+               stations=4, grasp_axis=(0.0, 0.0, 1.0), direction=(0.0, 0.0, 1.0), margin=0.0, object_margin=0.0, who="lift_terms"):
+    """gq_lift_check (host only, no GPU) of the scene (an ``ops.SceneSDF``, an ``ops.SceneSDFSet``, or None: the parameters alone,
+    before a scene exists), a launch's shapes and the carry: ``batch`` = n_grids * rows_per_grid = ``n_obj`` * ``batch_each``,
+    ``n_object_points`` >= 0, finite ``height`` >= 0 and ``retreat`` >= 0 that are not both zero, ``stations`` in 1..32, a finite
+    non-zero ``grasp_axis`` and ``direction`` (used as given), a finite ``margin`` >= 0 and a finite ``object_margin``.  Raises
+    ValueError; the library's message contains "lift" and names the argument."""
+    if scene is not None and not isinstance(scene, (SceneSDF, SceneSDFSet)):
+        raise ValueError(f"{who}: lift: scene must be an ops.SceneSDF or an ops.SceneSDFSet, got {type(scene).__name__}")
+    if int(stations) != stations:
+        raise ValueError(f"{who}: lift: n_stations = {stations!r} must be an integer in 1..32")
+    grids = None if scene is None else _pregrasp_grids(scene.values, scene.origin, scene.voxel)
+    G = 1 if grids is None else max(int(grids.n_grids), 1)
+    if int(batch) % G:
+        raise ValueError(f"{who}: lift: batch = {batch} is not divisible by n_grids = {G}")
+    if batch_each is None:
+        batch_each = int(batch) if n_obj is None else int(batch) // max(int(n_obj), 1)
+    if n_obj is None:
+        n_obj = int(batch) // max(int(batch_each), 1)
+    ax, u = _axis_c(_axis3(grasp_axis)), _axis_c(_axis3(direction))
+    try:
+        _C.call("gq_lift_check", None if grids is None else ctypes.byref(grids), ctypes.c_int64(int(batch)),
+                ctypes.c_int64(int(batch) // G), int(n_links), ctypes.c_int64(int(n_samples)), ctypes.c_int64(int(n_obj)),
+                ctypes.c_int64(int(batch_each)), ctypes.c_int64(int(n_object_points)), float(height), float(retreat), int(stations),
+                ctypes.cast(ax, ctypes.c_void_p), ctypes.cast(u, ctypes.c_void_p), float(margin), float(object_margin))
+    except RuntimeError as e:
+        raise ValueError(f"{who}: {e}") from None
+
+
+def _lift_call(grids, margin, object_margin, height, retreat, stations, hp, points, link, n_links, Rg, LT, object_points, n_obj,
+               batch_each, n_object_points, axis, direction, up_lift, w_lift, e_lift, e_object, accumulate, wrench, gRt, st=None):
+    p, (B, D) = _dev, hp.shape
+    _C.call("gq_lift_terms", ctypes.byref(grids), ctypes.c_int64(B // max(grids.n_grids, 1)), float(margin), float(object_margin),
+            float(height), float(retreat), int(stations), _C.f32(points), p(link, torch.int32), ctypes.c_int64(points.shape[0]),
+            int(n_links), _C.f32(hp), D, p(Rg), p(LT), ctypes.c_int64(B), p(object_points) if n_object_points else None,
+            ctypes.c_int64(int(n_obj)), ctypes.c_int64(int(batch_each)), ctypes.c_int64(int(n_object_points)),
+            ctypes.cast(_axis_c(axis), ctypes.c_void_p), ctypes.cast(_axis_c(direction), ctypes.c_void_p), p(up_lift), float(w_lift),
+            p(e_lift), p(e_object), int(accumulate), p(wrench), p(gRt), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::lift_terms", mutates_args=(), device_types="cuda")
+def _lift_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+             origin: List[float], voxel: float, grasp_axis: List[float], direction: List[float], height: float, retreat: float,
+             stations: int, object_points: Tensor, batch_each: int, margin: float, object_margin: float) -> Tuple[Tensor, Tensor]:
+    """-> (E_lift (B), the object's share of it (B)), unweighted: the mean over the stations k = 1..stations of the hinge sums of
+    the hand's surface samples and of ``object_points`` (n_obj,M,3) carried by (k / stations) (height direction - retreat R
+    grasp_axis).  ``values`` is one grid (nx,ny,nz) or a stack (G,nx,ny,nz).  The kinematic state (Rg, link_T) is the one of
+    ``hand_pose``."""
+    hp, v, op = _c(hand_pose), _c(values), _c(object_points)
+    B = hp.shape[0]
+    e, eo = torch.empty(B, device=hp.device), torch.empty(B, device=hp.device)
+    _lift_call(_pregrasp_grids(v, origin, voxel), margin, object_margin, height, retreat, stations, hp, _c(points),
+               _c(link, torch.int32), n_links, _c(Rg), _c(LT), op, op.shape[0], batch_each, op.shape[1], grasp_axis, direction, None,
+               0.0, e, eo, 0, None, None)
+    return e, eo
+
+
+@_lift_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, direction, height, retreat, stations,
+      object_points, batch_each, margin, object_margin):
+    return hand_pose.new_empty(hand_pose.shape[0]), hand_pose.new_empty(hand_pose.shape[0])
+
+
+@_custom_op("graspqp_amd::lift_terms_backward", mutates_args=(), device_types="cuda")
+def _lift_bwd_op(hand_pose: Tensor, points: Tensor, link: Tensor, n_links: int, Rg: Tensor, LT: Tensor, values: Tensor,
+                 origin: List[float], voxel: float, grasp_axis: List[float], direction: List[float], height: float, retreat: float,
+                 stations: int, object_points: Tensor, batch_each: int, margin: float, object_margin: float,
+                 g_lift: Tensor) -> Tuple[Tensor, Tensor]:
+    """Upstream row gradients (B) on E_lift -> (link wrench (B,L,6), gRt (B,12)) for fk_backward.  One launch."""
+    hp, v, op = _c(hand_pose), _c(values), _c(object_points)
+    B, dev = hp.shape[0], hp.device
+    wrench, gRt = torch.empty(B, n_links, 6, device=dev), torch.empty(B, 12, device=dev)
+    _lift_call(_pregrasp_grids(v, origin, voxel), margin, object_margin, height, retreat, stations, hp, _c(points),
+               _c(link, torch.int32), n_links, _c(Rg), _c(LT), op, op.shape[0], batch_each, op.shape[1], grasp_axis, direction,
+               _c(g_lift), 0.0, None, None, 0, wrench, gRt)
+    return wrench, gRt
+
+
+@_lift_bwd_op.register_fake
+def _(hand_pose, points, link, n_links, Rg, LT, values, origin, voxel, grasp_axis, direction, height, retreat, stations,
+      object_points, batch_each, margin, object_margin, g_lift):
+    B = hand_pose.shape[0]
+    return hand_pose.new_empty(B, n_links, 6), hand_pose.new_empty(B, 12)
+
+
+class _LiftTerms(torch.autograd.Function):
+    """Glue between two registered ops (lift_terms + fk_backward), as _ApproachTerms.  The object's share comes back beside the
+    energy and is not differentiable on its own: its gradient is part of E_lift's."""
+
+    @staticmethod
+    def forward(ctx, hand_pose, hand, samples, idx, Rg, LT, ws, scene, object_points, par):
+        hp = _c(hand_pose.detach())
+        args = (hp, samples.points, samples.link, hand.L, Rg, LT, scene.values, list(scene.origin), scene.voxel) + par[:5] + \
+               (object_points,) + par[5:]
+        e, eo = _Eager.lift_terms(*args)
+        ctx.save_for_backward(hp, idx, Rg, LT, ws, samples.points, samples.link, scene.values, object_points)
+        ctx.hand, ctx.args = hand, args
+        ctx.mark_non_differentiable(eo)
+        return e, eo
+
+    @staticmethod
+    def backward(ctx, g_lift, _g_object):
+        hp, idx, Rg, LT, ws = ctx.saved_tensors[:5]
+        wrench, gRt = _Eager.lift_terms_backward(*ctx.args, _c(g_lift))
+        gp = _fk_backward(ctx.hand, hp, idx, Rg, LT, ws, None, None, None, wrench, gRt, None)
+        return (gp,) + (None,) * 9
+
+
+def lift_terms(hand_pose, hand: HandHandle, samples: SurfaceSamples, idx, Rg, LT, ws, scene, grasp_axis, height, retreat, stations,
+               object_points, batch_each, direction=(0.0, 0.0, 1.0), margin=0.0, object_margin=0.0, return_object=False):
+    """-> E_lift (B) = (1/K) sum over the stations k = 1..K of [ sum over ``samples`` of max(margin - phi(x_w^k), 0) + sum over the
+    object's points of max(object_margin - phi(x^{j,k}), 0) ] on the grid of ``scene`` (an ``ops.SceneSDF`` or an
+    ``ops.SceneSDFSet``, row b reads grid b // (B / G); it must not contain the target): hand and held object carried together by
+    (k / K) (``height`` u - ``retreat`` R a), u = ``direction`` (object frame, normalised here once in double), a = ``grasp_axis``
+    (hand frame).  ``object_points`` (n_obj,M,3) in the object's frame, row b carries object b // ``batch_each``; None or M = 0 is
+    the hand alone.  ``object_margin`` may be negative.  Unweighted, differentiable w.r.t. ``hand_pose``; ``return_object`` = True
+    returns (E_lift, the object's share (B)).  ``idx``, ``Rg``, ``LT``, ``ws`` are the kinematic state of ``hand_pose``
+    (fk_contacts); K = ``stations`` in 1..32, ``height`` and ``retreat`` >= 0 in metres, not both zero."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if samples.n_links != hand.L:
+        raise ValueError(f"lift_terms: the samples refer to {samples.n_links} links, the hand has {hand.L}")
+    if not isinstance(scene, (SceneSDF, SceneSDFSet)):
+        raise ValueError(f"lift_terms: scene must be an ops.SceneSDF or an ops.SceneSDFSet, got {type(scene).__name__}")
+    B = hand_pose.shape[0]
+    if int(batch_each) != batch_each or int(batch_each) < 1 or B % int(batch_each):
+        raise ValueError(f"lift_terms: batch = {B} is not divisible by batch_each = {batch_each!r}")
+    n_obj = B // int(batch_each)
+    if object_points is None:
+        object_points = hand_pose.new_empty(n_obj, 0, 3)
+    if object_points.dim() != 3 or object_points.shape[0] != n_obj or object_points.shape[2] != 3:
+        raise ValueError(f"lift_terms: object_points must be ({n_obj}, M, 3), got {tuple(object_points.shape)}")
+    axis, u = [float(a) for a in _axis3(grasp_axis)], lift_direction(direction)
+    lift_check(scene, B, hand.L, samples.Ns, n_obj, int(batch_each), object_points.shape[1], height, retreat, stations, axis, u, margin,
+               object_margin)
+    par = (axis, u, float(height), float(retreat), int(stations), int(batch_each), float(margin), float(object_margin))
+    e, eo = _LiftTerms.apply(hand_pose, hand, samples, _c(idx, torch.int64), Rg.detach(), LT.detach(), ws, scene,
+                             _c(object_points.detach()).to(hand_pose.device), par)
+    return (e, eo) if return_object else e
+
+
 @_custom_op("graspqp_amd::scene_compose", mutates_args=("out_values",), device_types="cuda")
 def _scene_compose_op(out_values: Tensor, origin: List[float], voxel: float, target_T: Tensor, part_values: List[Tensor],
                       part_origins: List[float], part_voxels: List[float], part_T: Tensor, exclude: Optional[Tensor],
@@ -3042,6 +3196,8 @@ _eager("track_terms", _track_op)
 _eager("track_terms_backward", _track_bwd_op)
 _eager("arm_terms", _arm_op)
 _eager("arm_terms_backward", _arm_bwd_op)
+_eager("lift_terms", _lift_op)
+_eager("lift_terms_backward", _lift_bwd_op)
 _eager("scene_compose", _scene_compose_op)
 _eager("tsdf_integrate", _tsdf_integrate_op)
 _eager("tsdf_surfels", _tsdf_surfels_op)

@@ -77,6 +77,16 @@ joint move between waypoints and its worst waypoint; ``terms`` gets [E_track] ap
 ``arm_on_track`` = True makes E_arm read the path's configurations at the stations (``track_station_q``) in place of ``reach_q``: the
 launch order is then reach, track, arm.  With weight 0 and the switch off nothing changes.
 
+Lift mode (a weight on "E_lift" and a grid, ``lift_scene`` or else ``scene``; the grid must not contain the target): every obstacle term
+above follows the hand on its way in; this one asks whether hand and object get out.  Station k = 1..``lift_stations`` is the rigid body
+"hand + held object" carried by (k / K) (``lift_height`` u - ``lift_retreat`` R a), u = ``lift_direction`` in the object's frame, a the
+grasp axis; E_lift is the mean over the stations of the hinge sums of the hand's surface samples (margin ``lift_margin``) and of the
+object's points (``lift_object_points``, or an even stride of ``surf``; margin ``lift_object_margin``, which may be negative).  One more
+launch (gq_lift_terms) with the other hand-surface launches before gq_fk_backward adds its link wrenches and gRt; ``lift_object`` (B)
+holds the object's share of the last evaluation; ``terms`` gets [E_lift] appended last, its share of the row total is one more
+gq_scene_total launch, ``select`` gates it at 0 by default, and the proposal and the accept step are the stand-alone launches.  With
+weight 0 nothing changes.
+
 Clutter (``scene`` is an ``ops.SceneSDFSet`` with one grid per object): the same two launches read a stack of grids and pick the
 grid from the row, row // batch_each (gq_clutter_terms / gq_clutter_corridor_terms, the same row bodies: bit for bit the single-grid
 launch's numbers on that grid).  ``ops.scene_compose`` refills the stack in place, also between replays of a captured graph.
@@ -103,6 +113,7 @@ SQUEEZE_TERMS = ("E_squeeze",)
 REACH_TERMS = ("E_reach",)
 ARM_TERMS = ("E_arm",)
 TRACK_TERMS = ("E_track",)
+LIFT_TERMS = ("E_lift",)
 DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, "E_joints": 1.0}  # fit.py:51-55
 
 
@@ -111,11 +122,11 @@ OBSTACLE_TERMS = SCENE_TERMS + APPROACH_TERMS + PREGRASP_TERMS
 
 def select_tolerances(term_names, gates=None):
     """The gates of ``GraspStepper.select`` as one tolerance per term of ``term_names`` (+inf: not gated).  ``gates`` = {term name:
-    tol}; None gates every obstacle term that is switched on (E_scene, E_approach, E_pregrasp, and E_arm for the arm) at 0.0 and
-    nothing else -- the "collision-free" of ``init_avoid_scene``.  A name that is no term of the stepper, or that names a switched-off term, raises,
-    and so does a NaN tolerance."""
+    tol}; None gates every obstacle term that is switched on (E_scene, E_approach, E_pregrasp, E_arm for the arm, E_lift for the
+    way out) at 0.0 and nothing else -- the "collision-free" of ``init_avoid_scene``.  A name that is no term of the stepper, or
+    that names a switched-off term, raises, and so does a NaN tolerance."""
     if gates is None:
-        gates = {k: 0.0 for k in OBSTACLE_TERMS + ARM_TERMS if k in term_names}
+        gates = {k: 0.0 for k in OBSTACLE_TERMS + ARM_TERMS + LIFT_TERMS if k in term_names}
     tol = [float("inf")] * len(term_names)
     for k, v in gates.items():
         if k not in term_names:
@@ -128,11 +139,13 @@ def select_tolerances(term_names, gates=None):
 
 def merge_weights(weights=None):
     """DEFAULT_WEIGHTS (+ zero weights of the tabletop terms, of the scene term, of the approach term, of the pre-grasp term, of
-    the squeeze term, of the reach term, of the arm clearance term and of the tracking term) updated with ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and
-    never used), and so does a negative weight of one of the terms that are switched by their weight."""
-    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS + ARM_TERMS + TRACK_TERMS
+    the squeeze term, of the reach term, of the arm clearance term, of the tracking term and of the lift term) updated with
+    ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and so does a
+    negative weight of one of the terms that are switched by their weight."""
+    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS + ARM_TERMS + TRACK_TERMS + LIFT_TERMS
     w = dict(DEFAULT_WEIGHTS)
-    w.update({k: 0.0 for k in TRACK_TERMS + ARM_TERMS + REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})  # (the obstacle terms keep the end of the listing)
+    # (the obstacle terms keep the end of the listing)
+    w.update({k: 0.0 for k in LIFT_TERMS + TRACK_TERMS + ARM_TERMS + REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})
     for k, v in (weights or {}).items():
         if k not in w:
             raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
@@ -164,7 +177,10 @@ class GraspStepper:
                  pregrasp_stations=None, pregrasp_margin=None, squeeze_min_travel: float = 5e-3, squeeze_damping: float = 1e-3,
                  arm=None, arm_base=None, reach_distance: float = 0.10, reach_stations: int = 0, reach_iterations: int = 24,
                  reach_damping: float = 1e-4, reach_rot_scale: float = 0.1, arm_scene=None, arm_margin=None, arm_damping: float = 1e-6,
-                 track_waypoints: int = 8, track_updates: int = 3, arm_on_track: bool = False, init_avoid_scene: bool = False):
+                 track_waypoints: int = 8, track_updates: int = 3, arm_on_track: bool = False,
+                 lift_height: float = 0.05, lift_retreat: float = 0.0, lift_stations: int = 4, lift_direction=(0.0, 0.0, 1.0),
+                 lift_margin=None, lift_object_margin: float = 0.0, lift_object_samples: int = 512, lift_object_points=None,
+                 lift_scene=None, init_avoid_scene: bool = False):
         """object_meshes: an ``ops.MeshSet``, or an ``ops.PointCloudSet`` for objects given as oriented point clouds -- the
         contact query is then gq_cloud_forward, always a launch of its own (the FK forward launch gets no SDF descriptor);
         everything downstream reads the same four buffers.
@@ -207,7 +223,15 @@ class GraspStepper:
         ``track_waypoints`` in 1..64 waypoints beyond the first, ``track_updates`` in 1..16 updates per waypoint.  ``track_q``,
         ``track_step`` and ``track_worst`` hold the last evaluation.  No default weight is set.  ``arm_on_track`` = True makes E_arm read
         the tracked path's configurations at the stations (``track_station_q``) in place of ``reach_q``: it needs both terms on and
-        ``reach_stations`` dividing ``track_waypoints``.  With weight 0 and the switch off the three arguments change nothing."""
+        ``reach_stations`` dividing ``track_waypoints``.  With weight 0 and the switch off the three arguments change nothing.
+        weights["E_lift"] > 0 selects the lift mode (module docstring): ``lift_scene`` (an ``ops.SceneSDF``, or an ``ops.SceneSDFSet``
+        with one grid per object; None takes ``scene``) must not contain the target; ``lift_height`` and ``lift_retreat`` >= 0 in
+        metres, not both zero; ``lift_stations`` in 1..32; ``lift_direction`` in the object's frame, normalised here; ``lift_margin``
+        = None takes ``scene_margin``; ``lift_object_margin`` may be negative.  ``lift_object_points`` (n_obj,M,3) are the object's
+        points in its own frame; None takes M = min(``lift_object_samples``, P) points of ``surface_points`` at the indices
+        floor(j P / M) (the stored order is Morton order, so an even stride is an even cover); M = 0 is the hand alone.
+        ``lift_object`` (B) holds the object's share of the last evaluation.  No default weight is set; with weight 0 the
+        arguments change nothing."""
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -297,13 +321,45 @@ class GraspStepper:
             if int(track_waypoints) % int(reach_stations):
                 raise ValueError(f"GraspStepper: arm_on_track=True needs reach_stations = {reach_stations} to divide track_waypoints = "
                                  f"{track_waypoints}")
+        self.lift_mode = self.w["E_lift"] > 0
+        if self.lift_mode:
+            lift_scene = scene if lift_scene is None else lift_scene
+            if not isinstance(lift_scene, (ops.SceneSDF, ops.SceneSDFSet)):
+                raise ValueError('GraspStepper: weights["E_lift"] > 0 needs lift_scene= or scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
+            if isinstance(lift_scene, ops.SceneSDFSet) and lift_scene.n_grids != self.n_obj:
+                raise ValueError(f"GraspStepper: lift_scene has n_grids = {lift_scene.n_grids}, the stepper has n_obj = {self.n_obj} objects")
+            lift_margin = scene_margin if lift_margin is None else lift_margin
+            if lift_object_points is None:
+                if int(lift_object_samples) != lift_object_samples or int(lift_object_samples) < 0:
+                    raise ValueError(f"GraspStepper: lift_object_samples = {lift_object_samples!r} must be an integer >= 0")
+                M = min(int(lift_object_samples), self.P)
+                pick = (torch.arange(M, device=self.dev) * self.P) // max(M, 1)  # floor(j P / M)
+                lift_object_points = self.surf[:, pick]
+            lift_object_points = torch.as_tensor(lift_object_points, dtype=torch.float32).detach().to(self.dev).contiguous()
+            if lift_object_points.dim() != 3 or lift_object_points.shape[0] != self.n_obj or lift_object_points.shape[2] != 3:
+                raise ValueError(f"GraspStepper: lift_object_points must be ({self.n_obj}, M, 3), got {tuple(lift_object_points.shape)}")
+            try:
+                lift_direction = ops.lift_direction(lift_direction)
+            except ValueError:
+                raise ValueError(f"GraspStepper: lift_direction = {lift_direction!r} must be three finite numbers, not all zero") from None
+            for name, v in (("lift_height", lift_height), ("lift_retreat", lift_retreat)):
+                if not 0.0 <= float(v) < float("inf"):
+                    raise ValueError(f"GraspStepper: {name} = {v!r} must be finite and >= 0")
+            if not float(lift_height) + float(lift_retreat) > 0.0:
+                raise ValueError("GraspStepper: lift_height and lift_retreat must not both be zero")
+            if int(lift_stations) != lift_stations or not 1 <= int(lift_stations) <= 32:
+                raise ValueError(f"GraspStepper: lift_stations = {lift_stations!r} must be an integer in 1..32")
+            if not 0.0 <= float(lift_margin) < float("inf"):
+                raise ValueError(f"GraspStepper: lift_margin = {lift_margin!r} must be finite and >= 0")
+            if not abs(float(lift_object_margin)) < float("inf"):
+                raise ValueError(f"GraspStepper: lift_object_margin = {lift_object_margin!r} must be finite")
         self.init_avoid_scene = bool(init_avoid_scene)
         if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
             raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
         self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
                            + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ())
                            + (SQUEEZE_TERMS if self.squeeze_mode else ()) + (REACH_TERMS if self.reach_mode else ()) + (ARM_TERMS if self.arm_mode else ())
-                           + (TRACK_TERMS if self.track_mode else ()))
+                           + (TRACK_TERMS if self.track_mode else ()) + (LIFT_TERMS if self.lift_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -430,11 +486,11 @@ class GraspStepper:
             self._alt_desc = ad
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
         self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode or self.squeeze_mode
-                               or self.reach_mode)
+                               or self.reach_mode or self.lift_mode)
         self.samples, self.g_R = None, None
         self._n_surface_points, self._select_fk = int(n_surface_points), None
         self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode or self.approach_mode else (None, 0.0)
-        if self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode:  # one set of surface samples for all modes
+        if self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode or self.lift_mode:  # one set of surface samples for all modes
             if surface_samples is None:
                 from .utils import meshes as mesh_utils
 
@@ -514,6 +570,19 @@ class GraspStepper:
             self.track_step, self.track_worst = f(B), f(B)
             if self.arm_on_track:
                 self.track_station_q = f(B, self.reach_stations + 1, self.arm.N)
+        self.lift_scene, self.lift_object, self.lift_object_points = None, None, None
+        if self.lift_mode:
+            self._i_lift = self.term_names.index("E_lift")
+            self.lift_scene, self.lift_object_points, self.lift_object = lift_scene, lift_object_points, f(B)
+            self.lift_height, self.lift_retreat, self.lift_stations = float(lift_height), float(lift_retreat), int(lift_stations)
+            self.lift_margin, self.lift_object_margin = float(lift_margin), float(lift_object_margin)
+            self.lift_direction = tuple(lift_direction)
+            self._lift_u = ops._axis_c(lift_direction)
+            self._lift_grids = ops._pregrasp_grids(lift_scene.values, lift_scene.origin, lift_scene.voxel)  # a single grid: the stack of one
+            ops.lift_check(lift_scene, B, L, self.samples.Ns, self.n_obj, self.be, lift_object_points.shape[1], self.lift_height,
+                           self.lift_retreat, self.lift_stations, hand.spec.grasp_axis, lift_direction, self.lift_margin,
+                           self.lift_object_margin, "GraspStepper")
+            self._ptr.lift_points, self._ptr.lift_object = _C.f32(self.lift_object_points), _C.f32(self.lift_object)
         self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
@@ -532,8 +601,9 @@ class GraspStepper:
                                                                   int(m["annealing_period"]))
         ac.energy, ac.pose, ac.idx, ac.grad = (t.data_ptr() for t in (self.energy, self.hand_pose, self.contact_idx, self.grad))
         ac.accept, ac.temperature = self.accept.data_ptr(), self.temperature.data_ptr()
-        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach, pre-grasp, squeeze
-        # and reach mode (six to twelve terms) never take the fused loop (_fuse_loop above) and merge their terms in the stand-alone accept launch
+        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach, pre-grasp, squeeze,
+        # reach (with arm and track, which need it) and lift mode (six to fifteen terms) never take the fused loop (_fuse_loop above)
+        # and merge their terms in the stand-alone accept launch
         assert self._fuse_loop == (nT == len(TERM_NAMES))
         ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
@@ -675,6 +745,15 @@ class GraspStepper:
                         self.reach_stations, None, self.w["E_track"], self.terms_new[self._i_track], self.track_q, self.track_worst,
                         self.track_step, self.track_station_q, 1, self.gRt, st)
 
+    def _eval_lift(self, pose, st):
+        """E_lift -> its row of terms_new (``_i_lift``), the object's share -> ``lift_object``; the gradient of w_lift E_lift is added
+        to the link wrenches and gRt that the FK backward reads.  g_R and g_theta are not touched."""
+        p = self._ptr
+        ops._lift_call(self._lift_grids, self.lift_margin, self.lift_object_margin, self.lift_height, self.lift_retreat, self.lift_stations,
+                       pose, self.samples.points, p.link, self.L, p.Rg, p.LT, p.lift_points, self.n_obj, self.be,
+                       self.lift_object_points.shape[1], self._axis, self._lift_u, None, self.w["E_lift"], p.e[self._i_lift],
+                       p.lift_object, 1, p.wrench, p.gRt, st)
+
     def _eval_tail(self, pose, idx, st, loop=False):
         B, n = self.B, self.n
         f32 = _C.f32
@@ -723,6 +802,8 @@ class GraspStepper:
             self._eval_tabletop(pose, st)
         for _, _, evaluate in self._obstacle_terms:  # scene, approach, pre-grasp
             evaluate(pose, st)
+        if self.lift_mode:  # with the other hand-surface launches: it adds to the link wrenches and gRt
+            self._eval_lift(pose, st)
         if self.squeeze_mode:
             self._eval_squeeze(idx, st)
         if self.reach_mode:
@@ -748,6 +829,9 @@ class GraspStepper:
                     ctypes.c_int64(self.B), st)
         if self.track_mode:
             _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_track]), float(self.w["E_track"]),
+                    ctypes.c_int64(self.B), st)
+        if self.lift_mode:
+            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_lift]), float(self.w["E_lift"]),
                     ctypes.c_int64(self.B), st)
 
     def evaluate(self, pose, idx):

@@ -867,6 +867,50 @@ int gq_track_terms(const gqArm* arm, const float* hand_pose /* (B,pose_dim) */, 
                    float* track_q /* (B,T+1,N) or NULL */, float* track_worst /* (B) or NULL */, float* track_step /* (B) or NULL */,
                    float* track_station_q /* (B,K+1,N) or NULL */, int accumulate, float* gRt /* (B,12) or NULL */, void* stream);
 
+/* ---- lift clearance of the stepper: E_lift, the hand and the held object on the way out --------------------------------------
+ * Every obstacle term above follows the hand on its way in.  This one asks what happens after the fingers close: hand and object
+ * leave as one rigid body, and the object is usually wider than the hand.  Row b of object o = b / batch_each with rotation R (Rg)
+ * and translation t; a = grasp_axis (hand frame, used as given), u = direction (a unit vector of the object's frame, which is the
+ * grid's; used as given, the caller normalises), H = height >= 0 and D = retreat >= 0 in metres with H + D > 0, K = n_stations in
+ * 1..32, d_k = D k / K and h_k = H k / K for k = 1..K.  The carry is the straight translation by (k / K) (H u - D R a): D = 0 is a
+ * pure lift, H = 0 the reverse of the approach.
+ *   hand sample, x_h = T_link p:   y_k = x_h - d_k a      x_w^k = R y_k + (t + h_k u)
+ *   object point p_j of object o:  x^{j,k} = p_j + h_k u - d_k R a           (object_points (n_obj,M,3), object frame, device)
+ *   E_lift = (1/K) sum_k [ sum_s max(margin - phi(x_w^k), 0) + sum_j max(object_margin - phi(x^{j,k}), 0) ]
+ * phi is the trilinear interpolant under exactly the contract of "scene obstacles": a point outside the volume is free space, a
+ * non-finite one makes the row's energy and gradient NaN and touches no memory.  margin >= 0 is finite; object_margin is finite
+ * and may be negative (an object dragged along its support sits at phi ~ 0).  Station 0 is not part of the term: the hand there is
+ * E_scene, the object at rest touches what it stands on.  M = n_object_points = 0 is the hand alone.  The grid of row b is grid
+ * b / rows_per_grid of the stack (n_grids = 1: the single scene, as in gq_arm_terms) and must not contain the target.
+ * e_lift is written UNWEIGHTED; e_object (B, optional) is the object's share of it, (1/K) sum_k sum_j.  The gradient carries
+ * up = (up_lift[row] if given, else w_lift) (1/K), in the conventions of gq_approach_terms, with g_h = R' (-up grad phi):
+ *   active hand (s,k):    f_l = sum g_h, m_l = sum x_h x g_h (x_h unshifted), gsum = -sum g_h, K9 += g_h (x) y_k; the world shift
+ *                         h_k u depends on nothing and adds nothing
+ *   active object (j,k):  K9 += g_h (x) (-d_k a) and nothing else: t does not move the object (no gsum), no joint does (no wrench).
+ *                         With D = 0 the object part has a value and no gradient, the same value for every row of an object.
+ * g_R and g_theta of gq_fk_backward are not touched.  accumulate, links without samples, n_samples or M not a multiple of 64 and
+ * link ids outside the hand are as in gq_approach_terms.  One block of eight wavefronts per row; a wavefront takes its hand chunks,
+ * then its chunks of 64 object points, stations ascending inside a lane; fixed-order sums, no atomics: bitwise reproducible run to
+ * run, a row's bits do not depend on the batch around it.  With H = 0 and M = 0 the launch gives BIT FOR BIT e, link_wrench and
+ * gRt of gq_clutter_corridor_terms at the same inputs.  The row total takes gq_scene_total(total, e_lift, w, B).
+ * gq_lift_check is the argument check on its own (host only, no GPU; grids = NULL checks the parameters alone, before a scene
+ * exists -- gq_lift_terms itself refuses a NULL stack): everything gq_clutter_check refuses, batch != n_obj * batch_each,
+ * n_object_points outside 0..2^24, a height or retreat that is negative or not finite, height + retreat == 0, n_stations outside
+ * 1..32, a NULL, non-finite or all-zero grasp_axis or direction, a margin that is negative or not finite, an object_margin that is
+ * not finite; its message contains "lift" and names the argument.                                                            */
+int gq_lift_check(const gqClutterGrids* grids, int64_t batch, int64_t rows_per_grid, int n_links, int64_t n_samples, int64_t n_obj,
+                  int64_t batch_each, int64_t n_object_points, float height, float retreat, int n_stations,
+                  const float* grasp_axis /* (3) host */, const float* direction /* (3) host */, float margin, float object_margin);
+int gq_lift_terms(const gqClutterGrids* grids, int64_t rows_per_grid, float margin, float object_margin, float height, float retreat,
+                  int n_stations, const float* samples /* (Ns,3) link frame, device */, const int32_t* sample_link /* (Ns) */,
+                  int64_t n_samples, int n_links, const float* hand_pose, int pose_dim, const float* Rg /* (B,9) */,
+                  const float* link_T /* (B,L,12) */, int64_t batch, const float* object_points /* (n_obj,M,3) or NULL with M = 0 */,
+                  int64_t n_obj, int64_t batch_each, int64_t n_object_points, const float* grasp_axis /* (3) host */,
+                  const float* direction /* (3) host */, const float* up_lift /* (B) or NULL */, float w_lift,
+                  float* e_lift /* (B) or NULL, unweighted */, float* e_object /* (B) or NULL */,
+                  int accumulate /* 1: add to the two gradient buffers, 0: overwrite */, float* link_wrench /* (B,L,6) or NULL */,
+                  float* gRt /* (B,12) or NULL */, void* stream);
+
 /* ---- scenes from depth images: TSDF fusion on the device into scene grids ---------------------------------------------
  * What a robot has is depth images, not a signed-distance volume.  gq_tsdf_integrate fuses a batch of depth frames into a
  * gqClutterGrids stack IN PLACE, one launch per batch (n_grids = 1 is the single world grid).  State: `values` of the stack IS
