@@ -97,6 +97,7 @@ gq_cloud_forward, always a launch of its own; it fills the same four buffers, so
 
 from __future__ import annotations
 
+import collections
 import ctypes
 import types
 
@@ -119,6 +120,48 @@ DEFAULT_WEIGHTS = {"E_dis": 100.0, "E_fc": 1.0, "E_pen": 100.0, "E_spen": 10.0, 
 
 OBSTACLE_TERMS = SCENE_TERMS + APPROACH_TERMS + PREGRASP_TERMS
 
+# The optional terms, one row each, in DECLARATION order: the order of their rows in ``term_names`` / ``terms`` and of their shares in
+# the fp32 total ("how a term enters the stepper").  A term is on when one of its weights is > 0.
+#   key      the term's pieces in GraspStepper: _check_<key>, _bind_<key>, _launch_<key>
+#   names    its rows of ``terms``
+#   flag     the public attribute that says whether it is on
+#   gated    ``select`` gates it at 0.0 by default
+#   samples  it reads the hand's surface samples
+#   g_theta  its launch writes ``g_theta``, which the FK backward must then be handed
+#   total    the entry that adds its share to the total: gq_scene_total once per name, gq_tabletop_total once for both names
+#   off      the public attributes that are None while the term is off
+Term = collections.namedtuple("Term", "key names flag gated samples g_theta total off")
+TERMS = (
+    Term("tabletop", TABLETOP_TERMS, "tabletop", False, True, False, "gq_tabletop_total", ()),
+    Term("scene", SCENE_TERMS, "scene_mode", True, True, False, "gq_scene_total", ()),
+    Term("approach", APPROACH_TERMS, "approach_mode", True, True, False, "gq_scene_total", ()),
+    Term("pregrasp", PREGRASP_TERMS, "pregrasp_mode", True, True, True, "gq_scene_total", ()),
+    Term("squeeze", SQUEEZE_TERMS, "squeeze_mode", False, False, True, "gq_scene_total", ("squeeze_theta",)),
+    Term("reach", REACH_TERMS, "reach_mode", False, False, False, "gq_scene_total", ("arm", "arm_base", "reach_q", "reach_seed")),
+    Term("arm", ARM_TERMS, "arm_mode", True, False, False, "gq_scene_total", ("arm_scene",)),
+    Term("track", TRACK_TERMS, "track_mode", False, False, False, "gq_scene_total",
+         ("track_q", "track_step", "track_worst", "track_station_q")),
+    Term("lift", LIFT_TERMS, "lift_mode", True, True, False, "gq_scene_total", ("lift_scene", "lift_object", "lift_object_points")),
+)
+# LAUNCH order, between the joined branches and gq_fk_backward: the hand-surface launches (they add to the link wrenches), then
+# squeeze (it adds to the g_theta of pre-grasp), then reach, then track before arm (track starts at reach_q, arm may read the path)
+LAUNCH_ORDER = ("tabletop", "scene", "approach", "pregrasp", "lift", "squeeze", "reach", "track", "arm")
+assert sorted(LAUNCH_ORDER) == sorted(t.key for t in TERMS)
+# the order in which merge_weights lists the switched weights (it shows in its error message): the youngest term first, the
+# obstacle terms at the end
+_SWITCHED = tuple(k for t in reversed(TERMS) if t.names[0] not in OBSTACLE_TERMS for k in t.names) + OBSTACLE_TERMS
+
+
+def term_plan(weights):
+    """What a dict of weights (missing keys: 0) makes of the table, on the host alone: ``term_names`` (TERM_NAMES + the names of the
+    terms that are on, declaration order), ``launch`` (their keys in launch order), ``fuse_loop`` (no optional term is on: proposal
+    and accept step ride in the FK launches), ``needs_samples`` and ``g_theta`` (some term that is on has the column set)."""
+    on = [t for t in TERMS if any(weights.get(k, 0.0) > 0 for k in t.names)]
+    keys = {t.key for t in on}
+    return types.SimpleNamespace(term_names=TERM_NAMES + tuple(k for t in on for k in t.names),
+                                 launch=tuple(k for k in LAUNCH_ORDER if k in keys), fuse_loop=not on,
+                                 needs_samples=any(t.samples for t in on), g_theta=any(t.g_theta for t in on))
+
 
 def select_tolerances(term_names, gates=None):
     """The gates of ``GraspStepper.select`` as one tolerance per term of ``term_names`` (+inf: not gated).  ``gates`` = {term name:
@@ -126,7 +169,7 @@ def select_tolerances(term_names, gates=None):
     way out) at 0.0 and nothing else -- the "collision-free" of ``init_avoid_scene``.  A name that is no term of the stepper, or
     that names a switched-off term, raises, and so does a NaN tolerance."""
     if gates is None:
-        gates = {k: 0.0 for k in OBSTACLE_TERMS + ARM_TERMS + LIFT_TERMS if k in term_names}
+        gates = {k: 0.0 for t in TERMS if t.gated for k in t.names if k in term_names}
     tol = [float("inf")] * len(term_names)
     for k, v in gates.items():
         if k not in term_names:
@@ -142,15 +185,13 @@ def merge_weights(weights=None):
     the squeeze term, of the reach term, of the arm clearance term, of the tracking term and of the lift term) updated with
     ``weights``; a key that names no term of the stepper raises (it would otherwise be accepted and never used), and so does a
     negative weight of one of the terms that are switched by their weight."""
-    switched = TABLETOP_TERMS + OBSTACLE_TERMS + SQUEEZE_TERMS + REACH_TERMS + ARM_TERMS + TRACK_TERMS + LIFT_TERMS
     w = dict(DEFAULT_WEIGHTS)
-    # (the obstacle terms keep the end of the listing)
-    w.update({k: 0.0 for k in LIFT_TERMS + TRACK_TERMS + ARM_TERMS + REACH_TERMS + SQUEEZE_TERMS + TABLETOP_TERMS + OBSTACLE_TERMS})
+    w.update({k: 0.0 for k in _SWITCHED})
     for k, v in (weights or {}).items():
         if k not in w:
             raise ValueError(f"GraspStepper: unknown energy term {k!r} in weights (known: {', '.join(w)})")
         w[k] = float(v)
-        if k in switched and not w[k] >= 0.0:  # these terms are switched by their weight: > 0 on, 0 off
+        if k in _SWITCHED and not w[k] >= 0.0:  # these terms are switched by their weight: > 0 on, 0 off
             raise ValueError(f"GraspStepper: weights[{k!r}] = {v!r} must be >= 0")
     return w
 
@@ -232,6 +273,7 @@ class GraspStepper:
         floor(j P / M) (the stored order is Morton order, so an even stride is an even cover); M = 0 is the hand alone.
         ``lift_object`` (B) holds the object's share of the last evaluation.  No default weight is set; with weight 0 the
         arguments change nothing."""
+        a = types.SimpleNamespace(**locals())  # the arguments, for the terms' checks (which fill in the fall-backs) and binds
         if energy_type not in ("graspqp", "dexgrasp", "tdg") or optimizer not in ("mala_star", "dexgraspnet"):
             raise NotImplementedError(f"energy_type={energy_type!r} / optimizer={optimizer!r}")
         self.energy_type, self.optimizer = energy_type, optimizer
@@ -247,119 +289,21 @@ class GraspStepper:
         self.J, self.L, self.S = hand.J, hand.L, hand.S
         self.D = 9 + self.J
         self.w = merge_weights(weights)
-        self.tabletop = any(self.w[k] > 0 for k in TABLETOP_TERMS)
-        self.scene_mode = self.w["E_scene"] > 0
-        if self.scene_mode and not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
-            raise ValueError('GraspStepper: weights["E_scene"] > 0 needs scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
-        if not float(scene_margin) >= 0.0:
-            raise ValueError(f"GraspStepper: scene_margin = {scene_margin!r} must be >= 0")
-        self.approach_mode = self.w["E_approach"] > 0
-        # clutter: one grid per object, the two launches pick the grid from the row (row // batch_each)
-        self.clutter = (self.scene_mode or self.approach_mode) and isinstance(scene, ops.SceneSDFSet)
-        if self.clutter and scene.n_grids != self.n_obj:
-            raise ValueError(f"GraspStepper: scene has n_grids = {scene.n_grids}, the stepper has n_obj = {self.n_obj} objects")
-        if self.approach_mode:
-            if not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
-                raise ValueError('GraspStepper: weights["E_approach"] > 0 needs scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
-            approach_margin = scene_margin if approach_margin is None else approach_margin
-            _check_corridor("approach", approach_margin, approach_distance, approach_stations, 1)
-        self.pregrasp_mode = self.w["E_pregrasp"] > 0
-        if self.pregrasp_mode:
-            pregrasp_scene = scene if pregrasp_scene is None else pregrasp_scene
-            if not isinstance(pregrasp_scene, (ops.SceneSDF, ops.SceneSDFSet)):
-                raise ValueError('GraspStepper: weights["E_pregrasp"] > 0 needs pregrasp_scene= or scene=ops.SceneSDF(...) or '
-                                 'ops.SceneSDFSet(...)')
-            if isinstance(pregrasp_scene, ops.SceneSDFSet) and pregrasp_scene.n_grids != self.n_obj:
-                raise ValueError(f"GraspStepper: pregrasp_scene has n_grids = {pregrasp_scene.n_grids}, the stepper has n_obj = "
-                                 f"{self.n_obj} objects")
-            pregrasp_margin = scene_margin if pregrasp_margin is None else pregrasp_margin
-            pregrasp_distance = approach_distance if pregrasp_distance is None else pregrasp_distance
-            pregrasp_stations = approach_stations if pregrasp_stations is None else pregrasp_stations
-            _check_corridor("pregrasp", pregrasp_margin, pregrasp_distance, pregrasp_stations, 0)
-            if not 0.0 <= float(pregrasp_opening) <= 1.0:
-                raise ValueError(f"GraspStepper: pregrasp_opening = {pregrasp_opening!r} must be in [0, 1]")
-        self.squeeze_mode = self.w["E_squeeze"] > 0
-        if self.squeeze_mode:
-            ops.squeeze_check(hand, n_contact, squeeze_min_travel, squeeze_damping, "GraspStepper")
-        self.reach_mode = self.w["E_reach"] > 0
-        if self.reach_mode:
-            if not isinstance(arm, (ops.ArmSpec, ops.ArmHandle)):
-                raise ValueError('GraspStepper: weights["E_reach"] > 0 needs arm=ops.ArmSpec(...) or ops.ArmHandle(...)')
-            if arm_base is None:
-                raise ValueError('GraspStepper: weights["E_reach"] > 0 needs arm_base, (3,4) or (n_obj,3,4)')
-            ops.reach_check(arm, reach_distance, reach_stations, reach_iterations, reach_damping, reach_rot_scale, hand.spec.grasp_axis,
-                            "GraspStepper")
-            arm_base = ops.reach_base(arm_base, self.n_obj, "GraspStepper")
-        self.arm_mode = self.w["E_arm"] > 0
-        if self.arm_mode:
-            if not self.reach_mode:
-                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs weights["E_reach"] > 0: the term reads the reach term\'s reach_q')
-            if not (arm.spec if isinstance(arm, ops.ArmHandle) else arm).n_spheres:
-                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs an arm with collision spheres (ArmSpec.with_spheres / '
-                                 'with_link_spheres)')
-            arm_scene = scene if arm_scene is None else arm_scene
-            if not isinstance(arm_scene, (ops.SceneSDF, ops.SceneSDFSet)):
-                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs arm_scene= or scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
-            if isinstance(arm_scene, ops.SceneSDFSet) and arm_scene.n_grids != self.n_obj:
-                raise ValueError(f"GraspStepper: arm_scene has n_grids = {arm_scene.n_grids}, the stepper has n_obj = {self.n_obj} objects")
-            arm_margin = scene_margin if arm_margin is None else arm_margin
-            ops.arm_check(arm, ops._arm_scene_grids(arm_scene, "GraspStepper"), self.B, arm_margin, arm_damping, reach_rot_scale,
-                          reach_distance, reach_stations, hand.spec.grasp_axis, "GraspStepper")
-        self.track_mode = self.w["E_track"] > 0
-        if self.track_mode:
-            if not self.reach_mode:
-                raise ValueError('GraspStepper: weights["E_track"] > 0 needs weights["E_reach"] > 0: the path starts at the reach term\'s '
-                                 'reach_q[:, reach_stations]')
-            if int(reach_stations) < 1:
-                raise ValueError('GraspStepper: weights["E_track"] > 0 needs reach_stations >= 1: the path starts at the retreated station')
-            ops.track_check(arm, reach_distance, track_waypoints, track_updates, reach_damping, reach_rot_scale, hand.spec.grasp_axis,
-                            reach_stations, False, "GraspStepper")
-        self.arm_on_track = bool(arm_on_track)
-        if self.arm_on_track:
-            if not (self.track_mode and self.arm_mode):
-                raise ValueError('GraspStepper: arm_on_track=True needs weights["E_track"] > 0 and weights["E_arm"] > 0')
-            if int(track_waypoints) % int(reach_stations):
-                raise ValueError(f"GraspStepper: arm_on_track=True needs reach_stations = {reach_stations} to divide track_waypoints = "
-                                 f"{track_waypoints}")
-        self.lift_mode = self.w["E_lift"] > 0
-        if self.lift_mode:
-            lift_scene = scene if lift_scene is None else lift_scene
-            if not isinstance(lift_scene, (ops.SceneSDF, ops.SceneSDFSet)):
-                raise ValueError('GraspStepper: weights["E_lift"] > 0 needs lift_scene= or scene=ops.SceneSDF(...) or ops.SceneSDFSet(...)')
-            if isinstance(lift_scene, ops.SceneSDFSet) and lift_scene.n_grids != self.n_obj:
-                raise ValueError(f"GraspStepper: lift_scene has n_grids = {lift_scene.n_grids}, the stepper has n_obj = {self.n_obj} objects")
-            lift_margin = scene_margin if lift_margin is None else lift_margin
-            if lift_object_points is None:
-                if int(lift_object_samples) != lift_object_samples or int(lift_object_samples) < 0:
-                    raise ValueError(f"GraspStepper: lift_object_samples = {lift_object_samples!r} must be an integer >= 0")
-                M = min(int(lift_object_samples), self.P)
-                pick = (torch.arange(M, device=self.dev) * self.P) // max(M, 1)  # floor(j P / M)
-                lift_object_points = self.surf[:, pick]
-            lift_object_points = torch.as_tensor(lift_object_points, dtype=torch.float32).detach().to(self.dev).contiguous()
-            if lift_object_points.dim() != 3 or lift_object_points.shape[0] != self.n_obj or lift_object_points.shape[2] != 3:
-                raise ValueError(f"GraspStepper: lift_object_points must be ({self.n_obj}, M, 3), got {tuple(lift_object_points.shape)}")
-            try:
-                lift_direction = ops.lift_direction(lift_direction)
-            except ValueError:
-                raise ValueError(f"GraspStepper: lift_direction = {lift_direction!r} must be three finite numbers, not all zero") from None
-            for name, v in (("lift_height", lift_height), ("lift_retreat", lift_retreat)):
-                if not 0.0 <= float(v) < float("inf"):
-                    raise ValueError(f"GraspStepper: {name} = {v!r} must be finite and >= 0")
-            if not float(lift_height) + float(lift_retreat) > 0.0:
-                raise ValueError("GraspStepper: lift_height and lift_retreat must not both be zero")
-            if int(lift_stations) != lift_stations or not 1 <= int(lift_stations) <= 32:
-                raise ValueError(f"GraspStepper: lift_stations = {lift_stations!r} must be an integer in 1..32")
-            if not 0.0 <= float(lift_margin) < float("inf"):
-                raise ValueError(f"GraspStepper: lift_margin = {lift_margin!r} must be finite and >= 0")
-            if not abs(float(lift_object_margin)) < float("inf"):
-                raise ValueError(f"GraspStepper: lift_object_margin = {lift_object_margin!r} must be finite")
+        self._plan = plan = term_plan(self.w)
+        self.term_names = plan.term_names
+        self._row = {k: i for i, k in enumerate(self.term_names)}
+        for t in TERMS:
+            setattr(self, t.flag, t.key in plan.launch)
+            for k in t.off:
+                setattr(self, k, None)
+        self.scene, self.scene_margin, self.clutter = None, 0.0, False  # of the terms that read ``scene`` (_check_scene, _bind_scene_arg)
+        # every check in declaration order, for the terms that are off too (a rule between terms stands in the later one's check):
+        # which error comes first is part of the interface, and all of them come before the first device allocation
+        for t in TERMS:
+            getattr(self, "_check_" + t.key)(a, getattr(self, t.flag))
         self.init_avoid_scene = bool(init_avoid_scene)
         if self.init_avoid_scene and not (self.scene_mode or self.approach_mode):
             raise ValueError('GraspStepper: init_avoid_scene=True needs weights["E_scene"] > 0 or weights["E_approach"] > 0')
-        self.term_names = (TERM_NAMES + (TABLETOP_TERMS if self.tabletop else ()) + (SCENE_TERMS if self.scene_mode else ())
-                           + (APPROACH_TERMS if self.approach_mode else ()) + (PREGRASP_TERMS if self.pregrasp_mode else ())
-                           + (SQUEEZE_TERMS if self.squeeze_mode else ()) + (REACH_TERMS if self.reach_mode else ()) + (ARM_TERMS if self.arm_mode else ())
-                           + (TRACK_TERMS if self.track_mode else ()) + (LIFT_TERMS if self.lift_mode else ()))
         nT = len(self.term_names)
         self.fc = dict(ops.FC_DEFAULTS)
         if fc_cfg:
@@ -485,12 +429,10 @@ class GraspStepper:
             ad.e_fc = self.terms_new[1].data_ptr()
             self._alt_desc = ad
         # MalaStar.try_step / accept_step as head / tail of the FK kernels
-        self._fuse_loop = not (self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode or self.squeeze_mode
-                               or self.reach_mode or self.lift_mode)
+        self._fuse_loop = plan.fuse_loop
         self.samples, self.g_R = None, None
         self._n_surface_points, self._select_fk = int(n_surface_points), None
-        self.scene, self.scene_margin = (scene, float(scene_margin)) if self.scene_mode or self.approach_mode else (None, 0.0)
-        if self.tabletop or self.scene_mode or self.approach_mode or self.pregrasp_mode or self.lift_mode:  # one set of surface samples for all modes
+        if plan.needs_samples:  # one set of surface samples for all modes
             if surface_samples is None:
                 from .utils import meshes as mesh_utils
 
@@ -502,87 +444,17 @@ class GraspStepper:
             self._ptr = types.SimpleNamespace(link=_C.i32(self.samples.link), Rg=_C.f32(self.Rg), LT=_C.f32(self.link_T),
                                               wrench=_C.f32(self.wrench), gRt=_C.f32(self.gRt), g_theta=_C.f32(self.g_theta),
                                               e=[_C.f32(self.terms_new[i]) for i in range(nT)])
-        # the switched-on obstacle terms in launch order: (row of terms_new, weight, evaluate)
-        self._obstacle_terms = []
-        if self.scene_mode or self.approach_mode:  # the grid struct of both launches: the stack (clutter) or the one grid
-            self._scene_grid = scene.grid_set if self.clutter else scene.grid
-        if self.scene_mode:
-            self._i_scene = self.term_names.index("E_scene")
-            self._obstacle_terms.append((self._i_scene, float(self.w["E_scene"]), self._eval_scene))
-            scene.check(B, self.be, L, self.samples.Ns) if self.clutter else scene.check(B, L, self.samples.Ns)
-        if self.approach_mode:
-            self._i_approach = self.term_names.index("E_approach")
-            self._obstacle_terms.append((self._i_approach, float(self.w["E_approach"]), self._eval_approach))
-            self.approach_distance, self.approach_stations = float(approach_distance), int(approach_stations)
-            self.approach_margin = float(approach_margin)
-            ops.approach_check(scene, B, L, self.samples.Ns, self.approach_distance, self.approach_stations,
-                               hand.spec.grasp_axis)
-        if self.pregrasp_mode:
-            self._i_pregrasp = self.term_names.index("E_pregrasp")
-            self._obstacle_terms.append((self._i_pregrasp, float(self.w["E_pregrasp"]), self._eval_pregrasp))
-            self.pregrasp_scene = pregrasp_scene
-            self.pregrasp_distance, self.pregrasp_stations = float(pregrasp_distance), int(pregrasp_stations)
-            self.pregrasp_margin, self.pregrasp_opening = float(pregrasp_margin), float(pregrasp_opening)
-            if pregrasp_joints is None:
-                self.pregrasp_joints = ops.default_open_joints(hand.spec, self.dev)
-            else:
-                self.pregrasp_joints = torch.as_tensor(pregrasp_joints, dtype=torch.float32).detach().to(self.dev).contiguous()
-            if self.pregrasp_joints.shape != (self.J,):
-                raise ValueError(f"GraspStepper: pregrasp_joints must be ({self.J},), got {tuple(self.pregrasp_joints.shape)}")
-            ops.pregrasp_check(pregrasp_scene, B, L, self.samples.Ns, self.pregrasp_distance, self.pregrasp_stations,
-                               hand.spec.grasp_axis, self.pregrasp_opening)
-            self._ptr.joints = _C.f32(self.pregrasp_joints)
-            # the stack view of the grid (a single grid is the stack of one): row b reads grid b // (B / n_grids)
-            self._pregrasp_grids = ops._pregrasp_grids(pregrasp_scene.values, pregrasp_scene.origin, pregrasp_scene.voxel)
-        if self.tabletop:
-            self.g_R = f(B, 9)
-            self.table_z = float(table_z)
-            # d (w_prior E_prior) / d R = w_prior * grasp_axis in row 2 does not depend on the pose: set here, once; the launch
-            # of every evaluation adds to wrench / gRt and is given no g_R
-            self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._axis), device=self.dev)
-        self.squeeze_theta, self._g_R_const = None, self.g_R
-        if self.squeeze_mode:
-            self._i_squeeze = self.term_names.index("E_squeeze")
-            self.squeeze_min_travel, self.squeeze_damping = float(squeeze_min_travel), float(squeeze_damping)
-            self.squeeze_theta = f(B, self.J)
-            # the g_R the FK backward reads in this mode: written by every evaluation (E_prior's constant + this term's part)
-            self.g_R = f(B, 9)
-        self.arm, self.arm_base, self.reach_q, self.reach_seed = None, None, None, None
-        if self.reach_mode:
-            self._i_reach = self.term_names.index("E_reach")
-            self.arm = arm if isinstance(arm, ops.ArmHandle) else ops.ArmHandle(arm, self.dev)
-            self.arm_base = arm_base.to(self.dev)
-            self.reach_distance, self.reach_stations, self.reach_iterations = float(reach_distance), int(reach_stations), int(reach_iterations)
-            self.reach_damping, self.reach_rot_scale = float(reach_damping), float(reach_rot_scale)
-            self.reach_q = f(B, self.reach_stations + 1, self.arm.N)
-            self.reach_seed = torch.zeros(B, self.reach_stations + 1, dtype=torch.int32, device=self.dev)
-            self._reach_axis = (ctypes.c_float * 3)(*(float(a) for a in hand.spec.grasp_axis))
-        self.arm_scene = None
-        if self.arm_mode:
-            self._i_arm = self.term_names.index("E_arm")
-            self.arm_scene, self.arm_margin, self.arm_damping = arm_scene, float(arm_margin), float(arm_damping)
-            self._arm_grids = ops._arm_scene_grids(arm_scene, "GraspStepper")  # the stack view: a single grid is the stack of one
-        self.track_q, self.track_step, self.track_worst, self.track_station_q = None, None, None, None
-        if self.track_mode:
-            self._i_track = self.term_names.index("E_track")
-            self.track_waypoints, self.track_updates = int(track_waypoints), int(track_updates)
-            self.track_q = f(B, self.track_waypoints + 1, self.arm.N)
-            self.track_step, self.track_worst = f(B), f(B)
-            if self.arm_on_track:
-                self.track_station_q = f(B, self.reach_stations + 1, self.arm.N)
-        self.lift_scene, self.lift_object, self.lift_object_points = None, None, None
-        if self.lift_mode:
-            self._i_lift = self.term_names.index("E_lift")
-            self.lift_scene, self.lift_object_points, self.lift_object = lift_scene, lift_object_points, f(B)
-            self.lift_height, self.lift_retreat, self.lift_stations = float(lift_height), float(lift_retreat), int(lift_stations)
-            self.lift_margin, self.lift_object_margin = float(lift_margin), float(lift_object_margin)
-            self.lift_direction = tuple(lift_direction)
-            self._lift_u = ops._axis_c(lift_direction)
-            self._lift_grids = ops._pregrasp_grids(lift_scene.values, lift_scene.origin, lift_scene.voxel)  # a single grid: the stack of one
-            ops.lift_check(lift_scene, B, L, self.samples.Ns, self.n_obj, self.be, lift_object_points.shape[1], self.lift_height,
-                           self.lift_retreat, self.lift_stations, hand.spec.grasp_axis, lift_direction, self.lift_margin,
-                           self.lift_object_margin, "GraspStepper")
-            self._ptr.lift_points, self._ptr.lift_object = _C.f32(self.lift_object_points), _C.f32(self.lift_object)
+        on = [t for t in TERMS if getattr(self, t.flag)]
+        for t in on:
+            getattr(self, "_bind_" + t.key)(a)
+        self._launches = [getattr(self, "_launch_" + k) for k in plan.launch]
+        # the shares of the total after the FK backward, whose own total holds the five terms: total += w e in declaration order
+        # (the order decides the rounding of the fp32 total)
+        self._shares = []
+        for t in on:
+            pairs = [(_C.f32(self.terms_new[self._row[k]]), float(self.w[k])) for k in t.names]
+            for group in ([(p,) for p in pairs] if t.total == "gq_scene_total" else [pairs]):
+                self._shares.append((t.total, _C.f32(self.total_new), *(x for p in group for x in p), ctypes.c_int64(B)))
         self.init_feasible = torch.zeros(self.n_obj, dtype=torch.int32, device=self.dev)
         self._slot_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)
         m, pr = self.mala, _C.ProposeDesc()
@@ -601,10 +473,8 @@ class GraspStepper:
                                                                   int(m["annealing_period"]))
         ac.energy, ac.pose, ac.idx, ac.grad = (t.data_ptr() for t in (self.energy, self.hand_pose, self.contact_idx, self.grad))
         ac.accept, ac.temperature = self.accept.data_ptr(), self.temperature.data_ptr()
-        # the fused accept tail merges the five terms of the FK backward's own total; tabletop, scene, approach, pre-grasp, squeeze,
-        # reach (with arm and track, which need it) and lift mode (six to fifteen terms) never take the fused loop (_fuse_loop above)
-        # and merge their terms in the stand-alone accept launch
-        assert self._fuse_loop == (nT == len(TERM_NAMES))
+        # the fused accept tail merges the five terms of the FK backward's own total; with an optional term on (six to fifteen
+        # terms) the stepper never takes the fused loop (_fuse_loop above) and merges its terms in the stand-alone accept launch
         ac.n_terms, ac.terms_new, ac.terms = len(TERM_NAMES), self.terms_new.data_ptr(), self.terms.data_ptr()
         ac.slot_ctr, ac.slots = self._slot_ctr.data_ptr(), 64
         self._propose_desc, self._accept_desc = pr, ac
@@ -682,76 +552,284 @@ class GraspStepper:
                 _C.f32(self.pen_dis), float(self.w["E_pen"]), _C.f32(self.terms_new[2]), _C.ptr(self._span),
                 _C.ptr(self._span_acc), st)
 
-    def _eval_tabletop(self, pose, st):
+    # ---- the optional terms (module table TERMS): per key a check (host only: the constructor's arguments ``a``, fall-backs filled
+    # in, errors raised; called whether the term is ``on`` or not), a bind (buffers, public attributes, pointers converted once, the
+    # grid struct; only when on) and a launch (pose, idx, st) -------------------------------------------------------------------
+    def term_row(self, name):
+        """The row of ``terms`` / ``terms_new`` that holds the term ``name``; KeyError when it is switched off."""
+        return self._row[name]
+
+    def _zeros(self, *shape):
+        return torch.zeros(*shape, device=self.dev)
+
+    def _check_n_grids(self, name, scene):
+        if isinstance(scene, ops.SceneSDFSet) and scene.n_grids != self.n_obj:
+            raise ValueError(f"GraspStepper: {name} has n_grids = {scene.n_grids}, the stepper has n_obj = {self.n_obj} objects")
+
+    def _scene_arg(self, term, name, given, fallback=None):
+        """The grid that ``term`` reads: its argument ``name``, or ``fallback`` (the argument ``scene``) where that is None -- an
+        ops.SceneSDF, or an ops.SceneSDFSet with one grid per object (of ``scene`` itself the clutter rule of _check_scene asks that)."""
+        scene = fallback if given is None else given
+        if not isinstance(scene, (ops.SceneSDF, ops.SceneSDFSet)):
+            arg = "scene=" if name == "scene" else f"{name}= or scene="
+            raise ValueError(f'GraspStepper: weights["{term}"] > 0 needs {arg}ops.SceneSDF(...) or ops.SceneSDFSet(...)')
+        if name != "scene":
+            self._check_n_grids(name, scene)
+        return scene
+
+    def _bind_scene_arg(self, a):
+        """What scene and approach share: the public ``scene`` / ``scene_margin`` and the grid struct of both launches, the stack
+        (clutter) or the one grid."""
+        self.scene, self.scene_margin = a.scene, float(a.scene_margin)
+        self._scene_grid = a.scene.grid_set if self.clutter else a.scene.grid
+
+    def _check_tabletop(self, a, on):
+        pass
+
+    def _bind_tabletop(self, a):
+        self.g_R = self._zeros(self.B, 9)
+        self.table_z = float(a.table_z)
+        # d (w_prior E_prior) / d R = w_prior * grasp_axis in row 2 does not depend on the pose: set here, once; the launch
+        # of every evaluation adds to wrench / gRt and is given no g_R
+        self.g_R[:, 6:9] = float(self.w["E_prior"]) * torch.tensor(list(self._axis), device=self.dev)
+
+    def _launch_tabletop(self, pose, idx, st):
         """E_prior / E_wall -> terms_new[5:7]; the gradient of w_wall E_wall is added to the penetration branch's link
         wrenches and gRt (inputs of the FK backward, like the constant g_R of w_prior E_prior)."""
         p = self._ptr
         ops._tabletop_call(pose, self.samples.points, p.link, self.L, p.Rg, p.LT, self._axis, self.table_z, None, self.w["E_wall"],
-                           None, self.w["E_prior"], p.e[6], p.e[5], 1, p.wrench, p.gRt, None, st)
+                           None, self.w["E_prior"], p.e[self._row["E_wall"]], p.e[self._row["E_prior"]], 1, p.wrench, p.gRt, None, st)
 
-    def _eval_scene(self, pose, st):
-        """E_scene -> terms_new[-1]; the gradient of w_scene E_scene is added to the link wrenches and gRt that the FK
+    def _check_scene(self, a, on):
+        if on:
+            self._scene_arg("E_scene", "scene", a.scene)
+        # two rules of the argument that scene and approach share, whichever of them is on.  scene_margin is the fall-back of
+        # every grid term's margin; clutter: one grid per object, the two launches pick the grid from the row (row // batch_each)
+        if not float(a.scene_margin) >= 0.0:
+            raise ValueError(f"GraspStepper: scene_margin = {a.scene_margin!r} must be >= 0")
+        self.clutter = (on or self.approach_mode) and isinstance(a.scene, ops.SceneSDFSet)
+        if self.clutter:
+            self._check_n_grids("scene", a.scene)
+
+    def _bind_scene(self, a):
+        self._bind_scene_arg(a)
+        B, L, Ns = self.B, self.L, self.samples.Ns
+        a.scene.check(B, self.be, L, Ns) if self.clutter else a.scene.check(B, L, Ns)
+
+    def _launch_scene(self, pose, idx, st):
+        """E_scene -> its row of terms_new; the gradient of w_scene E_scene is added to the link wrenches and gRt that the FK
         backward reads."""
         p = self._ptr
         ops._scene_call(self._scene_grid, self.scene_margin, pose, self.samples.points, p.link, self.L, p.Rg, p.LT, None,
-                        self.w["E_scene"], p.e[self._i_scene], 1, p.wrench, p.gRt, st)
+                        self.w["E_scene"], p.e[self._row["E_scene"]], 1, p.wrench, p.gRt, st)
 
-    def _eval_approach(self, pose, st):
-        """E_approach -> terms_new[-1]; the gradient of w_approach E_approach is added to the link wrenches and gRt that the
+    def _check_approach(self, a, on):
+        if on:
+            self._scene_arg("E_approach", "scene", a.scene)
+            a.approach_margin = a.scene_margin if a.approach_margin is None else a.approach_margin
+            _check_corridor("approach", a.approach_margin, a.approach_distance, a.approach_stations, 1)
+
+    def _bind_approach(self, a):
+        self._bind_scene_arg(a)
+        self.approach_distance, self.approach_stations = float(a.approach_distance), int(a.approach_stations)
+        self.approach_margin = float(a.approach_margin)
+        ops.approach_check(a.scene, self.B, self.L, self.samples.Ns, self.approach_distance, self.approach_stations,
+                           self.hand.spec.grasp_axis)
+
+    def _launch_approach(self, pose, idx, st):
+        """E_approach -> its row of terms_new; the gradient of w_approach E_approach is added to the link wrenches and gRt that the
         FK backward reads."""
         p = self._ptr
         ops._approach_call(self._scene_grid, self.approach_margin, self.approach_distance, self.approach_stations, pose,
                            self.samples.points, p.link, self.L, p.Rg, p.LT, self._axis, None, self.w["E_approach"],
-                           p.e[self._i_approach], 1, p.wrench, p.gRt, st)
+                           p.e[self._row["E_approach"]], 1, p.wrench, p.gRt, st)
 
-    def _eval_pregrasp(self, pose, st):
-        """E_pregrasp -> terms_new[-1]; the root-pose part of the gradient of w_pregrasp E_pregrasp is added to the gRt that the
+    def _check_pregrasp(self, a, on):
+        if on:
+            a.pregrasp_scene = self._scene_arg("E_pregrasp", "pregrasp_scene", a.pregrasp_scene, a.scene)
+            a.pregrasp_margin = a.scene_margin if a.pregrasp_margin is None else a.pregrasp_margin
+            a.pregrasp_distance = a.approach_distance if a.pregrasp_distance is None else a.pregrasp_distance
+            a.pregrasp_stations = a.approach_stations if a.pregrasp_stations is None else a.pregrasp_stations
+            _check_corridor("pregrasp", a.pregrasp_margin, a.pregrasp_distance, a.pregrasp_stations, 0)
+            if not 0.0 <= float(a.pregrasp_opening) <= 1.0:
+                raise ValueError(f"GraspStepper: pregrasp_opening = {a.pregrasp_opening!r} must be in [0, 1]")
+
+    def _bind_pregrasp(self, a):
+        self.pregrasp_scene = a.pregrasp_scene
+        self.pregrasp_distance, self.pregrasp_stations = float(a.pregrasp_distance), int(a.pregrasp_stations)
+        self.pregrasp_margin, self.pregrasp_opening = float(a.pregrasp_margin), float(a.pregrasp_opening)
+        if a.pregrasp_joints is None:
+            self.pregrasp_joints = ops.default_open_joints(self.hand.spec, self.dev)
+        else:
+            self.pregrasp_joints = torch.as_tensor(a.pregrasp_joints, dtype=torch.float32).detach().to(self.dev).contiguous()
+        if self.pregrasp_joints.shape != (self.J,):
+            raise ValueError(f"GraspStepper: pregrasp_joints must be ({self.J},), got {tuple(self.pregrasp_joints.shape)}")
+        ops.pregrasp_check(a.pregrasp_scene, self.B, self.L, self.samples.Ns, self.pregrasp_distance, self.pregrasp_stations,
+                           self.hand.spec.grasp_axis, self.pregrasp_opening)
+        self._ptr.joints = _C.f32(self.pregrasp_joints)
+        # the stack view of the grid (a single grid is the stack of one): row b reads grid b // (B / n_grids)
+        self._pregrasp_grids = ops._pregrasp_grids(a.pregrasp_scene.values, a.pregrasp_scene.origin, a.pregrasp_scene.voxel)
+
+    def _launch_pregrasp(self, pose, idx, st):
+        """E_pregrasp -> its row of terms_new; the root-pose part of the gradient of w_pregrasp E_pregrasp is added to the gRt that the
         FK backward reads (the opened hand shares the closed hand's root pose), the joint part overwrites ``g_theta``."""
         p = self._ptr
         ops._pregrasp_call(self.hand, self._pregrasp_grids, self.pregrasp_margin, self.pregrasp_distance, self.pregrasp_stations,
                            self.pregrasp_opening, p.joints, pose, self.samples.points, p.link, p.Rg, self._axis, None,
-                           self.w["E_pregrasp"], p.e[self._i_pregrasp], 1, p.g_theta, p.gRt, st)
+                           self.w["E_pregrasp"], p.e[self._row["E_pregrasp"]], 1, p.g_theta, p.gRt, st)
 
-    def _eval_squeeze(self, idx, st):
-        """E_squeeze -> terms_new[-1], the joint velocities -> ``squeeze_theta``; the gradient of w_squeeze E_squeeze is added to
+    def _check_squeeze(self, a, on):
+        if on:
+            ops.squeeze_check(a.hand, a.n_contact, a.squeeze_min_travel, a.squeeze_damping, "GraspStepper")
+
+    def _bind_squeeze(self, a):
+        self.squeeze_min_travel, self.squeeze_damping = float(a.squeeze_min_travel), float(a.squeeze_damping)
+        self.squeeze_theta = self._zeros(self.B, self.J)
+        # the g_R the FK backward reads in this mode: written by every evaluation (E_prior's constant + this term's part)
+        self._g_R_const, self.g_R = self.g_R, self._zeros(self.B, 9)
+
+    def _launch_squeeze(self, pose, idx, st):
+        """E_squeeze -> its row of terms_new, the joint velocities -> ``squeeze_theta``; the gradient of w_squeeze E_squeeze is added to
         ``g_cpts`` (the contact branch has written it), written to ``g_theta`` (added when the pre-grasp launch has written it) and
         written, on top of E_prior's constant, to the ``g_R`` the FK backward reads."""
         ops._squeeze_call(self.hand, idx, self.Rg, self.link_T, self.fk_ws, self.d2, self.obj_normal, self.closest, self.cpts,
-                          self.squeeze_min_travel, self.squeeze_damping, None, self.w["E_squeeze"], self.terms_new[self._i_squeeze],
+                          self.squeeze_min_travel, self.squeeze_damping, None, self.w["E_squeeze"], self.terms_new[self._row["E_squeeze"]],
                           self.squeeze_theta, 3 if self.pregrasp_mode else 1, self.g_theta, self.g_R, self._g_R_const, self.g_cpts, st)
 
-    def _eval_reach(self, pose, st):
-        """E_reach -> its row of terms_new (``_i_reach``), the winning arm configurations -> ``reach_q`` / ``reach_seed``; the gradient of w_reach E_reach
+    def _check_reach(self, a, on):
+        if on:
+            if not isinstance(a.arm, (ops.ArmSpec, ops.ArmHandle)):
+                raise ValueError('GraspStepper: weights["E_reach"] > 0 needs arm=ops.ArmSpec(...) or ops.ArmHandle(...)')
+            if a.arm_base is None:
+                raise ValueError('GraspStepper: weights["E_reach"] > 0 needs arm_base, (3,4) or (n_obj,3,4)')
+            ops.reach_check(a.arm, a.reach_distance, a.reach_stations, a.reach_iterations, a.reach_damping, a.reach_rot_scale,
+                            a.hand.spec.grasp_axis, "GraspStepper")
+            a.arm_base = ops.reach_base(a.arm_base, self.n_obj, "GraspStepper")
+
+    def _bind_reach(self, a):
+        self.arm = a.arm if isinstance(a.arm, ops.ArmHandle) else ops.ArmHandle(a.arm, self.dev)
+        self.arm_base = a.arm_base.to(self.dev)
+        self.reach_distance, self.reach_stations, self.reach_iterations = float(a.reach_distance), int(a.reach_stations), int(a.reach_iterations)
+        self.reach_damping, self.reach_rot_scale = float(a.reach_damping), float(a.reach_rot_scale)
+        self.reach_q = self._zeros(self.B, self.reach_stations + 1, self.arm.N)
+        self.reach_seed = torch.zeros(self.B, self.reach_stations + 1, dtype=torch.int32, device=self.dev)
+        self._reach_axis = (ctypes.c_float * 3)(*(float(x) for x in self.hand.spec.grasp_axis))
+
+    def _launch_reach(self, pose, idx, st):
+        """E_reach -> its row of terms_new, the winning arm configurations -> ``reach_q`` / ``reach_seed``; the gradient of w_reach E_reach
         is ADDED to ``gRt`` (the penetration branch has written it).  g_R and g_theta are not touched."""
         ops._reach_call(self.arm, pose, self.Rg, self.arm_base, self.be, self._reach_axis, self.reach_distance, self.reach_stations,
                         self.reach_iterations, self.reach_damping, self.reach_rot_scale, None, self.w["E_reach"],
-                        self.terms_new[self._i_reach], self.reach_q, self.reach_seed, 1, self.gRt, st)
+                        self.terms_new[self._row["E_reach"]], self.reach_q, self.reach_seed, 1, self.gRt, st)
 
-    def _eval_arm(self, pose, st):
-        """E_arm -> its row of terms_new (``_i_arm``) from the ``reach_q`` the reach launch of this evaluation has just written; the
-        gradient of w_arm E_arm is ADDED to ``gRt``.  g_R and g_theta are not touched."""
+    def _check_arm(self, a, on):
+        if on:
+            if not self.reach_mode:
+                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs weights["E_reach"] > 0: the term reads the reach term\'s reach_q')
+            if not (a.arm.spec if isinstance(a.arm, ops.ArmHandle) else a.arm).n_spheres:
+                raise ValueError('GraspStepper: weights["E_arm"] > 0 needs an arm with collision spheres (ArmSpec.with_spheres / '
+                                 'with_link_spheres)')
+            a.arm_scene = self._scene_arg("E_arm", "arm_scene", a.arm_scene, a.scene)
+            a.arm_margin = a.scene_margin if a.arm_margin is None else a.arm_margin
+            ops.arm_check(a.arm, ops._arm_scene_grids(a.arm_scene, "GraspStepper"), self.B, a.arm_margin, a.arm_damping, a.reach_rot_scale,
+                          a.reach_distance, a.reach_stations, a.hand.spec.grasp_axis, "GraspStepper")
+
+    def _bind_arm(self, a):
+        self.arm_scene, self.arm_margin, self.arm_damping = a.arm_scene, float(a.arm_margin), float(a.arm_damping)
+        self._arm_grids = ops._arm_scene_grids(a.arm_scene, "GraspStepper")  # the stack view: a single grid is the stack of one
+
+    def _launch_arm(self, pose, idx, st):
+        """E_arm -> its row of terms_new from the ``reach_q`` the reach launch of this evaluation has just written (``track_station_q``
+        of the track launch with ``arm_on_track``); the gradient of w_arm E_arm is ADDED to ``gRt``.  g_R and g_theta are not touched."""
         ops._arm_call(self.arm, self._arm_grids, self.arm_margin, self.arm_damping, self.reach_rot_scale, pose, self.Rg, self.arm_base,
                       self.be, self._reach_axis, self.reach_distance, self.reach_stations,
                       self.track_station_q if self.arm_on_track else self.reach_q, None, self.w["E_arm"],
-                      self.terms_new[self._i_arm], 1, self.gRt, st)
+                      self.terms_new[self._row["E_arm"]], 1, self.gRt, st)
 
-    def _eval_track(self, pose, st):
-        """E_track -> its row of terms_new (``_i_track``) from the start configuration ``reach_q[:, K]`` the reach launch of this
+    def _check_track(self, a, on):
+        if on:
+            if not self.reach_mode:
+                raise ValueError('GraspStepper: weights["E_track"] > 0 needs weights["E_reach"] > 0: the path starts at the reach term\'s '
+                                 'reach_q[:, reach_stations]')
+            if int(a.reach_stations) < 1:
+                raise ValueError('GraspStepper: weights["E_track"] > 0 needs reach_stations >= 1: the path starts at the retreated station')
+            ops.track_check(a.arm, a.reach_distance, a.track_waypoints, a.track_updates, a.reach_damping, a.reach_rot_scale,
+                            a.hand.spec.grasp_axis, a.reach_stations, False, "GraspStepper")
+        self.arm_on_track = bool(a.arm_on_track)  # the switch between arm and track: checked with the later of the two
+        if self.arm_on_track:
+            if not (on and self.arm_mode):
+                raise ValueError('GraspStepper: arm_on_track=True needs weights["E_track"] > 0 and weights["E_arm"] > 0')
+            if int(a.track_waypoints) % int(a.reach_stations):
+                raise ValueError(f"GraspStepper: arm_on_track=True needs reach_stations = {a.reach_stations} to divide track_waypoints = "
+                                 f"{a.track_waypoints}")
+
+    def _bind_track(self, a):
+        self.track_waypoints, self.track_updates = int(a.track_waypoints), int(a.track_updates)
+        self.track_q = self._zeros(self.B, self.track_waypoints + 1, self.arm.N)
+        self.track_step, self.track_worst = self._zeros(self.B), self._zeros(self.B)
+        if self.arm_on_track:
+            self.track_station_q = self._zeros(self.B, self.reach_stations + 1, self.arm.N)
+
+    def _launch_track(self, pose, idx, st):
+        """E_track -> its row of terms_new from the start configuration ``reach_q[:, K]`` the reach launch of this
         evaluation has just written (a view: pointer and row stride, no copy); the path -> ``track_q``, ``track_step``,
         ``track_worst`` (and ``track_station_q`` for ``arm_on_track``); the gradient of w_track E_track is ADDED to ``gRt``.  g_R and
         g_theta are not touched."""
         ops._track_call(self.arm, pose, self.Rg, self.arm_base, self.be, self._reach_axis, self.reach_distance, self.track_waypoints,
                         self.track_updates, self.reach_damping, self.reach_rot_scale, self.reach_q[:, self.reach_stations],
-                        self.reach_stations, None, self.w["E_track"], self.terms_new[self._i_track], self.track_q, self.track_worst,
+                        self.reach_stations, None, self.w["E_track"], self.terms_new[self._row["E_track"]], self.track_q, self.track_worst,
                         self.track_step, self.track_station_q, 1, self.gRt, st)
 
-    def _eval_lift(self, pose, st):
-        """E_lift -> its row of terms_new (``_i_lift``), the object's share -> ``lift_object``; the gradient of w_lift E_lift is added
+    def _check_lift(self, a, on):
+        if not on:
+            return
+        a.lift_scene = self._scene_arg("E_lift", "lift_scene", a.lift_scene, a.scene)
+        a.lift_margin = a.scene_margin if a.lift_margin is None else a.lift_margin
+        pts = a.lift_object_points
+        if pts is None:
+            if int(a.lift_object_samples) != a.lift_object_samples or int(a.lift_object_samples) < 0:
+                raise ValueError(f"GraspStepper: lift_object_samples = {a.lift_object_samples!r} must be an integer >= 0")
+            M = min(int(a.lift_object_samples), self.P)
+            pick = (torch.arange(M, device=self.dev) * self.P) // max(M, 1)  # floor(j P / M)
+            pts = self.surf[:, pick]
+        a.lift_object_points = pts = torch.as_tensor(pts, dtype=torch.float32).detach().to(self.dev).contiguous()
+        if pts.dim() != 3 or pts.shape[0] != self.n_obj or pts.shape[2] != 3:
+            raise ValueError(f"GraspStepper: lift_object_points must be ({self.n_obj}, M, 3), got {tuple(pts.shape)}")
+        try:
+            a.lift_direction = ops.lift_direction(a.lift_direction)
+        except ValueError:
+            raise ValueError(f"GraspStepper: lift_direction = {a.lift_direction!r} must be three finite numbers, not all zero") from None
+        for name in ("lift_height", "lift_retreat"):
+            if not 0.0 <= float(getattr(a, name)) < float("inf"):
+                raise ValueError(f"GraspStepper: {name} = {getattr(a, name)!r} must be finite and >= 0")
+        if not float(a.lift_height) + float(a.lift_retreat) > 0.0:
+            raise ValueError("GraspStepper: lift_height and lift_retreat must not both be zero")
+        if int(a.lift_stations) != a.lift_stations or not 1 <= int(a.lift_stations) <= 32:
+            raise ValueError(f"GraspStepper: lift_stations = {a.lift_stations!r} must be an integer in 1..32")
+        if not 0.0 <= float(a.lift_margin) < float("inf"):
+            raise ValueError(f"GraspStepper: lift_margin = {a.lift_margin!r} must be finite and >= 0")
+        if not abs(float(a.lift_object_margin)) < float("inf"):
+            raise ValueError(f"GraspStepper: lift_object_margin = {a.lift_object_margin!r} must be finite")
+
+    def _bind_lift(self, a):
+        self.lift_scene, self.lift_object_points, self.lift_object = a.lift_scene, a.lift_object_points, self._zeros(self.B)
+        self.lift_height, self.lift_retreat, self.lift_stations = float(a.lift_height), float(a.lift_retreat), int(a.lift_stations)
+        self.lift_margin, self.lift_object_margin = float(a.lift_margin), float(a.lift_object_margin)
+        self.lift_direction = tuple(a.lift_direction)
+        self._lift_u = ops._axis_c(a.lift_direction)
+        self._lift_grids = ops._pregrasp_grids(a.lift_scene.values, a.lift_scene.origin, a.lift_scene.voxel)  # a single grid: the stack of one
+        ops.lift_check(a.lift_scene, self.B, self.L, self.samples.Ns, self.n_obj, self.be, a.lift_object_points.shape[1], self.lift_height,
+                       self.lift_retreat, self.lift_stations, self.hand.spec.grasp_axis, a.lift_direction, self.lift_margin,
+                       self.lift_object_margin, "GraspStepper")
+        self._ptr.lift_points, self._ptr.lift_object = _C.f32(self.lift_object_points), _C.f32(self.lift_object)
+
+    def _launch_lift(self, pose, idx, st):
+        """E_lift -> its row of terms_new, the object's share -> ``lift_object``; the gradient of w_lift E_lift is added
         to the link wrenches and gRt that the FK backward reads.  g_R and g_theta are not touched."""
         p = self._ptr
         ops._lift_call(self._lift_grids, self.lift_margin, self.lift_object_margin, self.lift_height, self.lift_retreat, self.lift_stations,
                        pose, self.samples.points, p.link, self.L, p.Rg, p.LT, p.lift_points, self.n_obj, self.be,
-                       self.lift_object_points.shape[1], self._axis, self._lift_u, None, self.w["E_lift"], p.e[self._i_lift],
+                       self.lift_object_points.shape[1], self._axis, self._lift_u, None, self.w["E_lift"], p.e[self._row["E_lift"]],
                        p.lift_object, 1, p.wrench, p.gRt, st)
 
     def _eval_tail(self, pose, idx, st, loop=False):
@@ -759,7 +837,7 @@ class GraspStepper:
         f32 = _C.f32
         _C.call("gq_fk_backward", self.hand.handle, f32(pose), _C.i64(idx), B, n, f32(self.Rg), f32(self.link_T),
                 f32(self.g_cpts), f32(self.g_cnrm), f32(self.g_sph_w) if self.S > 0 else None, f32(self.wrench),
-                f32(self.gRt), f32(self.g_theta) if self.pregrasp_mode or self.squeeze_mode else None, f32(self.g_R), f32(self.grad_new),
+                f32(self.gRt), f32(self.g_theta) if self._plan.g_theta else None, f32(self.g_R), f32(self.grad_new),
                 ctypes.byref(self._row_energy),
                 ctypes.byref(self._accept_desc) if loop else None, _C.ptr(self.fk_ws), self.fk_nb, st)
 
@@ -798,41 +876,11 @@ class GraspStepper:
                 self._eval_spen(pose, ctypes.c_void_p(sb.cuda_stream))
             self._eval_pen(pose, ctypes.c_void_p(sb.cuda_stream), timer)
             main.wait_stream(sb)
-        if self.tabletop:
-            self._eval_tabletop(pose, st)
-        for _, _, evaluate in self._obstacle_terms:  # scene, approach, pre-grasp
-            evaluate(pose, st)
-        if self.lift_mode:  # with the other hand-surface launches: it adds to the link wrenches and gRt
-            self._eval_lift(pose, st)
-        if self.squeeze_mode:
-            self._eval_squeeze(idx, st)
-        if self.reach_mode:
-            self._eval_reach(pose, st)
-        if self.track_mode:  # right after the reach launch (it starts at reach_q[:, K]); before the arm launch, which may read its stations
-            self._eval_track(pose, st)
-        if self.arm_mode:  # after the reach launch (it reads reach_q), before the FK backward (it adds to gRt)
-            self._eval_arm(pose, st)
+        for launch in self._launches:  # the optional terms that are on, in launch order: they add to what the FK backward reads
+            launch(pose, idx, st)
         self._eval_tail(pose, idx, st, loop)
-        if self.tabletop:  # the FK backward's total holds the five terms
-            _C.call("gq_tabletop_total", _C.f32(self.total_new), _C.f32(self.terms_new[5]), float(self.w["E_prior"]),
-                    _C.f32(self.terms_new[6]), float(self.w["E_wall"]), ctypes.c_int64(self.B), st)
-        for i, w, _ in self._obstacle_terms:  # the generic total += w e
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[i]), w, ctypes.c_int64(self.B), st)
-        if self.squeeze_mode:
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_squeeze]), float(self.w["E_squeeze"]),
-                    ctypes.c_int64(self.B), st)
-        if self.reach_mode:
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_reach]), float(self.w["E_reach"]),
-                    ctypes.c_int64(self.B), st)
-        if self.arm_mode:
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_arm]), float(self.w["E_arm"]),
-                    ctypes.c_int64(self.B), st)
-        if self.track_mode:
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_track]), float(self.w["E_track"]),
-                    ctypes.c_int64(self.B), st)
-        if self.lift_mode:
-            _C.call("gq_scene_total", _C.f32(self.total_new), _C.f32(self.terms_new[self._i_lift]), float(self.w["E_lift"]),
-                    ctypes.c_int64(self.B), st)
+        for args in self._shares:  # the FK backward's total holds the five terms: total += w e, in declaration order
+            _C.call(*args, st)
 
     def evaluate(self, pose, idx):
         """Energy terms, total and d total / d pose at an arbitrary (pose, idx); returns clones."""

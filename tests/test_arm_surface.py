@@ -98,8 +98,8 @@ def test_weights_term_order_and_select_tolerances():
     for bad in (-1.0, float("nan")):
         with pytest.raises(ValueError, match="E_arm"):
             S.merge_weights({"E_arm": bad})
-    src = inspect.getsource(S.GraspStepper.__init__)
-    assert src.index("REACH_TERMS if self.reach_mode") < src.index("ARM_TERMS if self.arm_mode")  # appended after the reach term
+    plan = S.term_plan({"E_scene": 1.0, "E_approach": 1.0, "E_pregrasp": 1.0, "E_reach": 1.0, "E_arm": 1.0})
+    assert plan.term_names.index("E_reach") < plan.term_names.index("E_arm")  # appended after the reach term
     inf = float("inf")
     on = S.TERM_NAMES + S.SCENE_TERMS + S.REACH_TERMS + S.ARM_TERMS
     assert S.select_tolerances(on) == [inf] * 5 + [0.0, inf, 0.0]  # gated at 0 by default, like the other obstacle terms
@@ -109,9 +109,9 @@ def test_weights_term_order_and_select_tolerances():
     with pytest.raises(ValueError, match="E_arm"):
         S.select_tolerances(off, {"E_arm": 0.0})
     # the launch sits right after the reach launch and before the FK backward, not among the obstacle terms (they run before it)
-    ev = inspect.getsource(S.GraspStepper._evaluate)
-    assert ev.index("for _, _, evaluate in self._obstacle_terms") < ev.index("self._eval_reach(") < ev.index("self._eval_arm(") < \
-        ev.index("self._eval_tail(")
+    # (the launch keys are followed by the FK backward: tests/test_gpu_stepper_terms.py)
+    at = plan.launch.index
+    assert max(at("scene"), at("approach"), at("pregrasp")) < at("reach") < at("arm") and plan.launch[-1] == "arm"
     assert "E_arm" not in S.OBSTACLE_TERMS
 
 
@@ -125,17 +125,9 @@ def test_stepper_arguments_and_errors():
     assert (p["arm_scene"].default, p["arm_margin"].default, p["arm_damping"].default, p["reach_damping"].default) == (None, None, 1e-6, 1e-4)
     p = inspect.signature(HandModel.set_arm_scene).parameters
     assert (p["scene"].default, p["margin"].default, p["damping"].default) == (None, None, 1e-6)
-    # the errors come before the stepper touches the device: a stand-in hand and object set are enough to get there
-    src = inspect.getsource(GraspStepper.__init__)
-    i = src.index('self.arm_mode = self.w["E_arm"] > 0')
-    assert src.index("ops.reach_base(") < i < src.index("self.gen = torch.Generator")
-    block = src[i:src.index("self.init_avoid_scene = bool(")]
-    assert block.index('needs weights["E_reach"] > 0') < block.index("collision spheres") < block.index("needs arm_scene= or scene=") < \
-        block.index("ops.arm_check(")
-    assert "arm_scene = scene if arm_scene is None else arm_scene" in block and "arm_margin = scene_margin if arm_margin is None" in block
-    assert "arm_scene.n_grids != self.n_obj" in block
-    # the same through the constructor: the argument checks come before the stepper touches the device, so stand-ins for the hand
-    # and the object set are enough to reach them
+    # the argument checks come before the stepper touches the device, so stand-ins for the hand and the object set are enough to
+    # reach them; no call below has a scene, so each is wrong in a later way too: reach first, then the spheres, then the scene (what
+    # follows the scene -- the fall-backs of arm_scene and arm_margin, n_grids, arm_check -- needs a grid: tests/test_gpu_arm.py)
     hand = type("H", (), {"spec": get_hand_spec("allegro"), "L": 1, "J": 16, "S": 0})()
     objs = type("M", (), {"n_mesh": 1})()
     make = lambda **kw: GraspStepper(hand, objs, torch.zeros(1, 8, 3), 4, 4, device="cpu", **kw)

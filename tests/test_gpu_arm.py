@@ -253,6 +253,24 @@ def test_evaluate_adds_the_weighted_oracle_term(gq, mode):
     assert (err[nz] <= 1e-3 * gn[nz] + noise[nz]).all()
 
 
+def test_stepper_fall_backs_and_what_follows_the_scene_check(gq):
+    """arm_scene=None takes ``scene`` and arm_margin=None takes ``scene_margin``; after the scene argument come n_grids and
+    ops.arm_check (the checks before it need no grid: tests/test_arm_surface.py)."""
+    cs = _case(gq, "elbow6")
+    kw = {k: v for k, v in _kw(gq, cs).items() if not k.startswith("arm_s") and k != "arm_margin"}
+    w = {"E_reach": W_REACH, "E_arm": W_ARM}
+    scene, other = cs["field"].scene(gq), _small_scene(gq)
+    st = _stepper(gq, weights=w, scene=scene, arm_scene=None, scene_margin=0.03, arm_margin=0.01, **kw)
+    assert st.arm_scene is scene and st.arm_margin == 0.01 and st.scene is None  # ``scene`` itself belongs to E_scene / E_approach
+    st = _stepper(gq, weights=w, scene=scene, arm_scene=other, scene_margin=0.03, arm_margin=None, **kw)
+    assert st.arm_scene is other and st.arm_margin == 0.03
+    three = gq.ops.SceneSDFSet(torch.stack([cs["field"].values] * 3).cuda(), [float(o) for o in cs["field"].origin], float(cs["field"].voxel))
+    with pytest.raises(ValueError, match="arm_scene has n_grids = 3, the stepper has n_obj = 2 objects"):
+        _stepper(gq, weights=w, arm_scene=three, arm_margin=-1.0, **kw)  # the margin is wrong too: n_grids comes first
+    with pytest.raises(ValueError, match="margin"):
+        _stepper(gq, weights=w, arm_scene=scene, arm_margin=-1.0, **kw)
+
+
 def _draws(st, seed):
     g = torch.Generator(device="cuda").manual_seed(seed)
     return (torch.rand(st.B, st.n, device="cuda", generator=g),

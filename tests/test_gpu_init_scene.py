@@ -205,7 +205,7 @@ def test_scores_are_the_steppers_terms_bit_for_bit(gq, hand_name, stack):
     st.reset(pose, idx)
     sel = info["sel"].long()
     es, ea = info["e_scene"].gather(1, sel).reshape(-1), info["e_approach"].gather(1, sel).reshape(-1)
-    assert torch.equal(st.terms[st._i_scene], es) and torch.equal(st.terms[st._i_approach], ea)
+    assert torch.equal(st.terms[st.term_row("E_scene")], es) and torch.equal(st.terms[st.term_row("E_approach")], ea)
     assert float(info["e_scene"].max()) > 0 and float(info["e_approach"].max()) > 0  # the walls are met
     pen = w["E_scene"] * info["e_scene"].double() + w["E_approach"] * info["e_approach"].double()
     assert torch.equal(info["penalty"] <= 0, pen <= 0) and torch.allclose(info["penalty"].double(), pen, rtol=1e-6, atol=0)
@@ -296,7 +296,7 @@ def test_stepper_initialises_and_resets_outside_the_obstacles(gq):
         assert st.init_feasible.dtype == torch.int32 and st.init_feasible.shape == (N_OBJ,) and st.init_feasible.is_cuda
         ok = (st.init_feasible >= BE).repeat_interleave(BE)
         assert ok.all(), "1600 candidates per object: every object has enough collision-free ones"
-        assert float(st.terms[st._i_scene][ok].abs().max()) == 0.0 and float(st.terms[st._i_approach][ok].abs().max()) == 0.0
+        assert float(st.terms[st.term_row("E_scene")][ok].abs().max()) == 0.0 and float(st.terms[st.term_row("E_approach")][ok].abs().max()) == 0.0
         seen = {}
 
         def at(step):
@@ -310,7 +310,7 @@ def test_stepper_initialises_and_resets_outside_the_obstacles(gq):
         assert torch.isfinite(st.energy).all() and torch.isfinite(st.hand_pose).all() and torch.isfinite(st.terms).all()
         m = seen["mask"] & seen["ok"]
         assert int(m.sum()) > 0, "the schedule must actually reset rows"
-        assert float(seen["terms"][st._i_scene][m].abs().max()) == 0.0 and float(seen["terms"][st._i_approach][m].abs().max()) == 0.0
+        assert float(seen["terms"][st.term_row("E_scene")][m].abs().max()) == 0.0 and float(seen["terms"][st.term_row("E_approach")][m].abs().max()) == 0.0
         outs.append((st.hand_pose.clone(), st.energy.clone(), st.contact_idx.clone(), st.init_feasible.clone(), seen["mask"]))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
@@ -334,7 +334,7 @@ def test_stepper_without_the_switch_is_the_parent_route(gq):
     # the approach term alone is enough
     st = _stepper(gq, hand, raw, scene, {"E_approach": 20.0}, init_avoid_scene=True)
     st.initialize()
-    assert (st.init_feasible >= BE).all() and float(st.terms[st._i_approach].abs().max()) == 0.0
+    assert (st.init_feasible >= BE).all() and float(st.terms[st.term_row("E_approach")].abs().max()) == 0.0
 
 
 # ---- the class surface -------------------------------------------------------------------------------------------------

@@ -34,8 +34,8 @@ def test_term_names_order_and_select_tolerances():
     """E_reach is appended last, after E_squeeze; not gated by default (it is no obstacle term)."""
     from graspqp_amd import stepper as S
 
-    src = inspect.getsource(S.GraspStepper.__init__)
-    assert src.index("SQUEEZE_TERMS if self.squeeze_mode") < src.index("REACH_TERMS if self.reach_mode")
+    plan = S.term_plan({"E_squeeze": 1.0, "E_reach": 1.0})
+    assert plan.term_names.index("E_squeeze") < plan.term_names.index("E_reach")
     names = S.TERM_NAMES + S.SCENE_TERMS + S.SQUEEZE_TERMS + S.REACH_TERMS
     inf = float("inf")
     assert S.select_tolerances(names) == [inf] * 5 + [0.0, inf, inf]
@@ -44,9 +44,9 @@ def test_term_names_order_and_select_tolerances():
         S.select_tolerances(S.TERM_NAMES, {"E_reach": 1e-6})  # a gate on the switched-off term
     assert "E_reach" not in S.OBSTACLE_TERMS
     # in reach mode the fused loop is off, and the launch sits between the squeeze launch and the FK backward
-    assert "or self.reach_mode" in src[src.index("self._fuse_loop ="):src.index("self._fuse_loop =") + 250]
-    ev = inspect.getsource(S.GraspStepper._evaluate)
-    assert ev.index("self._eval_squeeze(") < ev.index("self._eval_reach(") < ev.index("self._eval_tail(")
+    # (the launch keys are followed by the FK backward: tests/test_gpu_stepper_terms.py)
+    assert not S.term_plan({"E_reach": 1.0}).fuse_loop
+    assert plan.launch.index("squeeze") < plan.launch.index("reach") and plan.launch[-1] == "reach"
 
 
 def test_arm_spec_validation():
@@ -110,9 +110,19 @@ def test_reach_check_and_stepper_arguments():
         with pytest.raises(ValueError, match="arm_base"):
             ops.reach_base(b, n, "GraspStepper")
     # the stepper checks them only when the term is on, and before it touches the device
-    src = inspect.getsource(GraspStepper.__init__)
-    assert src.index("ops.reach_check(") < src.index("ops.reach_base(") < src.index("self.gen = torch.Generator")
-    assert 'needs arm=' in src and 'needs arm_base' in src
+    # the device: a stand-in hand and CPU tensors get as far as the checks -- the arm, the base, reach_check, then reach_base
+    import types
+
+    hand = types.SimpleNamespace(J=16, L=5, S=0, spec=types.SimpleNamespace(grasp_axis=(0.0, 0.0, 1.0)))
+    make = lambda **kw: GraspStepper(hand, None, torch.zeros(2, 8, 3), 4, 4, weights={"E_reach": 1.0}, device="cpu", **kw)
+    with pytest.raises(ValueError, match="needs arm="):
+        make(arm_base=np.eye(4)[:3], reach_stations=7)
+    with pytest.raises(ValueError, match="needs arm_base"):
+        make(arm=arm, reach_stations=7)
+    with pytest.raises(ValueError, match="GraspStepper: reach_stations"):
+        make(arm=arm, arm_base=np.zeros((3, 3)), reach_stations=7)  # the base is wrong too: reach_check comes first
+    with pytest.raises(ValueError, match="GraspStepper: arm_base"):
+        make(arm=arm, arm_base=np.zeros((3, 3, 4)))  # three bases for two objects
     with pytest.raises(RuntimeError, match="CUDA"):
         ops.reach_terms(torch.zeros(2, 25), None, torch.zeros(2, 4, dtype=torch.long), None, None, None, None, None, 1, (0, 0, 1))
 

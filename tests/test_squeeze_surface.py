@@ -34,8 +34,8 @@ def test_term_names_order_and_select_tolerances():
     """E_squeeze is appended last, after E_pregrasp (the stepper builds term_names in this order); not gated by default."""
     from graspqp_amd import stepper as S
 
-    src = inspect.getsource(S.GraspStepper.__init__)
-    assert src.index("PREGRASP_TERMS if self.pregrasp_mode") < src.index("SQUEEZE_TERMS if self.squeeze_mode")
+    on = S.term_plan({"E_pregrasp": 1.0, "E_squeeze": 1.0}).term_names
+    assert on.index("E_pregrasp") < on.index("E_squeeze")
     names = S.TERM_NAMES + S.SCENE_TERMS + S.PREGRASP_TERMS + S.SQUEEZE_TERMS
     inf = float("inf")
     assert S.select_tolerances(names) == [inf] * 5 + [0.0, 0.0, inf]
@@ -64,8 +64,17 @@ def test_parameters_are_validated():
         with pytest.raises(ValueError, match=word):
             ops.squeeze_check(None, 1, tau, lam, "GraspStepper")
     # the stepper checks them only when the term is on, and before it touches the device
-    src = inspect.getsource(GraspStepper.__init__)
-    assert src.index("ops.squeeze_check(") < src.index("self.gen = torch.Generator")
+    # the device: a stand-in hand and CPU tensors get as far as the check
+    from graspqp_amd.hands import get_hand_spec
+
+    hand = type("H", (), {"spec": get_hand_spec("allegro"), "L": 1, "J": 16, "S": 0})()
+    make = lambda **kw: GraspStepper(hand, None, torch.zeros(1, 8, 3), 4, 4, device="cpu", **kw)
+    with pytest.raises(ValueError, match="GraspStepper: squeeze_damping"):
+        make(weights={"E_squeeze": 1.0}, squeeze_damping=0.0)
+    with pytest.raises(ValueError, match="GraspStepper: squeeze_min_travel"):
+        make(weights={"E_squeeze": 1.0}, squeeze_min_travel=float("nan"))
+    with pytest.raises(ValueError, match="init_avoid_scene"):  # with the term off they are not read: a later wrong argument raises
+        make(weights={"E_squeeze": 0.0}, squeeze_damping=0.0, init_avoid_scene=True)
     with pytest.raises(RuntimeError, match="CUDA"):
         ops.squeeze_terms(torch.zeros(2, 25), None, torch.zeros(2, 4, dtype=torch.long), None, None, None, None, None, None, None)
 

@@ -97,9 +97,9 @@ for n_obj in args.n_objects:
     after = {}
     for name, st in (("unscreened", plain), ("screened", screened)):
         st.initialize()
-        e = st.terms[st._i_scene]
+        e = st.terms[st.term_row("E_scene")]
         after[name] = {"rows_with_E_scene_gt_0": float((e > 0).float().mean()), "E_scene_mean": float(e.mean()),
-                       "rows_with_E_approach_gt_0": float((st.terms[st._i_approach] > 0).float().mean())}
+                       "rows_with_E_approach_gt_0": float((st.terms[st.term_row("E_approach")] > 0).float().mean())}
     after["screened"]["init_feasible"] = screened.init_feasible.tolist()
     screened.capture()
     for _ in range(20):

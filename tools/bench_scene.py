@@ -138,11 +138,11 @@ def clutter_bench():
     ap_slice = lambda grid, p, R, T, ee, w6, g12: ops._approach_call(grid, args.scene_margin, args.approach_distance, K, p, sm.points,
                                                                      sm.link, st.L, R, T, spec.grasp_axis, None, args.w_approach,
                                                                      ee, 1, w6, g12)
-    rec["scene_launch"] = alternate({"gq_clutter_terms": lambda: st._eval_scene(pose, ptr()),
-                                     "gq_scene_terms": lambda: one._eval_scene(one.pose_new, ptr()),
+    rec["scene_launch"] = alternate({"gq_clutter_terms": lambda: st._launch_scene(pose, None, ptr()),
+                                     "gq_scene_terms": lambda: one._launch_scene(one.pose_new, None, ptr()),
                                      f"{G} row-slice gq_scene_terms": lambda: sliced(sc_slice)}, 200)
-    rec["corridor_launch"] = alternate({"gq_clutter_corridor_terms": lambda: st._eval_approach(pose, ptr()),
-                                        "gq_approach_terms": lambda: one._eval_approach(one.pose_new, ptr()),
+    rec["corridor_launch"] = alternate({"gq_clutter_corridor_terms": lambda: st._launch_approach(pose, None, ptr()),
+                                        "gq_approach_terms": lambda: one._launch_approach(one.pose_new, None, ptr()),
                                         f"{G} row-slice gq_approach_terms": lambda: sliced(ap_slice)}, 200)
     # compose: G targets around the object, G parts (the object's own grid, posed around the bin), the bin as the base
     pn = args.part_grid
@@ -245,7 +245,7 @@ with open(args.out, "a") as f:
         summ["E_scene_mean_final"] = float(st.terms[-1].mean())
         # the launch on its own, on the final state
         st.evaluate(st.hand_pose.clone(), st.contact_idx.clone())
-        summ["scene_launch_us"] = launch_us(lambda: st._eval_scene(st.pose_new, ops._C.stream_ptr()))
+        summ["scene_launch_us"] = launch_us(lambda: st._launch_scene(st.pose_new, None, ops._C.stream_ptr()))
     if "approach" in steppers:
         st = steppers["approach"]
         summ.update({"w_approach": args.w_approach, "approach_distance": args.approach_distance,
@@ -261,12 +261,12 @@ with open(args.out, "a") as f:
         if ref is not None:
             if ref is not st:
                 ref.evaluate(st.hand_pose.clone(), st.contact_idx.clone())
-            scene_us = launch_us(lambda: ref._eval_scene(ref.pose_new, ops._C.stream_ptr()))
+            scene_us = launch_us(lambda: ref._launch_scene(ref.pose_new, None, ops._C.stream_ptr()))
             summ["approach_launch"]["scene_launch_us_same_inputs"] = scene_us
         keep = st.approach_stations
         for K in (1, 4, 8):
             st.approach_stations = K
-            us = launch_us(lambda: st._eval_approach(st.pose_new, ops._C.stream_ptr()))
+            us = launch_us(lambda: st._launch_approach(st.pose_new, None, ops._C.stream_ptr()))
             summ["approach_launch"][f"K{K}"] = {"approach_launch_us": us,
                                                 "K_scene_launches_us": None if scene_us is None else K * scene_us}
         st.approach_stations = keep
