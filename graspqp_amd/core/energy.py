@@ -96,7 +96,7 @@ def calculate_energy(hand_model, object_model, energy_fnc=None, energy_names=[],
         (losses["E_dis"], losses["E_fc"], losses["E_joints"], losses["E_pen"], losses["E_spen"], distance, contact_normal,
          _lambda) = _FusedTerms.apply(hand_model.hand_pose, hand_model, object_model, energy_fnc.fc_config(svd_gain=svd_gain),
                                       method == "gendexgrasp")
-        return _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model)
+        return _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model, energy_fnc, svd_gain)
     distance, contact_normal = object_model.cal_distance(hand_model.contact_points)
     # (each term below is one launch that also writes its derivative, csrc/terms.hip: the torch expressions of the
     # reference, energy.py:25-28,47-52,58-61, cost a dozen launches each, forward and backward, in a host-bound loop)
@@ -118,10 +118,10 @@ def calculate_energy(hand_model, object_model, energy_fnc=None, energy_names=[],
     losses["E_pen"] = ops.energy_pen(distances)  # sum of where(distances <= 0, 0, distances)
     losses["E_spen"] = hand_model.self_penetration()
 
-    return _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model)
+    return _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model, energy_fnc, svd_gain)
 
 
-def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model=None):
+def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, object_model=None, energy_fnc=None, svd_gain=0.1):
     if "E_prior" in energy_names:  # energy.py:68-74: the grasp axis should point down
         forward_axis = (hand_model.global_rotation @ hand_model.grasp_axis.view(1, -1, 1)).view(-1, 3)
         axis_prior = torch.tensor([0, 0, -1], dtype=torch.float, device=forward_axis.device).view(1, 3)
@@ -186,6 +186,25 @@ def _extra_terms(losses, hand_model, energy_names, distance, contact_normal, obj
         losses["E_squeeze"] = ops.squeeze_terms(hand_model.hand_pose, hand_model._hand, hand_model._fk_idx, hand_model.global_rotation,
                                                 hand_model.current_status, hand_model._fk_ws, d2.reshape(B, n), onrm.reshape(B, n, 3),
                                                 cls.reshape(B, n, 3), cp, tau, lam)
+
+    if "E_hold" in energy_names:
+        # payload holding as ONE launch (ops.hold_terms; loads and force bound: HandModel.set_hold) on the contact query and the cone
+        # parameters of E_fc above; the gradient reaches the pose through the contact points
+        if getattr(hand_model, "hold", None) is None:
+            raise ValueError('calculate_energy: "E_hold" needs HandModel.set_hold(loads, max_force, ...)')
+        if not hasattr(energy_fnc, "fc_config"):
+            raise ValueError('calculate_energy: "E_hold" takes the cone parameters of the friction-cone span metric (GRASPQP)')
+        cfg = energy_fnc.fc_config(svd_gain=svd_gain)
+        lw, lw_dev, max_force, _lim, iters = hand_model.hold
+        cp = hand_model.contact_points
+        B, n, _ = cp.shape
+        be = object_model.batch_size_each
+        ops.hold_check(hand_model._hand, n, cfg["n_cone_vecs"], lw, max_force, ops.HOLD_DEFAULTS["ridge"], iters, cfg["friction"],
+                       cfg["torque_weight"], n_obj=B // be, who="calculate_energy")
+        losses["E_hold"] = ops._hold_terms_checked(
+            hand_model._hand, hand_model._fk_idx, hand_model.global_rotation, hand_model.current_status, hand_model._fk_ws,
+            contact_normal, cp, ops._hold_cog(object_model.cog, B, be, "calculate_energy"), lw_dev, B if lw.shape[0] == 1 else be,
+            cfg["friction"], cfg["torque_weight"], cfg["n_cone_vecs"], max_force, ops.HOLD_DEFAULTS["ridge"], iters, None).e
 
     if "E_reach" in energy_names:
         # arm reachability as ONE launch (ops.reach_terms; arm and parameters: HandModel.set_reach)

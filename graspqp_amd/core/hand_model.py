@@ -272,6 +272,19 @@ class HandModel:
         ops.squeeze_check(None, 1, min_travel, damping, "HandModel.set_squeeze")
         self.squeeze = (float(min_travel), float(damping))
 
+    def set_hold(self, loads, max_force, torque_limits=None, iterations=16):
+        """The load of calculate_energy(..., energy_names=[..., "E_hold"]): ``loads`` (L,6) for every object or (n_obj,L,6) per
+        object, wrenches (N, N m) on the object about its centre (``ops.hold_loads``), ``max_force`` the bound on every cone-edge
+        coefficient in newtons, ``iterations`` PDIPM iterations per load.  The term takes the contact query and the cone parameters
+        (friction, n_cone_vecs, torque_weight) that E_fc takes there.  ``torque_limits`` (JA) is kept for ``ops.hold_terms(...,
+        return_details=True)``: the energy itself does not depend on it."""
+        lw = ops.hold_check(None, None, 4, loads, max_force, ops.HOLD_DEFAULTS["ridge"], iterations, torque_limits=torque_limits,
+                            who="HandModel.set_hold")
+        lim = None if torque_limits is None else torch.as_tensor(torque_limits, dtype=torch.float32).reshape(-1).to(self.device)
+        if lim is not None and lim.numel() != self.n_dofs:
+            raise ValueError(f"HandModel.set_hold: torque_limits must be ({self.n_dofs},), got {tuple(lim.shape)}")
+        self.hold = (lw, lw.to(self.device), float(max_force), lim, int(iterations))
+
     def set_reach(self, arm, arm_base, distance=0.10, stations=0, iterations=24, damping=1e-4, rot_scale=0.1):
         """The arm of calculate_energy(..., energy_names=[..., "E_reach"]): ``arm`` an ``ops.ArmSpec`` or ``ops.ArmHandle``,
         ``arm_base`` (3,4) or (n_obj,3,4) the arm base in the frame of each object, and the parameters of ``ops.reach_terms``

@@ -50,14 +50,21 @@ def grasp_snapshot(hand_model, energy, object_model):
             "values": energy.detach(), "contact_idx": hand_model.contact_point_indices.detach()}
 
 
-def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None, arm_path=None, selection=None):
+def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None, arm_path=None, hold=None, selection=None):
     """One dict per object in the reference's on-disk layout (CPU tensors).  ``selection`` (an ``ops.GraspSelection``, e.g. of
     ``GraspStepper.select``): each object's dict holds only its selected rows, in pick order, and two more keys,
     ``selected_rows`` (int64, the rows' indices within the object) and ``n_feasible`` (int); an object with nothing selected
     gets zero-length tensors.  The consumer reads by key, so the extra keys are harmless.  ``arm_path`` (B,T+1,N), such as
     ``GraspStepper.track_q``: the arm's joint path along the approach, waypoint 0 the retreated pose and waypoint T the grasp,
-    written under the key ``arm_path`` for the rows each object's dict holds (in pick order under a ``selection``).  Pass both by
+    written under the key ``arm_path`` for the rows each object's dict holds (in pick order under a ``selection``).  ``hold`` (an
+    ``ops.HoldResult`` of the same rows, e.g. of ``GraspStepper.hold``): the contact forces (rows,L,n,3; newtons, object frame) and
+    the joint torques (rows,L,JA) that carry its loads, under the keys ``hold_force`` and ``hold_torque``.  Pass all three by
     keyword: ``selection`` stays the last parameter."""
+    if hold is not None:
+        hold_force, hold_torque = hold.force.detach().cpu(), hold.torque.detach().cpu()
+        if hold_force.dim() != 4 or hold_force.shape[0] != n_objects * batch_size or hold_torque.shape[:2] != hold_force.shape[:2]:
+            raise ValueError(f"snapshot_dicts: hold must be an ops.HoldResult of {n_objects * batch_size} rows, got force "
+                             f"{tuple(hold_force.shape)} and torque {tuple(hold_torque.shape)}")
     if arm_path is not None:
         arm_path = torch.as_tensor(arm_path).detach().cpu()
         if arm_path.dim() != 3 or arm_path.shape[0] != n_objects * batch_size:
@@ -81,6 +88,8 @@ def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, gras
         data["contact_links"] = hand_model._contact_links
         if arm_path is not None:
             data["arm_path"] = arm_path[rows].clone()
+        if hold is not None:
+            data["hold_force"], data["hold_torque"] = hold_force[rows].clone(), hold_torque[rows].clone()
         if selection is not None:
             data["selected_rows"] = rows - a * batch_size
             data["n_feasible"] = int(n_feas[a])
@@ -89,11 +98,12 @@ def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, gras
 
 
 def export_poses(hand_model, energy, object_model, object_code_list, batch_size, data_root_path, hand_name, n_contact,
-                 energy_name, suffix="None", grasp_type=None, arm_path=None, selection=None):
-    """fit.py:224-300 -> list of the files written.  ``selection`` and ``arm_path``: see ``snapshot_dicts``; None writes every row / no arm motion."""
+                 energy_name, suffix="None", grasp_type=None, arm_path=None, hold=None, selection=None):
+    """fit.py:224-300 -> list of the files written.  ``selection``, ``arm_path`` and ``hold``: see ``snapshot_dicts``; None writes every
+    row / no arm motion / no holding forces."""
     files = []
     dicts = snapshot_dicts(hand_model, energy, object_model, len(object_code_list), batch_size, grasp_type, arm_path=arm_path,
-                           selection=selection)
+                           hold=hold, selection=selection)
     for code, data in zip(object_code_list, dicts):
         path = os.path.join(get_result_path(data_root_path, code, hand_name, n_contact, energy_name, grasp_type),
                             code + f"{suffix}.dexgrasp.pt")

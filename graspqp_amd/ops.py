@@ -2188,6 +2188,212 @@ def squeeze_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, dist_sq, obj_nor
 
 
 # ----------------------------------------------------------------------------------------------------------
+# payload holding: E_hold (csrc/hold.hip), the load wrenches a grasp can carry as ONE launch: the E_fc step's cone matrix on the
+# inward normals, one box QP per load wrench side by side (low-rank PDIPM, a fixed number of iterations, row-local best iterate),
+# the unheld share of the load, the contact forces and the joint torques they ask of the hand
+# ----------------------------------------------------------------------------------------------------------
+HOLD_DEFAULTS = {"ridge": 1e-4, "iterations": 16}
+
+
+class HoldResult(NamedTuple):
+    """What ``hold_terms(..., return_details=True)`` and ``GraspStepper.hold`` return; every field unweighted."""
+    e: Tensor       # (B) E_hold = mean over the loads of V_l / |w_l|^2, the unheld share of the load
+    resid: Tensor   # (B,L) |F x_l + w_l| / |w_l| without the ridge part: what one gates on
+    x: Tensor       # (B,L,nz) cone-edge coefficients in [0, max_force]; normal force of contact c: sqrt(1 - mu^2) / k * sum_e x
+    force: Tensor   # (B,L,n,3) force of finger c on the object, world frame, newtons
+    torque: Tensor  # (B,L,JA) actuated joint torques J_act' R' force; values only, no gradient
+    effort: Optional[Tensor]  # (B) max |torque| / torque_limits, or None without limits; values only
+
+
+def hold_loads(mass, up=(0.0, 0.0, 1.0), accelerations=((0.0, 0.0, 0.0),), com_offset=None, g=9.81):
+    """-> the load wrenches of ``hold_terms`` as a CPU float32 tensor: (L,6) for a scalar ``mass`` in kg, (n_obj,L,6) for a
+    sequence of masses.  Load l is what the hand has to hold the object against while it accelerates with ``accelerations[l]``
+    (m/s^2, object frame) under gravity along -``up`` (normalised here): force -m (g up + a), torque ``com_offset`` x force about
+    the centre the contacts' ``cog`` stands for (``com_offset`` (3,) or (n_obj,3): where the true centre of mass lies relative
+    to it; None: no offset).  The default is the object's weight alone."""
+    m = torch.as_tensor(mass, dtype=torch.float64)
+    per_object = m.dim() > 0
+    m = m.reshape(-1)
+    upv = torch.as_tensor(up, dtype=torch.float64).reshape(-1)
+    acc = torch.as_tensor(accelerations, dtype=torch.float64)
+    if not (m.numel() >= 1 and bool(torch.isfinite(m).all()) and bool((m > 0).all())):
+        raise ValueError(f"hold_loads: mass = {mass!r} must be finite and > 0")
+    if upv.shape != (3,) or not bool(torch.isfinite(upv).all()) or float(upv.norm()) == 0.0:
+        raise ValueError(f"hold_loads: up = {up!r} must be a finite non-zero 3-vector")
+    if acc.dim() != 2 or acc.shape[1] != 3 or not 1 <= acc.shape[0] <= 8 or not bool(torch.isfinite(acc).all()):
+        raise ValueError(f"hold_loads: accelerations must be (L,3) with 1 <= L <= 8 and finite, got {tuple(acc.shape)}")
+    if not 0.0 < float(g) < float("inf"):
+        raise ValueError(f"hold_loads: g = {g!r} must be finite and > 0")
+    force = -m.view(-1, 1, 1) * (float(g) * (upv / upv.norm()).view(1, 1, 3) + acc.unsqueeze(0))  # (n_obj,L,3)
+    if com_offset is None:
+        torque = torch.zeros_like(force)
+    else:
+        off = torch.as_tensor(com_offset, dtype=torch.float64)
+        if off.shape not in ((3,), (m.numel(), 3)) or not bool(torch.isfinite(off).all()):
+            raise ValueError(f"hold_loads: com_offset must be (3,) or ({m.numel()},3) and finite, got {tuple(off.shape)}")
+        torque = torch.cross(off.reshape(-1, 1, 3).expand_as(force), force, dim=-1)
+    w = torch.cat([force, torque], -1).float()
+    return w if per_object else w[0]
+
+
+def hold_check(hand, n_contact, n_cone_vecs, loads, max_force, ridge=1e-4, iterations=16, friction=0.2, torque_weight=5.0,
+               torque_limits=None, n_obj=None, who="hold_terms"):
+    """The parameter checks of the payload-holding term (no GPU; raises ValueError): at most 64 contacts and joints, n_cone_vecs >=
+    3 and n_contact * n_cone_vecs <= 128 columns, ``loads`` (L,6) or (n_obj,L,6) with 1 <= L <= 8, every load finite with a
+    non-zero wrench once its torque is multiplied by ``torque_weight``, max_force and ridge finite and > 0, 1 <= iterations <= 64,
+    friction in (0, 1], ``torque_limits`` (JA) finite and > 0.  -> the loads as a CPU float32 tensor (n_sets,L,6)."""
+    lw = torch.as_tensor(loads).detach().to("cpu", torch.float32)
+    if lw.dim() == 2:
+        lw = lw.unsqueeze(0)
+    if lw.dim() != 3 or lw.shape[2] != 6 or not 1 <= lw.shape[1] <= 8 or lw.shape[0] < 1:
+        raise ValueError(f"{who}: loads must be (L,6) or (n_obj,L,6) with 1 <= L <= 8, got {tuple(torch.as_tensor(loads).shape)}")
+    if n_obj is not None and lw.shape[0] not in (1, int(n_obj)):
+        raise ValueError(f"{who}: loads are given for {lw.shape[0]} objects, the batch has {int(n_obj)}")
+    if not 0.0 <= float(torque_weight) < float("inf"):
+        raise ValueError(f"{who}: torque_weight = {torque_weight!r} must be finite and >= 0")
+    scaled = torch.cat([lw[..., :3], float(torque_weight) * lw[..., 3:]], -1)
+    if not bool(torch.isfinite(scaled).all()) or not bool((scaled.norm(dim=-1) > 0).all()):
+        raise ValueError(f"{who}: every load must be finite with a non-zero wrench (torque rows times torque_weight)")
+    if not 0.0 < float(max_force) < float("inf"):
+        raise ValueError(f"{who}: hold_max_force = {max_force!r} must be finite and > 0")
+    if not 0.0 < float(ridge) < float("inf"):
+        raise ValueError(f"{who}: ridge = {ridge!r} must be finite and > 0")
+    if not 1 <= int(iterations) <= 64:
+        raise ValueError(f"{who}: hold_iterations = {iterations!r} must be in 1..64")
+    if not 0.0 < float(friction) <= 1.0:
+        raise ValueError(f"{who}: friction = {friction!r} must be in (0, 1]")
+    if n_contact is not None and not (1 <= int(n_contact) <= 64 and int(n_cone_vecs) >= 3 and int(n_contact) * int(n_cone_vecs) <= 128):
+        raise ValueError(f"{who}: 1..64 contacts, n_cone_vecs >= 3 and at most 128 columns are supported, got n_contact = {n_contact}, "
+                         f"n_cone_vecs = {n_cone_vecs}")
+    if hand is not None and not (hand.spec.n_nodes <= 64 and hand.J <= 64):
+        raise ValueError(f"{who}: the hold term takes at most 64 joints, got {hand.spec.n_nodes}")
+    if torque_limits is not None:
+        tl = torch.as_tensor(torque_limits).detach().to("cpu", torch.float32).reshape(-1)
+        if (hand is not None and tl.numel() != hand.J) or not bool(torch.isfinite(tl).all()) or not bool((tl > 0).all()):
+            raise ValueError(f"{who}: torque_limits must be ({hand.J if hand is not None else 'JA'},) finite and > 0")
+    return lw.contiguous()
+
+
+def _hold_call(hand, idx, Rg, LT, ws, onrm, cpts, cog, loads, loads_each, k, mu, tw, max_force, ridge, iters, limits, up, w, e, resid, x,
+               force, torque, effort, accumulate, g_cpts, st=None):
+    """gq_hold_terms on loads the caller has checked (hold_check): the host copy is not passed."""
+    p, (B, n) = _dev, cpts.shape[:2]
+    kin = torque is not None or effort is not None
+    _C.call("gq_hold_terms", hand.handle if kin else None, _C.i64(idx) if kin else None, ctypes.c_int64(B), n, int(k), p(onrm), p(cpts),
+            p(cog), p(Rg) if kin else None, p(LT) if kin else None, _C.ptr(ws) if kin else None, ws.numel() if kin else 0, p(loads), None,
+            ctypes.c_int64(loads.shape[0]), int(loads.shape[1]), ctypes.c_int64(loads_each), float(mu), float(tw), float(max_force),
+            float(ridge), int(iters), p(limits), p(up), float(w), p(e), p(resid), p(x), p(force), p(torque), p(effort), int(accumulate),
+            p(g_cpts), _C.stream_ptr() if st is None else st)
+
+
+@_custom_op("graspqp_amd::hold_terms", mutates_args=(), device_types="cuda")
+def _hold_op(hand: int, idx: Tensor, Rg: Tensor, LT: Tensor, ws: Tensor, obj_normal: Tensor, contact_pts: Tensor, cog: Tensor,
+             loads: Tensor, loads_each: int, friction: float, torque_weight: float, n_cone_vecs: int, max_force: float, ridge: float,
+             iterations: int, torque_limits: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (E_hold (B), resid (B,L), x (B,L,nz), force (B,L,n,3), torque (B,L,JA), effort (B), or (0) without limits) of the contact
+    query (outward obj_normal, contact_pts, cog (B,3)) and the kinematic state (idx, Rg, LT, ws); loads (n_sets,L,6) on the device,
+    checked by the caller (hold_check)."""
+    h = _handle(hand)
+    ix = _c(idx, torch.int64)
+    (B, n), dev, L = ix.shape, ix.device, loads.shape[1]
+    f = lambda *s: torch.empty(*s, device=dev)
+    e, resid, x, force, torque = f(B), f(B, L), f(B, L, n * n_cone_vecs), f(B, L, n, 3), f(B, L, h.J)
+    effort = f(B) if torque_limits is not None else f(0)
+    _hold_call(h, ix, _c(Rg), _c(LT), ws, _c(obj_normal), _c(contact_pts), _c(cog), _c(loads), loads_each, n_cone_vecs, friction,
+               torque_weight, max_force, ridge, iterations, None if torque_limits is None else _c(torque_limits), None, 0.0, e, resid, x,
+               force, torque, effort if torque_limits is not None else None, 0, None)
+    return e, resid, x, force, torque, effort
+
+
+@_hold_op.register_fake
+def _(hand, idx, Rg, LT, ws, obj_normal, contact_pts, cog, loads, loads_each, friction, torque_weight, n_cone_vecs, max_force, ridge,
+      iterations, torque_limits):
+    (B, n), L, f = idx.shape, loads.shape[1], contact_pts.new_empty
+    return f(B), f(B, L), f(B, L, n * n_cone_vecs), f(B, L, n, 3), f(B, L, _handle(hand).J), f(B if torque_limits is not None else 0)
+
+
+@_custom_op("graspqp_amd::hold_terms_backward", mutates_args=(), device_types="cuda")
+def _hold_bwd_op(obj_normal: Tensor, contact_pts: Tensor, cog: Tensor, loads: Tensor, loads_each: int, friction: float,
+                 torque_weight: float, n_cone_vecs: int, max_force: float, ridge: float, iterations: int, g_hold: Tensor) -> Tensor:
+    """Upstream row gradients (B) on E_hold -> g_contact_pts (B,n,3), the envelope gradient through the torque rows of F (the
+    normals are constants).  One launch: the loads are solved again, nothing is kept from the forward."""
+    cp = _c(contact_pts)
+    g_cp = torch.empty_like(cp)
+    _hold_call(None, None, None, None, None, _c(obj_normal), cp, _c(cog), _c(loads), loads_each, n_cone_vecs, friction, torque_weight,
+               max_force, ridge, iterations, None, _c(g_hold), 1.0, None, None, None, None, None, None, 0, g_cp)
+    return g_cp
+
+
+@_hold_bwd_op.register_fake
+def _(obj_normal, contact_pts, cog, loads, loads_each, friction, torque_weight, n_cone_vecs, max_force, ridge, iterations, g_hold):
+    return torch.empty_like(contact_pts)
+
+
+def _hold_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[5], inputs[6], inputs[7], inputs[8])
+    ctx.par = tuple(inputs[9:16])
+    ctx.mark_non_differentiable(*output[1:])
+
+
+def _hold_bwd(ctx, g_e, *_):
+    onrm, cp, cog, loads = ctx.saved_tensors
+    g_cp = _Eager.hold_terms_backward(onrm, cp, cog, loads, *ctx.par, _c(g_e))
+    return (None,) * 6 + (g_cp,) + (None,) * 10
+
+
+torch.library.register_autograd("graspqp_amd::hold_terms", _hold_bwd, setup_context=_hold_setup)
+
+
+def _hold_cog(cog, B, batch_each, who):
+    cog = _c(cog.detach())
+    if cog.shape == (B, 3):
+        return cog
+    if cog.dim() == 2 and cog.shape[1] == 3 and cog.shape[0] * int(batch_each) == B:
+        return cog.repeat_interleave(int(batch_each), dim=0).contiguous()
+    raise ValueError(f"{who}: cog must be ({B}, 3) or (n_obj, 3) with n_obj * batch_each = {B}, got {tuple(cog.shape)}")
+
+
+def hold_terms(hand_pose, hand: HandHandle, idx, Rg, LT, ws, obj_normal, contact_pts, cog, loads, batch_each, friction, torque_weight,
+               n_cone_vecs, max_force, ridge=1e-4, iterations=16, torque_limits=None, return_details=False):
+    """-> E_hold (B) = (1/L) sum_l V_l(x_l) / |w_l|^2 with x_l = argmin_{0 <= x <= max_force} V_l(x) = |F x + w_l|^2 + ridge |x|^2:
+    the share of the load wrenches ``loads`` that the contacts cannot carry (1: nothing, down to a floor set by the ridge).  F is
+    the E_fc step's cone matrix of (``contact_pts``, ``obj_normal``, ``cog``, ``friction``, ``torque_weight``, ``n_cone_vecs``) on the
+    INWARD normals; ``loads`` (L,6) for every object or (n_obj,L,6) per object (``hold_loads``; row b belongs to object
+    b // batch_each) are wrenches (N, N m) on the object about ``cog``; ``max_force`` bounds every edge coefficient in newtons (the
+    normal force of a contact is sqrt(1 - mu^2) / k * sum_e x).  Exactly ``iterations`` PDIPM iterations per load, the iterate with
+    the load's own smallest residual: a row's result depends on that row alone.  Differentiable w.r.t. ``contact_pts`` ONLY (the
+    envelope gradient through the torque rows of F; the normals are constants as in E_fc): exact at the optimum, at the default
+    16 iterations within 7e-4 of it.  ``idx``, ``Rg``, ``LT``, ``ws``: the kinematic state of ``hand_pose`` (fk_contacts), read for
+    the joint torques.  ``return_details``: a ``HoldResult``; its torque and effort are values only.  Pass ``loads`` as a CPU tensor
+    (a CUDA one is fetched for the checks, which synchronises)."""
+    if not contact_pts.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if hand_pose.shape[1] != 9 + hand.J:
+        raise ValueError(f"hold_terms: hand_pose must be (B, {9 + hand.J}), got {tuple(hand_pose.shape)}")
+    B, n = idx.shape
+    if int(batch_each) < 1 or B % int(batch_each):
+        raise ValueError(f"hold_terms: batch_each = {batch_each!r} must divide the batch {B}")
+    lw = hold_check(hand, n, n_cone_vecs, loads, max_force, ridge, iterations, friction, torque_weight, torque_limits,
+                    B // int(batch_each))
+    if tuple(obj_normal.shape) != (B, n, 3) or tuple(contact_pts.shape) != (B, n, 3):
+        raise ValueError(f"hold_terms: obj_normal and contact_pts must be ({B}, {n}, 3)")
+    dev = contact_pts.device
+    lim = None if torque_limits is None else torch.as_tensor(torque_limits, dtype=torch.float32).reshape(-1).to(dev)
+    out = _hold_terms_checked(hand, idx, Rg, LT, ws, obj_normal, contact_pts, _hold_cog(cog, B, batch_each, "hold_terms"), lw.to(dev),
+                              B if lw.shape[0] == 1 else int(batch_each), friction, torque_weight, n_cone_vecs, max_force, ridge,
+                              iterations, lim)
+    return out if return_details else out.e
+
+
+def _hold_terms_checked(hand, idx, Rg, LT, ws, obj_normal, contact_pts, cog, loads_dev, loads_each, friction, torque_weight, n_cone_vecs,
+                        max_force, ridge, iterations, limits):
+    e, resid, x, force, torque, effort = _Eager.hold_terms(
+        hand.hid, _c(idx, torch.int64), _c(Rg.detach()), _c(LT.detach()), ws, _c(obj_normal.detach()), contact_pts, cog, loads_dev,
+        int(loads_each), float(friction), float(torque_weight), int(n_cone_vecs), float(max_force), float(ridge), int(iterations), limits)
+    return HoldResult(e, resid, x, force, torque, effort if limits is not None else None)
+
+
+# ----------------------------------------------------------------------------------------------------------
 # arm reachability: E_reach (csrc/reach.hip), batched damped-least-squares wrist IK as ONE launch: eight lanes per IK problem, the
 # seeds and stations of a row side by side in one block, the gradient in the gRt layout the FK backward takes
 # ----------------------------------------------------------------------------------------------------------
@@ -3190,6 +3396,8 @@ _eager("pregrasp_terms", _pregrasp_op)
 _eager("pregrasp_terms_backward", _pregrasp_bwd_op)
 _eager("squeeze_terms", _squeeze_op)
 _eager("squeeze_terms_backward", _squeeze_bwd_op)
+_eager("hold_terms", _hold_op, _hold_bwd, _hold_setup)
+_eager("hold_terms_backward", _hold_bwd_op)
 _eager("reach_terms", _reach_op)
 _eager("reach_terms_backward", _reach_bwd_op)
 _eager("track_terms", _track_op)

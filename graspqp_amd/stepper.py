@@ -1149,6 +1149,33 @@ class GraspStepper:
         return ops.grasp_select(self.hand_pose, Rg, LT, self.samples, self.be, score.to(self.dev, torch.float32), self.terms, tol,
                                 k, radius)
 
+    def hold(self, loads, max_force, torque_limits=None, iterations=16):
+        """Can the ACCEPTED grasps carry ``loads``?  -> ``ops.HoldResult`` (device tensors; the host does not wait): E_hold, the
+        residual share per load, the cone-edge coefficients, the contact forces (N, world frame) and the joint torques they ask
+        of the hand, with ``torque_limits`` (JA) also the effort.  ``loads`` (L,6) or (n_obj,L,6) from ``ops.hold_loads``,
+        ``max_force`` the bound on every cone-edge coefficient in newtons; friction, cone edges and torque weight are the
+        stepper's force-closure parameters.  Like ``select`` it reads ``hand_pose`` / ``contact_idx`` after ``flush``: one FK forward
+        and one object query into buffers of its own, then the hold launch.  Nothing of the chain's state is written: stepping on
+        afterwards gives the bits of a stepper that never called it.  To keep only grasps that hold the load:
+
+            h = st.hold(ops.hold_loads(0.5), max_force=20.0)
+            sel = st.select(k, score=torch.where(h.resid.amax(1) <= 0.05, st.energy, torch.inf))
+
+        (``ops.grasp_select`` treats a non-finite score as infeasible)."""
+        lw = ops.hold_check(self.hand, self.n, self.fc["n_cone_vecs"], loads, max_force, ops.HOLD_DEFAULTS["ridge"], iterations,
+                            self.fc["friction"], self.fc["torque_weight"], torque_limits, self.B // self.be, "GraspStepper.hold")
+        lim = None if torque_limits is None else torch.as_tensor(torque_limits, dtype=torch.float32).reshape(-1).to(self.dev)
+        self.flush()
+        with torch.no_grad():
+            Rg, LT, cp, _, _, ws = ops.fk_contacts(self.hand_pose, self.contact_idx, self.hand)
+            query = ops.sdf_cloud if self.cloud else ops.sdf_meshset
+            d2, sgn, nrm, _ = query(cp.reshape(-1, 3), self.objs, self.be * self.n)
+            _, onrm = ops.signed_distance(d2, sgn, nrm)
+            return ops._hold_terms_checked(self.hand, self.contact_idx, Rg, LT, ws, onrm.reshape(self.B, self.n, 3), cp, self.cog,
+                                           lw.to(self.dev), self.B if lw.shape[0] == 1 else self.be, self.fc["friction"],
+                                           self.fc["torque_weight"], self.fc["n_cone_vecs"], max_force, ops.HOLD_DEFAULTS["ridge"],
+                                           iterations, lim)
+
     def flush(self):
         """Run the iterations that ``step`` has queued for a multi-iteration graph but not yet replayed."""
         if self._graph_pending:

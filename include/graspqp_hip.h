@@ -724,6 +724,49 @@ int gq_squeeze_terms(const gqHand* h, const int64_t* contact_idx /* (B,n) */, in
                      float* g_R /* (B,9) or NULL */, const float* g_R_base /* (B,9) or NULL */,
                      float* g_contact_pts /* (B,n,3) or NULL */, void* stream);
 
+/* ---- payload holding: E_hold, the load wrenches a grasp can carry -----------------------------------------------------------
+ * Can these contacts, at this friction and with at most max_force newtons per cone edge, carry the object's load?  Row b has n
+ * contacts p_c with OUTWARD object normals n_c, k = n_cone cone edges per contact, nz = n k <= 128 columns, mu = friction,
+ * tw = torque_weight, cog (B,3): the inputs of the E_fc step.  Column i = (c, e) of F (6 x nz) is that step's cone column on the
+ * INWARD normal -n_c (a finger pushes): force rows f_i, torque rows tw (p_c - cog) x f_i.  A load l < L <= 8 is an external
+ * wrench on the object about its centre of mass in the object frame, (force in N, torque in N m); w_l is that wrench with its
+ * torque rows multiplied by tw.  loads is (n_load_sets, L, 6) on the device, row b takes set b / loads_each; loads_host holds the
+ * same values on the host for the checks (NULL: the caller has checked them; a load with |w_l| = 0 then gives NaN in its row's
+ * outputs, never a fault).
+ *   x_l = argmin over 0 <= x <= max_force of V_l(x) = |F x + w_l|^2 + ridge |x|^2       E_hold = (1/L) sum_l V_l(x_l) / |w_l|^2
+ * the unheld share of the load: dimensionless, 1 when the contacts can do nothing, down to a floor set by the ridge.  max_force
+ * bounds every EDGE coefficient; the normal force of contact c is sqrt(1 - mu^2) / k * sum_e x_(c,e) (the cone edges carry the
+ * 1/k of the E_fc step; nothing is rescaled).  x_l is the iterate with the problem's own smallest residual among exactly
+ * n_iterations PDIPM iterations (the shared loop with the low-rank solver, in fp64; p = F' w_l, bounds [0, max_force]; first strict
+ * minimum, a NaN never becomes best); the batch-global stop rule is NOT used, so a row's numbers depend on the row alone.
+ * Gradient (envelope theorem: E_hold is the optimal value, the box does not depend on the pose, no KKT backward):
+ *   dE/dF = (2 / (L |w_l|^2)) r_l x_l',  r_l = F x_l + w_l;  the normals are held fixed as in the E_fc step, so only the torque
+ *   rows carry it: g_contact_pts (B,n,3) = c sum_l sum_e tw f_i x g_tau,i with the row's upstream c = w (up[row] if given, else 1).
+ * It is exact at the optimum and an approximation at an iterate (DESIGN section 30 has the measured error per iteration count).
+ * Outputs, all UNWEIGHTED, any may be NULL:
+ *   e (B)             E_hold
+ *   resid (B,L)       |r_l| / |w_l|, the pure residual without the ridge part: what one gates on
+ *   x (B,L,nz)        edge coefficients
+ *   force (B,L,n,3)   force of finger c on the object, sum_e x f_i, world frame, newtons
+ *   torque (B,L,JA)   actuated joint torques tau = J_act' R' force with the linear contact Jacobian of gq_contact_jacobian (the
+ *                     squeeze term's column, J_act = J_tree C for a coupled hand); VALUES ONLY, no gradient flows through them
+ *   effort (B)        max over l, j of |tau_lj| / torque_limits[j] (JA, device, > 0); needs torque_limits; values only
+ * accumulate bit 0 adds to g_contact_pts, cleared it overwrites.  h, contact_idx, Rg, link_T / workspace (gq_fk_forward's of the
+ * same poses) are read for torque / effort only and may be NULL without them.  One block per row, one wavefront per load, no
+ * atomics, fixed-order sums: bitwise reproducible run to run and row by row, graph-capturable.  An error status, never a device
+ * fault, for: n, J, JA outside 1..64, n_cone < 3, nz > 128, L outside 1..8, n_iterations outside 1..64, a load that is not
+ * finite or has |w_l| = 0, max_force or ridge not finite and > 0, friction outside (0, 1], load sets that do not cover the batch. */
+int gq_hold_terms(const gqHand* h, const int64_t* contact_idx /* (B,n) */, int64_t batch, int n_contact, int n_cone,
+                  const float* obj_normal /* (B,n,3) outward */, const float* contact_pts /* (B,n,3) */,
+                  const float* cog /* (B,3) */, const float* Rg /* (B,9) */, const float* link_T /* (B,L,12) */,
+                  const void* workspace, size_t workspace_bytes, const float* loads /* (n_load_sets,L,6) device */,
+                  const float* loads_host /* the same on the host, or NULL */, int64_t n_load_sets, int n_loads, int64_t loads_each,
+                  float friction, float torque_weight, float max_force, float ridge, int n_iterations,
+                  const float* torque_limits /* (JA) or NULL */, const float* up /* (B) or NULL */, float w,
+                  float* e /* (B) */, float* resid /* (B,L) */, float* x /* (B,L,nz) */, float* force /* (B,L,n,3) */,
+                  float* torque /* (B,L,JA) */, float* effort /* (B) */, int accumulate,
+                  float* g_contact_pts /* (B,n,3) or NULL */, void* stream);
+
 /* ---- arm reachability of the stepper: E_reach, batched damped-least-squares wrist IK ----------------------------------------
  * Every other term treats the hand as a free-flying body; this one knows that it sits on an arm.  The arm is a serial chain of
  * N <= 8 revolute (1) or prismatic (2) joints with limits: FK(q) = base_T joint_T[0] m_0(q_0) ... joint_T[N-1] m_{N-1}(q_{N-1}) tool_T

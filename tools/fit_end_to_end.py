@@ -12,6 +12,7 @@ Evidence run, not a test: writes one JSON record (default gpurun_out/fit_end_to_
 
 usage: python tools/fit_end_to_end.py [--n_objects 1] [--batch_size 256] [--n_iter 7000] [--out file.json]
        [--w_squeeze 0] [--squeeze_min_travel 5e-3] [--squeeze_damping 1e-3]   (contact closing feasibility, E_squeeze)
+       [--hold_mass 0] [--hold_max_force 20] [--hold_tol 0.05]   (payload holding: export only the grasps that carry this mass)
        [--w_reach 0] [--arm arm7|file.urdf] [--arm_tip LINK] [--arm_base X Y Z YAW] [--reach_stations 0]   (arm reachability, E_reach)
        [--w_track 0] [--track_waypoints 8] [--track_updates 3] [--arm_on_track]   (approach tracking, E_track: needs --w_reach > 0 and
                                                                                    --reach_stations >= 1; the path is exported as arm_path)
@@ -70,6 +71,9 @@ ap.add_argument("--w_track", type=float, default=0.0)  # approach tracking: one 
 ap.add_argument("--track_waypoints", type=int, default=8)
 ap.add_argument("--track_updates", type=int, default=3)
 ap.add_argument("--arm_on_track", action="store_true")  # E_arm at the path's configurations (needs --w_arm and --w_track)
+ap.add_argument("--hold_mass", type=float, default=0.0)  # payload holding: > 0 gates the selection on carrying this mass (kg)
+ap.add_argument("--hold_max_force", type=float, default=20.0)  # newtons per cone edge
+ap.add_argument("--hold_tol", type=float, default=0.05)  # largest unheld share |r| / |w| of a load that still counts as held
 ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "fit_end_to_end.json"))
 args = ap.parse_args()
 
@@ -224,10 +228,20 @@ if TABLETOP:
         rel_oracle[k] = float(((got - v).abs() / v.abs().clamp_min(1e-4)).max())
 
 # ---- (3) export + reload the way the consumer does ----------------------------------------------------------------------
+hold = selection = hold_rec = None
+if args.hold_mass > 0:  # can the accepted grasps carry the object, at rest and braking at 3 m/s^2?  Only those are exported.
+    from graspqp_amd import ops
+
+    hold = st.hold(ops.hold_loads(args.hold_mass, accelerations=((0, 0, 0), (3, 0, 0), (0, 3, 0))), args.hold_max_force)
+    held = hold.resid.amax(1) <= args.hold_tol
+    selection = st.select(be, radius=0.0, score=torch.where(held, st.energy, torch.inf))
+    hold_rec = {"mass_kg": args.hold_mass, "max_force_N": args.hold_max_force, "tol": args.hold_tol, "rows_held": int(held.sum()),
+                "n_selected": selection.n_selected.cpu().tolist(), "E_hold_mean": float(hold.e.mean()),
+                "largest_contact_force_N": float(hold.force.norm(dim=-1).max()), "largest_joint_torque_Nm": float(hold.torque.abs().max())}
 with tempfile.TemporaryDirectory() as tmp:
     hm.set_parameters(st.hand_pose.clone(), st.contact_idx.clone())
     files = export_poses(hm, st.energy.clone(), om, codes, be, tmp, args.hand, n, "graspqp", suffix="",  # fit.py:521
-                         arm_path=st.track_q if TRACK else None)
+                         arm_path=st.track_q if TRACK else None, hold=hold, selection=selection)
     data = torch.load(files[0], weights_only=True)
     jn = list(spec.joint_names)
     params = torch.cat([data["parameters"]["root_pose"], torch.stack([data["parameters"][k] for k in jn], -1)], -1)
@@ -250,6 +264,8 @@ rec = {
     "check_oracle_fp64_rel_err_max_over_rows": rel_oracle, "oracle_rows": rows,
     "export": export,
 }
+if hold_rec is not None:
+    rec["hold"] = hold_rec
 assert rec["energy_mean_final"] < rec["energy_mean_initial"]
 assert rec["check_class_surface_rel_err"]["median"] < 1e-4
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
