@@ -272,6 +272,19 @@ class HandModel:
         ops.squeeze_check(None, 1, min_travel, damping, "HandModel.set_squeeze")
         self.squeeze = (float(min_travel), float(damping))
 
+    def close_fingers(self, grid, direction, steps=32, step=None, touch=5e-4):
+        """Close the fingers of the current poses (``set_parameters``) along ``direction`` (B,n_dofs) until they touch ``grid``, an
+        ``ops.SceneSDF`` or ``ops.SceneSDFSet`` that contains the target -> ``ops.CloseResult``: the class-surface form of
+        ``ops.close_fingers`` on the hand's surface samples.  Values only."""
+        if self.hand_pose is None:
+            raise ValueError("HandModel.close_fingers: call set_parameters(hand_pose, ...) first")
+        _, pts, lnk = self._surface_handle()
+        samples = getattr(self, "_close_samples", None)
+        if samples is None or samples[0] is not pts:
+            samples = self._close_samples = (pts, ops.SurfaceSamples(self.spec, pts, lnk, device=self.device))
+        return ops.close_fingers(self.hand_pose.detach(), self._hand, samples[1], self.global_rotation.detach(), grid,
+                                 torch.as_tensor(direction, dtype=torch.float32).to(self.device), steps, step, touch)
+
     def set_hold(self, loads, max_force, torque_limits=None, iterations=16):
         """The load of calculate_energy(..., energy_names=[..., "E_hold"]): ``loads`` (L,6) for every object or (n_obj,L,6) per
         object, wrenches (N, N m) on the object about its centre (``ops.hold_loads``), ``max_force`` the bound on every cone-edge

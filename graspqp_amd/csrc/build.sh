@@ -36,6 +36,7 @@ deps() {  # headers each translation unit includes
     pregrasp) echo "common.h wave.h kin_dev.h grid_stack.h scene_dev.h approach_dev.h sample_row_dev.h approach_row_dev.h pregrasp_dev.h" ;;
     squeeze) echo "common.h wave.h kin_dev.h squeeze_dev.h" ;;
     hold) echo "common.h wave.h kin_dev.h squeeze_dev.h fc_dev.h qp_core.h qp_kernels.h qp_lr.h hold_dev.h" ;;
+    close) echo "common.h wave.h kin_dev.h grid_stack.h scene_dev.h sample_row_dev.h close_dev.h" ;;
     reach) echo "common.h wave.h setup.h cluster_bound.h reach_dev.h reach_lanes.h" ;;
     track) echo "common.h wave.h reach_dev.h reach_lanes.h track_dev.h" ;;
     armscene) echo "common.h wave.h grid_stack.h scene_dev.h reach_dev.h armscene_dev.h" ;;
@@ -46,7 +47,7 @@ deps() {  # headers each translation unit includes
     *) echo "common.h" ;;
   esac
 }
-for f in api qp qp_lr qp_dense qp_nz16 qp_nz32 qp_nz48 qp_nz64 sdf bvh kin fc fcstep stage loop export init metric terms exact tabletop cloud scene approach clutter lift pregrasp squeeze hold reach track armscene tsdf surfel edt select; do
+for f in api qp qp_lr qp_dense qp_nz16 qp_nz32 qp_nz48 qp_nz64 sdf bvh kin fc fcstep stage loop export init metric terms exact tabletop cloud scene approach clutter lift pregrasp squeeze hold close reach track armscene tsdf surfel edt select; do
   stale=0
   [ -f "$OUT/$f.o" ] || stale=1
   for d in $f.hip $(deps $f); do [ "$HERE/$d" -nt "$OUT/$f.o" ] && stale=1; done

@@ -50,7 +50,8 @@ def grasp_snapshot(hand_model, energy, object_model):
             "values": energy.detach(), "contact_idx": hand_model.contact_point_indices.detach()}
 
 
-def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None, arm_path=None, hold=None, selection=None):
+def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, grasp_type=None, arm_path=None, hold=None, closed=None,
+                   selection=None):
     """One dict per object in the reference's on-disk layout (CPU tensors).  ``selection`` (an ``ops.GraspSelection``, e.g. of
     ``GraspStepper.select``): each object's dict holds only its selected rows, in pick order, and two more keys,
     ``selected_rows`` (int64, the rows' indices within the object) and ``n_feasible`` (int); an object with nothing selected
@@ -58,8 +59,15 @@ def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, gras
     ``GraspStepper.track_q``: the arm's joint path along the approach, waypoint 0 the retreated pose and waypoint T the grasp,
     written under the key ``arm_path`` for the rows each object's dict holds (in pick order under a ``selection``).  ``hold`` (an
     ``ops.HoldResult`` of the same rows, e.g. of ``GraspStepper.hold``): the contact forces (rows,L,n,3; newtons, object frame) and
-    the joint torques (rows,L,JA) that carry its loads, under the keys ``hold_force`` and ``hold_torque``.  Pass all three by
-    keyword: ``selection`` stays the last parameter."""
+    the joint torques (rows,L,JA) that carry its loads, under the keys ``hold_force`` and ``hold_torque``.  ``closed`` (an
+    ``ops.CloseResult`` of the same rows, e.g. of ``GraspStepper.close``): the joints after finger closing under the key
+    ``joint_positions_closed`` (a dict by joint name, like ``parameters``) and the number of touching links per row under
+    ``n_touched_links`` (int64).  Pass all four by keyword: ``selection`` stays the last parameter."""
+    if closed is not None:
+        closed_theta, n_touched = closed.theta.detach().cpu(), closed.touched.detach().cpu().sum(1)
+        if closed_theta.dim() != 2 or closed_theta.shape[0] != n_objects * batch_size:
+            raise ValueError(f"snapshot_dicts: closed must be an ops.CloseResult of {n_objects * batch_size} rows, got theta "
+                             f"{tuple(closed_theta.shape)}")
     if hold is not None:
         hold_force, hold_torque = hold.force.detach().cpu(), hold.torque.detach().cpu()
         if hold_force.dim() != 4 or hold_force.shape[0] != n_objects * batch_size or hold_torque.shape[:2] != hold_force.shape[:2]:
@@ -90,6 +98,9 @@ def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, gras
             data["arm_path"] = arm_path[rows].clone()
         if hold is not None:
             data["hold_force"], data["hold_torque"] = hold_force[rows].clone(), hold_torque[rows].clone()
+        if closed is not None:
+            data["joint_positions_closed"] = {names[i]: closed_theta[rows, i].clone() for i in range(len(names))}
+            data["n_touched_links"] = n_touched[rows].clone()
         if selection is not None:
             data["selected_rows"] = rows - a * batch_size
             data["n_feasible"] = int(n_feas[a])
@@ -98,12 +109,12 @@ def snapshot_dicts(hand_model, energy, object_model, n_objects, batch_size, gras
 
 
 def export_poses(hand_model, energy, object_model, object_code_list, batch_size, data_root_path, hand_name, n_contact,
-                 energy_name, suffix="None", grasp_type=None, arm_path=None, hold=None, selection=None):
-    """fit.py:224-300 -> list of the files written.  ``selection``, ``arm_path`` and ``hold``: see ``snapshot_dicts``; None writes every
-    row / no arm motion / no holding forces."""
+                 energy_name, suffix="None", grasp_type=None, arm_path=None, hold=None, closed=None, selection=None):
+    """fit.py:224-300 -> list of the files written.  ``selection``, ``arm_path``, ``hold`` and ``closed``: see ``snapshot_dicts``; None
+    writes every row / no arm motion / no holding forces / no closed joints (the file is then what it always was)."""
     files = []
     dicts = snapshot_dicts(hand_model, energy, object_model, len(object_code_list), batch_size, grasp_type, arm_path=arm_path,
-                           hold=hold, selection=selection)
+                           hold=hold, closed=closed, selection=selection)
     for code, data in zip(object_code_list, dicts):
         path = os.path.join(get_result_path(data_root_path, code, hand_name, n_contact, energy_name, grasp_type),
                             code + f"{suffix}.dexgrasp.pt")

@@ -2393,6 +2393,236 @@ def _hold_terms_checked(hand, idx, Rg, LT, ws, obj_normal, contact_pts, cog, loa
     return HoldResult(e, resid, x, force, torque, effort if limits is not None else None)
 
 
+def hold_contacts(contact_pts, obj_normal, cog, loads, batch_each, friction, torque_weight, n_cone_vecs, max_force, ridge=1e-4,
+                  iterations=16):
+    """-> (E_hold (B), resid (B,L), force (B,L,n,3)) of ``hold_terms`` on contacts that are NOT contact candidates of the hand: the
+    points and outward object normals (B,n,3) of ``CloseResult.contacts(n)``.  It is the same launch without kinematics, so there
+    are no joint torques: the torque of a force at an arbitrary link point needs a Jacobian of that point, which the package does
+    not have.  A slot with a zero normal has an all-zero cone column (t1 = n x b1 = 0, f = 0, tau = r x f = 0) and carries
+    nothing, so padded slots stand for "no contact".  Values only."""
+    if not contact_pts.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if contact_pts.dim() != 3 or contact_pts.shape[2] != 3 or tuple(obj_normal.shape) != tuple(contact_pts.shape):
+        raise ValueError(f"hold_contacts: contact_pts and obj_normal must both be (B,n,3), got {tuple(contact_pts.shape)} / "
+                         f"{tuple(obj_normal.shape)}")
+    B, n = contact_pts.shape[:2]
+    if int(batch_each) < 1 or B % int(batch_each):
+        raise ValueError(f"hold_contacts: batch_each = {batch_each!r} must divide the batch {B}")
+    lw = hold_check(None, n, n_cone_vecs, loads, max_force, ridge, iterations, friction, torque_weight, None, B // int(batch_each),
+                    who="hold_contacts")
+    dev = contact_pts.device
+    lw = lw.to(dev)
+    L = lw.shape[1]
+    e, resid, force = torch.empty(B, device=dev), torch.empty(B, L, device=dev), torch.empty(B, L, n, 3, device=dev)
+    _hold_call(None, None, None, None, None, _c(obj_normal.detach()), _c(contact_pts.detach()), _hold_cog(cog, B, batch_each, "hold_contacts"),
+               lw, B if lw.shape[0] == 1 else int(batch_each), n_cone_vecs, friction, torque_weight, max_force, ridge, iterations, None,
+               None, 0.0, e, resid, None, force, None, None, 0, None)
+    return e, resid, force
+
+
+# ----------------------------------------------------------------------------------------------------------
+# finger closing (csrc/close.hip): the joints stepped along a closing direction until the links touch the object grid, S + 1
+# dependent rounds of kinematics, grid query, per-link minimum, masks and update as ONE launch.  Values only.
+# ----------------------------------------------------------------------------------------------------------
+CLOSE_DEFAULTS = {"steps": 32, "touch": 5e-4, "step_revolute": 0.01, "step_prismatic": 5e-4}
+
+
+class CloseResult(NamedTuple):
+    """What ``close_fingers`` and ``GraspStepper.close`` return: the final state of finger closing (include/graspqp_hip.h)."""
+    theta: Tensor       # (B,JA) closed joints
+    touch_step: Tensor  # (B,L) int32, the first step at which link l touched; -1: never
+    joint_stop: Tensor  # (B,JA) int32, the first step at which a touch stopped joint a; -1: not stopped by a touch
+    phi: Tensor         # (B,L) smallest phi over the link's samples inside the volume, +inf without one; max(-phi, 0): overshoot
+    sample: Tensor      # (B,L) int32, the sample that has it, -1 if none
+    point: Tensor       # (B,L,3) its world position
+    normal: Tensor      # (B,L,3) the object's outward normal there, zeros where there is none
+    touched: Tensor     # (B,L) bool, touch_step >= 0
+
+    def contacts(self, n):
+        """-> (contact_pts, obj_normal), both (B,n,3), for ``hold_contacts``: the touched links in link order, at most ``n`` of
+        them; the unused slots hold zero points and ZERO normals, which give all-zero cone columns.  No host synchronisation."""
+        B, L = self.touched.shape
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"CloseResult.contacts: n = {n} must be >= 1")
+        order = torch.sort((~self.touched).to(torch.int32), dim=1, stable=True).indices  # touched links first, in link order
+        if n > L:
+            order = torch.cat([order, order[:, :1].expand(B, n - L)], 1)
+        order = order[:, :n]
+        used = torch.arange(n, device=order.device)[None] < self.touched.sum(1, keepdim=True)
+        pick = order.unsqueeze(-1).expand(B, n, 3)
+        keep = used.unsqueeze(-1)
+        zero = torch.zeros((), device=order.device)
+        return (torch.where(keep, self.point.gather(1, pick), zero).contiguous(),
+                torch.where(keep, self.normal.gather(1, pick), zero).contiguous())
+
+
+def _close_spec(spec_or_hand):
+    spec = getattr(spec_or_hand, "spec", spec_or_hand)
+    J, JA, L = int(spec.n_nodes), int(spec.n_dofs), int(spec.n_links)
+    C = np.asarray(spec.coupling, np.float64).reshape(J, JA) != 0 if spec.is_coupled else np.eye(J, dtype=bool)
+    return spec, J, JA, L, C
+
+
+def close_stop_masks_host(spec_or_hand) -> np.ndarray:
+    """``joint_links`` (JA) uint64 on the host: bit l of entry a is set when link l rides on a tree node in the subtree of a tree
+    node that actuated joint a drives (``coupling[j, a] != 0``; an uncoupled hand drives node a alone)."""
+    spec, J, JA, L, C = _close_spec(spec_or_hand)
+    if L > 64 or J > 64 or JA > 64:
+        raise ValueError(f"close: the hand must have at most 64 joints and 64 links, got J={J} JA={JA} L={L}")
+    parent = [int(p) for p in spec.node_parent]
+    masks = np.zeros(JA, np.uint64)
+    for l in range(L):
+        j = int(spec.link_node[l])
+        while j >= 0:  # the nodes between the link and the base
+            for a in np.nonzero(C[j])[0]:
+                masks[a] |= np.uint64(1) << np.uint64(l)
+            j = parent[j]
+    return masks
+
+
+def close_stop_masks(hand: HandHandle) -> Tensor:
+    """The ``joint_links`` tensor of ``close_fingers`` for ``hand``: (JA) int64 on the hand's device (the bits of the uint64 masks of
+    ``close_stop_masks_host``), built once per hand and kept on the handle."""
+    m = getattr(hand, "_close_masks", None)
+    if m is None:
+        m = torch.from_numpy(close_stop_masks_host(hand).view(np.int64).copy()).to(hand.device)
+        hand._close_masks = m
+    return m
+
+
+def close_default_step(spec_or_hand) -> np.ndarray:
+    """The default ``step`` (JA) float32: 0.01 rad for an actuated joint that drives revolute nodes, 5e-4 m for one that drives
+    prismatic nodes; a joint that drives both kinds (or none) raises ValueError."""
+    spec, J, JA, L, C = _close_spec(spec_or_hand)
+    ntype = np.asarray(spec.node_type).reshape(-1)
+    step = np.zeros(JA, np.float32)
+    for a in range(JA):
+        kinds = {int(ntype[j]) == 1 for j in np.nonzero(C[:, a])[0]}
+        if len(kinds) != 1:
+            raise ValueError(f"close: actuated joint {a} drives {'no node' if not kinds else 'revolute and prismatic nodes'}; pass step=")
+        step[a] = CLOSE_DEFAULTS["step_revolute"] if kinds.pop() else CLOSE_DEFAULTS["step_prismatic"]
+    return step
+
+
+def _close_step(hand, step):
+    """``step`` (None, a scalar or (JA)) -> (JA) float32 numpy"""
+    if step is None:
+        return close_default_step(hand)
+    s = np.asarray(step.detach().cpu() if torch.is_tensor(step) else step, dtype=np.float32).reshape(-1)
+    if s.size == 1:
+        s = np.full(hand.J, s[0], np.float32)
+    if s.shape != (hand.J,):
+        raise ValueError(f"close: step must be a scalar or ({hand.J},), got {tuple(s.shape)}")
+    return np.ascontiguousarray(s)
+
+
+def _scene_arg(grid, batch, who):
+    """An ``ops.SceneSDF`` or ``ops.SceneSDFSet`` whose grids divide the batch, else ValueError -> rows per grid."""
+    if not isinstance(grid, (SceneSDF, SceneSDFSet)):
+        raise ValueError(f"{who}: grid must be an ops.SceneSDF or an ops.SceneSDFSet")
+    G = grid.n_grids if isinstance(grid, SceneSDFSet) else 1
+    if int(batch) % G:
+        raise ValueError(f"{who}: batch = {batch} is not divisible by n_grids = {G}")
+    return int(batch) // G
+
+
+def close_check(grid, batch, hand, n_samples, steps, step, touch):
+    """gq_close_check (host only): the grid or stack against the batch, ``steps`` in 1..64, ``step`` (JA, numpy) finite and > 0,
+    ``touch`` finite and >= 0, at most 64 joints and links; raises ValueError with the library's message."""
+    rows = _scene_arg(grid, batch, "close")
+    spec = getattr(hand, "spec", hand)
+    st = None if step is None else np.ascontiguousarray(np.asarray(step, np.float32))
+    if st is not None and st.shape != (int(spec.n_dofs),):
+        raise ValueError(f"close: step must be ({int(spec.n_dofs)},), got {tuple(st.shape)}")
+    try:
+        _C.call("gq_close_check", ctypes.byref(_pregrasp_grids(grid.values, grid.origin, grid.voxel)), ctypes.c_int64(int(batch)),
+                ctypes.c_int64(rows), int(spec.n_nodes), int(spec.n_dofs), int(spec.n_links), ctypes.c_int64(int(n_samples)),
+                int(steps), None if st is None else st.ctypes.data_as(ctypes.c_void_p), float(touch))
+    except RuntimeError as e:
+        raise ValueError(f"close: {e}") from None
+
+
+def _close_call(hand, grids, points, link, hp, Rg, direction, steps, step, touch, masks, theta, touch_step, joint_stop, phi, sample,
+                point, normal, st=None):
+    """gq_close_fingers on arguments the caller has checked (close_check): the host copy of ``step`` is not passed."""
+    p, (B, D) = _dev, hp.shape
+    _C.call("gq_close_fingers", hand.handle, ctypes.byref(grids), ctypes.c_int64(B // max(grids.n_grids, 1)), _C.f32(points),
+            p(link, torch.int32), ctypes.c_int64(points.shape[0]), _C.f32(hp), D, p(Rg), ctypes.c_int64(B), p(direction), int(steps),
+            p(step), None, float(touch), p(masks, torch.int64), p(theta), p(touch_step, torch.int32), p(joint_stop, torch.int32), p(phi),
+            p(sample, torch.int32), p(point), p(normal), _C.stream_ptr() if st is None else st)
+
+
+def _close_outputs(hp, L):
+    B, JA, dev = hp.shape[0], hp.shape[1] - 9, hp.device
+    f = lambda *s: torch.empty(*s, device=dev)
+    i = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    return f(B, JA), i(B, L), i(B, JA), f(B, L), i(B, L), f(B, L, 3), f(B, L, 3)
+
+
+@_custom_op("graspqp_amd::close_fingers", mutates_args=(), device_types="cuda")
+def _close_op(hand_pose: Tensor, points: Tensor, link: Tensor, hand: int, Rg: Tensor, values: Tensor, origin: List[float],
+              voxel: float, direction: Tensor, steps: int, step: Tensor, touch: float,
+              joint_links: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (theta (B,JA), touch_step (B,L) int32, joint_stop (B,JA) int32, phi (B,L), sample (B,L) int32, point (B,L,3), normal
+    (B,L,3)): finger closing of the rows of ``hand_pose`` along ``direction`` (B,JA) on one grid (nx,ny,nz) or a stack
+    (G,nx,ny,nz) that contains the target; ``step`` (JA) and ``joint_links`` (JA) int64 on the device.  Values only."""
+    h = _handle(hand)
+    hp, v = _c(hand_pose), _c(values)
+    out = _close_outputs(hp, h.L)
+    _close_call(h, _pregrasp_grids(v, origin, voxel), _c(points), _c(link, torch.int32), hp, _c(Rg), _c(direction), steps, _c(step), touch,
+                _c(joint_links, torch.int64), *out)
+    return out
+
+
+@_close_op.register_fake
+def _(hand_pose, points, link, hand, Rg, values, origin, voxel, direction, steps, step, touch, joint_links):
+    B, JA, L = hand_pose.shape[0], hand_pose.shape[1] - 9, _handle(hand).L
+    f = hand_pose.new_empty
+    i = lambda *s: hand_pose.new_empty(*s, dtype=torch.int32)
+    return f(B, JA), i(B, L), i(B, JA), f(B, L), i(B, L), f(B, L, 3), f(B, L, 3)
+
+
+def _close_setup(ctx, inputs, output):
+    ctx.n_in = len(inputs)
+    ctx.mark_non_differentiable(*output)
+
+
+def _close_bwd(ctx, *grads):
+    return (None,) * ctx.n_in
+
+
+torch.library.register_autograd("graspqp_amd::close_fingers", _close_bwd, setup_context=_close_setup)
+
+
+def close_fingers(hand_pose, hand: HandHandle, samples: SurfaceSamples, Rg, grid, direction, steps=32, step=None, touch=5e-4):
+    """Close the fingers until they touch -> ``CloseResult``.  From the joints of ``hand_pose`` (B, 9 + JA; ``Rg`` its rotation, as
+    fk_contacts returns it) the actuated joints move along ``direction`` (B,JA), the fastest one by exactly its ``step`` per step,
+    for ``steps`` steps in 1..64.  After every step each link's smallest phi over its surface ``samples`` is read from ``grid``, an
+    ``ops.SceneSDF`` or an ``ops.SceneSDFSet`` (row b reads grid b // (B / G)) that CONTAINS THE TARGET; a link touches when that
+    phi is at or under ``touch`` metres, and from then on its own joint and every joint between it and the palm stand still
+    (``close_stop_masks``), while the joints beyond it keep closing up to their limits.  ``step`` (a scalar or (JA)) = None takes
+    0.01 rad for revolute and 5e-4 m for prismatic actuated joints.  There is no sub-step refinement: the overshoot is at most
+    step x lever arm and ``max(-phi, 0)`` reports it.  Values only: nothing here is differentiable.  One launch, bitwise
+    reproducible, graph-capturable."""
+    if not hand_pose.is_cuda:
+        raise RuntimeError("graspqp_amd ops need CUDA (ROCm) tensors; got a CPU tensor")
+    if samples.n_links != hand.L:
+        raise ValueError(f"close_fingers: the samples refer to {samples.n_links} links, the hand has {hand.L}")
+    B = hand_pose.shape[0]
+    if hand_pose.dim() != 2 or hand_pose.shape[1] != 9 + hand.J:
+        raise ValueError(f"close_fingers: hand_pose must be (B, {9 + hand.J}), got {tuple(hand_pose.shape)}")
+    if tuple(direction.shape) != (B, hand.J):
+        raise ValueError(f"close_fingers: direction must be ({B}, {hand.J}), got {tuple(direction.shape)}")
+    st = _close_step(hand, step)
+    close_check(grid, B, hand, samples.Ns, steps, st, touch)
+    dev = hand_pose.device
+    out = _Eager.close_fingers(_c(hand_pose.detach()), samples.points, samples.link, hand.hid, _c(Rg.detach()), grid.values,
+                               list(grid.origin), grid.voxel, _c(direction.detach()), int(steps), torch.from_numpy(st).to(dev),
+                               float(touch), close_stop_masks(hand))
+    return CloseResult(*out, out[1] >= 0)
+
+
 # ----------------------------------------------------------------------------------------------------------
 # arm reachability: E_reach (csrc/reach.hip), batched damped-least-squares wrist IK as ONE launch: eight lanes per IK problem, the
 # seeds and stations of a row side by side in one block, the gradient in the gRt layout the FK backward takes
@@ -3398,6 +3628,7 @@ _eager("squeeze_terms", _squeeze_op)
 _eager("squeeze_terms_backward", _squeeze_bwd_op)
 _eager("hold_terms", _hold_op, _hold_bwd, _hold_setup)
 _eager("hold_terms_backward", _hold_bwd_op)
+_eager("close_fingers", _close_op)
 _eager("reach_terms", _reach_op)
 _eager("reach_terms_backward", _reach_bwd_op)
 _eager("track_terms", _track_op)

@@ -432,6 +432,7 @@ class GraspStepper:
         self._fuse_loop = plan.fuse_loop
         self.samples, self.g_R = None, None
         self._n_surface_points, self._select_fk = int(n_surface_points), None
+        self._close_par = (float(a.squeeze_min_travel), float(a.squeeze_damping))  # close() reads them whether the term is on or off
         if plan.needs_samples:  # one set of surface samples for all modes
             if surface_samples is None:
                 from .utils import meshes as mesh_utils
@@ -1149,7 +1150,53 @@ class GraspStepper:
         return ops.grasp_select(self.hand_pose, Rg, LT, self.samples, self.be, score.to(self.dev, torch.float32), self.terms, tol,
                                 k, radius)
 
-    def hold(self, loads, max_force, torque_limits=None, iterations=16):
+    def _surface_samples(self):
+        if self.samples is None:
+            from .utils import meshes as mesh_utils
+
+            pts, link = mesh_utils.hand_surface_samples(self.hand.spec, self._n_surface_points)
+            self.samples = ops.SurfaceSamples(self.hand, pts, link, device=self.dev)
+        return self.samples
+
+    def close(self, grid, direction=None, steps=32, step=None, touch=5e-4):
+        """Close the fingers of the ACCEPTED grasps until they touch -> ``ops.CloseResult`` (device tensors; the host does not wait):
+        the closed joints, which links touch, at which step, where and with which object normal (``ops.close_fingers``).  It is the
+        step between ``select`` and ``hold``: close, then ask the payload question on the contacts that exist
+        (``hold(..., closed=c)``).  ``grid`` is an ``ops.SceneSDF``, or an ``ops.SceneSDFSet`` with one grid per object, that
+        CONTAINS THE TARGET (as ``pregrasp_scene``).  ``direction`` (B,JA) = None is the squeeze command of the accepted state: the
+        joint velocities the E_squeeze launch computes at ``squeeze_min_travel`` / ``squeeze_damping`` (whether or not the term is
+        on), NEGATED -- ``squeeze_theta`` follows the object's outward normals, the opening sense, and the closing sense moves the
+        contacts INTO the object: one closing step along the default direction lowers the smallest phi of the fingertip links
+        (tests/test_gpu_close.py::test_default_direction_closes).  Like ``select`` and ``hold`` it reads ``hand_pose`` /
+        ``contact_idx`` after ``flush``, with one FK forward (and for the default direction one object query and one squeeze
+        launch) into buffers of its own.  Nothing of the chain's state is written: stepping on afterwards gives the bits of a
+        stepper that never called it."""
+        grid = self._scene_arg("close", "grid", grid)
+        st_np = ops._close_step(self.hand, step)
+        samples = self._surface_samples()
+        ops.close_check(grid, self.B, self.hand, samples.Ns, steps, st_np, touch)
+        if direction is not None and tuple(direction.shape) != (self.B, self.J):
+            raise ValueError(f"GraspStepper.close: direction must be ({self.B}, {self.J}), got {tuple(direction.shape)}")
+        self.flush()
+        with torch.no_grad():
+            Rg, LT, cp, _, _, ws = ops.fk_contacts(self.hand_pose, self.contact_idx, self.hand)
+            if direction is None:
+                query = ops.sdf_cloud if self.cloud else ops.sdf_meshset
+                d2, sgn, nrm, _ = query(cp.reshape(-1, 3), self.objs, self.be * self.n)
+                _, onrm = ops.signed_distance(d2, sgn, nrm)
+                theta = torch.empty(self.B, self.J, device=self.dev)
+                ops._squeeze_call(self.hand, self.contact_idx, Rg.contiguous(), LT.contiguous(), ws, d2.reshape(self.B, self.n).contiguous(),
+                                  onrm.reshape(self.B, self.n, 3).contiguous(), None, None, self._close_par[0], self._close_par[1], None,
+                                  0.0, None, theta, 0, None, None, None, None)
+                direction = -theta
+            direction = direction.detach().to(self.dev, torch.float32).contiguous()
+            out = ops._close_outputs(self.hand_pose, self.L)
+            ops._close_call(self.hand, ops._pregrasp_grids(grid.values, grid.origin, grid.voxel), samples.points, samples.link,
+                            self.hand_pose, Rg.contiguous(), direction, int(steps), torch.from_numpy(st_np).to(self.dev), float(touch),
+                            ops.close_stop_masks(self.hand), *out)
+            return ops.CloseResult(*out, out[1] >= 0)
+
+    def hold(self, loads, max_force, torque_limits=None, iterations=16, closed=None, contacts=None):
         """Can the ACCEPTED grasps carry ``loads``?  -> ``ops.HoldResult`` (device tensors; the host does not wait): E_hold, the
         residual share per load, the cone-edge coefficients, the contact forces (N, world frame) and the joint torques they ask
         of the hand, with ``torque_limits`` (JA) also the effort.  ``loads`` (L,6) or (n_obj,L,6) from ``ops.hold_loads``,
@@ -1161,7 +1208,18 @@ class GraspStepper:
             h = st.hold(ops.hold_loads(0.5), max_force=20.0)
             sel = st.select(k, score=torch.where(h.resid.amax(1) <= 0.05, st.energy, torch.inf))
 
-        (``ops.grasp_select`` treats a non-finite score as infeasible)."""
+        (``ops.grasp_select`` treats a non-finite score as infeasible).
+
+        ``closed`` = the ``ops.CloseResult`` of ``close``: the question is asked on the contacts that exist after closing, the
+        touched links' points and object normals (``closed.contacts(contacts)``, ``contacts`` = None: as many slots as the stepper
+        has contacts), through ``ops.hold_contacts`` -> (E_hold, resid, force).  There are no joint torques on this route: the torque
+        of a force at an arbitrary link point needs a Jacobian of that point, which the package does not have."""
+        if closed is not None:
+            if torque_limits is not None:
+                raise ValueError("GraspStepper.hold: closed= has no joint torques, so torque_limits cannot be used with it")
+            cp, onrm = closed.contacts(self.n if contacts is None else int(contacts))
+            return ops.hold_contacts(cp, onrm, self.cog, loads, self.be, self.fc["friction"], self.fc["torque_weight"],
+                                     self.fc["n_cone_vecs"], max_force, ops.HOLD_DEFAULTS["ridge"], iterations)
         lw = ops.hold_check(self.hand, self.n, self.fc["n_cone_vecs"], loads, max_force, ops.HOLD_DEFAULTS["ridge"], iterations,
                             self.fc["friction"], self.fc["torque_weight"], torque_limits, self.B // self.be, "GraspStepper.hold")
         lim = None if torque_limits is None else torch.as_tensor(torque_limits, dtype=torch.float32).reshape(-1).to(self.dev)

@@ -767,6 +767,53 @@ int gq_hold_terms(const gqHand* h, const int64_t* contact_idx /* (B,n) */, int64
                   float* torque /* (B,L,JA) */, float* effort /* (B) */, int accumulate,
                   float* g_contact_pts /* (B,n,3) or NULL */, void* stream);
 
+/* ---- finger closing: where the hand really touches when the squeeze command is executed ---------------------------------------
+ * Kinematic only (no forces, no object motion): the actuated joints are stepped along a closing direction until the links touch the
+ * object grid, a joint limit, or the steps run out.  Per row b: theta_0 = the joints of hand_pose (B, 9 + JA), R = Rg (B,9), t the
+ * translation of hand_pose, v = direction (B,JA), the hand's surface samples (p_i in the frame of link sample_link[i]) and grid
+ * b / rows_per_grid of a gqClutterGrids stack that CONTAINS THE TARGET (a single grid is the stack of one with rows_per_grid =
+ * batch).  Parameters: S = n_steps in 1..64, step (JA) finite and > 0 (the largest increment of each actuated joint per step),
+ * tau = touch >= 0 (metres), joint_links (JA) 64-bit masks over the links.
+ *   direction  u_a = v_a / step_a, m = max_a |u_a|, Delta_a = step_a (u_a / m): the fastest joint moves exactly its step.  A row
+ *              with m = 0, or with any u_a not finite, has Delta = 0 and does not move.
+ *   steps      s = 0..S (S + 1 evaluations, S updates):
+ *     1. tree angles C theta_s + c0 for a coupled hand, link transforms T_l in the hand frame, as gq_fk_forward
+ *     2. every sample x_i = R (T_l p_i) + t, phi_i by the device body of "scene obstacles" on the row's grid; a sample outside the
+ *        volume, at a non-finite point or with a NaN phi takes no part (it never touches and loads nothing out of range)
+ *     3. per link l: m_l = min phi_i over its samples that take part, ties to the LOWEST sample index (+inf, no sample: none)
+ *     4. touched_l becomes true, and stays true, when m_l <= tau; touch_step_l = the first such s
+ *     5. joint a is stopped from step s on when a touched link lies in joint_links[a]; joint_stop_a = the first such s
+ *     6. if s < S: theta_(s+1),a = min(max(theta_s,a + Delta_a, lower_a), upper_a) for the joints that are not stopped and have
+ *        Delta_a != 0; every other joint keeps its value bit for bit
+ *   When step 6 changes no joint, every later evaluation repeats this one and the launch stops there (block-uniform).
+ * joint_links[a] has bit l set when link l rides on a tree node in the subtree of a tree node that joint a drives (coupling[j][a]
+ * != 0; an uncoupled hand drives node a alone); it is built on the host once per hand.  A touching link so stops its own joint
+ * and every joint between it and the palm, the joints beyond it keep closing; a link fixed to the base stops nothing.  A touched
+ * link never moves again, so the state of its first touch is its final state.  No sub-step refinement: the overshoot is at most
+ * step x lever arm and max(-phi, 0) reports it.
+ * Outputs, all of the final state theta_S, any may be NULL:
+ *   theta (B,JA)          closed joints
+ *   touch_step (B,L) i32  -1: never touched
+ *   joint_stop (B,JA) i32 -1: not stopped by a touch (it may stand on a joint limit)
+ *   phi (B,L)             m_l; +inf without a sample that takes part
+ *   sample (B,L) i32      the argmin sample, -1 if none
+ *   point (B,L,3)         world position of that sample (zeros if none)
+ *   normal (B,L,3)        grad phi / |grad phi| there, the object's outward normal; zeros if none or |grad phi| = 0
+ * One block of eight wavefronts per row; minima with a lowest-index tie-break, no sums, no atomics: bitwise reproducible run to run
+ * and row by row, graph-capturable, the host never waits.  An error status, never a device fault, for every bad argument.
+ * gq_close_check is the host-only part (no GPU): everything gq_clutter_check refuses (a stack that does not cover the batch), n_steps
+ * outside 1..64, a step that is not finite or <= 0 (step_host: the (JA) values on the host, NULL = the caller has checked them),
+ * touch < 0 or not finite, more than 64 tree joints, actuated joints or links; its message contains "close".              */
+int gq_close_check(const gqClutterGrids* grids, int64_t batch, int64_t rows_per_grid, int n_joints, int n_actuated, int n_links,
+                   int64_t n_samples, int n_steps, const float* step_host /* (JA) host or NULL */, float touch);
+int gq_close_fingers(const gqHand* h, const gqClutterGrids* grids, int64_t rows_per_grid, const float* samples /* (Ns,3) device */,
+                     const int32_t* sample_link /* (Ns) */, int64_t n_samples, const float* hand_pose, int pose_dim,
+                     const float* Rg /* (B,9) */, int64_t batch, const float* direction /* (B,JA) */, int n_steps,
+                     const float* step /* (JA) device */, const float* step_host /* (JA) host or NULL */, float touch,
+                     const int64_t* joint_links /* (JA) device, bit l = link l */, float* theta /* (B,JA) */,
+                     int32_t* touch_step /* (B,L) */, int32_t* joint_stop /* (B,JA) */, float* phi /* (B,L) */,
+                     int32_t* sample /* (B,L) */, float* point /* (B,L,3) */, float* normal /* (B,L,3) */, void* stream);
+
 /* ---- arm reachability of the stepper: E_reach, batched damped-least-squares wrist IK ----------------------------------------
  * Every other term treats the hand as a free-flying body; this one knows that it sits on an arm.  The arm is a serial chain of
  * N <= 8 revolute (1) or prismatic (2) joints with limits: FK(q) = base_T joint_T[0] m_0(q_0) ... joint_T[N-1] m_{N-1}(q_{N-1}) tool_T
